@@ -122,6 +122,36 @@ class CollectiveTimer:
         return {k: round(v / steps, 4) for k, v in out.items()}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(sess, it, out_dir):
+    """What the last timed step hands its caller, as <out_dir>/<name>.npy: the loss terms (`loss_terms`, float64), every
+    parameter the optimisers update, after the step and clip_z (`param<i>`), its gradient from that step's backward
+    (`param<i>_grad`), and the image the updated parameters render (`image`, drawer.synth without autograd).  Arrays are float32
+    except the losses; one larger than its share of the 64 MB budget is replaced by a fixed, seeded sample of its flattened
+    values.  The same arguments give the same inputs, so two builds can be compared file for file."""
+    import numpy as np
+    import torch
+    arrays = {"loss_terms": np.concatenate([np.asarray(l.detach().double().cpu() if isinstance(l, torch.Tensor) else l,
+                                                       dtype=np.float64).ravel() for l in sess.last_losses])}
+    params = [p for opt in sess.opts for g in opt.param_groups for p in g["params"]]
+    for i, p in enumerate(params):
+        arrays[f"param{i}"] = p.detach().float().cpu().numpy()
+        if p.grad is not None:
+            arrays[f"param{i}_grad"] = p.grad.detach().float().cpu().numpy()
+    with torch.no_grad():
+        arrays["image"] = sess.drawer.synth(it).detach().float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_MAX_BYTES // len(arrays)
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return list(arrays)
+
+
 def spawn_command(n, argv, port=None):
     """the command line `python bench.py --gpus n` re-executes itself under (one rank per GPU of this node over RCCL)"""
     import socket
@@ -162,10 +192,17 @@ def main():
     ap.add_argument("--cpu-sample-cutn", type=int, default=None)
     ap.add_argument("--profile-steps", type=int, default=3)
     ap.add_argument("--phase-steps", type=int, default=2, help="iterations of the synchronised phase breakdown (0: skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0): the loss "
+                         "terms, the drawer's parameters after the optimiser step, their gradients and the image they render")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch mechanics only: every rank joins a gloo group on the host, rank 0 prints {world, ranks} and exits "
                          "(CPU test of the bare `--gpus N` form; no GPU touched)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if args.dry_run:
         if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -273,6 +310,9 @@ def main():
         lt = torch.tensor([loss], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(lt, op=dist.ReduceOp.SUM, group=group)
         loss = float(lt.item())
+    if args.dump_outputs and rank == 0:
+        names = dump_outputs(sess, it, args.dump_outputs)
+        print(f"bench.py: wrote {', '.join(names)} to {args.dump_outputs}", file=sys.stderr, flush=True)
 
     # ---- per-collective device time (N > 1, or the forced 1-rank group) ------------------------------------------------
     collectives = None

@@ -1,8 +1,8 @@
 """Run pixray's own pure-torch fragments straight from the read-only reference checkout.
 
 `import pixray` is impossible offline (kornia, clip, taming, ... are missing), but single definitions can be
-pulled out of the source by AST and exec'd.  Only used in this container (tests skip when /root/reference is
-absent, e.g. on the GPU box); nothing is copied into the repository."""
+pulled out of the source by AST and exec'd.  Only tests/golden/make_golden.py uses it, to record what those fragments
+compute as fixtures; the tests read the fixtures and need no reference checkout.  Nothing is copied into the repository."""
 import ast
 import os
 

@@ -15,8 +15,21 @@ HF transformers are available):
   styleloss_golden.npz  outputs of pixray's OWN STROTSS functions and Vgg16_Extractor class (Losses/StyleLoss.py),
                         extracted by AST and executed on a torchvision-shaped VGG16 filled with the seeded weights of
                         pixray_amd.weights (torchvision and the pretrained net are absent): loss and d(loss)/d(image)
+  reference_live_golden.npz
+                        what the suite's cross-checks against pixray's own code compare with, recorded from that code so
+                        that the suite needs nothing outside the repository: Prompt / parse_prompt / vector_quantize on
+                        fresh inputs, Vgg16_Extractor's ten maps in both input spaces (shape, sums and a seeded sample of
+                        each), STROTSS loss and gradient at two more canvas sizes, and a digest of every row of the
+                        default vector-prompt table (vectors/textoff.json)
+  reference_parser_options.json
+                        every option of pixray.py's setup_parser: flags, default, type name, nargs
 Weights are NOT stored: they are re-derived from the seeds by pixray_amd.weights.synthetic_*.
+
+    python tests/golden/make_golden.py reference_live      # only the two reference_* fixtures
 """
+import ast
+import hashlib
+import json
 import os
 import sys
 
@@ -166,9 +179,106 @@ def styleloss_golden(out_dir):
     np.savez_compressed(os.path.join(out_dir, "styleloss_golden.npz"), **rec)
 
 
+FRAGMENT_PROMPTS = ((1.0, float("-inf")), (-2.0, float("-inf")), (0.5, 1.4))     # (weight, stop) of the live Prompt cross-check
+VGG_SAMPLE = 512                                                                  # values kept per VGG map
+STROTSS_LIVE_HW = ((132, 140), (77, 131))
+
+
+def vector_row_digest(row) -> str:
+    """sha256 of one row of a vector-prompt table, value for value (the json of its parsed floats)"""
+    return hashlib.sha256(json.dumps(row).encode()).hexdigest()
+
+
+def reference_parser_options() -> dict:
+    """{dest: [flags, default, type name, nargs]} of every add_argument in pixray.py's setup_parser, read from its source"""
+    tree = ast.parse(open(os.path.join(rx.REF, "pixray.py")).read())
+    fn = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "setup_parser")
+    ref = {}
+    for node in ast.walk(fn):
+        if isinstance(node, ast.Call) and getattr(node.func, "attr", "") == "add_argument":
+            kw = {k.arg: k.value for k in node.keywords}
+            ref[kw["dest"].value] = [[a.value for a in node.args], ast.literal_eval(kw["default"]),
+                                     kw["type"].id if "type" in kw else None,
+                                     ast.literal_eval(kw["nargs"]) if "nargs" in kw else None]
+    return ref
+
+
+def reference_live_golden(out_dir):
+    import warnings
+    rec = {}
+    # Prompt / parse_prompt / vector_quantize on fresh inputs (tests/test_oracle_golden.py)
+    ns = rx.pixray_prompt_ns()
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(16, 512, generator=g)
+    e = torch.randn(2, 512, generator=g)
+    rec.update(frag_x=x.numpy(), frag_e=e.numpy())
+    for i, (w, stop) in enumerate(FRAGMENT_PROMPTS):
+        xr = x.clone().requires_grad_(True)
+        loss = ns["Prompt"](e, w, stop)(xr)
+        rec[f"frag_loss_{i}"] = loss.detach().numpy()
+        rec[f"frag_grad_{i}"] = torch.autograd.grad(loss, xr)[0].numpy()
+    txt, w, stop = ns["parse_prompt"]("a cat:2:0.5")
+    rec["parse_text"] = np.array(txt)
+    rec["parse_weight_stop"] = np.array([w, stop], np.float64)
+    vs = rx.vqgan_ns()
+    xq = torch.randn(1, 8, 8, 32, generator=g)
+    cb = torch.randn(128, 32, generator=g)
+    rec.update(vq_x=xq.numpy(), vq_codebook=cb.numpy(), vq_q=vs["vector_quantize"](xq, cb).numpy())
+
+    # Vgg16_Extractor's ten maps in both input spaces (tests/test_oracle_pins.py): shape, float64 sum / sum of squares / max |.|,
+    # and the values at VGG_SAMPLE seeded positions of each map
+    sx = rx.styleloss_ns()
+    params = weights.synthetic_vgg16_params(0)
+    xv = torch.rand(2, 3, 48, 40, generator=torch.Generator().manual_seed(2)) * 2 - 1
+    rec["vgg_x"] = xv.numpy()
+    for space in ("uniform", "vgg"):
+        maps = rx.reference_vgg_extractor(sx, params, space)(xv.clone())
+        rec[f"vgg_{space}_count"] = np.int64(len(maps))
+        for i, m in enumerate(maps):
+            k, m64 = f"vgg_{space}_{i}", m.double()
+            idx = np.sort(np.random.default_rng(i).choice(m.numel(), min(VGG_SAMPLE, m.numel()), replace=False))
+            rec[k + "_shape"] = np.array(m.shape, np.int64)
+            rec[k + "_index"] = idx.astype(np.int64)
+            rec[k + "_sample"] = m.reshape(-1)[torch.from_numpy(idx)].numpy()
+            rec[k + "_stats"] = np.array([float(m64.sum()), float((m64 * m64).sum()), float(m64.abs().max())])
+
+    # STROTSS loss and d(loss)/d(image) at two more canvas sizes (tests/test_style_loss.py); the inputs are re-drawn from the seed
+    # there, their float64 sums are kept as a check of the draw
+    ex = rx.reference_vgg_extractor(sx, params)
+    for hw in STROTSS_LIVE_HW:
+        g = torch.Generator().manual_seed(31)
+        img = torch.rand(1, 3, *hw, generator=g)
+        style = torch.rand(1, 3, *hw, generator=g)
+        xr = img.clone().requires_grad_(True)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            np.random.seed(77)
+            loss = sx["strotss_loss"](xr, style, 8.0, extractor=ex)
+        k = f"strotss_{hw[0]}x{hw[1]}"
+        rec[k + "_input_sums"] = np.array([float(img.double().sum()), float(style.double().sum())])
+        rec[k + "_loss"] = loss.detach().numpy()
+        rec[k + "_grad"] = torch.autograd.grad(loss, xr)[0].numpy()
+
+    # the default vector-prompt table (tests/test_host_logic.py, tests/test_oracle_golden.py)
+    table = json.load(open(os.path.join(rx.REF, "vectors", "textoff.json")))
+    keys = sorted(table)
+    rec["textoff_keys"] = np.array(keys)
+    rec["textoff_shapes"] = np.array([[len(table[k]), len(table[k][0])] for k in keys], np.int64)
+    rec["textoff_finite"] = np.array([bool(np.isfinite(np.asarray(table[k], np.float64)).all()) for k in keys])
+    rec["textoff_sha256"] = np.array([vector_row_digest(table[k]) for k in keys])
+    np.savez_compressed(os.path.join(out_dir, "reference_live_golden.npz"), **rec)
+    with open(os.path.join(out_dir, "reference_parser_options.json"), "w") as f:
+        json.dump(reference_parser_options(), f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 def main():
     out = HERE
+    if sys.argv[1:] == ["reference_live"]:
+        reference_live_golden(out)
+        return
     styleloss_golden(out)
+    reference_live_golden(out)
     # ---- pixray's own fragments ----------------------------------------------------------------------------------
     ns = rx.pixray_prompt_ns()
     g = torch.Generator().manual_seed(123)

@@ -19,6 +19,15 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 
 
+@pytest.fixture(autouse=True)
+def _restore_torch_threads():
+    """the tests below size torch's intra-op pool for their single-process runs: hand the suite back the count it had, so that
+    later tests' CPU oracles reduce in the same order whether or not these ran first"""
+    n = torch.get_num_threads()
+    yield
+    torch.set_num_threads(n)
+
+
 def _collect(q, procs, world, timeout=240):
     """results of all ranks, failing fast when a worker died instead of waiting out the queue timeout"""
     import queue as _queue

@@ -69,24 +69,11 @@ def _settings(tmp_path, **kw):
 
 # ------------------------------------------------------------------------------------------------ settings
 def test_core_option_table_matches_the_reference_parser():
-    """every option of the reference's `setup_parser` (pixray.py:1722-1786), read from its source: same flags, destination,
-    default and type name"""
-    src_path = "/root/reference/pixray.py"
-    if not os.path.exists(src_path):
-        pytest.skip("needs the reference checkout")
-    import ast
-    tree = ast.parse(open(src_path).read())
-    fn = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "setup_parser")
-    ref = {}
-    for node in ast.walk(fn):
-        if isinstance(node, ast.Call) and getattr(node.func, "attr", "") == "add_argument":
-            flags = [a.value for a in node.args]
-            kw = {k.arg: k.value for k in node.keywords}
-            dest = kw["dest"].value
-            default = ast.literal_eval(kw["default"])
-            typ = kw["type"].id if "type" in kw else None
-            nargs = ast.literal_eval(kw["nargs"]) if "nargs" in kw else None
-            ref[dest] = (flags, default, typ, nargs)
+    """every option of the reference's `setup_parser` (pixray.py:1722-1786), read from its source by
+    tests/golden/make_golden.py (reference_parser_options.json): same flags, destination, default and type name"""
+    import json
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_parser_options.json")) as f:
+        ref = {dest: tuple(v) for dest, v in json.load(f).items()}
     mine = {}
     for short, long_, dest, typ, default, kw in fe.CORE_OPTIONS:
         mine[dest] = (([short] if short else []) + [long_], default, {str: "str", float: "float", int: "int", fe.str2bool: "str2bool"}[typ],
@@ -220,6 +207,8 @@ def test_return_display_yields_every_display_every_iterations_like_the_cog_loop(
     fac = _factories(2)
     orig = fe.do_init
     monkeypatch.setattr(fe, "do_init", lambda settings, run=None: orig(settings, run, **fac))
+    import tempfile
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp_path))      # predict's copy goes to the temporary directory: this test's own
     paths = list(fe.predict(dict(drawer="fast_pixel", clip_models="tiny-B/32", size=[64, 48], pixel_size=[8, 6], num_cuts=2,
                                  vector_prompts="none", init_noise="snow"), prompts="x", iterations=4, display_every=2, save_every=1,
                             outdir=str(tmp_path / "p")))

@@ -7,23 +7,24 @@
 * BASELINE.json configs[0]: the plugin surface end to end on the CPU (pixel-grid drawer, ViT-B/32, cutn=2, 10
   iterations) with the *oracle* supplying the perceptor / cutout / prompt arithmetic -- the Session loop is the product
   code under test, the oracle parts are test infrastructure;
-* unmodified reference plugins (Losses/SaturationLoss.py, Losses/SymmetryLoss.py, filters/colorlookup.py loaded from
-  /root/reference when present) drop into the loop.
+* third-party plugins written against pixray's module layout (Losses.LossInterface, ...) drop into the loop.
 """
 import argparse
 from collections import OrderedDict
 import ctypes
+import hashlib
 import importlib.util
+import json
 import os
 import sys
 import types
 
+import numpy as np
 import pytest
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-import _refextract as rx
 from oracle import step_ref, prompt_ref
 from pixray_amd import _lib, cutouts as pc, weights
 from pixray_amd.engine import Session
@@ -245,26 +246,68 @@ def test_fft_drawer_plugin_runs_with_its_own_optimiser_cpu():
         bad = FftDrawer(_Settings(size=(32, 32), fft_use="dwt")); bad.load_model(None, "cpu"); bad.init_from_tensor(None)
 
 
-def _load_reference_plugin(relpath, clsname):
+# two loss plugins as a third party writes them for pixray: their own modules, importing the interface from pixray's module
+# layout (`Losses.LossInterface`), one scoring the cutouts (a list with one term per cutout table), one the image
+_CUTOUT_PLUGIN = """
+import torch
+
+from Losses.LossInterface import LossInterface
+
+
+class CutoutContrastLoss(LossInterface):
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+
+    @staticmethod
+    def add_settings(parser):
+        parser.add_argument("--contrast_weight", type=float, default=1, dest="contrast_weight")
+        return parser
+
+    def get_loss(self, cur_cutouts, out, args, globals=None, lossGlobals=None):
+        return [-args.contrast_weight * torch.std(cutouts) for cutouts in cur_cutouts.values()]
+"""
+
+_IMAGE_PLUGIN = """
+from Losses.LossInterface import LossInterface
+
+
+class MirrorLoss(LossInterface):
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+
+    @staticmethod
+    def add_settings(parser):
+        parser.add_argument("--mirror_weight", type=float, default=1, dest="mirror_weight")
+        return parser
+
+    def get_loss(self, cur_cutouts, out, args, globals=None, lossGlobals=None):
+        return args.mirror_weight * (out - out.flip(3)).pow(2).mean()
+"""
+
+
+def _load_plugin(path, clsname):
     install_compat_modules()
-    spec = importlib.util.spec_from_file_location("refplugin_" + clsname, os.path.join(rx.REF, relpath))
+    spec = importlib.util.spec_from_file_location("plugin_" + clsname, path)
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return getattr(mod, clsname)
 
 
-@pytest.mark.skipif(not rx.available(), reason="/root/reference not present (GPU box)")
-def test_unmodified_reference_plugins_drop_in():
-    Sat = _load_reference_plugin("Losses/SaturationLoss.py", "SaturationLoss")
-    Sym = _load_reference_plugin("Losses/SymmetryLoss.py", "SymmetryLoss")
-    assert issubclass(Sat, LossInterface) and issubclass(Sym, LossInterface)      # bound to OUR interface module
-    parser = Sat.add_settings(Sym.add_settings(argparse.ArgumentParser()))
+def test_third_party_plugins_drop_in(tmp_path):
+    (tmp_path / "CutoutContrastLoss.py").write_text(_CUTOUT_PLUGIN)
+    (tmp_path / "MirrorLoss.py").write_text(_IMAGE_PLUGIN)
+    Con = _load_plugin(tmp_path / "CutoutContrastLoss.py", "CutoutContrastLoss")
+    Mir = _load_plugin(tmp_path / "MirrorLoss.py", "MirrorLoss")
+    assert issubclass(Con, LossInterface) and issubclass(Mir, LossInterface)      # bound to OUR interface module
+    parser = Con.add_settings(Mir.add_settings(argparse.ArgumentParser()))
     ns = parser.parse_args([])
-    assert ns.saturation_weight == 1 and ns.symmetry_weight == 1
-    losses = [{"loss": Sat(device="cpu"), "weight": 0.5}, {"loss": Sym(device="cpu"), "weight": 2.0}]
+    assert ns.contrast_weight == 1 and ns.mirror_weight == 1
+    losses = [{"loss": Con(device="cpu"), "weight": 0.5}, {"loss": Mir(device="cpu"), "weight": 2.0}]
     sess = _cpu_session(custom_losses=losses, iters=2)
+    for k, v in vars(ns).items():
+        setattr(sess.args, k, v)
     out = sess.ascend_txt()
-    assert len(out) == 3 and all(o.requires_grad for o in out)       # prompt + saturation (list of 1) + symmetry
+    assert len(out) == 3 and all(o.requires_grad for o in out)       # prompt + contrast (list of 1) + mirror
     sum(out).backward()
     assert sess.drawer.get_z().grad.abs().sum() > 0
 
@@ -791,6 +834,36 @@ def test_bench_bare_gpus_form_spawns_its_own_ranks():
     assert rec == {"dry_run": True, "world": 2, "ranks": [0, 1], "gpus": 2}
 
 
+def test_bench_dump_outputs_writes_what_the_last_step_computed(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR` (bench.dump_outputs) on the CPU session of configs[0]: the last step's loss terms in
+    float64, the drawer parameters after the step with their gradients and the image they render in float32; an array over its
+    share of the size budget becomes the same seeded sample on every call"""
+    root = os.path.dirname(HERE)
+    sys.path.insert(0, root)
+    try:
+        import bench
+    finally:
+        sys.path.remove(root)
+    sess = _cpu_session(iters=3)
+    sess.train(0)
+    sess.train(1)
+    names = bench.dump_outputs(sess, 2, str(tmp_path / "a"))
+    assert names == ["loss_terms", "param0", "param0_grad", "image"]
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    assert got["loss_terms"].dtype == np.float64 and all(got[n].dtype == np.float32 for n in names[1:])
+    assert np.array_equal(got["loss_terms"], np.array([float(l) for l in sess.last_losses]))
+    p = sess.opts[0].param_groups[0]["params"][0]
+    assert np.array_equal(got["param0"], p.detach().numpy()) and np.array_equal(got["param0_grad"], p.grad.numpy())
+    with torch.no_grad():
+        assert np.array_equal(got["image"], sess.drawer.synth(2).numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 1024)                 # 1024 bytes per array: 256 float32 values
+    for d in ("b", "c"):
+        bench.dump_outputs(sess, 2, str(tmp_path / d))
+    for n in names[1:]:
+        b, c = np.load(tmp_path / "b" / f"{n}.npy"), np.load(tmp_path / "c" / f"{n}.npy")
+        assert b.shape == (256,) and np.array_equal(b, c) and np.isin(b, got[n]).all()
+
+
 def test_reference_precision_mix_splits_into_f32_decoder_and_fp16_towers():
     from pixray_amd import _lib
     assert _lib.split_precision("ref") == ("f32", "fp16") and _lib.split_precision("REF") == ("f32", "fp16")
@@ -802,19 +875,17 @@ def test_reference_precision_mix_splits_into_f32_decoder_and_fp16_towers():
 
 def test_default_vector_prompt_table_is_the_references():
     """pixray's default `--vector_prompts textoff` (pixray.py:887-915, 1732): the package ships the reference's table rows for
-    the towers it implements, value for value (checked against /root/reference when present), resolved like the reference
+    the towers it implements, value for value (against the reference table's row digests, tests/golden), resolved like the reference
     resolves a bare name; a tower without a row is skipped with the reference's warning"""
     import json
     from pixray_amd import api
     t = api.load_vector_table("textoff")
     assert set(t) == {"RN50", "RN101", "RN50x4", "ViT-B/32", "ViT-B/16"}
     assert len(t["ViT-B/32"]) == 1 and len(t["ViT-B/32"][0]) == 512 and len(t["RN50x4"][0]) == 640
-    src = "/root/reference/vectors/textoff.json"
-    if os.path.exists(src):
-        with open(src) as f:
-            ref = json.load(f)
-        for k in t:
-            assert t[k] == ref[k]
+    d = np.load(os.path.join(HERE, "golden", "reference_live_golden.npz"))      # the reference table's row digests
+    ref = dict(zip(d["textoff_keys"].tolist(), d["textoff_sha256"].tolist()))
+    for k in t:
+        assert hashlib.sha256(json.dumps(t[k]).encode()).hexdigest() == ref[k], k
     assert api.WORKLOADS["cfg1"]["vector_prompts"] == ("textoff",) and api.WORKLOADS["cfg3"]["vector_prompts"] == ()
     from oracle import step_ref
     from pixray_amd import weights

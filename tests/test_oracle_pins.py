@@ -450,25 +450,31 @@ def test_fft_drawer_plugin_on_the_cpu_vs_the_explicit_dft_oracle(size):
 
 
 # ------------------------------------------------------------------------------------------------ VGG16 extractor (StyleLoss)
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="needs the reference checkout")
 def test_vgg_oracle_vs_the_reference_extractor_class_run_live():
     """`oracle/vgg_ref.forward` against the reference's OWN `Vgg16_Extractor.forward` (Losses/StyleLoss.py:24-47, pulled out by
-    AST and executed) wrapped around an nn.Sequential laid out like torchvision's vgg16().features: the same ten maps, bit for
-    bit in both input spaces -- the capture indices [1,3,6,8,11,13,15,22,29] and the ImageNet normalisation are the
-    reference's, executed, not restated"""
-    import _refextract as rx
+    AST and run by tests/golden/make_golden.py) wrapped around an nn.Sequential laid out like torchvision's vgg16().features:
+    the same ten maps in both input spaces -- shapes, float64 sums and sums of squares, and the values at 512 seeded positions
+    of every map (reference_live_golden.npz) -- so the capture indices [1,3,6,8,11,13,15,22,29] and the ImageNet
+    normalisation are the reference's, executed, not restated"""
     from oracle import vgg_ref
+    d = np.load(os.path.join(HERE, "golden", "reference_live_golden.npz"))
     params = weights.synthetic_vgg16_params(0)
-    ns = rx.styleloss_ns()
-    x = torch.rand(2, 3, 48, 40, generator=torch.Generator().manual_seed(2)) * 2 - 1
+    x = torch.from_numpy(d["vgg_x"])
     for space in ("uniform", "vgg"):
-        ref = rx.reference_vgg_extractor(ns, params, space)(x.clone())
         got = vgg_ref.forward(params, x.clone(), space)
-        assert len(ref) == len(got) == 10
-        for i, (r, o) in enumerate(zip(ref, got)):
-            assert r.shape == o.shape, (space, i)
+        assert int(d[f"vgg_{space}_count"]) == len(got) == 10
+        for i, o in enumerate(got):
+            k = f"vgg_{space}_{i}"
+            assert tuple(o.shape) == tuple(d[k + "_shape"]), (space, i)
+            r_sum, r_sq, r_max = d[k + "_stats"]
             # map 0 is the normalised input; the reference's in-place ReLUs overwrite the captured conv outputs, as here
-            assert float((r - o).abs().max()) <= 1e-6 * max(1.0, float(r.abs().max())), (space, i)
+            tol = 1e-6 * max(1.0, float(r_max))
+            sample = o.reshape(-1)[torch.from_numpy(d[k + "_index"])]
+            assert float((sample - torch.from_numpy(d[k + "_sample"])).abs().max()) <= tol, (space, i)
+            o64 = o.double()
+            assert abs(float(o64.abs().max()) - r_max) <= tol, (space, i)
+            assert abs(float(o64.sum()) - r_sum) <= tol * o.numel(), (space, i)
+            assert abs(float((o64 * o64).sum()) - r_sq) <= 2 * tol * float(o64.abs().sum()) + 1e-9 * r_sq, (space, i)
 
 
 # ------------------------------------------------------------------------------------------------ what the teacher-forced image rests on

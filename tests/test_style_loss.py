@@ -1,7 +1,8 @@
 """CPU tests (no GPU) of the StyleLoss plugin's STROTSS arithmetic (pixray_amd/style_loss.py) against the golden vectors
 produced by the REFERENCE'S OWN code (tests/golden/styleloss_golden.npz, made by tests/golden/make_golden.py from
-Losses/StyleLoss.py) -- and, when /root/reference is present, against that code run live.  The VGG16 features come from the
-CPU oracle here (test infrastructure); the HIP extractor is tested in test_path_gpu.py / test_e2e_gpu.py."""
+Losses/StyleLoss.py) -- and against more outputs of that code at other canvas sizes (reference_live_golden.npz).  The VGG16
+features come from the CPU oracle here (test infrastructure); the HIP extractor is tested in test_path_gpu.py /
+test_e2e_gpu.py."""
 import argparse
 import os
 import sys
@@ -16,12 +17,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
-import _refextract as rx  # noqa: E402
 from oracle import vgg_ref  # noqa: E402
 from pixray_amd import style_loss as sl  # noqa: E402
 from pixray_amd import weights  # noqa: E402
 
 GOLD = np.load(os.path.join(HERE, "golden", "styleloss_golden.npz"))
+LIVE = np.load(os.path.join(HERE, "golden", "reference_live_golden.npz"))
 
 
 class OracleExtractor:
@@ -63,29 +64,29 @@ def test_hypercolumn_sampling_matches_the_reference_golden(extractor):
     assert float((cols - torch.from_numpy(GOLD["hyper"])).abs().max()) < 1e-5
 
 
-@pytest.mark.skipif(not rx.available(), reason="/root/reference not present (GPU box)")
 @pytest.mark.parametrize("hw", [(132, 140), (77, 131)], ids=lambda t: f"{t[0]}x{t[1]}")
-def test_strotss_against_the_reference_code_run_live(extractor, hw):
-    """other sizes and seeds than the fixtures, the reference's functions executed here: three scales on an even canvas, and an
-    odd non-square one (every max pool floors an odd side, the sampling grid is ragged, the coarsest maps are 4 x 8) -- the sizes
-    `draw_plan` has to predict from the canvas shape alone"""
-    ns = rx.styleloss_ns()
-    ref_ex = rx.reference_vgg_extractor(ns, weights.synthetic_vgg16_params(0))
+def test_strotss_matches_the_reference_at_more_canvas_sizes(extractor, hw):
+    """other sizes and seeds than the fixtures above, against the reference's functions as run by tests/golden/make_golden.py
+    (reference_live_golden.npz): three scales on an even canvas, and an odd non-square one (every max pool floors an odd side,
+    the sampling grid is ragged, the coarsest maps are 4 x 8) -- the sizes `draw_plan` has to predict from the canvas shape alone.
+    The loss is held to the same 1e-5 as the fixtures.  The gradient runs through nearest-neighbour matches of noise features
+    and is piecewise: moving the canvas by 1e-6 (relative) moves it by up to 3e-3 in rel-L2, so a gradient recorded on one
+    machine's CPU is compared at 1e-2"""
+    k = f"strotss_{hw[0]}x{hw[1]}"
     g = torch.Generator().manual_seed(31)
     img = torch.rand(1, 3, *hw, generator=g)
     style = torch.rand(1, 3, *hw, generator=g)
-    a = img.clone().requires_grad_(True)
+    assert np.allclose([float(img.double().sum()), float(style.double().sum())], LIVE[k + "_input_sums"], rtol=1e-12, atol=0)
     b = img.clone().requires_grad_(True)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         np.random.seed(77)
-        la = ns["strotss_loss"](a, style, 8.0, extractor=ref_ex)
-        np.random.seed(77)
         lb = sl.strotss_loss(b, style, 8.0, extractor=extractor)
-    (ga,) = torch.autograd.grad(la, a)
+    la = float(LIVE[k + "_loss"])
+    ga = torch.from_numpy(LIVE[k + "_grad"])
     (gb,) = torch.autograd.grad(lb, b)
-    assert abs(float(la) - float(lb)) < 1e-5 * max(1.0, abs(float(la)))
-    assert float((ga - gb).norm() / ga.norm()) < 1e-4
+    assert abs(la - float(lb)) < 1e-5 * max(1.0, abs(la))
+    assert float((ga - gb).norm() / ga.norm()) < 1e-2
 
 
 def test_plugin_settings_skip_schedule_and_style_file(tmp_path, extractor):
