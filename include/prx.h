@@ -494,6 +494,48 @@ int prx_allreduce(prx_comm* c, void* data, size_t n_words, int op, prx_stream_t 
 int prx_comm_status(prx_comm* c);
 void prx_comm_destroy(prx_comm* c);
 
+/* --- built-in custom losses and filters (pixray Losses/, filters/): csrc/plugin_losses.hip, plugin_filters.hip.
+ * fp32 tensors, contiguous NCHW.  Every loss scalar is reduced in a fixed order: `partials` is a scratch of
+ * 4 * 1024 doubles, `ticket` one device word that is zero on entry and zero again on exit (as prx_prompt_loss_fwd_bwd's).
+ * `gout` / `gloss` are the incoming gradients of the loss scalars, read on the device.
+ * saturation: x [n][3][hw]; stats (4 doubles) saved for the backward.  loss = -(std_rggb + 0.3 mean_rggb) * w / 10 */
+int prx_saturation_fwd(const float* x, int n, int hw, float weight, double* partials, double* stats, float* loss, unsigned* ticket,
+                       prx_stream_t s);
+int prx_saturation_bwd(const float* x, int n, int hw, float weight, const double* stats, const float* gout, float* grad, prx_stream_t s);
+/* symmetry: MSE(x, flip_W(x)) * w over planes x h x w; grad = d loss / dx */
+int prx_symmetry_fwd_bwd(const float* x, int planes, int h, int w, float weight, double* partials, float* grad, float* loss,
+                         unsigned* ticket, prx_stream_t s);
+/* edge: x [planes = 3k][h][w] against colour (r, g, b): margin bands (pixels) weighted by inv_* = 1 / band elements (0 = band
+ * off), inv_all = global weight / all elements; everything times edge_weight */
+int prx_edge_fwd_bwd(const float* x, int planes, int h, int w, float r, float g, float b, int left, int right, int upper, int lower,
+                     float inv_l, float inv_r, float inv_u, float inv_d, float inv_all, float edge_weight, double* partials, float* grad,
+                     float* loss, unsigned* ticket, prx_stream_t s);
+/* palette: x [n][3][hw], palette [np <= 256][3]; loss = scale * sum over pixels of |pixel - nearest entry| */
+int prx_palette_fwd_bwd(const float* x, int n, int hw, const float* palette, int np, float scale, double* partials, float* grad,
+                        float* loss, unsigned* ticket, prx_stream_t s);
+/* smoothness: x [n][3][h][w] seen as [n*h][w][3]; type 0 default, 1 clipped, 2 log; edge_order 1 | 2; tfac [n*h*w] saved */
+int prx_smoothness_fwd(const float* x, int n, int h, int w, int type, int edge_order, float spacing, float weight, double* partials,
+                       float* tfac, float* loss, unsigned* ticket, prx_stream_t s);
+int prx_smoothness_bwd(const float* tfac, const float* x, int n, int h, int w, int edge_order, float spacing, float weight,
+                       const float* gout, float* grad, prx_stream_t s);
+/* depthwise valid k x k blur (k <= 33): y [planes][h-k+1][w-k+1]; the backward takes the input's h, w */
+int prx_blur_fwd(const float* x, int planes, int h, int w, const float* taps, int k, float* y, prx_stream_t s);
+int prx_blur_bwd(const float* gy, int planes, int h, int w, const float* taps, int k, float* gx, prx_stream_t s);
+/* lookup filter: x [b][c = 3 | 4][hw] -> out (straight-through nearest palette colour; alpha copied), lgrad = d loss / dx,
+ * loss = (beta + 1) * mean((q - x)^2) over the colour channels */
+int prx_color_lookup_fwd(const float* x, int b, int c, int hw, const float* palette, int np, float beta, double* partials, float* out,
+                         float* lgrad, float* loss, unsigned* ticket, prx_stream_t s);
+/* tiler / wallpaper filter: shifts = device {rand_h, rand_w}; em = --wallpaper_edge_match (0 off, else >= 2).
+ * out [planes][2h][w] in shift mode, else [planes][h - 2 th][w - 2 tw] with the edge-match trims; loss = the seam term */
+#define PRX_WALL_BOTH 0
+#define PRX_WALL_HORIZONTAL 1
+#define PRX_WALL_VERTICAL 2
+#define PRX_WALL_SHIFT 3
+int prx_wallpaper_fwd(const float* x, int planes, int h, int w, int mode, int em, const int* shifts, double* partials, float* out,
+                      float* loss, unsigned* ticket, prx_stream_t s);
+int prx_wallpaper_bwd(const float* x, const float* gout, int planes, int h, int w, int mode, int em, const int* shifts,
+                      const float* gloss, float* grad, prx_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

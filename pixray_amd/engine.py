@@ -450,6 +450,10 @@ class Session:
         for t in self.custom_losses:
             if getattr(t["loss"], "graph_capturable", False) and hasattr(t["loss"], "host_prep"):
                 t["loss"].host_prep(self.args, it)
+        # filters with host-drawn inputs (tiler / wallpaper shifts) likewise, once static buffers are on
+        for f in self.filters:
+            if getattr(f["filter"], "graph_capturable", False) and hasattr(f["filter"], "host_prep"):
+                f["filter"].host_prep(self.args, it)
         self._host_ready = True
 
     def _device_step(self):
@@ -556,6 +560,9 @@ class Session:
         for t in self.custom_losses:
             if hasattr(t["loss"], "enable_static_buffers"):
                 t["loss"].enable_static_buffers(dev)
+        for f in self.filters:
+            if hasattr(f["filter"], "enable_static_buffers"):
+                f["filter"].enable_static_buffers(dev)
         self.opts = opts
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))

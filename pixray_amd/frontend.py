@@ -13,8 +13,8 @@ pixray drives this package unchanged:
     pixray.reset_settings(); pixray.add_settings(prompts="...", quality="draft", outdir="out"); settings = pixray.apply_settings()
     pixray.do_init(settings); pixray.do_run(settings)
 
-Not carried over (outside SURVEY.md section 8): the notebook display calls, `--palette` / `--transparent_weight` parsing
-helpers of util.py that belong to PaletteLoss, the SLIP perceptors, ffmpeg video / gif assembly (the frame files are written;
+Not carried over (outside SURVEY.md section 8): the notebook display calls, the `--transparent_weight`
+parsing helper of util.py, the SLIP perceptors, ffmpeg video / gif assembly (the frame files are written;
 `make_video` / animation gif need ffmpeg and are skipped with a message when it is absent), the per-frame target-image prompt
 table of the animation mode (`pmsTargetTable`, pixray.py:772-795: target images score every frame here), the vdiff drawer (its
 source is not in the reference checkout).
@@ -41,6 +41,7 @@ import torch
 
 from . import plugins
 from .settings import get_file_path, get_learning_rate_drops, parse_unit, split_pipes
+from .palette import palette_from_string
 from .prompt import parse_prompt
 
 VERSION = "pixray_amd-0.4"
@@ -327,6 +328,8 @@ def process_args(parser: argparse.ArgumentParser, namespace=None, argv=None, run
         args.vector_prompts = [p.strip() for p in vp.split("|")] if isinstance(vp, str) else list(vp)
     else:
         args.vector_prompts = []
+    if getattr(args, "palette", None) is not None and isinstance(args.palette, str):        # pixray.py:1964-1965
+        args.palette = palette_from_string(args.palette)
     if args.overlay_image is not None and args.overlay_every <= 0:
         args.overlay_image = None
     args.clip_models = [m.strip() for m in args.clip_models.split(",")] if isinstance(args.clip_models, str) else list(args.clip_models)

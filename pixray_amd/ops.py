@@ -812,3 +812,282 @@ class _FftSynthFn(torch.autograd.Function):
 def fft_synth(params: torch.Tensor, handle: FftDrawerHandle, contrast: float = 0.9) -> torch.Tensor:
     """differentiable w.r.t. `params`; a backward differentiates the handle's LAST synth (one synth per backward, as the loop does)"""
     return _FftSynthFn.apply(params, handle, contrast)
+
+
+# --------------------------------------------------------------------------------------- built-in losses and filters
+# (csrc/plugin_losses.hip, plugin_filters.hip).  Every loss scalar comes out of its launch through the same fixed-order
+# "partials, then the last workgroup" reduction as the Prompt loss: `partials` is a scratch of 1024 rows x 4 doubles.
+_PLUGIN_PARTIALS = {}
+PALETTE_MAX = 256
+
+
+def _partials(device):
+    key = (str(device), _stream())
+    t = _PLUGIN_PARTIALS.get(key)
+    if t is None:
+        t = _PLUGIN_PARTIALS[key] = torch.empty(1024 * 4, dtype=torch.float64, device=device)
+    return t
+
+
+def _f32_nchw(x, what):
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise PrxError(f"{what}: expected an fp32 [N, C, H, W] tensor, got {tuple(x.shape)} {x.dtype}")
+    return x.contiguous()
+
+
+def _palette_dev(palette, device):
+    p = torch.as_tensor(palette, dtype=torch.float32, device=device).reshape(-1, 3).contiguous()
+    if not 1 <= p.shape[0] <= PALETTE_MAX:
+        raise PrxError(f"palette of {p.shape[0]} colours: 1 .. {PALETTE_MAX} are supported")
+    return p
+
+
+class _SaturationFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cutouts, weight):
+        _need_cuda(cutouts)
+        x = _f32_nchw(cutouts, "saturation_loss")
+        n, c, h, w = x.shape
+        assert c == 3
+        stats = torch.empty(4, dtype=torch.float64, device=x.device)
+        loss = torch.empty((), device=x.device)
+        call("prx_saturation_fwd", x, n, h * w, float(weight), _partials(x.device), stats, loss, _ticket(x.device), _stream())
+        ctx.save_for_backward(x, stats)
+        ctx.weight = float(weight)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        x, stats = ctx.saved_tensors
+        n, _, h, w = x.shape
+        grad = torch.empty_like(x)
+        call("prx_saturation_bwd", x, n, h * w, ctx.weight, stats, g.contiguous(), grad, _stream())
+        return grad, None
+
+
+def saturation_loss(cutouts, weight=1.0):
+    """SaturationLoss of ONE cutout batch [n, 3, S, S]: -(std_rggb + 0.3 mean_rggb) * weight / 10"""
+    return _SaturationFn.apply(cutouts, weight)
+
+
+class _LocalGradLossFn(torch.autograd.Function):
+    """a loss whose kernel wrote d loss / d input in the forward launch: the backward scales it"""
+    @staticmethod
+    def forward(ctx, x, launch):
+        loss, grad = launch()
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None
+
+
+def symmetry_loss(out, weight=1.0):
+    """SymmetryLoss: MSE(out, flip_W(out)) * weight"""
+    _need_cuda(out)
+    x = _f32_nchw(out, "symmetry_loss")
+    n, c, h, w = x.shape
+
+    def launch():
+        grad, loss = torch.empty_like(x), torch.empty((), device=x.device)
+        call("prx_symmetry_fwd_bwd", x, n * c, h, w, float(weight), _partials(x.device), grad, loss, _ticket(x.device), _stream())
+        return loss, grad
+    return _LocalGradLossFn.apply(out, launch)
+
+
+def edge_loss(out, color, margins, edge_weight, global_weight):
+    """EdgeLoss (flat colour, no mask image): `margins` = (left, right, upper, lower) in PIXELS"""
+    _need_cuda(out)
+    x = _f32_nchw(out, "edge_loss")
+    n, c, h, w = x.shape
+    if c != 3:
+        raise PrxError("edge_loss: expected 3 channels")
+    left, right, upper, lower = (int(m) for m in margins)
+    inner = max(0, (w - right) - left)
+    bands = (n * c * h * max(0, min(left, w)), n * c * h * max(0, min(right, w)), n * c * max(0, min(upper, h)) * inner,
+             n * c * max(0, min(lower, h)) * inner)
+    for m, cnt in zip((left, right, upper, lower), bands):
+        if m != 0 and cnt == 0:
+            raise PrxError(f"edge_loss: margins {margins} leave an empty band on a {h} x {w} image")
+    inv = [1.0 / cnt if m != 0 else 0.0 for m, cnt in zip((left, right, upper, lower), bands)]
+    inv_all = float(global_weight) / x.numel() if global_weight else 0.0
+
+    def launch():
+        grad, loss = torch.empty_like(x), torch.empty((), device=x.device)
+        call("prx_edge_fwd_bwd", x, n * c, h, w, float(color[0]), float(color[1]), float(color[2]), left, right, upper, lower,
+             *[float(v) for v in inv], inv_all, float(edge_weight), _partials(x.device), grad, loss, _ticket(x.device), _stream())
+        return loss, grad
+    return _LocalGradLossFn.apply(out, launch)
+
+
+def palette_loss(cutouts, palette, weight=1.0):
+    """PaletteLoss of ONE cutout batch: mean over pixels of |pixel - nearest palette colour| * n * weight / 10.  `palette`: a
+    [k, 3] device tensor (or anything torch.as_tensor takes)"""
+    _need_cuda(cutouts)
+    x = _f32_nchw(cutouts, "palette_loss")
+    n, c, h, w = x.shape
+    pal = palette if isinstance(palette, torch.Tensor) and palette.device == x.device and palette.dtype == torch.float32 \
+        and palette.is_contiguous() else _palette_dev(palette, x.device)
+    if not 1 <= pal.shape[0] <= PALETTE_MAX:
+        raise PrxError(f"palette of {pal.shape[0]} colours: 1 .. {PALETTE_MAX} are supported")
+    scale = n * float(weight) / 10.0 / (n * h * w)
+
+    def launch():
+        grad, loss = torch.empty_like(x), torch.empty((), device=x.device)
+        call("prx_palette_fwd_bwd", x, n, h * w, pal, pal.shape[0], float(scale), _partials(x.device), grad, loss,
+             _ticket(x.device), _stream())
+        return loss, grad
+    return _LocalGradLossFn.apply(cutouts, launch)
+
+
+SMOOTHNESS_TYPES = {"default": 0, "clipped": 1, "log": 2}
+
+
+class _SmoothnessFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cutouts, weight, type_code, spacing, edge_order):
+        x = cutouts.contiguous()
+        n, _, h, w = x.shape
+        tfac = torch.empty(n * h * w, device=x.device)
+        loss = torch.empty((), device=x.device)
+        call("prx_smoothness_fwd", x, n, h, w, int(type_code), int(edge_order), float(spacing), float(weight), _partials(x.device),
+             tfac, loss, _ticket(x.device), _stream())
+        ctx.save_for_backward(x, tfac)
+        ctx.cfg = (int(edge_order), float(spacing), float(weight))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        x, tfac = ctx.saved_tensors
+        eo, spacing, weight = ctx.cfg
+        n, _, h, w = x.shape
+        grad = torch.empty_like(x)
+        call("prx_smoothness_bwd", tfac, x, n, h, w, eo, spacing, weight, g.contiguous(), grad, _stream())
+        return grad, None, None, None, None
+
+
+class _BlurFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, taps):
+        x = x.contiguous()
+        n, c, h, w = x.shape
+        k = taps.shape[-1]
+        y = torch.empty(n, c, h - k + 1, w - k + 1, device=x.device)
+        call("prx_blur_fwd", x, n * c, h, w, taps, k, y, _stream())
+        ctx.save_for_backward(taps)
+        ctx.hw = (n * c, h, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        (taps,) = ctx.saved_tensors
+        planes, h, w = ctx.hw
+        gx = torch.empty((planes // 3, 3, h, w), device=g.device)
+        call("prx_blur_bwd", g.contiguous(), planes, h, w, taps, taps.shape[-1], gx, _stream())
+        return gx, None
+
+
+def gaussian_taps(kernel_size, std):
+    """the k x k table of pixray's GaussianSmoothing (Losses/SmoothnessLoss.py) for one channel, fp32 on the host: the product
+    of two exp(-((i - mean) / (2 std))^2) profiles, normalised to sum 1"""
+    import math
+    k = int(kernel_size)
+    g = torch.arange(k, dtype=torch.float32)
+    yy, xx = torch.meshgrid(g, g, indexing="ij")
+    kern = 1
+    mean = (kernel_size - 1) / 2
+    for grid in (yy, xx):
+        kern = kern * (1 / (std * math.sqrt(2 * math.pi)) * torch.exp(-((grid - mean) / (2 * std)) ** 2))
+    return kern / torch.sum(kern)
+
+
+def smoothness_loss(cutouts, weight=1.0, type="default", spacing=1, edge_order=1, blur_taps=None):
+    """SmoothnessLoss of ONE cutout batch: mean gradient magnitude over the [n*S, S, 3] view, optionally after the valid-padding
+    Gaussian blur whose k x k table `blur_taps` (a device tensor, gaussian_taps) holds.  Where the magnitude is exactly 0 the
+    backward uses the zero subgradient (the reference's sqrt gives NaN there)."""
+    _need_cuda(cutouts)
+    x = _f32_nchw(cutouts, "smoothness_loss")
+    if type not in SMOOTHNESS_TYPES:
+        raise PrxError(f"smoothness type {type!r}: want one of {sorted(SMOOTHNESS_TYPES)}")
+    if blur_taps is not None:
+        x = _BlurFn.apply(x, blur_taps)
+    return _SmoothnessFn.apply(x, weight, SMOOTHNESS_TYPES[type], spacing, edge_order)
+
+
+class _ColorLookupFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, palette, beta):
+        x = z.contiguous()
+        b, c, h, w = x.shape
+        out, lgrad = torch.empty_like(x), torch.empty_like(x)
+        loss = torch.empty((), device=x.device)
+        call("prx_color_lookup_fwd", x, b, c, h * w, palette, palette.shape[0], float(beta), _partials(x.device), out, lgrad, loss,
+             _ticket(x.device), _stream())
+        ctx.save_for_backward(lgrad)
+        return out, loss
+
+    @staticmethod
+    def backward(ctx, gout, gloss):
+        (lgrad,) = ctx.saved_tensors
+        return torch.addcmul(gout, lgrad, gloss), None, None
+
+
+def color_lookup(z, palette, beta):
+    """ColorLookup filter: (nearest palette colour with a straight-through gradient, beta * commitment + codebook loss).
+    z [B, 3 | 4, H, W] (alpha passes through); `palette` a [k <= 256, 3] fp32 device tensor"""
+    _need_cuda(z)
+    x = _f32_nchw(z, "color_lookup")
+    if x.shape[1] not in (3, 4):
+        raise PrxError("color_lookup: 3 or 4 channels")
+    return _ColorLookupFn.apply(x, palette, beta)
+
+
+WALLPAPER_MODES = {None: 0, "none": 0, "tiler": 0, "horizontal": 1, "vertical": 2, "shift": 3}
+
+
+class _WallpaperFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img, shifts, mode, em):
+        x = img.contiguous()
+        b, c, h, w = x.shape
+        if mode == 3:
+            ho, wo = 2 * h, w
+        else:
+            th = em // 2 if em and mode in (0, 2) else 0
+            tw = em // 2 if em and mode in (0, 1) else 0
+            ho, wo = h - 2 * th, w - 2 * tw
+        out = torch.empty(b, c, ho, wo, device=x.device)
+        loss = torch.empty((), device=x.device)
+        call("prx_wallpaper_fwd", x, b * c, h, w, mode, em, shifts, _partials(x.device), out, loss, _ticket(x.device), _stream())
+        ctx.save_for_backward(x, shifts)
+        ctx.cfg = (mode, em)
+        return out, loss
+
+    @staticmethod
+    def backward(ctx, gout, gloss):
+        x, shifts = ctx.saved_tensors
+        mode, em = ctx.cfg
+        b, c, h, w = x.shape
+        grad = torch.empty_like(x)
+        call("prx_wallpaper_bwd", x, gout.contiguous(), b * c, h, w, mode, em, shifts, gloss.contiguous(), grad, _stream())
+        return grad, None, None, None
+
+
+def wallpaper(img, shifts, mode="none", edge_match=0):
+    """TilerFilter / WallpaperFilter: -> (image, seam loss).  `shifts`: a 2-element int32 device tensor {rand_h, rand_w}, read by
+    the kernels (a replayed graph sees what was staged there last); mode None / "none" / "tiler" rolls both axes"""
+    _need_cuda(img)
+    x = _f32_nchw(img, "wallpaper")
+    if mode not in WALLPAPER_MODES:
+        raise PrxError(f"wallpaper type {mode!r}: want one of none, horizontal, vertical, shift")
+    m = WALLPAPER_MODES[mode]
+    em = int(edge_match or 0)
+    if m == 3:
+        em = 0                           # the reference's shift branch ignores --wallpaper_edge_match
+    if em == 1 or em < 0:
+        raise PrxError(f"--wallpaper_edge_match {edge_match}: 0 (off) or >= 2 (the trim is edge_match // 2 on each side)")
+    if shifts.dtype != torch.int32 or shifts.numel() != 2:
+        raise PrxError("wallpaper: shifts must be a 2-element int32 device tensor")
+    return _WallpaperFn.apply(x, shifts, m, em)

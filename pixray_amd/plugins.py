@@ -8,13 +8,16 @@ contributes its globals (`add_globals(args) -> dict`).  The result is the list o
 as `custom_losses=` and the `lossGlobals` dict handed to every `get_loss` call.
 
 `class_table` maps `--drawer` names to drawer classes (the HIP VQGAN drawer, the fft spectrum drawer, and the nearest-
-upsampled pixel grid that stands in for the reference's `fast_pixel`); `filters_class_table` starts empty (the reference's
-filters are plain torch modules and register themselves through `add_custom_filter`).
-
-Only `StyleLoss` ships with this package (the other reference losses are plain torch code and drop in unchanged through
-`add_custom_loss`; see tests/test_host_logic.py::test_unmodified_reference_plugins_drop_in)."""
+upsampled pixel grid that stands in for the reference's `fast_pixel`); `filters_class_table` holds the reference's three
+filters (`lookup`, `tiler`, `wallpaper`: builtin_filters.py) and `loss_class_table` its losses (`style`: style_loss.py;
+`palette`, `saturation`, `symmetry`, `smoothness`, `edge`: builtin_losses.py), all on HIP kernels.  `resmem` and
+`aesthetic` are registered so that asking for them says why they are unavailable (their model weights are not shipped).
+Further plugins register through `add_custom_filter` / `add_custom_loss`; the reference's own plain-torch plugin files drop
+in unchanged that way (see tests/test_host_logic.py::test_unmodified_reference_plugins_drop_in)."""
 from typing import Dict, List, Tuple
 
+from .builtin_filters import BUILTIN_FILTERS
+from .builtin_losses import BUILTIN_LOSSES, UNAVAILABLE_LOSSES
 from .fft_drawer import FftDrawer
 from .interfaces import DrawingInterface, FilterInterface, LossInterface
 from .pixel_grid_drawer import PixelGridDrawer
@@ -23,8 +26,8 @@ from .style_loss import StyleLoss
 from .vqgan_drawer import VqganDrawer
 
 class_table: Dict[str, type] = {"vqgan": VqganDrawer, "fft": FftDrawer, "fast_pixel": PixelGridDrawer}
-filters_class_table: Dict[str, type] = {}
-loss_class_table: Dict[str, type] = {"style": StyleLoss}
+filters_class_table: Dict[str, type] = dict(BUILTIN_FILTERS)
+loss_class_table: Dict[str, type] = {**BUILTIN_LOSSES, "style": StyleLoss, **UNAVAILABLE_LOSSES}
 
 
 def add_custom_drawer(name: str, customdrawer: type) -> None:
@@ -93,6 +96,8 @@ def setup_custom_losses(spec, args, device=None) -> Tuple[List[dict], dict, obje
             else:
                 name_part, instance_args = chunk, []
             loss_name, weight, _stop = parse_prompt(name_part)
+            if loss_name not in loss_class_table:
+                raise KeyError(f"Requested custom loss not found, aborting: {loss_name} (known: {', '.join(sorted(loss_class_table))})")
             cls = loss_class_table[loss_name]
             try:
                 inst = cls(device=device)
