@@ -536,6 +536,24 @@ int prx_wallpaper_fwd(const float* x, int planes, int h, int w, int mode, int em
 int prx_wallpaper_bwd(const float* x, const float* gout, int planes, int h, int w, int mode, int em, const int* shifts,
                       const float* gloss, float* grad, prx_stream_t s);
 
+/* --- pixel drawer (pixray pixeldrawer.py): csrc/pixel_raster.hip.  A w x h canvas of filled polygons, composited in index order
+ * ("over", nonzero winding, 2 x 2 jittered samples per pixel; conventions in INTEGRATION.md).
+ * verts [n][PRX_PIXEL_MAX_VERTS][2] (padded), nverts [n], colors [n][4] RGBA.  The canvas is cut into PRX_PIXEL_TILE-pixel
+ * square tiles, row-major, ceil(w / 16) per row: tile t lists the shapes that may cover it, ascending, in
+ * tile_shapes[tile_start[t] .. tile_start[t + 1]).  seed = one device word (the iteration).
+ * forward: out [4][h][w] (RGBA planes); ids [h][w][4] int32 = the topmost shape per sample (-1: none), or NULL.
+ * backward: gout [4][h][w] -> grad [n][4] = d loss / d colors; partials = scratch of 4 doubles per tile_shapes entry;
+ * shape k's entries (indices into tile_shapes, in tile order) are shape_entries[shape_start[k] .. shape_start[k + 1]).
+ * sample offsets: uv [h][w][4][2] = the jitter (u, v) of sample 2 sy + sx of every pixel for the seed in `seed`. */
+#define PRX_PIXEL_TILE 16
+#define PRX_PIXEL_MAX_VERTS 8
+int prx_pixel_raster_fwd(const float* verts, const int* nverts, const float* colors, const int* tile_start, const int* tile_shapes,
+                         int w, int h, const int* seed, float* out, int* ids, prx_stream_t s);
+int prx_pixel_raster_bwd(const float* verts, const int* nverts, const float* colors, const int* tile_start, const int* tile_shapes,
+                         int w, int h, const int* seed, const float* gout, double* partials, const int* shape_start,
+                         const int* shape_entries, int n_shapes, float* grad, prx_stream_t s);
+int prx_pixel_sample_offsets(int w, int h, const int* seed, float* uv, prx_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -454,6 +454,9 @@ class Session:
         for f in self.filters:
             if getattr(f["filter"], "graph_capturable", False) and hasattr(f["filter"], "host_prep"):
                 f["filter"].host_prep(self.args, it)
+        # and a drawer with host-staged inputs (PixelDrawer's jitter seed)
+        if getattr(self.drawer, "graph_capturable", False) and hasattr(self.drawer, "host_prep"):
+            self.drawer.host_prep(self.args, it)
         self._host_ready = True
 
     def _device_step(self):
@@ -563,6 +566,8 @@ class Session:
         for f in self.filters:
             if hasattr(f["filter"], "enable_static_buffers"):
                 f["filter"].enable_static_buffers(dev)
+        if hasattr(self.drawer, "enable_static_buffers"):
+            self.drawer.enable_static_buffers(dev)
         self.opts = opts
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))

@@ -1091,3 +1091,117 @@ def wallpaper(img, shifts, mode="none", edge_match=0):
     if shifts.dtype != torch.int32 or shifts.numel() != 2:
         raise PrxError("wallpaper: shifts must be a 2-element int32 device tensor")
     return _WallpaperFn.apply(x, shifts, m, em)
+
+
+# --------------------------------------------------------------------------------------- pixel drawer (csrc/pixel_raster.hip)
+PIXEL_TILE, PIXEL_MAX_VERTS = 16, 8
+
+
+class PixelRasterGeometry:
+    """Fixed polygons on a width x height canvas as the rasteriser reads them: vertices padded to 8, vertex counts, the per-tile
+    shape lists (16 x 16-pixel tiles, row-major; the shapes whose bounding box, grown by 1e-3 px, meets the tile, ascending) and
+    the inverse map (each shape's entries in those lists, in tile order).  `verts`: float32 [n, k <= 8, 2]."""
+
+    def __init__(self, verts, width: int, height: int, device):
+        import numpy as np
+        v = np.asarray(verts, dtype=np.float32)
+        if v.ndim != 3 or v.shape[2] != 2 or not 3 <= v.shape[1] <= PIXEL_MAX_VERTS or v.shape[0] < 1:
+            raise PrxError(f"pixel raster: vertices must be [n >= 1, 3 .. {PIXEL_MAX_VERTS}, 2], got {v.shape}")
+        n, k = v.shape[0], v.shape[1]
+        self.width, self.height, self.n_shapes = int(width), int(height), n
+        self.tiles_x = (self.width + PIXEL_TILE - 1) // PIXEL_TILE
+        self.tiles_y = (self.height + PIXEL_TILE - 1) // PIXEL_TILE
+        pad = np.zeros((n, PIXEL_MAX_VERTS, 2), dtype=np.float32)
+        pad[:, :k] = v
+        lo = v.astype(np.float64).min(axis=1) - 1e-3
+        hi = v.astype(np.float64).max(axis=1) + 1e-3
+        on = (hi[:, 0] >= 0) & (hi[:, 1] >= 0) & (lo[:, 0] < self.width) & (lo[:, 1] < self.height)
+        tx0 = np.clip(np.floor(lo[:, 0] / PIXEL_TILE), 0, self.tiles_x - 1).astype(np.int64)
+        tx1 = np.clip(np.floor(hi[:, 0] / PIXEL_TILE), 0, self.tiles_x - 1).astype(np.int64)
+        ty0 = np.clip(np.floor(lo[:, 1] / PIXEL_TILE), 0, self.tiles_y - 1).astype(np.int64)
+        ty1 = np.clip(np.floor(hi[:, 1] / PIXEL_TILE), 0, self.tiles_y - 1).astype(np.int64)
+        nx = tx1 - tx0 + 1
+        cnt = np.where(on, nx * (ty1 - ty0 + 1), 0)
+        shape_start = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+        total = int(shape_start[-1])
+        shape_of = np.repeat(np.arange(n, dtype=np.int64), cnt)
+        local = np.arange(total, dtype=np.int64) - np.repeat(shape_start[:-1], cnt)
+        tile = (ty0[shape_of] + local // nx[shape_of]) * self.tiles_x + tx0[shape_of] + local % nx[shape_of]
+        order = np.lexsort((shape_of, tile))                 # by tile, then by shape: the per-tile lists, ascending
+        entry_of = np.empty(total, dtype=np.int64)
+        entry_of[order] = np.arange(total, dtype=np.int64)   # each (shape, tile) pair's slot in the tile lists
+        tile_start = np.concatenate([[0], np.cumsum(np.bincount(tile, minlength=self.tiles_x * self.tiles_y))])
+        self.n_entries = total
+        as_dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt).to(device)    # noqa: E731
+        self.verts = as_dev(pad, torch.float32)
+        self.nverts = as_dev(np.full(n, k, dtype=np.int32), torch.int32)
+        self.tile_start = as_dev(tile_start, torch.int32)
+        self.tile_shapes = as_dev(shape_of[order], torch.int32)
+        self.shape_start = as_dev(shape_start, torch.int32)
+        self.shape_entries = as_dev(entry_of, torch.int32)
+
+    def _args(self):
+        return (self.verts, self.nverts)
+
+    def _tiles(self):
+        return (self.tile_start, self.tile_shapes, self.width, self.height)
+
+
+def _pixel_seed(seed):
+    if not isinstance(seed, torch.Tensor) or seed.dtype != torch.int32 or seed.numel() != 1:
+        raise PrxError("pixel raster: the seed must be a one-word int32 device tensor")
+    return seed
+
+
+def _pixel_colors(colors, geom):
+    if colors.dtype != torch.float32 or tuple(colors.shape) != (geom.n_shapes, 4):
+        raise PrxError(f"pixel raster: colours must be fp32 [{geom.n_shapes}, 4], got {tuple(colors.shape)} {colors.dtype}")
+    return colors.contiguous()
+
+
+class _PixelRasterFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, colors, geom, seed):
+        c = _pixel_colors(colors, geom)
+        out = torch.empty(1, 4, geom.height, geom.width, device=c.device)
+        call("prx_pixel_raster_fwd", *geom._args(), c, *geom._tiles(), seed, out, None, _stream())
+        ctx.save_for_backward(c, seed)
+        ctx.geom = geom
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        c, seed = ctx.saved_tensors
+        geom = ctx.geom
+        partials = torch.empty(max(geom.n_entries, 1) * 4, dtype=torch.float64, device=c.device)
+        grad = torch.empty_like(c)
+        call("prx_pixel_raster_bwd", *geom._args(), c, *geom._tiles(), seed, g.contiguous(), partials, geom.shape_start,
+             geom.shape_entries, geom.n_shapes, grad, _stream())
+        return grad, None, None
+
+
+def pixel_raster(colors, geom: PixelRasterGeometry, seed):
+    """The pixel drawer's image [1, 4, H, W] (RGBA) of the shapes in `geom` filled with `colors` [n, 4], differentiable w.r.t.
+    `colors`.  `seed`: a one-word int32 device tensor holding the jitter seed, read by the kernels (a replayed graph sees what was
+    staged there last)."""
+    _need_cuda(colors, seed)
+    return _PixelRasterFn.apply(colors, geom, _pixel_seed(seed))
+
+
+@torch.no_grad()
+def pixel_raster_ids(colors, geom: PixelRasterGeometry, seed):
+    """diagnostic: (image [1, 4, H, W], topmost shape id per sample [H, W, 4] int32, -1 where no shape covers the sample)"""
+    _need_cuda(colors, seed)
+    c = _pixel_colors(colors, geom)
+    out = torch.empty(1, 4, geom.height, geom.width, device=c.device)
+    ids = torch.empty(geom.height, geom.width, 4, dtype=torch.int32, device=c.device)
+    call("prx_pixel_raster_fwd", *geom._args(), c, *geom._tiles(), _pixel_seed(seed), out, ids, _stream())
+    return out, ids
+
+
+def pixel_sample_offsets(width: int, height: int, seed):
+    """diagnostic: the jitter (u, v) in [0, 1) of sample 2 sy + sx of every pixel, [H, W, 4, 2] fp32, for the seed in `seed`"""
+    _need_cuda(seed)
+    uv = torch.empty(int(height), int(width), 4, 2, device=seed.device)
+    call("prx_pixel_sample_offsets", int(width), int(height), _pixel_seed(seed), uv, _stream())
+    return uv
