@@ -119,8 +119,10 @@ int prx_k_gemm_gn(const prx_gemm_args* g, double* gn_stats, int gn_gs, const flo
  * (csrc/gemmfit_kernel.h FIT_EPI_*, csrc/gemm8p.hip: the descriptor patterns of the two runners, IEEE-half operands) -- tests use it to know that the specialised kernel,
  * not the generic one, produced what they compare. */
 long long prx_gemm_fit_spec_launches(void);
-/* ... and how many ran the row-streaming kernel (csrc/gemmrow.hip: row-major 16-bit problems with K <= 192, N a multiple of 128 or
- * 160, M N >= 5 Mi -- the ModifiedResNet runner's stage-1 / stage-2 1x1 convolutions; PRX_GEMM_ROWK=0 keeps them on the tiled kernels). */
+/* ... and how many ran a row-streaming kernel (csrc/gemmrow.hip: row-major 16-bit products with K <= 640 and N a multiple of 160, 128
+ * or 80 -- only 80 beyond K = 320 --, and implicit 3x3 convolutions with (N, Cin) in {40, 80}^2 or (160, 160); from M N >= 24 Mi output
+ * elements on (PRX_GEMM_ROWK_MIN, override -14) -- the ModifiedResNet runner's stage-1 / stage-2 convolutions; PRX_GEMM_ROWK=0 keeps
+ * them on the tiled kernels). */
 long long prx_gemm_row_launches(void);
 
 /* taming `Normalize` = GroupNorm(32, C, eps 1e-6) (+ swish `nonlinearity`) on an NHWC fp32
@@ -441,10 +443,14 @@ int prx_k_mha_fwd_f32(const float* qkv, float* out, float* lse, int N, int T, in
 int prx_k_mha_bwd_f32(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int N, int T, int C,
                       int heads, prx_stream_t s);
 
-/* tuning override of the tile / split-K heuristic of one context: bm,bn in {(128,128),(128,64),(64,64),(256,128)};
- * (0,0,0) = heuristic.  Negative bm selects a switch: (-1,_,v) XCD-aware tile order 0/1/2; (-2,_,n) LDS pipeline depth;
- * (-3,_,v) 1 = direct-to-LDS v2 kernel (default), 0 = register-staged v1; (-5,_,v) scalar-tap conv gather; (-14,_,n) plan the
- * launches of this context for n compute units (it shares the chip with concurrent chains on other streams; 0 = the device's). */
+/* tuning override of the tile / split-K heuristic of one context: bm,bn a 4-wave tile (128x128, 128x64, 64x64), the 8-phase 256x256
+ * or a fit tile (csrc/gemmfit.hip: 256x128, 160x256, ...; the three shapes both families have mean the 4-wave kernel unless (-12,_,1));
+ * (0,0,0) = heuristic.  Negative bm selects a switch: (-1,_,v) XCD-aware tile order 0 off / 1 on / 2 narrow row-major problems /
+ * 3 every tiled launch; (-2,_,n) LDS pipeline depth (0 = heuristic); (-3,_,v) 1 = direct-to-LDS v2 kernel (default), 0 = register-staged
+ * v1; (-5,_,v) scalar-tap conv gather; (-6,_,n) 256x256 8-phase tiles from n tiles on (0 = never); (-7,_,v) fit tiles; (-8,_,bits)
+ * fit kernel switches (bit 0 staggered wave groups); (-9,_,v) fit tiles for the implicit convolutions too; (-12,_,v) a forced
+ * 128x128 / 128x64 / 64x64 tile means the fit kernel of that shape; (-13,_,i) bisection aid: only the i-th fit convolution since
+ * this call gets its fit tile (-1: all, counted; -2: off); (-14,_,n) row-streaming kernels from n output elements on (0 = 24 Mi). */
 void prx_gemm_tile_override(prx_gemm_ctx* c, int bm, int bn, int splits);
 /* the same per problem shape (tools/gemm_rules.py): mode = a_mode + 2*up + 4*a_is_f32; splits 0 = heuristic; bm = 0 drops
  * the rule, M = 0 drops all rules */
@@ -452,8 +458,17 @@ void prx_gemm_tile_rule(prx_gemm_ctx* c, int M, int N, int K, int mode, int bm, 
 
 /* what the launch planner does with a row-major 16-bit C[M,N] = A[M,K] * Bt[N,K]^T (no launch, no device needed): returns the number of
  * leading rows it gives to the 256 x 256 8-phase kernel -- M (all), 0 (none: 4-wave kernels), or a multiple of 256 in between
- * (whole rounds of 256 tiles on the 8-phase kernel, the remaining rows on the 4-wave kernels).  c may be NULL (default tuning). */
+ * (whole rounds of 256 tiles on the 8-phase kernel, the remaining rows on the 4-wave kernels).  c may be NULL (default tuning); a forced
+ * tile in c, or a tile rule of c for that shape, gives 0: the launch then follows the override (= out[4] of prx_gemm_plan below). */
 int prx_gemm_plan_rows_8phase(prx_gemm_ctx* c, int M, int N, int K);
+/* the launch plan of the product prx_k_gemm(g, ws, ws_bytes, ...) would run with context c (NULL: default tuning; g->ctx is not read)
+ * on a device of n_cu compute units (0: 256), a 16-byte-aligned workspace of ws_bytes assumed; no launch, no device needed.  Returns
+ * 0 or prx_k_gemm's validation error.  out[9]: the kernel family of the first launch (0 register-staged 4-wave, 1 direct-to-LDS
+ * 4-wave, 2 exact-f32 4-wave, 3 fit, 4 8-phase, 5 row-streaming, 6 row-streaming 3x3 convolution), its bm, bn, split-K count;
+ * out[4] the 8-phase row split (as prx_gemm_plan_rows_8phase); out[5..8] the same four for the second launch that plans the rows
+ * after the split on their own (family -1: no second launch).  bn of the row-streaming kernels is their slab width, 80 for the
+ * convolutions (the convention of the timing dump). */
+int prx_gemm_plan(prx_gemm_ctx* c, const prx_gemm_args* g, size_t ws_bytes, int n_cu, int* out);
 
 /* per-launch GEMM timing (HIP events on the launch stream) for bench.py */
 void prx_profile_gemm_enable(prx_gemm_ctx* c, int on);

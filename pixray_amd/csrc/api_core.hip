@@ -90,7 +90,25 @@ prx_gemm_ctx* prx_gemm_ctx_create(void) { return (prx_gemm_ctx*)new GemmCtx(); }
 void prx_gemm_ctx_destroy(prx_gemm_ctx* c) { delete (GemmCtx*)c; }
 void prx_profile_gemm_enable(prx_gemm_ctx* c, int on) { prx_gemm_ctx_profile_enable((GemmCtx*)c, on); }
 void prx_gemm_tile_override(prx_gemm_ctx* c, int bm, int bn, int splits) { prx_gemm_ctx_force_tile((GemmCtx*)c, bm, bn, splits); }
-int prx_gemm_plan_rows_8phase(prx_gemm_ctx* c, int M, int N, int K) { return prx_gemm_plan_rows_8phase_impl((const GemmCtx*)c, M, N, K); }
+int prx_gemm_plan(prx_gemm_ctx* c, const prx_gemm_args* g, size_t ws_bytes, int n_cu, int* out) {
+    GemmDesc d;
+    int r = desc_of(g, d);
+    if (r) return r;
+    GemmPlan p;
+    r = prx_gemm_plan_impl(d, (const GemmCtx*)c, n_cu, ws_bytes, true, &p);
+    if (r) return r;
+    const GemmLaunchPlan& l0 = p.launch[0], l1 = p.n_launch == 2 ? p.launch[1] : GemmLaunchPlan{};
+    const int o[9] = {l0.family, l0.bm, l0.bn, l0.splits, p.rows_8p, p.n_launch == 2 ? (int)l1.family : -1, l1.bm, l1.bn, p.n_launch == 2 ? l1.splits : 0};
+    memcpy(out, o, sizeof o);
+    return 0;
+}
+int prx_gemm_plan_rows_8phase(prx_gemm_ctx* c, int M, int N, int K) {
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    prx_gemm_args g = {};
+    g.a_mode = PRX_A_ROWMAJOR; g.lda = g.ldb = K; g.M = M; g.N = N; g.K = K; g.alpha = 1.f;
+    int out[9];
+    return prx_gemm_plan(c, &g, 0, c ? ((GemmCtx*)c)->n_cu : 0, out) == 0 ? out[4] : 0;
+}
 void prx_gemm_tile_rule(prx_gemm_ctx* c, int M, int N, int K, int mode, int bm, int bn, int splits) {
     prx_gemm_ctx_tile_rule((GemmCtx*)c, M, N, K, mode, bm, bn, splits);
 }

@@ -47,6 +47,9 @@ struct GemmDesc {
     // optional: accumulate GroupNorm statistics of the fp32 output (sum, sum of squares per group of `gn_gs`
     // consecutive columns) into gn_stats[group*2 + {0,1}] (double, pre-zeroed) -- saves the separate stats pass over
     // the conv output.  Needs the vector epilogue (N % 4 == 0, gn_gs % 4 == 0).
+    // Exact mode (f32): only the fp32-operand fit kernels have this epilogue.  A product that plans onto the 4-wave fp32
+    // kernels runs without it, and the norm kernels' statistics pass follows over its output; that pass reads the output as
+    // ONE image (batch 1) of M pixels x N channels, so it needs a dense fp32 output (out_f32, ldc_f32 == N == 32 * gn_gs).
     double* gn_stats = nullptr;
     int gn_gs = 0;
     // ... or, when gnb_x is set, the BACKWARD sums of the GroupNorm(+swish) whose output gradient this GEMM produces
@@ -93,11 +96,34 @@ struct GemmCtx {
     std::mutex mu;                    // guards prof / prof_on (collect may run on another thread than the launches)
     GemmCtx();                        // reads the PRX_* tuning environment variables once
 };
+// The launch plan of one product: which kernel family, tile and split-K, decided on the host without a device (gemm_plan).
+// A product is one launch, or two for the 8-phase row split: rows [0, rows_8p) on the 8-phase kernel, the rest planned as a
+// second product on its own.  The family numbers are the ones prx_gemm_plan (include/prx.h) reports.
+enum GemmFamily { GEMM_TILED_V1 = 0, GEMM_TILED_GLDS = 1, GEMM_TILED_F32 = 2, GEMM_FIT = 3, GEMM_8PHASE = 4, GEMM_ROW = 5, GEMM_ROWCONV = 6 };
+struct GemmLaunchPlan {
+    GemmFamily family = GEMM_TILED_GLDS;
+    int bm = 0, bn = 0;              // the tile (the row kernels: 16 rows x their slab width; 80 for the convolutions, the profile's convention)
+    int splits = 1, kt_per_split = 0;
+    int stages = 2;                  // direct-to-LDS ring depth asked for (the kernel's LDS may cap it)
+    bool c64 = false;                // scalar-tap conv gather
+    int vec_epi = 0, xcd_swizzle = 0, fit_flags = 0;
+    int row_nt = 0, row_ksm = 0;     // row kernels: 16-column tiles per slab and K-step bucket (gemmrow.hip prx_gemmrow_plan)
+};
+struct GemmPlan {
+    GemmLaunchPlan launch[2];
+    int n_launch = 0;
+    int rows_8p = 0;                 // the 8-phase row split: launch[0] covers rows [0, rows_8p) (M: all of them, 0: no 8-phase plan)
+    bool stats_pass = false;         // exact mode: the product without its GroupNorm sums, then the norm kernels' statistics pass (gn_stats)
+    int dbg_used = 0;                // fit convolutions counted for the bisection aid (override -13); the launcher adds them to dbg_count
+};
+// Validation of the descriptor, then the plan: no HIP calls, nothing written to the context.  n_cu <= 0 means 256; ws_bytes is the
+// split-K workspace (0: none), ws_al16 whether it is 16-byte aligned.  Returns 0 or the PRX_REQUIRE error of prx_gemm_launch.
+int prx_gemm_plan_impl(const GemmDesc& d, const GemmCtx* c, int n_cu, size_t ws_bytes, bool ws_al16, GemmPlan* p);
+
 void prx_gemm_ctx_force_tile(GemmCtx* c, int bm, int bn, int splits);   // (0,0,0) restores the heuristic; bm < 0: switches, see .hip
 void prx_gemm_ctx_tile_rule(GemmCtx* c, int M, int N, int K, int mode, int bm, int bn, int splits);   // bm=0 drops it, M=0 drops all
 void prx_gemm_ctx_profile_enable(GemmCtx* c, int on);
 int prx_gemm_ctx_profile_collect(GemmCtx* c, double* total_ms, double* total_flop, long long* launches);
-int prx_gemm_plan_rows_8phase_impl(const GemmCtx* c, int M, int N, int K);   // host-only: the planner's decision for a plain row-major 16-bit product
 
 // Launch on `stream`.  `ws` is a scratch buffer for split-K partials (may be
 // null -> split-K disabled).  Returns 0 or a negative error code.

@@ -961,27 +961,25 @@ int prx_gemm_ctx_profile_collect(GemmCtx* c, double* total_ms, double* total_flo
 // (rows are independent; every row-indexed pointer of the descriptor is offset).  Costs from tools/micro/gemm8p.hip and
 // tools/lib_gemm_compare.py on MI355X (profiles/r03_lib_gemm_compare_8phase.txt): a round costs ~1.7 us per K tile + ~11 us
 // (epilogue included); the 4-wave kernels run ~650 TFLOP/s marginal + ~8 us.
-struct Plan8p { int main_rows; };     // rows [0, main_rows) on the 8-phase kernel (0: not at all), the rest on the 4-wave kernels
-static Plan8p plan_8phase(const GemmDesc& d, const GemmCtx& cx) {
-    Plan8p p{0};
-    if (cx.tile8p <= 0 || !prx_gemm8p_eligible(d)) return p;
+// -> rows [0, result) on the 8-phase kernel (0: not at all), the rest on the 4-wave kernels
+static int plan_8phase(const GemmDesc& d, const GemmCtx& cx, int n_cu) {
+    if (cx.tile8p <= 0 || !prx_gemm8p_eligible(d)) return 0;
     const int tm = ceil_div(d.M, 256), tn = ceil_div(d.N, 256), tiles = tm * tn;
-    if (tiles < cx.tile8p) return p;
-    const int n_cu = cx.n_cu > 0 ? cx.n_cu : 256;       // the launching context's device (256 on MI355X; the host-only planner query assumes it)
+    if (tiles < cx.tile8p) return 0;
     const double t_round = 1.7 * (d.K / 64) + 11.0;                                    // us
     auto t_4wave = [&](int rows) { return rows <= 0 ? 0.0 : 2.0 * rows * (double)d.N * d.K / 650e6 + 8.0; };   // us
     const int rounds_all = ceil_div(tiles, n_cu);
     double best = rounds_all * t_round;
-    p.main_rows = d.M;
+    int main_rows = d.M;
     const int full = tiles / n_cu;                                                      // whole rounds available
     if (full >= 1 && tiles % n_cu != 0) {
         const int rows8 = std::min(tm, (full * n_cu) / tn);                             // row tiles that fit `full` rounds
         const int m_main = std::min(d.M, rows8 * 256);
         const double t = full * t_round + t_4wave(d.M - m_main);
-        if (m_main > 0 && m_main < d.M && t < 0.9 * best) { best = t; p.main_rows = m_main; }
+        if (m_main > 0 && m_main < d.M && t < 0.9 * best) { best = t; main_rows = m_main; }
     }
-    if (t_4wave(d.M) < best) p.main_rows = 0;                                           // the 4-wave kernels win outright
-    return p;
+    if (t_4wave(d.M) < best) main_rows = 0;                                             // the 4-wave kernels win outright
+    return main_rows;
 }
 // the same descriptor restricted to rows [r0, r0 + rows) (row-major A only)
 static GemmDesc rows_of(const GemmDesc& d, int r0, int rows) {
@@ -997,62 +995,36 @@ static GemmDesc rows_of(const GemmDesc& d, int r0, int rows) {
     if (d.out_bf16_pre) s.out_bf16_pre = (char*)d.out_bf16_pre + (size_t)r0 * d.ldc_bf16 * esz;
     return s;
 }
+// ... and without its fused GroupNorm sums (the exact mode's product before the statistics pass)
+static GemmDesc without_stats(const GemmDesc& d) {
+    GemmDesc s = d;
+    s.gn_stats = nullptr; s.gnb_x = nullptr; s.gnb_fstats = nullptr; s.gnb_gamma = s.gnb_beta = nullptr;
+    return s;
+}
 
-static int gemm_launch_one(const GemmDesc& d, float* ws, size_t ws_bytes, hipStream_t stream, GemmCtx* ctx, int use8p);
 // (the 8-wave 256 x 128 member of this family -- PRX_BIG_TILE, measured neutral in round 2 and never the default -- was removed in
 // round 5: the descriptor it takes by value had outgrown its register budget (320 bytes of scratch per lane); 256 x 128 is a fit tile)
 static bool fourwave_tile(int bm, int bn) { return (bm == 128 && bn == 128) || (bm == 128 && bn == 64) || (bm == 64 && bn == 64); }
 
-int prx_gemm_plan_rows_8phase_impl(const GemmCtx* c, int M, int N, int K) {
-    static const GemmCtx k_default;
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    GemmDesc d;
-    d.a_mode = PRX_A_ROWMAJOR; d.M = M; d.N = N; d.K = K; d.lda = K; d.ldb = K;
-    return plan_8phase(d, c ? *c : k_default).main_rows;
+// the per-shape rule for d (tools/gemm_rules.py: in-pipeline sweeps), or null
+static const GemmTileRule* find_rule(const GemmDesc& d, const GemmCtx& cx) {
+    const GemmTileRule* rule = nullptr;
+    const int mode = d.a_mode + 2 * d.up + 4 * d.a_is_f32;
+    for (const GemmTileRule& r : cx.rules)
+        if (r.M == d.M && r.N == d.N && r.K == d.K && r.mode == mode) rule = &r;
+    return rule;
 }
 
-int prx_gemm_launch(const GemmDesc& d, float* ws, size_t ws_bytes, hipStream_t stream, GemmCtx* ctx) {
-    static const GemmCtx k_default;      // immutable: heuristics only
-    int cur_dev = -1;
-    if (ctx && (ctx->n_cu == 0 || (hipGetDevice(&cur_dev) == hipSuccess && cur_dev != ctx->n_cu_dev))) {
-        // the planners count tiles against the LAUNCHING device's CUs (cost constants stay MI355X's); re-asked when the context
-        // launches on another device than the one the count was taken from
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
-            { ctx->n_cu = cus; ctx->n_cu_dev = dev; }
-        else
-            ctx->n_cu = 256;
-    }
-    const GemmCtx& cx = ctx ? *ctx : k_default;
-    bool forced = cx.force_bm != 0;
-    if (!forced && !cx.rules.empty()) {          // a per-shape rule overrides the plan for THAT shape only (in-pipeline sweeps)
-        const int mode = d.a_mode + 2 * d.up + 4 * d.a_is_f32;
-        for (const GemmTileRule& r : cx.rules) forced = forced || (r.M == d.M && r.N == d.N && r.K == d.K && r.mode == mode);
-    }
-    if (!forced && d.M > 0 && d.N > 0 && d.K > 0) {
-        if (cx.rowk && (long long)d.M * d.N >= cx.rowk_min && prx_gemmrow_eligible(d)) return gemm_launch_one(d, ws, ws_bytes, stream, ctx, 2);     // skinny K, very tall: the row-streaming kernel (gemmrow.hip)
-        const Plan8p p = plan_8phase(d, cx);
-        if (p.main_rows >= d.M) return gemm_launch_one(d, ws, ws_bytes, stream, ctx, 1);
-        if (p.main_rows > 0) {
-            int r = gemm_launch_one(rows_of(d, 0, p.main_rows), ws, ws_bytes, stream, ctx, 1);
-            if (r) return r;
-            return gemm_launch_one(rows_of(d, p.main_rows, d.M - p.main_rows), ws, ws_bytes, stream, ctx, 0);
-        }
-    }
-    return gemm_launch_one(d, ws, ws_bytes, stream, ctx, 0);
-}
-
-static int gemm_launch_one(const GemmDesc& d, float* ws, size_t ws_bytes, hipStream_t stream, GemmCtx* ctx, int use8p) {
-    static const GemmCtx k_default;      // immutable: heuristics only
-    const GemmCtx& cx = ctx ? *ctx : k_default;
+// the descriptor checks that hold whatever the plan
+static int validate(const GemmDesc& d, const GemmCtx& cx) {
     PRX_REQUIRE(d.M > 0 && d.N > 0 && d.K > 0, "gemm: bad shape M=%d N=%d K=%d", d.M, d.N, d.K);
     PRX_REQUIRE(!(d.f32 && d.h16), "gemm: f32 and h16 are exclusive operand formats");
     const int kq = d.f32 ? 4 : 8;        // elements per 16-byte operand chunk
     PRX_REQUIRE(d.K % kq == 0 && d.ldb % kq == 0, "gemm: K (%d) and ldb (%d) must be multiples of %d", d.K, d.ldb, kq);
     PRX_REQUIRE(d.lda % kq == 0, "gemm: lda (%d) must be a multiple of %d", d.lda, kq);
     PRX_REQUIRE(((uintptr_t)d.A & 15) == 0 && ((uintptr_t)d.B & 15) == 0, "gemm: operands must be 16-byte aligned");
-    const bool c64 = d.a_mode == PRX_A_CONV3X3 && d.Cin % BK == 0 && cx.conv_c64 != 0;
     if (d.a_mode == PRX_A_CONV3X3) {
+        const bool c64 = d.Cin % BK == 0 && cx.conv_c64 != 0;
         PRX_REQUIRE(d.Cin % kq == 0 && d.K == 9 * d.Cin, "gemm/conv: need Cin %% %d == 0 and K == 9*Cin (Cin=%d K=%d)", kq, d.Cin, d.K);
         PRX_REQUIRE(d.H > 0 && d.W > 0 && d.M % (d.H * d.W) == 0, "gemm/conv: M (%d) must be NB*H*W (%dx%d)", d.M, d.H, d.W);
         PRX_REQUIRE(d.up != 1 || (d.H % 2 == 0 && d.W % 2 == 0), "gemm/conv: upsample needs even H, W");
@@ -1063,130 +1035,162 @@ static int gemm_launch_one(const GemmDesc& d, float* ws, size_t ws_bytes, hipStr
     PRX_REQUIRE((d.act != PRX_ACT_MUL_DQUICKGELU && d.act != PRX_ACT_MUL_RELUMASK && d.act != PRX_ACT_RELUMASK_POST) || d.aux,
                 "gemm: MUL_DQUICKGELU / MUL_RELUMASK / RELUMASK_POST need aux");
     PRX_REQUIRE(d.act != PRX_ACT_RELUMASK_POST || d.resid, "gemm: RELUMASK_POST masks product + residual: it needs resid");
-    // exact mode: the fused GroupNorm statistics live in the fp32-operand fit kernels (gemmfit_f32.hip); a problem those do not take
-    // runs without them here and gets the statistics from the norm kernels' own pass right after (gemm_launch_one below)
     PRX_REQUIRE(!d.f32 || d.row16 == 0, "gemm: 16-bit residual / GroupNorm-input streams (row16) belong to the 16-bit operand modes");
+    return 0;
+}
 
-    // ---- tile / split-K selection (tools/gemm_tune.py sweeps; MI355X: 256 CUs) -------------------------------
-    // Score each tile shape by how well its tile count fills whole "rounds" of resident blocks, weighted by the
-    // per-tile efficiency (bigger wave tiles do more MFMA per LDS byte).
-    const int n_cu = cx.n_cu > 0 ? cx.n_cu : 256;
-    int BM = 128, BN = 128;
-    auto ntiles = [&](int bm, int bn) { return ceil_div(d.M, bm) * ceil_div(d.N, bn); };
-    {
-        struct Cand { int bm, bn, per_cu; double eff; };
-        const Cand cands[3] = {{128, 128, 2, 1.0}, {128, 64, 3, 0.85}, {64, 64, 5, 0.75}};
-        double best = -1.0;
-        for (const Cand& c : cands) {
-            if (d.N <= 64 && c.bn > 64) continue;
-            const int t = ntiles(c.bm, c.bn);
-            const int slots = n_cu * c.per_cu;
-            const double fill = (double)t / ((double)ceil_div(t, slots) * slots);
-            const double score = fill * c.eff;
-            if (score > best) { best = score; BM = c.bm; BN = c.bn; }
-        }
-        // wide row-major problems (FC1 / W2^T: M=3200, N=3072): the fill model over-rates 64x64 (LDS-bound tiles);
-        // sweeps give 128x64 28 us vs 64x64 31 us vs 128x128 31.5 us
-        if (cx.wide_tile == 128 && d.a_mode == PRX_A_ROWMAJOR && d.N >= 2048 && BM == 64 && ntiles(128, 128) > 2 * n_cu) { BM = 128; BN = 64; }
+// 4-wave tiles (tools/gemm_tune.py sweeps; MI355X: 256 CUs): score each tile shape by how well its tile count fills whole "rounds" of
+// resident blocks, weighted by the per-tile efficiency (bigger wave tiles do more MFMA per LDS byte)
+static void fourwave_heuristic(const GemmDesc& d, const GemmCtx& cx, int n_cu, int* bm, int* bn) {
+    auto ntiles = [&](int tbm, int tbn) { return ceil_div(d.M, tbm) * ceil_div(d.N, tbn); };
+    struct Cand { int bm, bn, per_cu; double eff; };
+    const Cand cands[3] = {{128, 128, 2, 1.0}, {128, 64, 3, 0.85}, {64, 64, 5, 0.75}};
+    double best = -1.0;
+    for (const Cand& c : cands) {
+        if (d.N <= 64 && c.bn > 64) continue;
+        const int t = ntiles(c.bm, c.bn);
+        const int slots = n_cu * c.per_cu;
+        const double score = (double)t / ((double)ceil_div(t, slots) * slots) * c.eff;
+        if (score > best) { best = score; *bm = c.bm; *bn = c.bn; }
     }
-    // very large problems (ViT-L/14 at 256 cutouts: M = 65 792): the 8-wave 256 x 128 tile, when it still fills the chip
-    // several times over (A/B switch, off by default: see DESIGN.md section 6)
-    // fit tiles (gemmfit.hip): one workgroup per CU when a tile grid matches the chip (M = 3200: 240 tiles; the decoder's
-    // batch-1 convolutions: K split over the wave groups of a workgroup instead of over workgroups + a reduce launch)
-    // (three tile shapes -- 128 x 128, 128 x 64, 64 x 64 -- exist in BOTH kernel families: `fit_tile` says which one is meant)
-    bool fit_tile = false;
-    if (cx.fit && !use8p && (d.a_mode == PRX_A_ROWMAJOR || cx.fit_conv)) {
-        int fbm = 0, fbn = 0;
+    // wide row-major problems (FC1 / W2^T: M=3200, N=3072): the fill model over-rates 64x64 (LDS-bound tiles);
+    // sweeps give 128x64 28 us vs 64x64 31 us vs 128x128 31.5 us
+    if (cx.wide_tile == 128 && d.a_mode == PRX_A_ROWMAJOR && d.N >= 2048 && *bm == 64 && ntiles(128, 128) > 2 * n_cu) { *bm = 128; *bn = 64; }
+}
+
+// The plan of one launch of the product d.  In: p->family is GEMM_8PHASE, GEMM_ROW or GEMM_ROWCONV when prx_gemm_plan_impl's row /
+// 8-phase rules chose that kernel (the row kernels with p->row_nt / row_ksm set), anything else means "choose the tile here".  Out:
+// the whole plan.  *dbg: index of the next fit convolution the bisection aid counts (override -13).
+static void plan_launch(const GemmDesc& d, const GemmCtx& cx, int n_cu, size_t ws_bytes, bool ws_al16, GemmLaunchPlan* p, int* dbg) {
+    const bool row = p->family == GEMM_ROW || p->family == GEMM_ROWCONV;
+    const GemmTileRule* rule = find_rule(d, cx);
+    // the vector epilogue: a property of the descriptor and the workspace (it receives the split-K partials), not of the tile
+    auto al = [](const void* q, size_t a_) { return q == nullptr || ((uintptr_t)q % a_) == 0; };
+    const size_t opa = d.f32 ? 16 : 8;   // alignment of a 4-element operand-precision access
+    p->vec_epi = (d.N % 4 == 0) && al(d.bias_n, 16) && al(d.resid, (d.row16 & 1) ? 8 : 16) && (d.resid == nullptr || d.ldr % 4 == 0) &&
+                 al(d.aux, opa) && (d.aux == nullptr || d.ldaux % 4 == 0) && al(d.out_f32, 16) &&
+                 (d.out_f32 == nullptr || d.ldc_f32 % 4 == 0) && al(d.out_bf16, opa) && al(d.out_bf16_pre, opa) &&
+                 ((d.out_bf16 == nullptr && d.out_bf16_pre == nullptr) || d.ldc_bf16 % 4 == 0) && ws_al16;
+    // fit tiles (gemmfit.hip): one workgroup per CU when a tile grid matches the chip (M = 3200: 240 tiles; the decoder's batch-1
+    // convolutions: K split over the wave groups of a workgroup instead of over workgroups + a reduce launch).  Asked for every
+    // tiled launch, so the bisection aid counts a fit convolution even where a forced tile or a rule decides below.
+    int fbm = 0, fbn = 0;
+    if (!row && p->family != GEMM_8PHASE && cx.fit && (d.a_mode == PRX_A_ROWMAJOR || cx.fit_conv)) {
         prx_gemmfit_plan(d, n_cu, &fbm, &fbn);
-        if (fbm && ctx && d.a_mode != PRX_A_ROWMAJOR && cx.dbg_only >= -1) {       // bisection aid: only the dbg_only-th fit convolution since the last reset
-            const int idx = ctx->dbg_count++;
+        if (fbm && d.a_mode != PRX_A_ROWMAJOR && cx.dbg_only >= -1) {     // bisection aid: only the dbg_only-th fit convolution since the last reset
+            const int idx = (*dbg)++;
             if (cx.dbg_only >= 0 && idx != cx.dbg_only) fbm = 0;
         }
-        if (fbm) { BM = fbm; BN = fbn; fit_tile = true; }
     }
-    const bool rowk = use8p == 2;
-    if (use8p == 1) { BM = 256; BN = 256; fit_tile = false; }          // planned by plan_8phase (prx_gemm_launch)
-    if (rowk) { BM = 16; BN = (d.K > 320 || d.a_mode == PRX_A_CONV3X3) ? 80 : (d.N % 160 == 0 ? 160 : (d.N % 128 == 0 ? 128 : 80)); fit_tile = false; }
-    // a forced tile selects the fit kernel when the override says so (cx.force_fit), or when only that family has the shape
-    if (cx.force_bm) { BM = cx.force_bm; BN = cx.force_bn; fit_tile = prx_gemmfit_tile(BM, BN, nullptr) && (cx.force_fit || !fourwave_tile(BM, BN)); }
-    int rule_splits = 0;
-    if (!cx.rules.empty()) {
-        const int mode = d.a_mode + 2 * d.up + 4 * d.a_is_f32;
-        for (const GemmTileRule& r : cx.rules)
-            if (r.M == d.M && r.N == d.N && r.K == d.K && r.mode == mode) {
-                BM = r.bm; BN = r.bn; rule_splits = r.splits;
-                fit_tile = prx_gemmfit_tile(BM, BN, nullptr) && !fourwave_tile(BM, BN);
-            }
-    }
-    if (BM == 256 && BN == 256 && !prx_gemm8p_eligible(d)) { BM = 128; BN = 128; }     // row-major 16-bit operands, K % 128 == 0 only
-    if (fit_tile && !prx_gemmfit_eligible(d, BM, BN)) { fit_tile = false; if (!fourwave_tile(BM, BN)) { BM = 128; BN = 128; } }
-    if (d.f32 && BM == 256 && !fit_tile) BM = 128;    // the exact mode's 4-wave family has three tiles only (256 x 128 is a fit tile)
-    if (!fit_tile && BM == 256 && BN == 128) BM = 128;     // 256 x 128 exists as a fit tile only
-    const int bk = d.f32 ? BKF : BK;
-    GemmArgs a;
-    a.d = d;
-    a.tiles_m = ceil_div(d.M, BM);
-    a.tiles_n = ceil_div(d.N, BN);
-    a.kt_total = ceil_div(d.K, bk);
-    int tiles = a.tiles_m * a.tiles_n;
+    // the tile asked for: the row / 8-phase rule's, a rule for this shape, a forced tile, the fit planner's, else the 4-wave heuristic.
+    // want_fit: the fit kernel of that shape is meant (128 x 128, 128 x 64 and 64 x 64 exist in both families; a forced one means the fit
+    // kernel with override -12, a rule's never; the shapes only the fit family has always do)
+    int bm = 128, bn = 128;
+    bool want_fit = false;
+    if (row) { bm = 16; bn = p->family == GEMM_ROWCONV ? 80 : 16 * p->row_nt; }
+    else if (p->family == GEMM_8PHASE) { bm = bn = 256; }
+    else if (rule) { bm = rule->bm; bn = rule->bn; want_fit = prx_gemmfit_tile(bm, bn, nullptr) && !fourwave_tile(bm, bn); }
+    else if (cx.force_bm) { bm = cx.force_bm; bn = cx.force_bn; want_fit = prx_gemmfit_tile(bm, bn, nullptr) && (cx.force_fit || !fourwave_tile(bm, bn)); }
+    else if (fbm) { bm = fbm; bn = fbn; want_fit = true; }
+    else fourwave_heuristic(d, cx, n_cu, &bm, &bn);
+    // the kernel that runs it, one case each (they exclude one another):
+    //  * the fit kernel when it takes d (fit_takes) and d has the vector epilogue; without that epilogue (an unaligned workspace) the
+    //    128 x 128 4-wave kernel, still planned as a fit choice: no automatic split-K below (a forced split count applies);
+    //  * a fit tile the fit kernel does not take: the 4-wave kernel of that shape where there is one, else 128 x 128;
+    //  * 256 x 256: the 8-phase kernel where it takes d (row-major 16-bit operands, K % 128 == 0), else 128 x 128;
+    //  * another 256-row tile (forced): 128 rows in the exact mode, whose 4-wave family has no 256-row tile, and for 256 x 128, which
+    //    exists as a fit tile only; every other tile as asked.
+    const bool fit_takes = want_fit && prx_gemmfit_eligible(d, bm, bn);
+    const bool fit = fit_takes && p->vec_epi;
+    if ((fit_takes && !fit) || (want_fit && !fit_takes && !fourwave_tile(bm, bn)) || (bm == 256 && bn == 256 && !prx_gemm8p_eligible(d))) { bm = 128; bn = 128; }
+    else if (!want_fit && bm == 256 && bn != 256 && (d.f32 || bn == 128)) bm = 128;
+    const int kt_total = ceil_div(d.K, d.f32 ? BKF : BK);
+    const int tiles = ceil_div(d.M, bm) * ceil_div(d.N, bn);
     int splits = 1;
-    if (ws && tiles <= n_cu / 2 && a.kt_total >= 16 && !(BM == 256 && BN == 256) && !fit_tile && !rowk) {
+    if (ws_bytes && tiles <= n_cu / 2 && kt_total >= 16 && !(bm == 256 && bn == 256) && !fit_takes && !row) {
         // few tiles, long K (the 16x16 / 32x32 decoder convs): aim at ~320 blocks, >= 4 K tiles per split
-        splits = std::max(1, std::min(std::min((320 + tiles / 2) / tiles, a.kt_total / 4), 32));
+        splits = std::max(1, std::min(std::min((320 + tiles / 2) / tiles, kt_total / 4), 32));
         while (splits > 1 && (size_t)splits * d.M * d.N * sizeof(float) > ws_bytes) --splits;
     }
-    auto al = [](const void* p, size_t a_) { return p == nullptr || ((uintptr_t)p % a_) == 0; };
-    const size_t opa = d.f32 ? 16 : 8;   // alignment of a 4-element operand-precision access
-    a.vec_epi = (d.N % 4 == 0) && al(d.bias_n, 16) && al(d.resid, (d.row16 & 1) ? 8 : 16) && (d.resid == nullptr || d.ldr % 4 == 0) &&
-                al(d.aux, opa) && (d.aux == nullptr || d.ldaux % 4 == 0) && al(d.out_f32, 16) &&
-                (d.out_f32 == nullptr || d.ldc_f32 % 4 == 0) && al(d.out_bf16, opa) && al(d.out_bf16_pre, opa) &&
-                ((d.out_bf16 == nullptr && d.out_bf16_pre == nullptr) || d.ldc_bf16 % 4 == 0) && al(ws, 16);
-    PRX_REQUIRE(d.row16 == 0 || a.vec_epi, "gemm: 16-bit residual / GroupNorm-input streams need the vector epilogue (N %% 4 == 0, aligned operands)");
-    if (fit_tile && !a.vec_epi) {               // the fit kernel has the vector epilogue only
-        BM = 128; BN = 128; fit_tile = false;
-        a.tiles_m = ceil_div(d.M, BM); a.tiles_n = ceil_div(d.N, BN); tiles = a.tiles_m * a.tiles_n;
-    }
-    if ((cx.force_splits > 0 || rule_splits > 0) && ws && !fit_tile) {
-        splits = std::min(rule_splits > 0 ? rule_splits : cx.force_splits, a.kt_total);
+    const int forced_splits = rule && rule->splits > 0 ? rule->splits : cx.force_splits;
+    if (forced_splits > 0 && ws_bytes && !fit) {
+        splits = std::min(forced_splits, kt_total);
         while (splits > 1 && (size_t)splits * d.M * d.N * sizeof(float) > ws_bytes) --splits;
     }
+    p->kt_per_split = ceil_div(kt_total, splits);
+    if (bm == 256 && bn == 256) p->kt_per_split = (p->kt_per_split + 1) & ~1;      // the 8-phase loop body covers two K tiles
+    p->splits = ceil_div(kt_total, p->kt_per_split);
+    p->bm = bm; p->bn = bn;
+    if (!row) p->family = fit ? GEMM_FIT : d.f32 ? GEMM_TILED_F32 : (bm == 256 && bn == 256) ? GEMM_8PHASE
+                        : (!d.a_is_f32 && cx.use_glds) ? GEMM_TILED_GLDS : GEMM_TILED_V1;
     // measured (tools/gemm_tune.py xcd + bench.py A/B): +10-19% on the row-major N=768 ViT GEMMs, neutral-to-negative
     // on the implicit-conv shapes -> mode 2 (default) applies it to narrow row-major problems only
-    a.xcd_swizzle = tiles >= 16 && (cx.xcd_swizzle == 1 || (cx.xcd_swizzle == 2 && d.a_mode == PRX_A_ROWMAJOR && d.N <= 1024));
+    p->xcd_swizzle = tiles >= 16 && (cx.xcd_swizzle == 1 || (cx.xcd_swizzle == 2 && d.a_mode == PRX_A_ROWMAJOR && d.N <= 1024));
     // with the streaming producers / consumers split the same way (common.h, PRX_XCD_LOCAL): every tiled launch keeps an
     // XCD on a contiguous eighth of the tile rows, so activation rows stay in one L2 across kernel boundaries
-    if (cx.xcd_swizzle == 3) a.xcd_swizzle = tiles >= 16;
+    if (cx.xcd_swizzle == 3) p->xcd_swizzle = tiles >= 16;
     // 8-phase tiles (tools/micro/gemm8p.hip): +11 % at M = 65 792, N = 1024 and at M = 25 216, N = 3072; -2 % at 8192^3
-    if (BM == 256 && BN == 256 && cx.xcd_swizzle == 2) a.xcd_swizzle = tiles >= 512 && d.N <= 4096;
-    if (fit_tile && cx.xcd_swizzle == 2) a.xcd_swizzle = tiles >= 16;
+    if (bm == 256 && bn == 256 && cx.xcd_swizzle == 2) p->xcd_swizzle = tiles >= 512 && d.N <= 4096;
+    if (fit && cx.xcd_swizzle == 2) p->xcd_swizzle = tiles >= 16;
+    p->fit_flags = fit ? (cx.fit_flags & (15 | 64)) : (cx.fit_flags & 64);   // gemmfit.hip A/B switches (PRX_FIT_FLAGS); bit 6: generic epilogues only
+    if (fit && (cx.fit_flags & 32) == 0 && d.N > d.M) p->fit_flags |= 16;     // weight-heavy: column-major tile order (bit 5 of the switch word turns it off)
+    // LDS pipeline depth, tuned IN the iteration (tools/gemm_shapes.py), not on hot-cache microbenchmarks: every
+    // weight matrix is touched once per iteration (520 MB of packs > the 256 MB MALL), so each K tile of B comes
+    // from HBM and a 2-deep ring exposes that latency once per K tile.  A third stage on the 64x64 tiles (48 KB,
+    // still 3 workgroups/CU) gives -30 % on the 64^2 decoder convs and -8..-20 % on the other 64x64 launches; on
+    // the 128-wide tiles it halves the occupancy and loses 15-25 %.
+    p->stages = cx.force_stages ? cx.force_stages : ((bm == 64 && bn == 64) ? 3 : 2);
+    p->c64 = d.a_mode == PRX_A_CONV3X3 && d.Cin % BK == 0 && cx.conv_c64 != 0;
+}
+
+int prx_gemm_plan_impl(const GemmDesc& d, const GemmCtx* c, int n_cu, size_t ws_bytes, bool ws_al16, GemmPlan* p) {
+    static const GemmCtx k_default;      // immutable: heuristics only
+    const GemmCtx& cx = c ? *c : k_default;
+    *p = GemmPlan{};
+    const int v = validate(d, cx);
+    if (v) return v;
+    n_cu = n_cu > 0 ? n_cu : 256;
+    int dbg = cx.dbg_count;
+    GemmLaunchPlan& l0 = p->launch[0];
+    // a forced tile, or a per-shape rule for d, overrides these two rules
+    const bool forced = cx.force_bm != 0 || find_rule(d, cx) != nullptr;
+    if (!forced && cx.rowk && (long long)d.M * d.N >= cx.rowk_min && prx_gemmrow_plan(d, &l0.row_nt, &l0.row_ksm))
+        l0.family = d.a_mode == PRX_A_ROWMAJOR ? GEMM_ROW : GEMM_ROWCONV;      // skinny K, very tall: the row-streaming kernels (gemmrow.hip)
+    else if (!forced && (p->rows_8p = plan_8phase(d, cx, n_cu)) > 0)
+        l0.family = GEMM_8PHASE;
+    p->n_launch = p->rows_8p > 0 && p->rows_8p < d.M ? 2 : 1;
+    plan_launch(p->n_launch == 2 ? rows_of(d, 0, p->rows_8p) : d, cx, n_cu, ws_bytes, ws_al16, &l0, &dbg);
+    if (p->n_launch == 2) plan_launch(rows_of(d, p->rows_8p, d.M - p->rows_8p), cx, n_cu, ws_bytes, ws_al16, &p->launch[1], &dbg);
+    p->dbg_used = dbg - cx.dbg_count;
+
+    PRX_REQUIRE(d.row16 == 0 || l0.vec_epi, "gemm: 16-bit residual / GroupNorm-input streams need the vector epilogue (N %% 4 == 0, aligned operands)");
     if (d.gnb_x) {
         PRX_REQUIRE(d.gn_stats && d.gnb_fstats && d.gnb_gamma && d.gnb_beta && (d.out_f32 || d.out_bf16) && d.act == PRX_ACT_NONE,
                     "gemm: fused GroupNorm-backward sums need gn_stats, gnb_fstats, gnb_gamma, gnb_beta and a plain output");
         PRX_REQUIRE(((uintptr_t)d.gnb_x % 16) == 0 && ((uintptr_t)d.gnb_gamma % 16) == 0 && ((uintptr_t)d.gnb_beta % 16) == 0,
                     "gemm: gnb operands must be 16-byte aligned");
     }
-    if (d.f32 && d.gn_stats && !fit_tile) {
-        // the 4-wave fp32 kernels have no statistics epilogue: the product without them, then the norm kernels' statistics pass over
-        // the result (what the runner would have launched had it not asked for the fusion)
+    // exact mode with fused GroupNorm sums: only the fp32 fit kernels have that epilogue, so the plan above (made WITH the sums) decides.
+    // A fit tile keeps them.  Anything else means the product without them, then the norm kernels' statistics pass over its output (what
+    // the runner would have launched had it not asked for the fusion; gemm.h gn_stats).  That product gets a plan of its own: without
+    // the sums the fit kernels may take it after all, and the bisection aid counts it again.
+    p->stats_pass = d.f32 && d.gn_stats && l0.family != GEMM_FIT;
+    if (p->stats_pass) {
         PRX_REQUIRE(d.out_f32 && d.ldc_f32 == d.N && d.N == 32 * d.gn_gs, "gemm: fp32 GroupNorm statistics need a dense fp32 output with N == 32 * gn_gs");
-        GemmDesc d2 = d;
-        d2.gn_stats = nullptr; d2.gnb_x = nullptr; d2.gnb_fstats = nullptr; d2.gnb_gamma = d2.gnb_beta = nullptr;
-        int r = gemm_launch_one(d2, ws, ws_bytes, stream, ctx, use8p);
-        if (r) return r;
-        if (d.gnb_x) return prx_groupnorm_bwd_stats(d.out_f32, d.gnb_x, d.gnb_gamma, d.gnb_beta, d.gnb_fstats, d.gn_stats, 1, d.M, d.N, d.gnb_swish, d.gnb_eps, stream);
-        return prx_groupnorm_fwd(d.out_f32, nullptr, nullptr, d.gn_stats, nullptr, nullptr, 1, d.M, d.N, 0, 1e-6f, stream, /*zero_stats=*/0, /*stats_ready=*/0);
-    }
-    if (d.gn_stats) {
-        PRX_REQUIRE(a.vec_epi && d.gn_gs >= 4 && d.gn_gs % 4 == 0 && d.N == 32 * d.gn_gs && !d.a_is_f32 && (cx.use_glds || d.f32),
+        l0 = GemmLaunchPlan{};
+        plan_launch(without_stats(d), cx, n_cu, ws_bytes, ws_al16, &l0, &dbg);
+        p->dbg_used = dbg - cx.dbg_count;
+    } else if (d.gn_stats) {
+        PRX_REQUIRE(l0.vec_epi && d.gn_gs >= 4 && d.gn_gs % 4 == 0 && d.N == 32 * d.gn_gs && !d.a_is_f32 && (cx.use_glds || d.f32),
                     "gemm: fused GroupNorm statistics need the v2 kernel's vector epilogue and N == 32 * gn_gs");
     }
-    a.fit_flags = fit_tile ? (cx.fit_flags & (15 | 64)) : (cx.fit_flags & 64);   // gemmfit.hip A/B switches (PRX_FIT_FLAGS); bit 6: generic epilogues only
-    if (fit_tile && (cx.fit_flags & 32) == 0 && d.N > d.M) a.fit_flags |= 16;      // weight-heavy: column-major tile order (bit 5 of the switch word turns it off)
-    a.kt_per_split = ceil_div(a.kt_total, splits);
-    if (BM == 256 && BN == 256) a.kt_per_split = (a.kt_per_split + 1) & ~1;      // the 8-phase loop body covers two K tiles
-    splits = ceil_div(a.kt_total, a.kt_per_split);
-    a.splits = splits;
-    a.ws = ws;
+    return 0;
+}
+
+// one planned launch (and its split-K reduce), timed when the context profiles
+static int launch_planned(const GemmDesc& d, const GemmLaunchPlan& p, float* ws, int n_cu, hipStream_t stream, GemmCtx* ctx) {
+    const GemmArgs a{d, ceil_div(d.M, p.bm), ceil_div(d.N, p.bn), p.splits, p.kt_per_split, ceil_div(d.K, d.f32 ? BKF : BK), p.vec_epi,
+                     p.xcd_swizzle, p.fit_flags, ws};
 
     GemmProfRec rec{};
     bool prof = false;
@@ -1197,45 +1201,41 @@ static int gemm_launch_one(const GemmDesc& d, float* ws, size_t ws_bytes, hipStr
     if (prof) {
         PRX_CHECK_HIP(hipEventCreate(&rec.a));
         PRX_CHECK_HIP(hipEventCreate(&rec.b));
+        const bool row = p.family == GEMM_ROW || p.family == GEMM_ROWCONV;
         rec.flop = 2.0 * d.M * d.N * d.K;
-        rec.M = d.M; rec.N = d.N; rec.K = d.K; rec.mode = d.a_mode + 2 * d.up + 4 * d.a_is_f32 + 8 * d.f32; rec.bm = fit_tile ? BM + 1000 : (rowk ? BM + 2000 : BM); rec.bn = BN; rec.splits = splits;      // + 1000: the fit kernel of that tile shape
+        rec.M = d.M; rec.N = d.N; rec.K = d.K; rec.mode = d.a_mode + 2 * d.up + 4 * d.a_is_f32 + 8 * d.f32;
+        rec.bm = p.bm + (p.family == GEMM_FIT ? 1000 : (row ? 2000 : 0)); rec.bn = p.bn; rec.splits = p.splits;    // + 1000: the fit kernel of that tile shape
         PRX_CHECK_HIP(hipEventRecord(rec.a, stream));
     }
 
-    dim3 grid(tiles, splits);
-    if (rowk) {
-        int e = prx_gemmrow_launch(a, n_cu, stream);
-        if (e) return e;
-    } else if (fit_tile && d.f32) {
-        int e = prx_gemmfit_launch(a, BM, BN, grid, stream);      // fp32-operand fit kernels (gemmfit_f32.hip)
-        if (e) return e;
-    } else if (d.f32) {
-        if (BM == 128 && BN == 128) launch_f32<128, 128>(a, grid, stream);
-        else if (BM == 128 && BN == 64) launch_f32<128, 64>(a, grid, stream);
+    const dim3 grid(a.tiles_m * a.tiles_n, p.splits);
+    const bool t128 = p.bm == 128 && p.bn == 128, t12864 = p.bm == 128 && p.bn == 64;      // (other 4-wave tiles: the 64 x 64 kernel)
+    const bf16_t* zp = p.family == GEMM_TILED_GLDS ? zero_page_for_current_device() : nullptr;
+    PRX_REQUIRE(zp != nullptr || p.family != GEMM_TILED_GLDS, "gemm: could not allocate the zero page");
+    int e = 0;
+    switch (p.family) {
+    case GEMM_ROW: case GEMM_ROWCONV: prx_gemmrow_launch(a, p.row_nt, p.row_ksm, n_cu, stream); break;
+    case GEMM_FIT: e = prx_gemmfit_launch(a, p.bm, p.bn, grid, stream); break;      // the fp32-operand kernels too (gemmfit_f32.hip)
+    case GEMM_8PHASE: prx_gemm8p_launch(a, grid, stream); break;
+    case GEMM_TILED_F32:
+        if (t128) launch_f32<128, 128>(a, grid, stream);
+        else if (t12864) launch_f32<128, 64>(a, grid, stream);
         else launch_f32<64, 64>(a, grid, stream);
-    } else if (BM == 256 && BN == 256) {
-        prx_gemm8p_launch(a, grid, stream);
-    } else if (fit_tile) {
-        int e = prx_gemmfit_launch(a, BM, BN, grid, stream);
-        if (e) return e;
-    } else if (!d.a_is_f32 && cx.use_glds) {
-        const bf16_t* zp = zero_page_for_current_device();
-        PRX_REQUIRE(zp != nullptr, "gemm: could not allocate the zero page");
-        // LDS pipeline depth, tuned IN the iteration (tools/gemm_shapes.py), not on hot-cache microbenchmarks: every
-        // weight matrix is touched once per iteration (520 MB of packs > the 256 MB MALL), so each K tile of B comes
-        // from HBM and a 2-deep ring exposes that latency once per K tile.  A third stage on the 64x64 tiles (48 KB,
-        // still 3 workgroups/CU) gives -30 % on the 64^2 decoder convs and -8..-20 % on the other 64x64 launches; on
-        // the 128-wide tiles it halves the occupancy and loses 15-25 %.
-        int stages = (BM == 64 && BN == 64) ? 3 : 2;
-        if (cx.force_stages) stages = cx.force_stages;
-        if (BM == 128 && BN == 128) launch_glds<128, 128>(a, grid, stream, zp, stages, c64);
-        else if (BM == 128 && BN == 64) launch_glds<128, 64>(a, grid, stream, zp, stages, c64);
-        else launch_glds<64, 64>(a, grid, stream, zp, stages, c64);
-    } else if (BM == 128 && BN == 128) launch_cfg<128, 128>(a, grid, stream);
-    else if (BM == 128 && BN == 64) launch_cfg<128, 64>(a, grid, stream);
-    else launch_cfg<64, 64>(a, grid, stream);
+        break;
+    case GEMM_TILED_GLDS:
+        if (t128) launch_glds<128, 128>(a, grid, stream, zp, p.stages, p.c64);
+        else if (t12864) launch_glds<128, 64>(a, grid, stream, zp, p.stages, p.c64);
+        else launch_glds<64, 64>(a, grid, stream, zp, p.stages, p.c64);
+        break;
+    case GEMM_TILED_V1:
+        if (t128) launch_cfg<128, 128>(a, grid, stream);
+        else if (t12864) launch_cfg<128, 64>(a, grid, stream);
+        else launch_cfg<64, 64>(a, grid, stream);
+        break;
+    }
+    if (e) return e;
     PRX_LAUNCH_CHECK();
-    if (splits > 1) {
+    if (p.splits > 1) {
         size_t total = (size_t)d.M * d.N;
         int blocks = (int)std::min<size_t>((total + 255) / 256, 2048);
         PRX_OP_DISPATCH(d.f32, d.h16, T, hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3(blocks), dim3(256), 0, stream, a));
@@ -1247,4 +1247,31 @@ static int gemm_launch_one(const GemmDesc& d, float* ws, size_t ws_bytes, hipStr
         ctx->prof.push_back(rec);
     }
     return 0;
+}
+
+int prx_gemm_launch(const GemmDesc& d, float* ws, size_t ws_bytes, hipStream_t stream, GemmCtx* ctx) {
+    int cur_dev = -1;
+    if (ctx && (ctx->n_cu == 0 || (hipGetDevice(&cur_dev) == hipSuccess && cur_dev != ctx->n_cu_dev))) {
+        // the planners count tiles against the LAUNCHING device's CUs (cost constants stay MI355X's); re-asked when the context
+        // launches on another device than the one the count was taken from
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
+            { ctx->n_cu = cus; ctx->n_cu_dev = dev; }
+        else
+            ctx->n_cu = 256;
+    }
+    const int n_cu = ctx && ctx->n_cu > 0 ? ctx->n_cu : 256;
+    GemmPlan plan;
+    const int r = prx_gemm_plan_impl(d, ctx, n_cu, ws ? ws_bytes : 0, ((uintptr_t)ws & 15) == 0, &plan);
+    if (ctx) ctx->dbg_count += plan.dbg_used;
+    if (r) return r;
+    for (int i = 0; i < plan.n_launch; ++i) {
+        const GemmDesc di = plan.n_launch == 2 ? (i == 0 ? rows_of(d, 0, plan.rows_8p) : rows_of(d, plan.rows_8p, d.M - plan.rows_8p))
+                                               : (plan.stats_pass ? without_stats(d) : d);
+        const int e = launch_planned(di, plan.launch[i], ws, n_cu, stream, ctx);
+        if (e) return e;
+    }
+    if (!plan.stats_pass) return 0;
+    if (d.gnb_x) return prx_groupnorm_bwd_stats(d.out_f32, d.gnb_x, d.gnb_gamma, d.gnb_beta, d.gnb_fstats, d.gn_stats, 1, d.M, d.N, d.gnb_swish, d.gnb_eps, stream);
+    return prx_groupnorm_fwd(d.out_f32, nullptr, nullptr, d.gn_stats, nullptr, nullptr, 1, d.M, d.N, 0, 1e-6f, stream, /*zero_stats=*/0, /*stats_ready=*/0);
 }

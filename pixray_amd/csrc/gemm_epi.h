@@ -183,9 +183,11 @@ __device__ __forceinline__ void epilogue_store8(const GemmDesc& d, int row, int 
 // gemm8p.hip: the 256 x 256 8-phase kernel (row-major 16-bit operands, K % 128 == 0, no fused GroupNorm statistics)
 bool prx_gemm8p_eligible(const GemmDesc& d);
 void prx_gemm8p_launch(const prx_gemm_dev::GemmArgs& a, dim3 grid, hipStream_t s);      // grid = (tiles, splits), kt_per_split even
-// gemmrow.hip: the row-streaming kernels for skinny K (K <= 320; N % 160 == 0, N % 128 == 0 or N % 80 == 0; M N >= 5 Mi): weights resident in LDS
-bool prx_gemmrow_eligible(const GemmDesc& d);
-int prx_gemmrow_launch(const prx_gemm_dev::GemmArgs& a, int n_cu, hipStream_t s);
+// gemmrow.hip: the row-streaming kernels, weights resident in LDS: row-major 16-bit products with K <= 640 (160-, 128- or 80-column
+// slabs, 80 only beyond K = 320) and implicit 3x3 convolutions with (N, Cin) in {40, 80}^2 or (160, 160).  prx_gemmrow_plan: whether a
+// kernel takes d, and its slab (16-column tiles) and K bucket; the caller decides whether d is large enough (GemmCtx::rowk_min)
+bool prx_gemmrow_plan(const GemmDesc& d, int* nt, int* ksm);
+void prx_gemmrow_launch(const prx_gemm_dev::GemmArgs& a, int nt, int ksm, int n_cu, hipStream_t s);
 long long prx_gemmrow_launches();
 // gemmfit.hip: tiles whose count matches the chip (row-major 16-bit operands or implicit 3x3 convolutions with Cin % 64 == 0,
 // K % (64 ks) == 0, 16-byte-friendly epilogue operands, no split-K across workgroups)

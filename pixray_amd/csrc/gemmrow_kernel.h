@@ -31,6 +31,24 @@ using namespace prx_gemm_dev;
 
 constexpr int GR_WAVES = 8;          // waves per workgroup (all on one weight slab)
 
+// ---- the kernels that exist, written once: prx_gemmrow_plan (gemmrow.hip) accepts by these, launch_slab below instantiates by them ----
+// 16-column tiles per slab for N and ksteps = ceil(K / 32): 160-wide slabs (5 pairs), 128-wide (4 pairs), or 80 = 2 pairs + a lone
+// tile -- the only width whose weights fit the LDS beyond 10 K steps (0: none)
+constexpr int row_slab_tiles(int N, int ksteps) {
+    return ksteps > 10 ? (N % 80 == 0 ? 5 : 0) : (N % 160 == 0 ? 10 : (N % 128 == 0 ? 8 : (N % 80 == 0 ? 5 : 0)));
+}
+// the K bucket (KSM below): 6, 10 or 20 K steps of 32 (0: K > 640)
+constexpr int row_k_bucket(int ksteps) { return ksteps <= 6 ? 6 : (ksteps <= 10 ? 10 : (ksteps <= 20 ? 20 : 0)); }
+// the (activation, residual, slab) patterns with a kernel: the ModifiedResNet runner's conv3 / downsample forward and conv1 dgrad
+// (residual, none / ReLU / the ReLU mask after the residual add), its conv1 forward / conv3 dgrad (no residual, none / ReLU; the
+// forward output's ReLU mask on 80-column slabs) and the first block's conv1 dgrad (80 columns: residual, no activation)
+constexpr bool row_kernel_exists(int act, bool res, int nt, int ksm) {
+    return (ksm <= 10 || nt == 5) &&
+           (act == PRX_ACT_NONE || act == PRX_ACT_RELU || (res ? act == PRX_ACT_RELUMASK_POST : ((nt & 1) != 0 && act == PRX_ACT_MUL_RELUMASK)));
+}
+// the launch geometry (gemmrow.hip prx_gemmrow_launch)
+struct RowGrid { int nt, ksteps, nslab, row_tiles, nchunks, grid; };
+
 template <typename T16>
 __device__ __forceinline__ f32x4 gr_mfma(const bf16x8& a, const bf16x8& b, const f32x4& c) {
     if constexpr (std::is_same<T16, half_t>::value)
@@ -232,63 +250,38 @@ __global__ __launch_bounds__(GR_WAVES * 64) void gemmrow_kernel(GemmArgs a, int 
     }
 }
 
-// the (activation, residual) patterns that exist as kernels, per slab shape: the runner's conv3 / downsample forward and conv1 dgrad
-// (pairs only, N % 128 == 0 or N % 160 == 0), its conv1 forward / conv3 dgrad (N = 80: no residual) and the first block's conv1
-// dgrad (N = 80: residual, no activation)
+// The launch of one (activation, residual) pattern: only the kernels row_kernel_exists names are instantiated, and prx_gemmrow_plan
+// accepts only what it names, so an accepted descriptor always finds its kernel here.
+template <typename T16, int ACT, int RES, int NT, int KSM>
+inline void launch_act(const GemmArgs& a, const RowGrid& g, hipStream_t s) {
+    if constexpr (row_kernel_exists(ACT, RES != 0, NT, KSM))
+        hipLaunchKernelGGL((gemmrow_kernel<T16, ACT, RES, NT, KSM>), dim3(g.grid), dim3(GR_WAVES * 64), 0, s, a, g.ksteps, g.nslab, g.row_tiles, g.nchunks);
+}
 template <typename T16, int RES, int NT, int KSM>
-inline bool launch_instance(const GemmArgs& a, int ksteps, int nslab, int row_tiles, int nchunks, int grid, hipStream_t s) {
-#define GR_CASE(ACT_)                                                                                                                   \
-    case ACT_:                                                                                                                          \
-        hipLaunchKernelGGL((gemmrow_kernel<T16, ACT_, RES, NT, KSM>), dim3(grid), dim3(GR_WAVES * 64), 0, s, a, ksteps, nslab, row_tiles, nchunks); \
-        return true;
-    if constexpr (RES == 0) {
-        switch (a.d.act) {
-            GR_CASE(PRX_ACT_NONE) GR_CASE(PRX_ACT_RELU)
-            case PRX_ACT_MUL_RELUMASK:
-                if constexpr ((NT & 1) != 0) {
-                    hipLaunchKernelGGL((gemmrow_kernel<T16, PRX_ACT_MUL_RELUMASK, RES, NT, KSM>), dim3(grid), dim3(GR_WAVES * 64), 0, s, a, ksteps, nslab, row_tiles, nchunks);
-                    return true;
-                }
-                return false;
-            default: return false;
-        }
-    } else if constexpr ((NT & 1) == 0) {
-        switch (a.d.act) {
-            GR_CASE(PRX_ACT_NONE) GR_CASE(PRX_ACT_RELU) GR_CASE(PRX_ACT_RELUMASK_POST)
-            default: return false;
-        }
-    } else {
-        switch (a.d.act) {
-            GR_CASE(PRX_ACT_NONE) GR_CASE(PRX_ACT_RELU) GR_CASE(PRX_ACT_RELUMASK_POST)
-            default: return false;
-        }
+inline void launch_res(const GemmArgs& a, const RowGrid& g, hipStream_t s) {
+    switch (a.d.act) {
+    case PRX_ACT_NONE: launch_act<T16, PRX_ACT_NONE, RES, NT, KSM>(a, g, s); break;
+    case PRX_ACT_RELU: launch_act<T16, PRX_ACT_RELU, RES, NT, KSM>(a, g, s); break;
+    case PRX_ACT_MUL_RELUMASK: launch_act<T16, PRX_ACT_MUL_RELUMASK, RES, NT, KSM>(a, g, s); break;
+    case PRX_ACT_RELUMASK_POST: launch_act<T16, PRX_ACT_RELUMASK_POST, RES, NT, KSM>(a, g, s); break;
     }
-    return false;
-#undef GR_CASE
 }
-// K in (320, 640]: 80-column slabs only (the weights of a wider slab do not fit the LDS)
-template <typename T16, int RES_ON>
-inline bool launch_slab80_k640(const GemmArgs& a, int ksteps, int nslab, int row_tiles, int nchunks, int grid, hipStream_t s) {
-    return a.d.resid != nullptr ? launch_instance<T16, RES_ON, 5, 20>(a, ksteps, nslab, row_tiles, nchunks, grid, s)
-                                : launch_instance<T16, 0, 5, 20>(a, ksteps, nslab, row_tiles, nchunks, grid, s);
-}
+// one translation unit per (operand format, residual kind, K bucket): RES_ON = the residual kind of that format
 template <typename T16, int RES_ON, int KSM>
-inline bool launch_slab(const GemmArgs& a, int nt, int ksteps, int nslab, int row_tiles, int nchunks, int grid, hipStream_t s) {
+inline void launch_slab(const GemmArgs& a, const RowGrid& g, hipStream_t s) {
     const bool res = a.d.resid != nullptr;
-    if (nt == 10) return res ? launch_instance<T16, RES_ON, 10, KSM>(a, ksteps, nslab, row_tiles, nchunks, grid, s)
-                             : launch_instance<T16, 0, 10, KSM>(a, ksteps, nslab, row_tiles, nchunks, grid, s);
-    if (nt == 8) return res ? launch_instance<T16, RES_ON, 8, KSM>(a, ksteps, nslab, row_tiles, nchunks, grid, s)
-                            : launch_instance<T16, 0, 8, KSM>(a, ksteps, nslab, row_tiles, nchunks, grid, s);
-    if (nt == 5) return res ? launch_instance<T16, RES_ON, 5, KSM>(a, ksteps, nslab, row_tiles, nchunks, grid, s)
-                            : launch_instance<T16, 0, 5, KSM>(a, ksteps, nslab, row_tiles, nchunks, grid, s);
-    return false;
+    switch (g.nt) {
+    case 10: res ? launch_res<T16, RES_ON, 10, KSM>(a, g, s) : launch_res<T16, 0, 10, KSM>(a, g, s); break;
+    case 8: res ? launch_res<T16, RES_ON, 8, KSM>(a, g, s) : launch_res<T16, 0, 8, KSM>(a, g, s); break;
+    case 5: res ? launch_res<T16, RES_ON, 5, KSM>(a, g, s) : launch_res<T16, 0, 5, KSM>(a, g, s); break;
+    }
 }
 }  // namespace prx_gemmrow_dev
 
-// one translation unit per (operand format, K range): gemmrow_h6.hip, gemmrow_h10.hip, gemmrow_b6.hip, gemmrow_b10.hip
-bool prx_gemmrow_launch_h6(const prx_gemm_dev::GemmArgs& a, int nt, int ksteps, int nslab, int row_tiles, int nchunks, int grid, hipStream_t s);
-bool prx_gemmrow_launch_h10(const prx_gemm_dev::GemmArgs& a, int nt, int ksteps, int nslab, int row_tiles, int nchunks, int grid, hipStream_t s);
-bool prx_gemmrow_launch_b6(const prx_gemm_dev::GemmArgs& a, int nt, int ksteps, int nslab, int row_tiles, int nchunks, int grid, hipStream_t s);
-bool prx_gemmrow_launch_b10(const prx_gemm_dev::GemmArgs& a, int nt, int ksteps, int nslab, int row_tiles, int nchunks, int grid, hipStream_t s);
-bool prx_gemmrow_launch_h20(const prx_gemm_dev::GemmArgs& a, int ksteps, int nslab, int row_tiles, int nchunks, int grid, hipStream_t s);
-bool prx_gemmrow_launch_b20(const prx_gemm_dev::GemmArgs& a, int ksteps, int nslab, int row_tiles, int nchunks, int grid, hipStream_t s);
+// gemmrow_h6.hip, gemmrow_h10.hip, gemmrow_h20.hip: IEEE half operands, 16-bit residual streams; gemmrow_b*.hip: bf16, fp32 residuals
+void prx_gemmrow_launch_h6(const prx_gemm_dev::GemmArgs& a, const prx_gemmrow_dev::RowGrid& g, hipStream_t s);
+void prx_gemmrow_launch_h10(const prx_gemm_dev::GemmArgs& a, const prx_gemmrow_dev::RowGrid& g, hipStream_t s);
+void prx_gemmrow_launch_h20(const prx_gemm_dev::GemmArgs& a, const prx_gemmrow_dev::RowGrid& g, hipStream_t s);
+void prx_gemmrow_launch_b6(const prx_gemm_dev::GemmArgs& a, const prx_gemmrow_dev::RowGrid& g, hipStream_t s);
+void prx_gemmrow_launch_b10(const prx_gemm_dev::GemmArgs& a, const prx_gemmrow_dev::RowGrid& g, hipStream_t s);
+void prx_gemmrow_launch_b20(const prx_gemm_dev::GemmArgs& a, const prx_gemmrow_dev::RowGrid& g, hipStream_t s);

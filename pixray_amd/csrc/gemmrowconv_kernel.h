@@ -16,6 +16,19 @@
 
 namespace prx_gemmrow_dev {
 
+// ---- the kernels that exist, written once: prx_gemmrow_plan (gemmrow.hip) accepts by these, launch_conv below instantiates by them ----
+// (N, Cin) -> NT, RING, WAVES (see the kernel).  Measured: the ring + 16 waves loses on Cin = 80 -- N = 80: 125 -> 133 us, N = 40: 371 ->
+// 466 us -- where a tile's 23 fragments fit the registers; 16 waves of the register form win on the stem's 40 -> 40: 239 -> 176 us
+struct RowConvShape { int n, cin, nt, ring, waves; };
+constexpr RowConvShape kRowConvShapes[] = {{80, 80, 5, 0, 8}, {80, 40, 5, 0, 8}, {40, 80, 3, 0, 8}, {40, 40, 3, 0, 16}, {160, 160, 3, 9, 16}};
+constexpr int row_conv_shape(int N, int Cin) {      // index into kRowConvShapes, -1: none
+    for (int i = 0; i < (int)(sizeof(kRowConvShapes) / sizeof(kRowConvShapes[0])); ++i)
+        if (kRowConvShapes[i].n == N && kRowConvShapes[i].cin == Cin) return i;
+    return -1;
+}
+// the epilogues: bias + ReLU forward, the saved activation's ReLU mask backward
+constexpr bool row_conv_act(int act) { return act == PRX_ACT_RELU || act == PRX_ACT_MUL_RELUMASK; }
+
 // NT: 16-column tiles of a slab (5: 80 columns as 2 pairs + a lone tile; 3: 40 columns as 1 pair + the first half of a lone tile)
 // CIN8: Cin / 8
 // RING: 0 = all K steps of a tile live in registers (9 Cin <= 736); else the K loop runs over a ring of RING operand fragments, each
@@ -198,30 +211,28 @@ __global__ __launch_bounds__(WAVES * 64) void gemmrowconv_kernel(GemmArgs a, int
     }
 }
 
-template <typename T16, int ACT>
-inline bool launch_conv_act(const GemmArgs& a, int row_tiles, int n_cu, hipStream_t s) {
-    const int N = a.d.N, Cin = a.d.Cin;
-    // one persistent workgroup per CU; the grid is a whole number of (8 XCDs x nslab) groups
-#define GRC_CASE(N_, CIN_, NT_, RING_, WAVES_)                                                                                            \
-    if (N == N_ && Cin == CIN_) {                                                                                                \
-        const int nslab = N_ / (NT_ == 5 ? 80 : 40), group = 8 * nslab;                                                          \
-        const int grid = (n_cu / group > 0 ? n_cu / group : 1) * group, nchunks = (grid / group) * 8;                            \
-        hipLaunchKernelGGL((gemmrowconv_kernel<T16, ACT, NT_, CIN_ / 8, RING_, WAVES_>), dim3(grid), dim3(WAVES_ * 64), 0, s, a, row_tiles, nchunks, nslab); \
-        return true;                                                                                                             \
-    }
-    // (measured: the ring + 16 waves loses on Cin = 80 -- N = 80: 125 -> 133 us, N = 40: 371 -> 466 us -- where a tile's 23 fragments fit the
-    // registers; 16 waves of the register form win on the stem's 40 -> 40: 239 -> 176 us)
-    GRC_CASE(80, 80, 5, 0, 8) GRC_CASE(80, 40, 5, 0, 8) GRC_CASE(40, 80, 3, 0, 8) GRC_CASE(40, 40, 3, 0, 16) GRC_CASE(160, 160, 3, 9, 16)
-#undef GRC_CASE
-    return false;
+// one persistent workgroup per CU; the grid is a whole number of (8 XCDs x nslab) groups
+template <typename T16, int ACT, int I>
+inline void launch_conv_shape(const GemmArgs& a, int row_tiles, int n_cu, hipStream_t s) {
+    constexpr RowConvShape c = kRowConvShapes[I];
+    const int nslab = c.n / (c.nt == 5 ? 80 : 40), group = 8 * nslab;
+    const int grid = (n_cu / group > 0 ? n_cu / group : 1) * group, nchunks = (grid / group) * 8;
+    hipLaunchKernelGGL((gemmrowconv_kernel<T16, ACT, c.nt, c.cin / 8, c.ring, c.waves>), dim3(grid), dim3(c.waves * 64), 0, s, a, row_tiles, nchunks, nslab);
 }
+template <typename T16, int ACT, int I = 0>
+inline void launch_conv_act(const GemmArgs& a, int shape, int row_tiles, int n_cu, hipStream_t s) {
+    if constexpr (I < (int)(sizeof(kRowConvShapes) / sizeof(kRowConvShapes[0]))) {
+        if (shape == I) launch_conv_shape<T16, ACT, I>(a, row_tiles, n_cu, s);
+        else launch_conv_act<T16, ACT, I + 1>(a, shape, row_tiles, n_cu, s);
+    }
+}
+// shape: the kRowConvShapes entry of (N, Cin) (prx_gemmrow_plan found it; the activation is one of row_conv_act's)
 template <typename T16>
-inline bool launch_conv(const GemmArgs& a, int row_tiles, int n_cu, hipStream_t s) {
-    if (a.d.act == PRX_ACT_RELU) return launch_conv_act<T16, PRX_ACT_RELU>(a, row_tiles, n_cu, s);
-    if (a.d.act == PRX_ACT_MUL_RELUMASK) return launch_conv_act<T16, PRX_ACT_MUL_RELUMASK>(a, row_tiles, n_cu, s);
-    return false;
+inline void launch_conv(const GemmArgs& a, int shape, int row_tiles, int n_cu, hipStream_t s) {
+    if (a.d.act == PRX_ACT_RELU) launch_conv_act<T16, PRX_ACT_RELU>(a, shape, row_tiles, n_cu, s);
+    else launch_conv_act<T16, PRX_ACT_MUL_RELUMASK>(a, shape, row_tiles, n_cu, s);
 }
 }  // namespace prx_gemmrow_dev
 
-bool prx_gemmrowconv_launch_h(const prx_gemm_dev::GemmArgs& a, int row_tiles, int n_cu, hipStream_t s);
-bool prx_gemmrowconv_launch_b(const prx_gemm_dev::GemmArgs& a, int row_tiles, int n_cu, hipStream_t s);
+void prx_gemmrowconv_launch_h(const prx_gemm_dev::GemmArgs& a, int shape, int row_tiles, int n_cu, hipStream_t s);
+void prx_gemmrowconv_launch_b(const prx_gemm_dev::GemmArgs& a, int shape, int row_tiles, int n_cu, hipStream_t s);

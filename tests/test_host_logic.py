@@ -807,6 +807,105 @@ def test_gemm_planner_gives_the_8phase_kernel_whole_rounds_of_tiles():
         assert r == M or r % 256 == 0
 
 
+def test_gemm_plan_query_gives_the_runner_launches_and_follows_the_overrides():
+    """The launch planner through prx_gemm_plan (host code, no device): kernel family, tile and split-K of the first launch, the
+    8-phase row split and the launch of the rows after it.  The runner products are the distinct ones of BASELINE.json
+    configs[1..3] (configs[1] also at precision f32), with the tile and split-K the engine's per-launch profile dump recorded for
+    them on an MI355X (256 CUs) before the planner was separated from the launch; then the tuning overrides of a context and a workspace too small for the split-K rule."""
+    lib = _lib.load()
+    V1, GLDS, F32, FIT, P8, ROW, ROWCONV = range(7)
+
+    def plan(M, N, K, prec="fp16", conv=None, act=0, ws=64 << 20, ctx=None, n_cu=256):
+        g = _lib.GemmArgs(ctx=None)
+        g.A, g.B, g.bias_n, g.out_bf16 = 1 << 20, 2 << 20, 3 << 20, 4 << 20      # 16-byte aligned; never dereferenced
+        g.M, g.N, g.K, g.lda, g.ldb, g.ldc_bf16, g.alpha, g.act = M, N, K, K, K, N, 1.0, act
+        g.f32 = {"bf16": 0, "f32": 1, "fp16": 2}[prec]
+        if conv:
+            g.a_mode, g.H, g.W, g.Cin, g.lda = 1, conv[0], conv[1], K // 9, K // 9
+        out = (ctypes.c_int * 9)()
+        assert lib.prx_gemm_plan(ctx, ctypes.byref(g), ws, n_cu, out) == 0, _lib.last_error()
+        return tuple(out[:4]) if out[4] == 0 else (tuple(out[:4]), out[4], tuple(out[5:]))     # (the 8-phase rows: first launch, rows, rest)
+
+    # the launches the profile dump recorded at the parent of the planner (tests/golden/gemm_plan_launches.csv: config, M, N, K, mode,
+    # tile -- + 1000 a fit tile, + 2000 a row-streaming kernel --, bn, splits), and the plan of each runner product against them
+    with open(os.path.join(HERE, "golden", "gemm_plan_launches.csv")) as f:
+        dumped = {tuple([r[0]] + [int(v) for v in r[1:]]) for r in (line.strip().split(",") for line in f.readlines()[1:])}
+
+    def runner(cfg, expect, M, N, K, prec="fp16", conv=None, **kw):
+        got = plan(M, N, K, prec, conv, **kw)
+        assert got == expect, (M, N, K, got)
+        mode = (1 if conv else 0) + (8 if prec == "f32" else 0)
+        launches = [(M, got)] if len(got) == 4 else [(got[1], got[0])] + ([(M - got[1], got[2])] if got[2][0] >= 0 else [])
+        for rows, (fam, bm, bn, splits) in launches:
+            tile = bm + (1000 if fam == FIT else 2000 if fam in (ROW, ROWCONV) else 0)
+            assert (cfg, rows, N, K, mode, tile, bn, splits) in dumped, (cfg, rows, N, K, mode, tile, bn, splits)
+
+    # configs[1] (VQGAN 256^2 + ViT-B/32, 64 cutouts), IEEE half operands: fit tiles for the tower and most decoder convolutions
+    runner("cfg1", (FIT, 160, 256, 1), 3200, 3072, 768)
+    runner("cfg1", (FIT, 80, 128, 1), 3200, 768, 3072)
+    runner("cfg1", (FIT, 160, 192, 1), 3200, 2304, 768)
+    runner("cfg1", (FIT, 256, 128, 1), 65536, 128, 1152, conv=(256, 256))
+    runner("cfg1", (FIT, 256, 16, 1), 65536, 8, 1152, conv=(256, 256))
+    runner("cfg1", (FIT, 16, 32, 1), 256, 512, 4608, conv=(16, 16))
+    runner("cfg1", (GLDS, 64, 64, 1), 256, 512, 256)
+    runner("cfg1", (GLDS, 128, 64, 1), 64, 3072, 768)
+    # ... in the exact mode: fp32 fit kernels, the 4-wave fp32 kernels with split-K
+    runner("cfg1_f32", (FIT, 256, 128, 1), 3200, 2304, 768, "f32")
+    runner("cfg1_f32", (F32, 128, 64, 1), 3200, 3072, 768, "f32")
+    runner("cfg1_f32", (F32, 64, 64, 3), 256, 1536, 512, "f32")
+    runner("cfg1_f32", (F32, 128, 64, 6), 64, 3072, 768, "f32")
+    runner("cfg1_f32", (F32, 128, 128, 1), 65536, 128, 72, "f32", conv=(256, 256))
+    # configs[2] (ViT-B/16 at 128 cutouts + RN50x4): the 8-phase split, the row-streaming kernels
+    runner("cfg2", ((P8, 256, 256, 1), 21760, (GLDS, 64, 64, 1)), 25216, 768, 768)
+    runner("cfg2", ((P8, 256, 256, 1), 25216, (-1, 0, 0, 0)), 25216, 3072, 768)
+    runner("cfg2", (ROW, 16, 160, 1), 41472, 1280, 320, act=3)
+    runner("cfg2", (ROW, 16, 80, 1), 663552, 80, 320)
+    runner("cfg2", (ROWCONV, 16, 80, 1), 165888, 160, 1440, conv=(72, 72), act=3)
+    runner("cfg2", (GLDS, 128, 128, 1), 41472, 320, 2880, conv=(72, 72), act=3)
+    # configs[3] (ViT-L/14 at 256 cutouts + the StyleLoss VGG16): 4-wave split-K, the 8-phase split with a fit tile after it
+    runner("cfg3", (GLDS, 64, 64, 4), 1024, 128, 1152, conv=(32, 32), act=3)
+    runner("cfg3", (GLDS, 64, 64, 4), 256, 592, 1024)
+    runner("cfg3", ((P8, 256, 256, 1), 65536, (FIT, 16, 64, 1)), 65792, 1024, 4096)
+    assert lib.prx_gemm_plan_rows_8phase(None, 65792, 1024, 4096) == 65536
+    # the workspace bounds split-K; another CU count moves the 8-phase split
+    assert plan(256, 592, 1024, ws=2 * 256 * 592 * 4) == (GLDS, 64, 64, 2)
+    assert plan(256, 592, 1024, ws=0) == (GLDS, 64, 64, 1)
+    assert plan(65792, 1024, 4096, n_cu=304) == ((P8, 256, 256, 1), 65792, (-1, 0, 0, 0))
+
+    ctx = lib.prx_gemm_ctx_create()
+    try:
+        ov = lambda bm, splits, bn=0: lib.prx_gemm_tile_override(ctx, bm, bn, splits)
+        ov(-7, 0)                                              # no fit tiles
+        assert plan(3200, 3072, 768, ctx=ctx) == (GLDS, 128, 64, 1)
+        ov(-7, 1); ov(-9, 0)                                   # no fit tiles for the implicit convolutions
+        assert plan(65536, 128, 1152, conv=(256, 256), ctx=ctx) == (GLDS, 128, 128, 1)
+        assert plan(3200, 3072, 768, ctx=ctx) == (FIT, 160, 256, 1)
+        ov(-9, 1); ov(-3, 0)                                   # the register-staged 4-wave kernels
+        assert plan(256, 512, 256, ctx=ctx) == (V1, 64, 64, 1)
+        ov(-3, 1)
+        ov(128, 1, 64)                                         # a forced tile overrides the fit, 8-phase and row rules
+        assert plan(3200, 3072, 768, ctx=ctx) == (GLDS, 128, 64, 1)
+        assert plan(25216, 768, 768, ctx=ctx) == (GLDS, 128, 64, 1)
+        assert plan(41472, 1280, 320, act=3, ctx=ctx) == (GLDS, 128, 64, 1)
+        ov(128, 4, 128)                                        # ... with split-K, when there is a workspace
+        assert plan(3200, 768, 3072, ctx=ctx) == (GLDS, 128, 128, 4)
+        assert plan(3200, 768, 3072, ws=0, ctx=ctx) == (GLDS, 128, 128, 1)
+        ov(-12, 1); ov(128, 1, 128)                            # a shape both families have: the fit kernel
+        assert plan(3200, 3072, 768, ctx=ctx) == (FIT, 128, 128, 1)
+        ov(-12, 0); ov(0, 0)
+        lib.prx_gemm_tile_rule(ctx, 3200, 768, 3072, 0, 128, 64, 2)      # a rule: that shape only
+        lib.prx_gemm_tile_rule(ctx, 25216, 768, 768, 0, 128, 128, 0)
+        assert plan(3200, 768, 3072, ctx=ctx) == (GLDS, 128, 64, 2)
+        assert plan(3200, 3072, 768, ctx=ctx) == (FIT, 160, 256, 1)
+        assert plan(25216, 768, 768, ctx=ctx) == (GLDS, 128, 128, 1)
+        lib.prx_gemm_tile_rule(ctx, 0, 0, 0, 0, 0, 0, 0)
+        assert plan(4096, 1280, 320, act=3, ctx=ctx) == (GLDS, 64, 64, 1)
+        ov(-14, 1 << 20)                                       # row-streaming kernels from 1 Mi output elements on
+        assert plan(4096, 1280, 320, act=3, ctx=ctx) == (ROW, 16, 160, 1)
+    finally:
+        lib.prx_gemm_ctx_destroy(ctx)
+
+
 def test_bench_bare_gpus_form_spawns_its_own_ranks():
     """`python bench.py --gpus N` without a launcher (it raised SystemExit) re-executes itself under
     torch.distributed.run with the driver's own flags; --dry-run checks the mechanics on the host: N ranks rendezvous on
