@@ -569,6 +569,29 @@ int prx_pixel_raster_bwd(const float* verts, const int* nverts, const float* col
                          const int* shape_entries, int n_shapes, float* grad, prx_stream_t s);
 int prx_pixel_sample_offsets(int w, int h, const int* seed, float* uv, prx_stream_t s);
 
+/* --- stroke drawers (pixray linedrawer.py `line_sketch`, clipdrawer.py `clipdraw`): csrc/stroke_raster.hip.  A w x h canvas of
+ * open paths of cubic Bezier segments, stroked with a pre-filtered coverage clamp(width - d + 0.5, 0, 1) (width = the
+ * half-width, d = the distance to the centre line), composited in index order over an optional paper colour ("over", 2 x 2
+ * jittered samples per pixel, the pixel drawer's jitter; conventions in INTEGRATION.md).
+ * points [P][2] (pixels); path k owns points[path_start[k] .. path_start[k + 1]), 1 + 3 S of them for S segments, at most
+ * max_points (<= PRX_STROKE_MAX_POINTS); widths [n], colors [n][4] RGBA; paper [4] RGBA or NULL.  seed = one device word.
+ * Workspaces, sized from n, max_points and the canvas alone (tiles = ceil(w / 16) * ceil(h / 16)): boxes [n][4] fp32,
+ * tile_count [tiles] int32, tile_paths [tiles][n] int32; the backward's partials [tiles][n][2 max_points + 5] fp64 and
+ * paper_partials [tiles][4] fp64.  Both calls rebuild boxes and tile lists from the points on the device.
+ * forward: out [h][w][4] RGBA.  backward: gout [h][w][4] -> grad_points [P][2], grad_widths [n], grad_colors [n][4], and
+ * grad_paper [4] when not NULL (then paper and paper_partials are required).  Fixed summation order: a run repeats bit for bit.
+ * sample offsets: uv [h][w][4][2], as prx_pixel_sample_offsets. */
+#define PRX_STROKE_TILE 16
+#define PRX_STROKE_MAX_POINTS 193
+int prx_stroke_raster_fwd(const float* points, const int* path_start, int n_paths, int max_points, const float* widths,
+                          const float* colors, const float* paper, int w, int h, const int* seed, float* boxes, int* tile_count,
+                          int* tile_paths, float* out, prx_stream_t s);
+int prx_stroke_raster_bwd(const float* points, const int* path_start, int n_paths, int max_points, const float* widths,
+                          const float* colors, const float* paper, int w, int h, const int* seed, const float* gout, float* boxes,
+                          int* tile_count, int* tile_paths, double* partials, double* paper_partials, float* grad_points,
+                          float* grad_widths, float* grad_colors, float* grad_paper, prx_stream_t s);
+int prx_stroke_sample_offsets(int w, int h, const int* seed, float* uv, prx_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

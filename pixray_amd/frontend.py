@@ -17,8 +17,7 @@ Not carried over (outside SURVEY.md section 8): the notebook display calls, the 
 parsing helper of util.py, the SLIP perceptors, ffmpeg video / gif assembly (the frame files are written;
 `make_video` / animation gif need ffmpeg and are skipped with a message when it is absent), the per-frame target-image prompt
 table of the animation mode (`pmsTargetTable`, pixray.py:772-795: target images score every frame here), the vdiff drawer (its
-source is not in the reference checkout), and the `line_sketch` and `clipdraw` drawers (strokes differentiated with respect to
-their control points).
+source is not in the reference checkout), and the super_resolution drawer (it needs RealESRGAN weights).
 """
 from __future__ import annotations
 

@@ -544,7 +544,7 @@ def prompt_loss(input, embed, weight=1.0, stop=float("-inf"), denom=None):
 def adam_clamp_step_dev(z, exp_avg, exp_avg_sq, grad, zmin, zmax, hyper, betas=(0.9, 0.999), eps=1e-8):
     """Same, with {lr / bias_correction1, sqrt(bias_correction2)} read from the device tensor `hyper` (graph replay)."""
     _need_cuda(z, grad, hyper)
-    hw = z.shape[-1] * z.shape[-2]
+    hw = z.shape[-1] * z.shape[-2] if z.dim() >= 2 else z.numel()     # 1-D leaves (stroke widths, paper): one plane
     call("prx_adam_clamp_step_dev", z, exp_avg, exp_avg_sq, grad, zmin, zmax, hw, z.numel(), hyper, float(betas[0]),
          float(betas[1]), float(eps), _stream())
 
@@ -553,7 +553,7 @@ def adam_clamp_step(z, exp_avg, exp_avg_sq, grad, zmin, zmax, lr, step, betas=(0
     """In-place Adam step on z fused with the per-channel clip_z clamp."""
     _need_cuda(z, grad)
     assert z.is_contiguous() and grad.is_contiguous() and z.dtype == torch.float32
-    hw = z.shape[-1] * z.shape[-2]
+    hw = z.shape[-1] * z.shape[-2] if z.dim() >= 2 else z.numel()     # 1-D leaves (stroke widths, paper): one plane
     call("prx_adam_clamp_step", z, exp_avg, exp_avg_sq, grad, zmin, zmax, hw, z.numel(), float(lr), float(betas[0]),
          float(betas[1]), float(eps), int(step), _stream())
 
@@ -1204,4 +1204,99 @@ def pixel_sample_offsets(width: int, height: int, seed):
     _need_cuda(seed)
     uv = torch.empty(int(height), int(width), 4, 2, device=seed.device)
     call("prx_pixel_sample_offsets", int(width), int(height), _pixel_seed(seed), uv, _stream())
+    return uv
+
+
+# --------------------------------------------------------------------------------------- stroke drawers (csrc/stroke_raster.hip)
+STROKE_TILE, STROKE_MAX_POINTS = 16, 193
+STROKE_MAX_PATHS = 16384
+STROKE_MAX_WORKSPACE = 8 << 30          # bytes of fp64 partials the backward may ask for
+
+
+class StrokeRasterScene:
+    """The static sizes of a stroke scene and the kernels' workspaces, allocated once (the drawer's load_model): path k owns
+    points[path_start[k] .. path_start[k + 1]) (1 + 3 S points for S cubic segments, at most STROKE_MAX_POINTS); the per-path
+    boxes, the per-tile path lists ([tiles][n]: none can overflow) and the backward's per-(tile, path) partial gradients are
+    sized from the path count, the longest path and the canvas alone, so that nothing is allocated or sized from device data
+    in an iteration.  The geometry itself (points, widths) is read by every launch."""
+
+    def __init__(self, path_start, width: int, height: int, device):
+        import numpy as np
+        ps = np.asarray(path_start, dtype=np.int64)
+        if ps.ndim != 1 or len(ps) < 2 or ps[0] != 0:
+            raise PrxError("stroke raster: path_start must be [n + 1] offsets from 0")
+        counts = np.diff(ps)
+        n = len(counts)
+        if (counts < 1).any() or ((counts - 1) % 3 != 0).any():
+            raise PrxError("stroke raster: every path needs 1 + 3 S points (S cubic segments)")
+        if int(counts.max()) > STROKE_MAX_POINTS:
+            raise PrxError(f"stroke raster: a path has {int(counts.max())} points; at most {STROKE_MAX_POINTS} "
+                           f"({(STROKE_MAX_POINTS - 1) // 3} segments) are supported")
+        if n > STROKE_MAX_PATHS:
+            raise PrxError(f"stroke raster: {n} paths; at most {STROKE_MAX_PATHS} are supported")
+        self.width, self.height, self.n_paths, self.n_points = int(width), int(height), n, int(ps[-1])
+        if self.width < 1 or self.height < 1:
+            raise PrxError(f"stroke raster: canvas {width} x {height}")
+        self.max_points = int(counts.max())
+        self.tiles = ((self.width + STROKE_TILE - 1) // STROKE_TILE) * ((self.height + STROKE_TILE - 1) // STROKE_TILE)
+        self.slot = 2 * self.max_points + 5
+        need = self.tiles * n * self.slot * 8
+        if need > STROKE_MAX_WORKSPACE:
+            raise PrxError(f"stroke raster: {n} paths of up to {self.max_points} points on a {width} x {height} canvas need "
+                           f"{need / 2 ** 30:.1f} GiB of gradient partials; at most {STROKE_MAX_WORKSPACE >> 30} GiB are supported")
+        self.device = torch.device(device)
+        self.path_start = torch.from_numpy(ps.astype(np.int32)).to(self.device)
+        self.boxes = torch.empty(n, 4, device=self.device)
+        self.tile_count = torch.empty(self.tiles, dtype=torch.int32, device=self.device)
+        self.tile_paths = torch.empty(self.tiles * n, dtype=torch.int32, device=self.device)
+        self.partials = torch.empty(self.tiles * n * self.slot, dtype=torch.float64, device=self.device)
+        self.paper_partials = torch.empty(self.tiles * 4, dtype=torch.float64, device=self.device)
+
+    def _check(self, points, widths, colors, paper):
+        n = self.n_paths
+        for t, shape, what in ((points, (self.n_points, 2), "points"), (widths, (n,), "widths"), (colors, (n, 4), "colours")):
+            if t.dtype != torch.float32 or tuple(t.shape) != shape:
+                raise PrxError(f"stroke raster: {what} must be fp32 {list(shape)}, got {tuple(t.shape)} {t.dtype}")
+        if paper is not None and (paper.dtype != torch.float32 or tuple(paper.shape) != (4,)):
+            raise PrxError(f"stroke raster: the paper colour must be fp32 [4], got {tuple(paper.shape)} {paper.dtype}")
+
+
+class _StrokeRasterFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, widths, colors, paper, scene, seed):
+        scene._check(points, widths, colors, paper)
+        p, w, c = points.contiguous(), widths.contiguous(), colors.contiguous()
+        pa = paper.contiguous() if paper is not None else None
+        out = torch.empty(scene.height, scene.width, 4, device=p.device)
+        call("prx_stroke_raster_fwd", p, scene.path_start, scene.n_paths, scene.max_points, w, c, pa, scene.width, scene.height, seed,
+             scene.boxes, scene.tile_count, scene.tile_paths, out, _stream())
+        ctx.save_for_backward(p, w, c, pa, seed)
+        ctx.scene = scene
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        p, w, c, pa, seed = ctx.saved_tensors
+        sc = ctx.scene
+        gp, gw, gc = torch.empty_like(p), torch.empty_like(w), torch.empty_like(c)
+        gpa = torch.empty_like(pa) if pa is not None and ctx.needs_input_grad[3] else None
+        call("prx_stroke_raster_bwd", p, sc.path_start, sc.n_paths, sc.max_points, w, c, pa, sc.width, sc.height, seed, g.contiguous(),
+             sc.boxes, sc.tile_count, sc.tile_paths, sc.partials, sc.paper_partials, gp, gw, gc, gpa, _stream())
+        need = ctx.needs_input_grad
+        return gp if need[0] else None, gw if need[1] else None, gc if need[2] else None, gpa, None, None
+
+
+def stroke_raster(points, widths, colors, paper, scene: StrokeRasterScene, seed):
+    """The stroke drawers' raster [H, W, 4] (RGBA, un-premultiplied) of the open cubic paths of `scene`: `points` [P, 2] in
+    pixels, `widths` [n] (half-widths), `colors` [n, 4] RGBA, `paper` [4] RGBA under everything or None.  Differentiable
+    w.r.t. all four.  `seed`: a one-word int32 device tensor holding the jitter seed, read by the kernels."""
+    _need_cuda(points, widths, colors, seed)
+    return _StrokeRasterFn.apply(points, widths, colors, paper, scene, _pixel_seed(seed))
+
+
+def stroke_sample_offsets(width: int, height: int, seed):
+    """diagnostic: the stroke kernels' jitter (u, v) of sample 2 sy + sx of every pixel, [H, W, 4, 2] fp32"""
+    _need_cuda(seed)
+    uv = torch.empty(int(height), int(width), 4, 2, device=seed.device)
+    call("prx_stroke_sample_offsets", int(width), int(height), _pixel_seed(seed), uv, _stream())
     return uv

@@ -8,7 +8,8 @@ contributes its globals (`add_globals(args) -> dict`).  The result is the list o
 as `custom_losses=` and the `lossGlobals` dict handed to every `get_loss` call.
 
 `class_table` maps `--drawer` names to drawer classes (the HIP VQGAN drawer, the fft spectrum drawer, the polygon grid of the
-reference's `pixel` drawer on the HIP rasteriser, and the nearest-upsampled pixel grid that stands in for its `fast_pixel`); `filters_class_table` holds the reference's three
+reference's `pixel` drawer on the HIP rasteriser, the nearest-upsampled pixel grid that stands in for its `fast_pixel`, and its
+`line_sketch` and `clipdraw` stroke drawers on the HIP stroke rasteriser); `filters_class_table` holds the reference's three
 filters (`lookup`, `tiler`, `wallpaper`: builtin_filters.py) and `loss_class_table` its losses (`style`: style_loss.py;
 `palette`, `saturation`, `symmetry`, `smoothness`, `edge`: builtin_losses.py), all on HIP kernels.  `resmem` and
 `aesthetic` are registered so that asking for them says why they are unavailable (their model weights are not shipped).
@@ -23,10 +24,12 @@ from .interfaces import DrawingInterface, FilterInterface, LossInterface
 from .pixel_drawer import PixelDrawer
 from .pixel_grid_drawer import PixelGridDrawer
 from .prompt import parse_prompt
+from .stroke_drawer import ClipDrawer, LineDrawer
 from .style_loss import StyleLoss
 from .vqgan_drawer import VqganDrawer
 
-class_table: Dict[str, type] = {"vqgan": VqganDrawer, "pixel": PixelDrawer, "fft": FftDrawer, "fast_pixel": PixelGridDrawer}
+class_table: Dict[str, type] = {"vqgan": VqganDrawer, "pixel": PixelDrawer, "fft": FftDrawer, "fast_pixel": PixelGridDrawer,
+                               "line_sketch": LineDrawer, "clipdraw": ClipDrawer}
 filters_class_table: Dict[str, type] = dict(BUILTIN_FILTERS)
 loss_class_table: Dict[str, type] = {**BUILTIN_LOSSES, "style": StyleLoss, **UNAVAILABLE_LOSSES}
 
