@@ -427,6 +427,34 @@ int prx_adam_clamp_step_dev(float* z, float* exp_avg, float* exp_avg_sq, const f
                             const float* zmax, int hw, size_t n, const float* hyper, float beta1, float beta2, float eps,
                             prx_stream_t s);
 
+/* --- the other rules of --optimiser (pixray.py:541-550: optim.AdamW / Adagrad / Adamax, torch_optimizer's DiffGrad), only `lr`
+ * given as there, each fused with VqganDrawer.clip_z (vqgan.py:202-204); the step-dependent scalars are read from device memory
+ * like prx_adam_clamp_step_dev's.  p / grad / state tensors: n fp32 elements.  zmin / zmax: per channel, both or both NULL; with
+ * them p is seen as [rows, C, hw] (n a multiple of C * hw), without them C and hw are ignored.  State tensors and hyper[0..2]:
+ *   PRX_OPT_ADAMW    s1 exp_avg, s2 exp_avg_sq, s3 NULL        {lr / (1 - beta1^t), sqrt(1 - beta2^t), 1 - lr * weight_decay}
+ *   PRX_OPT_ADAGRAD  s1 sum, s2 NULL, s3 NULL (betas unused)   {lr}
+ *   PRX_OPT_ADAMAX   s1 exp_avg, s2 exp_inf, s3 NULL           {lr / (1 - beta1^t)}
+ *   PRX_OPT_DIFFGRAD s1 exp_avg, s2 exp_avg_sq, s3 prev. grad  {lr * sqrt(1 - beta2^t) / (1 - beta1^t)}
+ * hyper holds 4 floats.  The betas are doubles so that 1 - beta is formed before it is rounded to fp32. */
+#define PRX_OPT_ADAMW 0
+#define PRX_OPT_ADAGRAD 1
+#define PRX_OPT_ADAMAX 2
+#define PRX_OPT_DIFFGRAD 3
+int prx_optim_step_dev(int rule, float* p, float* s1, float* s2, float* s3, const float* grad, const float* zmin,
+                       const float* zmax, int C, int hw, size_t n, const float* hyper, double beta1, double beta2, float eps,
+                       prx_stream_t s);
+
+/* --- torch_optimizer's AdamP([z], lr) (pixray.py:549-550; delta as given, weight decay 0, nesterov off) fused with clip_z: two
+ * launches, no atomics (pass 1: moments + per-workgroup partial dot products into `scratch`; pass 2: every workgroup adds the
+ * partials in the same order, takes the projection decision and applies update and clamp).  rows >= 1: the tensor's shape[0], the
+ * test runs on the [rows, n / rows] view, then on [1, n]; rows == 0: a 1-D tensor, never projected.  rows <= 4096.
+ * hyper = {lr / (1 - beta1^t), sqrt(1 - beta2^t)} (4 floats); scratch: prx_optim_adamp_scratch_floats(rows, n) floats, 16-byte
+ * aligned, `scratch_floats` its size; bounds as for prx_optim_step_dev. */
+size_t prx_optim_adamp_scratch_floats(int rows, size_t n);
+int prx_optim_adamp_step_dev(float* p, float* exp_avg, float* exp_avg_sq, const float* grad, const float* zmin,
+                             const float* zmax, int rows, int C, int hw, size_t n, const float* hyper, float* scratch,
+                             size_t scratch_floats, double beta1, double beta2, float eps, float delta, prx_stream_t s);
+
 int prx_k_vq_nearest(const float* z, long long tok_stride, long long ch_stride, const float* codebook,
                      const float* cnorm, int P, int NC, int D, float* pmin, int* pidx, int* idx_out, float* zq,
                      prx_stream_t s);

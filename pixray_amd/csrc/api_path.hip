@@ -9,6 +9,7 @@
 #include "cutouts.h"
 #include "prompt_vq.h"
 #include "elementwise.h"
+#include "optim.h"
 #include "gemm.h"
 #include "../../include/prx.h"
 
@@ -154,6 +155,19 @@ int prx_adam_clamp_step_dev(float* z, float* exp_avg, float* exp_avg_sq, const f
                             prx_stream_t s) {
     PRX_REQUIRE(z && exp_avg && exp_avg_sq && grad && hyper, "prx_adam_clamp_step_dev: null argument");
     return prx_adam_clamp_dev(z, exp_avg, exp_avg_sq, grad, zmin, zmax, hw, n, hyper, beta1, beta2, eps, S_(s));
+}
+
+int prx_optim_step_dev(int rule, float* p, float* s1, float* s2, float* s3, const float* grad, const float* zmin,
+                       const float* zmax, int C, int hw, size_t n, const float* hyper, double beta1, double beta2, float eps,
+                       prx_stream_t s) {
+    return prx_optim_elementwise(rule, p, s1, s2, s3, grad, zmin, zmax, C, hw, n, hyper, beta1, beta2, eps, S_(s));
+}
+size_t prx_optim_adamp_scratch_floats(int rows, size_t n) { return prx_adamp_scratch_floats(rows, n); }
+int prx_optim_adamp_step_dev(float* p, float* exp_avg, float* exp_avg_sq, const float* grad, const float* zmin,
+                             const float* zmax, int rows, int C, int hw, size_t n, const float* hyper, float* scratch,
+                             size_t scratch_floats, double beta1, double beta2, float eps, float delta, prx_stream_t s) {
+    return prx_optim_adamp(p, exp_avg, exp_avg_sq, grad, zmin, zmax, rows, C, hw, n, hyper, scratch, scratch_floats, beta1, beta2,
+                           eps, delta, S_(s));
 }
 
 // kernel-level entries for the pieces above (tests)

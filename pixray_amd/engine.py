@@ -24,6 +24,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 import torch.nn.functional as F
 
+from .optimisers import HipOptimiser, check_name, make_optimiser
 from .prompt import Prompt
 
 
@@ -170,7 +171,8 @@ class Session:
                  prompts: Dict[str, Sequence[object]], *, learning_rate: float = 0.2, iterations: int = 250,
                  batches: int = 1, learning_rate_drops: Sequence[int] = (), custom_losses: Sequence[dict] = (),
                  filters: Sequence[dict] = (), args=None, init_weight: float = 0.0, init_weight_dist: float = 0.0,
-                 z_orig=None, optimiser_factory=None, seed: int = 0, group=None, rank: int = 0, world_size: int = 1,
+                 z_orig=None, optimiser_factory=None, optimiser: str = "Adam", seed: int = 0, group=None, rank: int = 0,
+                 world_size: int = 1,
                  auto_stop: bool = False, image_prompts: Optional[Dict[str, Sequence[torch.Tensor]]] = None,
                  image_prompt_weight: Optional[float] = None, image_prompt_shuffle: bool = False,
                  z_labels: Sequence[torch.Tensor] = (), image_label_weight: float = 1.0, init_weight_pix: float = 0.0,
@@ -237,6 +239,8 @@ class Session:
                 img.putalpha(overlay_alpha)
             self.overlay_image_rgba = img
         self.optimiser_factory = optimiser_factory
+        # --optimiser (pixray.py:539-550): the rule for a drawer that leaves the optimiser to the session; an `optimiser_factory` wins
+        self.optimiser = check_name(optimiser)
         # class of the throwaway Prompts built per iteration for image prompts (pixray.py:1331-1333); the HIP Prompt unless a
         # caller assembles the loop from other parts (CPU tests)
         self.prompt_factory = prompt_factory if prompt_factory is not None else Prompt
@@ -293,9 +297,9 @@ class Session:
                 if hasattr(self.drawer, "_zmin_flat"):
                     bounds = (self.drawer._zmin_flat, self.drawer._zmax_flat)
                     self.drawer._fused_clamp = True
-                new_opts = [HipAdam([z], lr=lr, bounds=bounds)]
+                new_opts = [make_optimiser(self.optimiser, [z], lr, bounds)]     # "Adam": HipAdam
             else:
-                new_opts = [torch.optim.Adam([z], lr=lr)]
+                new_opts = [make_optimiser(self.optimiser, [z], lr)]             # "Adam": torch.optim.Adam
         return new_opts
 
     # ------------------------------------------------------------------ forward of one iteration
@@ -545,7 +549,7 @@ class Session:
         dev = params[0].device
         # the fused Adam kernel reads its step scalars from a fixed device buffer; a drawer plugin's plain torch Adam (FftDrawer)
         # keeps them on the host, so it is swapped for the kernel (same rule, state carried over) -- for a replayed session only
-        opts = [o if isinstance(o, HipAdam) else HipAdam.from_adam(o) for o in self.opts]
+        opts = [o if isinstance(o, (HipAdam, HipOptimiser)) else HipAdam.from_adam(o) for o in self.opts]
         if any(o is None for o in opts):
             return self._no_graph("an optimiser the fused Adam kernel cannot stand in for")
         if getattr(self.args, "transparent", False):      # the RGBA squash uses this iteration's host-drawn gray as a constant
@@ -580,7 +584,7 @@ class Session:
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         if self.cur_iteration >= self.iterations or self.cur_iteration in self.learning_rate_drops or \
-                self.apply_overlay(self.cur_iteration) or not all(isinstance(o, HipAdam) for o in self.opts):
+                self.apply_overlay(self.cur_iteration) or not all(isinstance(o, (HipAdam, HipOptimiser)) for o in self.opts):
             return self._no_graph("the next iteration is not a plain one")     # the next iteration is not a plain one: stay eager (call enable_graph again later)
         self._host_prep(self.cur_iteration)
         for o in self.opts:

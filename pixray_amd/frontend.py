@@ -520,6 +520,8 @@ def do_init(args, run: Optional[Run] = None, *, perceptor_factory: Optional[Call
     hand in CPU stand-ins."""
     from PIL import Image
     from .engine import Session
+    from .optimisers import check_name
+    check_name(args.optimiser)               # before any model is loaded (the reference dies in rebuild_optimisers, after them)
     run = run if run is not None else _RUN
     seed = resolve_seed(args.seed)
     print("Using seed:", seed)
@@ -660,7 +662,7 @@ def do_init(args, run: Optional[Run] = None, *, perceptor_factory: Optional[Call
                    init_weight_cos=args.init_weight_cos, init_image_tensor=init_image_tensor, spot_prompts=spot,
                    spot_prompts_off=spot_off, overlay_image=overlay, overlay_every=args.overlay_every,
                    overlay_offset=args.overlay_offset, overlay_until=args.overlay_until, overlay_alpha=None,
-                   prompt_factory=prompt_factory, loss_globals=loss_globals)
+                   prompt_factory=prompt_factory, loss_globals=loss_globals, optimiser=args.optimiser)
     sess.max_loss_drops = len(args.learning_rate_drops)                                       # pixray.py:1979
     sess.iter_drop_delay = 12                                                                 # pixray.py:1980
     run.session = sess

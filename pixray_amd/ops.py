@@ -558,6 +558,46 @@ def adam_clamp_step(z, exp_avg, exp_avg_sq, grad, zmin, zmax, lr, step, betas=(0
          float(betas[1]), float(eps), int(step), _stream())
 
 
+OPTIM_RULES = {"AdamW": 0, "Adagrad": 1, "Adamax": 2, "DiffGrad": 3}      # PRX_OPT_* (include/prx.h)
+
+
+def _clamp_view(p, zmin, zmax):
+    """(C, hw) of the [rows, C, hw] view the fused clip_z clamps in; (1, 1) without bounds (the kernels ignore them then)"""
+    if zmin is None:
+        assert zmax is None
+        return 1, 1
+    assert p.dim() >= 3 and zmin.numel() == zmax.numel() == p.shape[-3], "bounds are per channel of a [..., C, h, w] tensor"
+    return p.shape[-3], p.shape[-2] * p.shape[-1]
+
+
+def optim_step_dev(rule, p, states, grad, zmin, zmax, hyper, betas=(0.9, 0.999), eps=1e-8):
+    """In-place AdamW / Adagrad / Adamax / DiffGrad step on p fused with the per-channel clip_z clamp; `states`: the rule's
+    state tensors in the order of include/prx.h, `hyper`: its step scalars on the device (graph replay)."""
+    _need_cuda(p, grad, hyper)
+    assert p.is_contiguous() and grad.is_contiguous() and p.dtype == torch.float32 and all(s.is_contiguous() for s in states)
+    C, hw = _clamp_view(p, zmin, zmax)
+    s1, s2, s3 = (list(states) + [None, None])[:3]
+    call("prx_optim_step_dev", OPTIM_RULES[rule], p, s1, s2, s3, grad, zmin, zmax, C, hw, p.numel(), hyper, float(betas[0]),
+         float(betas[1]), float(eps), _stream())
+
+
+def adamp_scratch(p):
+    """the partial-sum buffer of `adamp_step_dev` for p (allocated once: a captured graph keeps its address)"""
+    rows = p.shape[0] if p.dim() > 1 else 0
+    return torch.empty(call("prx_optim_adamp_scratch_floats", rows, p.numel()), dtype=torch.float32, device=p.device)
+
+
+def adamp_step_dev(p, exp_avg, exp_avg_sq, grad, zmin, zmax, hyper, scratch, betas=(0.9, 0.999), eps=1e-8, delta=0.1):
+    """In-place AdamP step on p (projection test on the [shape[0], -1] view, then on [1, -1]) fused with the clip_z clamp:
+    two launches, no atomics."""
+    _need_cuda(p, grad, hyper, scratch)
+    assert p.is_contiguous() and grad.is_contiguous() and p.dtype == torch.float32
+    C, hw = _clamp_view(p, zmin, zmax)
+    rows = p.shape[0] if p.dim() > 1 else 0
+    call("prx_optim_adamp_step_dev", p, exp_avg, exp_avg_sq, grad, zmin, zmax, rows, C, hw, p.numel(), hyper, scratch,
+         scratch.numel(), float(betas[0]), float(betas[1]), float(eps), float(delta), _stream())
+
+
 # --------------------------------------------------------------------------------------- VGG16 features (StyleLoss plugin)
 VGG16_CONV_INDICES = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)       # torchvision vgg16().features conv layers
 VGG16_CAPTURE_LAYERS = (1, 3, 6, 8, 11, 13, 15, 22, 29)                     # Losses/StyleLoss.py:31
