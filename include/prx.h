@@ -159,6 +159,55 @@ int prx_k_image_head_bwd(const float* x, int ldc, const float* gimg, float* dx, 
 int prx_k_mha_fwd(const void* qkv, void* out, int N, int T, int C, int heads, prx_stream_t s);
 int prx_k_mha_bwd(const void* qkv, const void* dout, void* dqkv, int N, int T, int C, int heads, prx_stream_t s);
 
+/* The same kernels with EVERY argument of the internal functions exposed (test surface only; the product's Python never calls
+ * these): `h16` selects the 16-bit operand format (0 bf16, 1 IEEE half with saturating conversion), `s16` the lean layout
+ * (stream inputs are 16-bit tensors in that format: a flag for GroupNorm / upsample / LayerNorm forward, bits 1 = x, 2 = g,
+ * 4 = add for the LayerNorm backward), `*16` outputs may be the only output (fp32 twin null), `add_every` > 0 reads `add` on
+ * the rows that are multiples of it only, `zero_stats` / `stats_ready` skip the memset / the statistics pass (sums supplied by
+ * the caller), `gscale` is a device scalar multiplying the outgoing gradient, `prec` a PRX_PREC_* value, `f32` the element
+ * type of an untyped buffer.  tests/test_kernels_half_gpu.py holds each variant to a float64 reference. */
+int prx_k_groupnorm_fwd_op(const void* x, const float* gamma, const float* beta, double* stats, void* out16, float* out_f32,
+                           int NB, int P, int C, int swish, float eps, int zero_stats, int stats_ready, int h16, int s16,
+                           prx_stream_t s);
+int prx_k_groupnorm_bwd_op(const void* g, const void* x, const float* gamma, const float* beta, const double* fstats,
+                           double* bstats, const void* add, float* dx, void* dx16, int NB, int P, int C, int swish, float eps,
+                           int zero_stats, int stats_ready, int h16, int s16, prx_stream_t s);
+int prx_k_layernorm_fwd_op(const void* x, long long ldx, const float* gamma, const float* beta, void* out16, float* out_f32,
+                           float* mean, float* rstd, int rows, int C, float eps, int h16, int s16, prx_stream_t s);
+int prx_k_layernorm_bwd_op(const void* g, long long ldg, const void* x, long long ldx, const float* gamma, const float* mean,
+                           const float* rstd, const void* add, long long ldadd, float* dx, long long lddx, void* dx16,
+                           long long lddxb, int rows, int C, int h16, int add_every, int s16, prx_stream_t s);
+int prx_k_mha_fwd_op(const void* qkv, void* out, int N, int T, int C, int heads, int h16, prx_stream_t s);
+int prx_k_mha_bwd_op(const void* qkv, const void* dout, void* dqkv, int N, int T, int C, int heads, int h16, prx_stream_t s);
+int prx_k_mha_fwd_gen_op(const void* qkv, void* out, float* lse, int N, int T, int C, int heads, int h16, prx_stream_t s);
+int prx_k_mha_bwd_gen_op(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int N, int T, int C,
+                         int heads, int h16, prx_stream_t s);
+/* forward only, causal mask (CLIP text transformer) */
+int prx_k_mha_fwd_causal_op(const void* qkv, void* out, int N, int T, int C, int heads, int h16, prx_stream_t s);
+int prx_k_softmax_rows_op(const float* S, int lds_, float scale, void* P, int ldp, void* PT, int ldpt, int rows, int cols,
+                          int prec, prx_stream_t s);
+int prx_k_softmax_rows_bwd_op(const void* P, int ldp, const float* dP, int lddp, float scale, void* dS, int ldds, void* dST,
+                              int lddst, int rows, int cols, int prec, prx_stream_t s);
+int prx_k_transpose_op(const void* in, int ldin, void* out, int ldout, int R, int C, int f32, prx_stream_t s);
+int prx_k_upsample2x_bwd_op(const void* hi, float* low, void* low16, int NB, int Hl, int Wl, int C, int h16, int s16,
+                            prx_stream_t s);
+int prx_k_nchw_to_nhwc_op(const float* in, float* out_f32, void* out16, int NB, int C, int HW, int Cpad, int h16, prx_stream_t s);
+int prx_k_image_head_bwd_op(const float* x, int ldc, const float* gimg, float* dx, void* dx16, int ldo, int NB, int C, int HW,
+                            int h16, const float* gscale, prx_stream_t s);
+/* ... written as the im2col matrix [H*W][ldk] of the 3x3 convolution that follows (tap-major, 8 channels per tap, columns
+ * 72 .. ldk-1 zero); batch 1 */
+int prx_k_image_head_bwd_im2col(const float* x, int ldc, const float* gimg, void* col, int ldk, int C, int H, int W, int h16,
+                                const float* gscale, prx_stream_t s);
+/* power-of-two gradient scale of the half mode: scale2 = {S, 1/S}, S * max|g| in [2^(T-1), 2^T), T = target_log2; S = 1 for an
+ * all-zero gradient or one that holds an inf or a NaN.  part: nparts floats of scratch (count * nparts_each for _multi) */
+int prx_k_grad_scale(const float* g, size_t n, float* part, int nparts, int target_log2, float* scale2, prx_stream_t s);
+int prx_k_grad_scale_multi(const float* const* gs, const size_t* ns, int count, float* part, int nparts_each, int target_log2,
+                           float* scale2, prx_stream_t s);
+/* x[i] *= *scale (device scalar); out16 (optional): the scaled values in the 16-bit operand format */
+int prx_k_scale_dev(float* x, size_t n, const float* scale, void* out16, int h16, prx_stream_t s);
+int prx_k_f32_to_op16(const float* in, void* out16, size_t n, int h16, prx_stream_t s);
+int prx_k_add_f32(const float* a, const float* b, float* out, size_t n, prx_stream_t s);
+
 /* ------------------------------------------------------------------------ */
 /* Path-level operators: the drop-in boundary of the hot path                */
 /* ------------------------------------------------------------------------ */

@@ -243,7 +243,10 @@ __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* __restric
 // ---- power-of-two gradient scale of the half (PRX_PREC_F16) mode: scale2 = {S, 1/S} with S * max|g| in [2^(T-1), 2^T) --------
 __global__ __launch_bounds__(256) void amax_partial_kernel(const float* __restrict__ g, size_t n, float* __restrict__ part) {
     float m = 0.f;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) m = fmaxf(m, fabsf(g[i]));
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const float a = fabsf(g[i]);
+        m = fmaxf(m, a == a ? a : INFINITY);       // fmaxf drops a NaN operand: a NaN counts as non-finite (S = 1, elementwise.h)
+    }
     m = wave_max(m);
     __shared__ float s[4];
     if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = m;

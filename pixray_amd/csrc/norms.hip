@@ -61,10 +61,21 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const GNArgs a) {
         be = reinterpret_cast<const float4*>(a.beta)[cq];
     }
     float s0 = 0.f, s1 = 0.f;
+    int cnt = 0;
+    // forward: the same sums once more in float64 from the first product on.  With x^2 and the running sums rounded to fp32,
+    // var = E[x^2] - m^2 keeps mean^2 / var units of fp32 round-off: harmless for the decoder's activations (means within a few standard
+    // deviations of zero), but rstd is off by 3e-6 at 32 sigma, which the backward inherits.  A thread whose own values say
+    // mean^2 > 64 var hands on its float64 sums, every other thread its fp32 sums as before.  8 fp64 operations per 16 bytes loaded:
+    // the pass stays HBM-bound
+    double d0 = 0.0, d1 = 0.0;
     auto accum = [&](const float4& v, const float4& gg) {
         if (MODE == 0) {
             s0 += (v.x + v.y) + (v.z + v.w);
             s1 += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+            const double x0 = v.x, x1 = v.y, x2 = v.z, x3 = v.w;
+            d0 += (x0 + x1) + (x2 + x3);
+            d1 += (x0 * x0 + x1 * x1) + (x2 * x2 + x3 * x3);
+            cnt += 4;
         } else {
             float xv[4] = {v.x, v.y, v.z, v.w}, gv[4] = {gg.x, gg.y, gg.z, gg.w};
             float gav[4] = {ga.x, ga.y, ga.z, ga.w}, bev[4] = {be.x, be.y, be.z, be.w};
@@ -95,9 +106,10 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const GNArgs a) {
         }
         for (; p < a.P; p += stride) accum(X((size_t)p * C4 + cq), MODE ? G((size_t)p * C4 + cq) : z4);
     }
-    __shared__ float red[256][2];
-    red[threadIdx.x][0] = s0;
-    red[threadIdx.x][1] = s1;
+    __shared__ double red[256][2];
+    const bool far = MODE == 0 && d0 * d0 > 64.0 * ((double)cnt * d1 - d0 * d0);      // (sum x)^2 > 64 (n sum x^2 - (sum x)^2)
+    red[threadIdx.x][0] = far ? d0 : (double)s0;
+    red[threadIdx.x][1] = far ? d1 : (double)s1;
     __syncthreads();
     if (threadIdx.x < 64) {
         // threads 0..31 -> moment 0 of group t, 32..63 -> moment 1
@@ -105,7 +117,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const GNArgs a) {
         const int q0 = gidx * gs / 4, q1 = (gidx + 1) * gs / 4;
         double acc = 0.0;
         for (int pp = 0; pp < ppb; ++pp)
-            for (int q = q0; q < q1; ++q) acc += (double)red[pp * C4 + q][mom];
+            for (int q = q0; q < q1; ++q) acc += red[pp * C4 + q][mom];
         atomicAdd(&a.stats[((size_t)b * 32 + gidx) * 2 + mom], acc);
     }
 }

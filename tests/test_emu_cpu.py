@@ -32,11 +32,12 @@ pytestmark = pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/clang
 def emu():
     with _emu.enable() as lib:
         import test_kernels_gpu as tk
+        import test_kernels_half_gpu as th
         import test_path_gpu as tp
-        for m in (tk, tp):
+        for m in (tk, th, tp):
             m.DEV = "cpu"
-        yield types_ns(lib=lib, tk=tk, tp=tp)
-        for m in (tk, tp):
+        yield types_ns(lib=lib, tk=tk, th=th, tp=tp)
+        for m in (tk, th, tp):
             m.DEV = "cuda"
 
 
@@ -48,7 +49,7 @@ def types_ns(**kw):
 def test_emulated_library_exports_the_whole_c_abi(emu):
     from pixray_amd import _lib
     assert emu.lib.prx_abi_version() == 3
-    assert len(_lib._protos) >= 79 and all(hasattr(emu.lib, name) for name in _lib._protos)
+    assert len(_lib._protos) >= 136 and all(hasattr(emu.lib, name) for name in _lib._protos)
 
 
 # ------------------------------------------------------------------------------------------------ GEMM engine
@@ -207,6 +208,14 @@ def test_norms_attention_layout_and_image_head_kernels(emu):
     tk.test_image_head()
     tk.test_mha_fwd_bwd(3, 64)
     tk.test_mha_general_fwd_bwd(2, 65, 1.0)
+
+
+def test_half_mode_and_lean_layout_kernel_variants(emu):
+    """tests/test_kernels_half_gpu.py at CPU sizes: the instantiations the product's default launches (IEEE-half operands, 16-bit
+    streams, 16-bit-only outputs, add_every, device gscale, every softmax precision, the gradient scale) and their bf16 twins,
+    each against float64 at the gates that file derives; every variant flag at least once"""
+    figs = emu.th.emu_subset()
+    assert len(figs[0]) == len(figs[1]) == 4
 
 
 def test_strotss_and_hypercolumn_kernels(emu):

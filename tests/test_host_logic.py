@@ -102,7 +102,7 @@ def test_library_loads_and_exports_every_declared_symbol():
         import __graft_entry__ as ge
         ge.build()
     protos = _lib.parse_header()
-    assert len(protos) >= 35
+    assert len(protos) >= 136
     lib = ctypes.CDLL(_lib.LIB_PATH) if False else _lib.load()
     for name in protos:
         assert hasattr(lib, name), f"{name} declared in include/prx.h but not exported"
