@@ -54,6 +54,11 @@ int prx_device_info(int* cu_count, char* arch_name, int arch_name_len);
 #define PRX_ACT_MUL_RELUMASK 4   /* multiply by (aux > 0): ReLU backward, aux = the forward output */
 #define PRX_ACT_RELUMASK_POST 5  /* the same mask applied AFTER the residual add: (acc + resid) * (aux > 0) -- the gradient
                                     arriving at a Bottleneck's output ReLU, formed in the epilogue of the GEMM that sums it */
+#define PRX_ACT_GELU 6           /* the exact GELU, 0.5 t (1 + erf(t / sqrt 2)) (timm VisionTransformer MLP: the SLIP towers); writes the
+                                    pre-activation to out_bf16_pre as PRX_ACT_QUICKGELU does.  This code and the next: 16-bit operand
+                                    modes with the vector epilogue (N % 4 == 0, aligned operands) only; the exact-f32 kernels refuse them
+                                    (the ViT runner's parity mode applies the activation in a pass of its own) */
+#define PRX_ACT_MUL_DGELU 7      /* multiply by GELU'(aux) = Phi(aux) + aux phi(aux) (backward) */
 #define PRX_A_ROWMAJOR 0
 #define PRX_A_CONV3X3 1          /* implicit im2col of an NHWC tensor, 3x3 pad 1 */
 
@@ -397,6 +402,47 @@ typedef struct prx_clip_vit_config {
 } prx_clip_vit_config;
 int prx_clip_vit_create(prx_clip_vit** out, const prx_clip_vit_config* cfg, const float* const* weights, int n_weights,
                         prx_stream_t s);
+/* --- the same runner for a tower FAMILY: SLIP_Base.encode_image (slip.py:151-157) runs a timm VisionTransformer
+ *     (`timm.create_model(vit_*_patch16_224, num_classes=0)`) followed by `@ image_projection` [UPSTREAM facebookresearch/SLIP
+ *     models.py, timm vision_transformer.py; the SLIP/ submodule is absent from the reference checkout, parity unpinned].
+ *     Against the CLIP tower it has a patch-embed bias, no ln_pre, LayerNorm eps 1e-6, the exact GELU, and is fed through
+ *     `Normalize` with the ImageNet constants (slip.py:117-121).  Returns the same handle type: minmax / encode /
+ *     backward_reduce / backward_finish / destroy / gemm_ctx above are shared.
+ * family PRX_VIT_FAMILY_CLIP: weights[] as for prx_clip_vit_create (ln_eps, mean, std as given: 1e-5 and CLIP's constants
+ *   reproduce it bit for bit).
+ * family PRX_VIT_FAMILY_SLIP: weights[] are fp32 device tensors in timm state-dict order under `visual.`:
+ *   patch_embed.proj.weight [width,3,P,P], patch_embed.proj.bias, cls_token [1,1,width], pos_embed [1,T,width],
+ *   per block i: blocks.i.norm1.{weight,bias}, blocks.i.attn.qkv.{weight [3 width, width] rows q|k|v, bias},
+ *                blocks.i.attn.proj.{weight,bias}, blocks.i.norm2.{weight,bias}, blocks.i.mlp.fc1.{weight,bias},
+ *                blocks.i.mlp.fc2.{weight,bias},
+ *   norm.{weight,bias}, then `image_projection` [width, output_dim] (no bias).
+ * head_dim: 0 / 64, or 32 / 16 (= width / heads; SLIP's ViT-S/16 has 12 heads of 32 on width 384).  Narrower heads are zero-padded
+ *   to 64 when the weights are packed (q, k, v rows of qkv.weight / qkv.bias, input columns of proj.weight; sqrt(64 / head_dim)
+ *   folded into the q rows): the values and gradients of the narrow heads, at 64 / head_dim times the qkv, attention and
+ *   out-projection work.  width must be a multiple of 128. */
+#define PRX_VIT_FAMILY_CLIP 0
+#define PRX_VIT_FAMILY_SLIP 1
+typedef struct prx_vit_tower_config {
+    int input_resolution;  /* 224 */
+    int patch_size;        /* 16 */
+    int width;             /* 768 | 1024 */
+    int layers;            /* 12 | 24 */
+    int heads;             /* 12 | 16 */
+    int output_dim;        /* 512 */
+    int max_batch;         /* capacity in cutouts */
+    int precision;         /* PRX_PREC_F16 | PRX_PREC_BF16 | PRX_PREC_F32 (the reference runs this family in fp32 on a GPU) */
+    int family;            /* PRX_VIT_FAMILY_* */
+    int head_dim;          /* 0 = 64; 32 | 16: padded to 64 */
+    float ln_eps;          /* 1e-6 (timm) | 1e-5 (CLIP) */
+    float mean[3];         /* Normalize constants of the fused preprocessing: ImageNet's (0.485, 0.456, 0.406) */
+    float std[3];          /* (0.229, 0.224, 0.225) */
+} prx_vit_tower_config;
+int prx_vit_tower_create(prx_clip_vit** out, const prx_vit_tower_config* cfg, const float* const* weights, int n_weights,
+                         prx_stream_t s);
+/* TEST DIAGNOSTIC, not part of the ABI contract (it may change or go without a version bump; no product code calls it): copies the
+ * d(qkv) buffer as the last backward left it -- block 0's gradient, [n * T][3 * heads * 64] in the handle's operand format, padded
+ * lanes included -- to dst.  Returns the bytes copied, or -1 when no forward is in flight or max_bytes is too small. */
+long long prx_vit_tower_debug_dqkv(prx_clip_vit* h, void* dst, long long max_bytes, prx_stream_t s);
 void prx_clip_vit_destroy(prx_clip_vit* h);
 int prx_clip_vit_minmax(prx_clip_vit* h, const float* cutouts, int n, float* mm, prx_stream_t s);
 int prx_clip_vit_encode(prx_clip_vit* h, const float* cutouts, int n, const float* mm, float* embeds, prx_stream_t s);

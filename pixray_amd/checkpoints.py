@@ -8,6 +8,7 @@ are exercised in tests with randomly initialised upstream-format state dicts; th
 * taming-transformers VQGAN Lightning checkpoint (`vqgan.py:124-140`): `state_dict` with `decoder.*`,
   `post_quant_conv.*`, `quantize.embedding.weight` for the decoder runner, plus `encoder.*` / `quant_conv.*` for the
   encoder runner when the checkpoint has them (`loss.*` is dropped, as `del model.loss` does at vqgan.py:139).
+* facebookresearch/SLIP checkpoints (`models/slip_base_100ep.pt`, ..., slip.py:90-140): `load_slip`.
 * torchvision `vgg16` (`models.vgg16(pretrained=True)`, Losses/StyleLoss.py:27): `features.{0,2,5,...,28}.{weight,bias}`;
   the `classifier.*` tensors are dropped (the StyleLoss extractor stops at relu5_3).
 """
@@ -16,7 +17,7 @@ from typing import Dict
 
 import torch
 
-from .weights import (ClipTextConfig, ClipVitConfig, VqganConfig, clip_text_param_shapes, clip_vit_param_shapes,
+from .weights import (ClipTextConfig, ClipVitConfig, VqganConfig, clip_text_param_shapes, clip_vit_param_shapes, slip_vit_param_shapes,
                       vgg16_param_shapes, vqgan_encoder_param_shapes, vqgan_param_shapes)
 
 
@@ -172,6 +173,30 @@ def clip_config_from_state_dict(sd: Dict[str, torch.Tensor], name: str = "checkp
     layers = len({k.split(".")[3] for k in sd if k.startswith("visual.transformer.resblocks.")})
     grid = round((sd["visual.positional_embedding"].shape[0] - 1) ** 0.5)
     return ClipVitConfig(name, patch * grid, patch, width, layers, width // 64, sd["visual.proj"].shape[1])
+
+
+def load_slip(path: str, cfg, text_cfg: ClipTextConfig):
+    """A facebookresearch/SLIP checkpoint (`models/slip_*.pt` / `clip_*.pt`, slip.py:90-140): `{"state_dict": ..., "args":
+    argparse.Namespace, ...}` saved from a DistributedDataParallel model, so every key carries `module.`.  -> (image-side
+    parameters: the timm `visual.*` entries with the prefix stripped + `image_projection`; text-side parameters under the names
+    of `clip_text_param_shapes`).  The SSL-only entries (`image_mlp.*`, SLIP's SimCLR head) and `logit_scale` are dropped: neither
+    encode_image nor encode_text reads them.  Loaded with `weights_only=True`; the only non-tensor class admitted is the
+    `argparse.Namespace` of `ckpt['args']`.  A missing or mis-shaped tensor is reported by name."""
+    import argparse
+    with torch.serialization.safe_globals([argparse.Namespace]):
+        blob = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(blob, dict) or "state_dict" not in blob:
+        raise ValueError(f"{path}: not a SLIP checkpoint (no 'state_dict' entry)")
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in blob["state_dict"].items()}
+    image = {k[len("visual."):]: v for k, v in sd.items() if k.startswith("visual.")}
+    if "image_projection" in sd:
+        image["image_projection"] = sd["image_projection"]
+    text_names = set(clip_text_param_shapes(text_cfg))
+    text = {k: v for k, v in sd.items() if k in text_names}
+    try:
+        return _check(image, slip_vit_param_shapes(cfg)), _check(text, clip_text_param_shapes(text_cfg))
+    except (KeyError, ValueError) as e:
+        raise type(e)(f"{path}: {e.args[0]}") from None
 
 
 def vgg16_from_torchvision(state_dict: Dict[str, torch.Tensor]):

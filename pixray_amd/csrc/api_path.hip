@@ -116,6 +116,22 @@ int prx_clip_vit_create(prx_clip_vit** out, const prx_clip_vit_config* c, const 
     return prx_vit_create_impl((PrxVit**)out, c->input_resolution, c->patch_size, c->width, c->layers, c->heads,
                                c->output_dim, c->max_batch, c->precision, weights, n_weights, S_(s));
 }
+int prx_vit_tower_create(prx_clip_vit** out, const prx_vit_tower_config* c, const float* const* weights, int n_weights,
+                         prx_stream_t s) {
+    PRX_REQUIRE(out && c && weights, "prx_vit_tower_create: null argument");
+    PRX_REQUIRE(c->family == PRX_VIT_FAMILY_CLIP || c->family == PRX_VIT_FAMILY_SLIP, "prx_vit_tower_create: unknown family %d", c->family);
+    PRX_REQUIRE(c->head_dim == 0 || c->head_dim == 64 || c->head_dim == 32 || c->head_dim == 16,
+                "prx_vit_tower_create: head dim %d (want 64, or 32 / 16: padded to 64)", c->head_dim);
+    VitFamily f = prx_vit_family_clip();
+    if (c->family == PRX_VIT_FAMILY_SLIP) { f.patch_bias = 1; f.ln_pre = 0; f.act = PRX_ACT_GELU; f.dact = PRX_ACT_MUL_DGELU; }
+    f.eps = c->ln_eps; f.head_dim = c->head_dim;
+    for (int i = 0; i < 3; ++i) { f.norm.mean[i] = c->mean[i]; f.norm.std[i] = c->std[i]; }
+    return prx_vit_create_impl((PrxVit**)out, c->input_resolution, c->patch_size, c->width, c->layers, c->heads,
+                               c->output_dim, c->max_batch, c->precision, weights, n_weights, S_(s), &f);
+}
+long long prx_vit_tower_debug_dqkv(prx_clip_vit* h, void* dst, long long max_bytes, prx_stream_t s) {
+    return prx_vit_debug_dqkv_impl((PrxVit*)h, dst, max_bytes, S_(s));
+}
 void prx_clip_vit_destroy(prx_clip_vit* h) { prx_vit_destroy_impl((PrxVit*)h); }
 prx_gemm_ctx* prx_clip_vit_gemm_ctx(prx_clip_vit* h) { return (prx_gemm_ctx*)prx_vit_gemm_ctx_impl((PrxVit*)h); }
 int prx_clip_vit_minmax(prx_clip_vit* h, const float* cutouts, int n, float* mm, prx_stream_t s) {

@@ -17,11 +17,16 @@ int prx_warp_b_bwd(const float* a, int Ha, int Wa, const double* desc, const flo
 int prx_rescale_fwd(const float* pooled, float* base, int C, int S, int Hb, int Wb, hipStream_t s);
 int prx_rescale_bwd(const float* g_base, float* g_pooled, int C, int S, int Hb, int Wb, hipStream_t s);
 int prx_minmax(const float* x, size_t n, float* part, int nparts, float* mm, hipStream_t s);
-int prx_patchify_fwd(const float* cut, const float* mm, void* A, int prec, int N, int S, int P, int T, hipStream_t s);   // A at operand precision (PRX_PREC_*)
+// channel constants of the `Normalize` fused into the tower's first kernel and its backward: CLIP's (slip.py:55) or, for the SLIP
+// towers, ImageNet's (slip.py:121)
+struct PatchNorm { float mean[3], std[3]; };
+inline PatchNorm prx_patch_norm_clip() { return PatchNorm{{0.48145466f, 0.4578275f, 0.40821073f}, {0.26862954f, 0.26130258f, 0.27577711f}}; }
+int prx_patchify_fwd(const float* cut, const float* mm, void* A, int prec, int N, int S, int P, int T, hipStream_t s,
+                     const PatchNorm& norm = prx_patch_norm_clip());   // A at operand precision (PRX_PREC_*)
 int prx_patchify_bwd_reduce(const float* cut, const float* mm, const float* dA, double* acc, int N, int S, int P, int T,
-                            hipStream_t s);
+                            hipStream_t s, const PatchNorm& norm = prx_patch_norm_clip());
 int prx_patchify_bwd_apply(const float* cut, const float* mm, const float* dA, const double* acc, float* gcut, int N,
-                           int S, int P, int T, hipStream_t s);
+                           int S, int P, int T, hipStream_t s, const PatchNorm& norm = prx_patch_norm_clip());
 // gradient through slip.py:21-42 (batch-global min/max renorm + mean/std) for an image-layout gradient dY[N][3][S][S]
 int prx_preproc_bwd_reduce(const float* cut, const float* mm, const float* dY, double* acc, int N, int S, hipStream_t s);
 int prx_preproc_bwd_apply(const float* cut, const float* mm, const float* dY, const double* acc, float* gcut, int N, int S,

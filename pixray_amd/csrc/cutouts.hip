@@ -1373,15 +1373,12 @@ __global__ __launch_bounds__(256) void minmax_final_kernel(const float* __restri
     }
 }
 
-__constant__ float c_clip_mean[3] = {0.48145466f, 0.4578275f, 0.40821073f};
-__constant__ float c_clip_std[3] = {0.26862954f, 0.26130258f, 0.27577711f};
-
 // A[(n*T + 1 + gy*G + gx)][c*P*P + py*P + px] = ((x - mn)/(mx - mn) - mean_c)/std_c ; row n*T is zero (class token).
 // Kp = 3*P*P rounded up to a multiple of 8 (zero columns): ViT-L/14 has 588 -> 592.
 // TOp: operand precision of A (bf16, or fp32 in the exact mode)
 template <typename TOp>
 __global__ __launch_bounds__(256) void patchify_fwd_kernel(const float* __restrict__ cut, const float* __restrict__ mm,
-                                                           TOp* __restrict__ A, int N, int S, int P, int T, int Kp) {
+                                                           TOp* __restrict__ A, int N, int S, int P, int T, int Kp, PatchNorm nm) {
     const int G = S / P;
     const int K = 3 * P * P;
     const int K8 = Kp / 8;
@@ -1401,7 +1398,7 @@ __global__ __launch_bounds__(256) void patchify_fwd_kernel(const float* __restri
                 const int k = k8 * 8;
                 const int c = k / (P * P), py = (k / P) % P, px = k % P;
                 const float* src = cut + (((size_t)n * 3 + c) * S + gy * P + py) * S + gx * P + px;
-                const float im = c_clip_mean[c], is = 1.f / c_clip_std[c];
+                const float im = nm.mean[c], is = 1.f / nm.std[c];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) r[e] = (((src[e] - mn) * inv) - im) * is;
             } else {
@@ -1411,7 +1408,7 @@ __global__ __launch_bounds__(256) void patchify_fwd_kernel(const float* __restri
                     if (k < K) {
                         const int c = k / (P * P), py = (k / P) % P, px = k % P;
                         const float v = cut[(((size_t)n * 3 + c) * S + gy * P + py) * S + gx * P + px];
-                        r[e] = (((v - mn) * inv) - c_clip_mean[c]) / c_clip_std[c];
+                        r[e] = (((v - mn) * inv) - nm.mean[c]) / nm.std[c];
                     }
                 }
             }
@@ -1425,7 +1422,7 @@ __global__ __launch_bounds__(256) void patchify_fwd_kernel(const float* __restri
 __global__ __launch_bounds__(256) void patchify_bwd_reduce_kernel(const float* __restrict__ cut,
                                                                   const float* __restrict__ mm,
                                                                   const float* __restrict__ dA, double* __restrict__ acc,
-                                                                  int N, int S, int P, int T, int K) {
+                                                                  int N, int S, int P, int T, int K, PatchNorm nm) {
     const int G = S / P;
     const size_t total = (size_t)N * 3 * S * S;
     const float mn = mm[0], mx = mm[1];
@@ -1442,7 +1439,7 @@ __global__ __launch_bounds__(256) void patchify_bwd_reduce_kernel(const float* _
         const int ty = y / P, tx = x / P;
         const int tok = 1 + ty * G + tx;
         const int k = c * P * P + (y - ty * P) * P + (x - tx * P);
-        const float gy = dA[((size_t)n * T + tok) * K + k] / c_clip_std[c];
+        const float gy = dA[((size_t)n * T + tok) * K + k] / nm.std[c];
         const float xv = cut[idx];
         s1 += gy; s2 += gy * ((xv - mn) * inv);
         cmin += (xv == mn); cmax += (xv == mx);
@@ -1461,7 +1458,7 @@ __global__ __launch_bounds__(256) void patchify_bwd_apply_kernel(const float* __
                                                                  const float* __restrict__ mm,
                                                                  const float* __restrict__ dA,
                                                                  const double* __restrict__ acc, float* __restrict__ gcut,
-                                                                 int N, int S, int P, int T, int K) {
+                                                                 int N, int S, int P, int T, int K, PatchNorm nm) {
     const int G = S / P;
     const size_t total = (size_t)N * 3 * S * S;
     const float mn = mm[0], mx = mm[1];
@@ -1478,7 +1475,7 @@ __global__ __launch_bounds__(256) void patchify_bwd_apply_kernel(const float* __
         const int ty = y / P, tx = x / P;
         const int tok = 1 + ty * G + tx;
         const int k = c * P * P + (y - ty * P) * P + (x - tx * P);
-        const float gy = dA[((size_t)n * T + tok) * K + k] / c_clip_std[c];
+        const float gy = dA[((size_t)n * T + tok) * K + k] / nm.std[c];
         const float xv = cut[idx];
         float g = gy * inv;
         if (xv == mn) g += gmin;
@@ -1622,28 +1619,28 @@ int prx_minmax(const float* x, size_t n, float* part, int nparts, float* mm, hip
 }
 static inline int patch_kp(int P) { return (3 * P * P + 7) / 8 * 8; }
 
-int prx_patchify_fwd(const float* cut, const float* mm, void* A, int prec, int N, int S, int P, int T, hipStream_t s) {
+int prx_patchify_fwd(const float* cut, const float* mm, void* A, int prec, int N, int S, int P, int T, hipStream_t s, const PatchNorm& norm) {
     PRX_REQUIRE(S % P == 0 && T == (S / P) * (S / P) + 1, "patchify: bad geometry S=%d P=%d T=%d", S, P, T);
     const int Kp = patch_kp(P);
     const dim3 grid(ew_grid((size_t)N * T * Kp / 8));
     PRX_OP_DISPATCH(prec_is_f32(prec), prec_is_h16(prec), TO,
-                    hipLaunchKernelGGL(patchify_fwd_kernel<TO>, grid, dim3(256), 0, s, cut, mm, (TO*)A, N, S, P, T, Kp));
+                    hipLaunchKernelGGL(patchify_fwd_kernel<TO>, grid, dim3(256), 0, s, cut, mm, (TO*)A, N, S, P, T, Kp, norm));
     PRX_LAUNCH_CHECK();
     return 0;
 }
 int prx_patchify_bwd_reduce(const float* cut, const float* mm, const float* dA, double* acc, int N, int S, int P, int T,
-                            hipStream_t s) {
+                            hipStream_t s, const PatchNorm& norm) {
     PRX_REQUIRE((size_t)N * 3 * S * S < ((size_t)1 << 31), "patchify backward: %d cutouts of %dx%d exceed the 32-bit index range", N, S, S);
     PRX_CHECK_HIP(hipMemsetAsync(acc, 0, sizeof(double) * 4, s));
     hipLaunchKernelGGL(patchify_bwd_reduce_kernel, dim3(std::min(ew_grid((size_t)N * 3 * S * S), 2048)), dim3(256), 0, s,
-                       cut, mm, dA, acc, N, S, P, T, patch_kp(P));
+                       cut, mm, dA, acc, N, S, P, T, patch_kp(P), norm);
     PRX_LAUNCH_CHECK();
     return 0;
 }
 int prx_patchify_bwd_apply(const float* cut, const float* mm, const float* dA, const double* acc, float* gcut, int N,
-                           int S, int P, int T, hipStream_t s) {
+                           int S, int P, int T, hipStream_t s, const PatchNorm& norm) {
     hipLaunchKernelGGL(patchify_bwd_apply_kernel, dim3(ew_grid((size_t)N * 3 * S * S)), dim3(256), 0, s, cut, mm, dA, acc,
-                       gcut, N, S, P, T, patch_kp(P));
+                       gcut, N, S, P, T, patch_kp(P), norm);
     PRX_LAUNCH_CHECK();
     return 0;
 }
@@ -1656,7 +1653,7 @@ int prx_preproc_bwd_reduce(const float* cut, const float* mm, const float* dY, d
     PRX_REQUIRE((size_t)N * 3 * S * S < ((size_t)1 << 31), "preprocessing backward: %d cutouts of %dx%d exceed the 32-bit index range", N, S, S);
     const int K = 3 * S * S;
     hipLaunchKernelGGL(patchify_bwd_reduce_kernel, dim3(std::min(ew_grid((size_t)N * 3 * S * S), 2048)), dim3(256), 0, s,
-                       cut, mm, dY - K, acc, N, S, S, 1, K);
+                       cut, mm, dY - K, acc, N, S, S, 1, K, prx_patch_norm_clip());
     PRX_LAUNCH_CHECK();
     return 0;
 }
@@ -1664,7 +1661,7 @@ int prx_preproc_bwd_apply(const float* cut, const float* mm, const float* dY, co
                           hipStream_t s) {
     const int K = 3 * S * S;
     hipLaunchKernelGGL(patchify_bwd_apply_kernel, dim3(ew_grid((size_t)N * 3 * S * S)), dim3(256), 0, s, cut, mm, dY - K, acc,
-                       gcut, N, S, S, 1, K);
+                       gcut, N, S, S, 1, K, prx_patch_norm_clip());
     PRX_LAUNCH_CHECK();
     return 0;
 }

@@ -16,7 +16,14 @@
 enum { PRX_ACT_NONE = 0, PRX_ACT_QUICKGELU = 1, PRX_ACT_MUL_DQUICKGELU = 2,
        PRX_ACT_RELU = 3,            // max(v, 0) after bias / residual (CLIP ModifiedResNet)
        PRX_ACT_MUL_RELUMASK = 4,    // v *= (aux > 0): ReLU backward with the forward OUTPUT as aux
-       PRX_ACT_RELUMASK_POST = 5 }; // the same mask after the residual add: (acc + resid) * (aux > 0)
+       PRX_ACT_RELUMASK_POST = 5,   // the same mask after the residual add: (acc + resid) * (aux > 0)
+       PRX_ACT_GELU = 6,            // exact (erf) GELU after the bias; saves the pre-activation like QUICKGELU (timm ViT MLP)
+       PRX_ACT_MUL_DGELU = 7 };     // v *= GELU'(aux)
+// activation codes that read `aux` / that write the pre-activation twin `out_bf16_pre`
+inline __host__ __device__ bool prx_act_needs_aux(int act) {
+    return act == PRX_ACT_MUL_DQUICKGELU || act == PRX_ACT_MUL_RELUMASK || act == PRX_ACT_RELUMASK_POST || act == PRX_ACT_MUL_DGELU;
+}
+inline __host__ __device__ bool prx_act_saves_pre(int act) { return act == PRX_ACT_QUICKGELU || act == PRX_ACT_GELU; }
 enum { PRX_A_ROWMAJOR = 0, PRX_A_CONV3X3 = 1 };
 
 struct GemmDesc {
@@ -42,7 +49,7 @@ struct GemmDesc {
     int act = PRX_ACT_NONE;
     float* out_f32 = nullptr; int ldc_f32 = 0;
     void* out_bf16 = nullptr;        // post-activation, operand precision (the next GEMM's A)
-    void* out_bf16_pre = nullptr;    // pre-activation (QUICKGELU only), operand precision
+    void* out_bf16_pre = nullptr;    // pre-activation (QUICKGELU / GELU only), operand precision
     int ldc_bf16 = 0;
     // optional: accumulate GroupNorm statistics of the fp32 output (sum, sum of squares per group of `gn_gs`
     // consecutive columns) into gn_stats[group*2 + {0,1}] (double, pre-zeroed) -- saves the separate stats pass over

@@ -1032,8 +1032,7 @@ static int validate(const GemmDesc& d, const GemmCtx& cx) {
         PRX_REQUIRE(d.up != 2 || d.f32 || (c64 && !d.a_is_f32 && cx.use_glds),
                     "gemm/conv: the stride-2 gather needs a bf16 operand with Cin %% 64 == 0 (Cin=%d)", d.Cin);
     }
-    PRX_REQUIRE((d.act != PRX_ACT_MUL_DQUICKGELU && d.act != PRX_ACT_MUL_RELUMASK && d.act != PRX_ACT_RELUMASK_POST) || d.aux,
-                "gemm: MUL_DQUICKGELU / MUL_RELUMASK / RELUMASK_POST need aux");
+    PRX_REQUIRE(!prx_act_needs_aux(d.act) || d.aux, "gemm: MUL_DQUICKGELU / MUL_DGELU / MUL_RELUMASK / RELUMASK_POST need aux");
     PRX_REQUIRE(d.act != PRX_ACT_RELUMASK_POST || d.resid, "gemm: RELUMASK_POST masks product + residual: it needs resid");
     PRX_REQUIRE(!d.f32 || d.row16 == 0, "gemm: 16-bit residual / GroupNorm-input streams (row16) belong to the 16-bit operand modes");
     return 0;
@@ -1163,6 +1162,8 @@ int prx_gemm_plan_impl(const GemmDesc& d, const GemmCtx* c, int n_cu, size_t ws_
     if (p->n_launch == 2) plan_launch(rows_of(d, p->rows_8p, d.M - p->rows_8p), cx, n_cu, ws_bytes, ws_al16, &p->launch[1], &dbg);
     p->dbg_used = dbg - cx.dbg_count;
 
+    PRX_REQUIRE((d.act != PRX_ACT_GELU && d.act != PRX_ACT_MUL_DGELU) || (l0.vec_epi && !d.f32),
+                "gemm: the GELU / MUL_DGELU epilogues need the vector epilogue (N %% 4 == 0, aligned operands) of the 16-bit operand kernels");
     PRX_REQUIRE(d.row16 == 0 || l0.vec_epi, "gemm: 16-bit residual / GroupNorm-input streams need the vector epilogue (N %% 4 == 0, aligned operands)");
     if (d.gnb_x) {
         PRX_REQUIRE(d.gn_stats && d.gnb_fstats && d.gnb_gamma && d.gnb_beta && (d.out_f32 || d.out_bf16) && d.act == PRX_ACT_NONE,

@@ -1,5 +1,5 @@
 // Device-side pieces shared by the GEMM kernels of gemm.hip and gemm8p.hip: the launch argument block and the fused epilogue
-// (bias, residual, QuickGELU / ReLU forms, operand-precision twins, GroupNorm statistics) -- see gemm.h for the semantics.
+// (bias, residual, QuickGELU / GELU / ReLU forms, operand-precision twins, GroupNorm statistics) -- see gemm.h for the semantics.
 #pragma once
 #include "gemm.h"
 #include <type_traits>
@@ -19,6 +19,11 @@ __device__ __forceinline__ float quickgelu_f(float t) { return t * sigmoidf_(1.7
 __device__ __forceinline__ float dquickgelu_f(float t) {
     float s = sigmoidf_(1.702f * t);
     return s * (1.f + 1.702f * t * (1.f - s));
+}
+// the exact GELU of timm's VisionTransformer MLP (nn.GELU()) and its derivative Phi(t) + t phi(t)
+__device__ __forceinline__ float gelu_f(float t) { return 0.5f * t * (1.f + erff(t * 0.70710678f)); }
+__device__ __forceinline__ float dgelu_f(float t) {
+    return 0.5f * (1.f + erff(t * 0.70710678f)) + t * (0.39894228f * __expf(-0.5f * t * t));
 }
 
 // ---- fused GroupNorm-backward sums (GemmDesc::gnb_*) --------------------------------------------------------------
@@ -58,6 +63,8 @@ __device__ __forceinline__ void gnb_accum(const GemmDesc& d, const GnbConst& c, 
 }
 
 // TOp = element type of the operand-precision pointers (aux, out_bf16, out_bf16_pre): bf16_t, or float in the exact mode
+// (the scalar form has no PRX_ACT_GELU / PRX_ACT_MUL_DGELU: erff would no longer let it unroll -- see the note at the residual
+// below --, so those two codes need the vector epilogue, checked on the host like row16)
 template <typename TOp>
 __device__ __forceinline__ void epilogue_store(const GemmDesc& d, int row, int col, float v) {
     const TOp* aux = reinterpret_cast<const TOp*>(d.aux);
@@ -92,6 +99,9 @@ __device__ __forceinline__ float4 epilogue_math4(int act, float alpha, float4 v,
     if (act == PRX_ACT_MUL_DQUICKGELU) {
         v.x *= dquickgelu_f(aux[0]); v.y *= dquickgelu_f(aux[1]); v.z *= dquickgelu_f(aux[2]); v.w *= dquickgelu_f(aux[3]);
     }
+    if (act == PRX_ACT_MUL_DGELU) {
+        v.x *= dgelu_f(aux[0]); v.y *= dgelu_f(aux[1]); v.z *= dgelu_f(aux[2]); v.w *= dgelu_f(aux[3]);
+    }
     // ReLU backward: the mask (aux > 0) multiplies the product (MUL_RELUMASK) or the product + residual (RELUMASK_POST)
     const bool masked = act == PRX_ACT_MUL_RELUMASK || act == PRX_ACT_RELUMASK_POST;
     const bool k0 = !masked || aux[0] > 0.f, k1 = !masked || aux[1] > 0.f, k2 = !masked || aux[2] > 0.f, k3 = !masked || aux[3] > 0.f;
@@ -116,6 +126,10 @@ __device__ __forceinline__ float4 epilogue_math4(int act, float alpha, float4 v,
         pre = make_float4((float)op_cvt<TOp>(v.x), (float)op_cvt<TOp>(v.y), (float)op_cvt<TOp>(v.z), (float)op_cvt<TOp>(v.w));
         v.x = quickgelu_f(pre.x); v.y = quickgelu_f(pre.y); v.z = quickgelu_f(pre.z); v.w = quickgelu_f(pre.w);
     }
+    if (act == PRX_ACT_GELU) {
+        pre = make_float4((float)op_cvt<TOp>(v.x), (float)op_cvt<TOp>(v.y), (float)op_cvt<TOp>(v.z), (float)op_cvt<TOp>(v.w));
+        v.x = gelu_f(pre.x); v.y = gelu_f(pre.y); v.z = gelu_f(pre.z); v.w = gelu_f(pre.w);
+    }
     return v;
 }
 
@@ -127,7 +141,7 @@ __device__ __forceinline__ float4 epilogue_value4(const GemmDesc& d, int row, in
     if (d.bias_n) bias = *reinterpret_cast<const float4*>(d.bias_n + col);
     const float bias_m = d.bias_m ? d.bias_m[row] : 0.f;
     float4 ax = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (d.act == PRX_ACT_MUL_DQUICKGELU || d.act == PRX_ACT_MUL_RELUMASK || d.act == PRX_ACT_RELUMASK_POST)
+    if (prx_act_needs_aux(d.act))
         ax = op_ld4v(reinterpret_cast<const TOp*>(d.aux), (size_t)row * d.ldaux + col);
     const float aux[4] = {ax.x, ax.y, ax.z, ax.w};
     float4 res = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -142,7 +156,7 @@ template <typename TOp>
 __device__ __forceinline__ float4 epilogue_store4(const GemmDesc& d, int row, int col, float4 v) {
     float4 pre;
     v = epilogue_value4<TOp>(d, row, col, v, pre);
-    if (d.act == PRX_ACT_QUICKGELU && d.out_bf16_pre)
+    if (prx_act_saves_pre(d.act) && d.out_bf16_pre)
         op_st4(reinterpret_cast<TOp*>(d.out_bf16_pre), (size_t)row * d.ldc_bf16 + col, pre.x, pre.y, pre.z, pre.w);
     if (d.out_f32) *reinterpret_cast<float4*>(d.out_f32 + (size_t)row * d.ldc_f32 + col) = v;
     if (d.out_bf16) op_st4(reinterpret_cast<TOp*>(d.out_bf16), (size_t)row * d.ldc_bf16 + col, v.x, v.y, v.z, v.w);
@@ -158,7 +172,7 @@ __device__ __forceinline__ void epilogue_store8(const GemmDesc& d, int row, int 
     float4 p0, p1;
     v0 = epilogue_value4<T16>(d, row, col, v0, p0);
     v1 = epilogue_value4<T16>(d, row, col + 4, v1, p1);
-    if (d.act == PRX_ACT_QUICKGELU && d.out_bf16_pre) {
+    if (prx_act_saves_pre(d.act) && d.out_bf16_pre) {
         t16x8 r;
         r[0] = op_cvt<T16>(p0.x); r[1] = op_cvt<T16>(p0.y); r[2] = op_cvt<T16>(p0.z); r[3] = op_cvt<T16>(p0.w);
         r[4] = op_cvt<T16>(p1.x); r[5] = op_cvt<T16>(p1.y); r[6] = op_cvt<T16>(p1.z); r[7] = op_cvt<T16>(p1.w);

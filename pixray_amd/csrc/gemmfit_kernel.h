@@ -207,7 +207,7 @@ __device__ __forceinline__ void fit_finish(const GemmArgs& p, float* const fl, f
     const float alpha = d.alpha_dev ? d.alpha * *d.alpha_dev : d.alpha;
     const bool has_resid = d.resid != nullptr;
     const bool row16 = has_resid ? (d.row16 & 1) != 0 : (d.row16 & 2) != 0;      // the row operand (residual / GroupNorm input) is a 16-bit stream
-    const bool need_aux = act == PRX_ACT_MUL_DQUICKGELU || act == PRX_ACT_MUL_RELUMASK || act == PRX_ACT_RELUMASK_POST;
+    const bool need_aux = prx_act_needs_aux(act);
     // the 80-row-granular tiles are the token-batch (ViT tower) tiles: no GroupNorm there, and their epilogue is compiled without the
     // statistics code (the fit kernels' epilogues are sensitive to every register and branch: profiles/r05_ln_fold/)
     constexpr bool STATS = BM % 80 != 0;
@@ -287,7 +287,7 @@ __device__ __forceinline__ void fit_finish(const GemmArgs& p, float* const fl, f
                 }
                 v0 = epilogue_math4<T16>(act, alpha, v0, bias0, pbm[ic][ps], a0, has_resid, r0, p0);
                 v1 = epilogue_math4<T16>(act, alpha, v1, bias1, pbm[ic][ps], a1, has_resid, r1, p1);
-                if (act == PRX_ACT_QUICKGELU && d.out_bf16_pre) {
+                if (prx_act_saves_pre(act) && d.out_bf16_pre) {
                     t16x8 q;
                     q[0] = op_cvt<T16>(p0.x); q[1] = op_cvt<T16>(p0.y); q[2] = op_cvt<T16>(p0.z); q[3] = op_cvt<T16>(p0.w);
                     q[4] = op_cvt<T16>(p1.x); q[5] = op_cvt<T16>(p1.y); q[6] = op_cvt<T16>(p1.z); q[7] = op_cvt<T16>(p1.w);

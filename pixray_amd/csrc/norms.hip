@@ -242,9 +242,15 @@ __global__ __launch_bounds__(256) void gn_apply_bwd_kernel(const GNArgs a, const
 }
 
 // ---------------------------------------------------------------------------
-// LayerNorm over rows of width C (C % 256 == 0, C <= 2048): one wave per row.
+// LayerNorm over rows of width C (C % 128 == 0, C <= 2048): one wave per row.
+// RAG (C % 256 == 128: the 384-wide ViT-S/16 towers): the last float4 vector of a row is held by lanes 0 .. 31 only; `ln_own`
+// says whether vector i of this lane exists.  With RAG = false it is `i < nv`, the expression the kernels had before.
 // ---------------------------------------------------------------------------
-template <int MAXV, bool S16>
+template <bool RAG>
+__device__ __forceinline__ bool ln_own(int i, int nv, int lane, int C) {
+    return RAG ? (i * 64 + lane) * 4 < C : i < nv;
+}
+template <int MAXV, bool S16, bool RAG = false>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const void* __restrict__ x, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, bf16_t* __restrict__ out_bf16,
                                                      float* __restrict__ out_f32, float* __restrict__ mean_out,
@@ -253,7 +259,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const void* __restrict__ x,
     const int lane = threadIdx.x & 63;
     const int row = (xcd ? xcd_linear(blockIdx.x, gridDim.x) : blockIdx.x) * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const int nv = C >> 8;  // float4 per lane
+    const int nv = (C + 255) >> 8;  // float4 per lane
     const size_t xr4 = (size_t)row * ldx / 4;          // ldx % 4 == 0 (checked on the host)
     // every load of the row -- x, gamma, beta -- is requested up front with a CLAMPED vector index (i >= nv re-reads vector 0 and is
     // ignored), not inside `if (i < nv)`: a wave-uniform branch around a load is a join point at which the compiler waits for
@@ -261,20 +267,20 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const void* __restrict__ x,
     // of a kernel that is one round trip + two wave reductions long
     float4 v[MAXV], gav[MAXV], bev[MAXV];
 #pragma unroll
-    for (int i = 0; i < MAXV; ++i) v[i] = stream_ld4<S16>(x, xr4 + (i < nv ? i : 0) * 64 + lane, h16);
+    for (int i = 0; i < MAXV; ++i) v[i] = stream_ld4<S16>(x, xr4 + (ln_own<RAG>(i, nv, lane, C) ? i * 64 + lane : (RAG ? 0 : lane)), h16);
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
-        gav[i] = reinterpret_cast<const float4*>(gamma)[(i < nv ? i : 0) * 64 + lane];
-        bev[i] = reinterpret_cast<const float4*>(beta)[(i < nv ? i : 0) * 64 + lane];
+        gav[i] = reinterpret_cast<const float4*>(gamma)[(ln_own<RAG>(i, nv, lane, C) ? i * 64 + lane : (RAG ? 0 : lane))];
+        bev[i] = reinterpret_cast<const float4*>(beta)[(ln_own<RAG>(i, nv, lane, C) ? i * 64 + lane : (RAG ? 0 : lane))];
     }
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < MAXV; ++i) s += i < nv ? (v[i].x + v[i].y) + (v[i].z + v[i].w) : 0.f;
+    for (int i = 0; i < MAXV; ++i) s += ln_own<RAG>(i, nv, lane, C) ? (v[i].x + v[i].y) + (v[i].z + v[i].w) : 0.f;
     const float mean = wave_sum(s) / (float)C;
     float ss = 0.f;
 #pragma unroll
     for (int i = 0; i < MAXV; ++i)
-        if (i < nv) {
+        if (ln_own<RAG>(i, nv, lane, C)) {
             float a0 = v[i].x - mean, a1 = v[i].y - mean, a2 = v[i].z - mean, a3 = v[i].w - mean;
             ss += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
         }
@@ -286,7 +292,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const void* __restrict__ x,
     }
 #pragma unroll
     for (int i = 0; i < MAXV; ++i)
-        if (i < nv) {
+        if (ln_own<RAG>(i, nv, lane, C)) {
             const int c4 = i * 64 + lane;
             const float4 ga = gav[i], be = bev[i];
             float o0 = (v[i].x - mean) * rstd * ga.x + be.x;
@@ -301,7 +307,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const void* __restrict__ x,
 }
 
 // dx_out[row] = (add ? add[row] : 0) + rstd*(dxhat - mean(dxhat) - xhat*mean(dxhat*xhat)),  dxhat = g*gamma
-template <int MAXV, int S16>     // S16 bits: 1 = x, 2 = g, 4 = add are 16-bit streams
+template <int MAXV, int S16, bool RAG = false>     // S16 bits: 1 = x, 2 = g, 4 = add are 16-bit streams
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ g, long long ldg,
                                                      const void* __restrict__ x, long long ldx,
                                                      const float* __restrict__ gamma, const float* __restrict__ mean_in,
@@ -312,7 +318,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ g,
     const int row = (xcd ? xcd_linear(blockIdx.x, gridDim.x) : blockIdx.x) * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     if (add_every > 0 && row % add_every != 0) add = nullptr;      // wave-uniform
-    const int nv = C >> 8;
+    const int nv = (C + 255) >> 8;
     const float mean = mean_in[row], rstd = rstd_in[row];
     const size_t xr4 = (size_t)row * ldx / 4, gr4 = (size_t)row * ldg / 4;        // leading dimensions are multiples of 4 (host check)
     // all loads of the row up front with clamped vector indices (ln_fwd_kernel's note); `add` is wave-uniform: clamped to x when absent
@@ -321,14 +327,14 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ g,
         float4 xv[MAXV], gv[MAXV], ga[MAXV];
 #pragma unroll
         for (int i = 0; i < MAXV; ++i) {
-            const int c4 = (i < nv ? i : 0) * 64 + lane;
+            const int c4 = (ln_own<RAG>(i, nv, lane, C) ? i * 64 + lane : (RAG ? 0 : lane));
             xv[i] = stream_ld4<(S16 & 1) != 0>(x, xr4 + c4, h16);
             gv[i] = stream_ld4<(S16 & 2) != 0>(g, gr4 + c4, h16);
             ga[i] = reinterpret_cast<const float4*>(gamma)[c4];
         }
         if (add) {
 #pragma unroll
-            for (int i = 0; i < MAXV; ++i) adv[i] = stream_ld4<(S16 & 4) != 0>(add, (size_t)row * ldadd / 4 + (i < nv ? i : 0) * 64 + lane, h16);
+            for (int i = 0; i < MAXV; ++i) adv[i] = stream_ld4<(S16 & 4) != 0>(add, (size_t)row * ldadd / 4 + (ln_own<RAG>(i, nv, lane, C) ? i * 64 + lane : (RAG ? 0 : lane)), h16);
         }
 #pragma unroll
         for (int i = 0; i < MAXV; ++i) {
@@ -339,14 +345,14 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ g,
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
-        s1 += i < nv ? (dh[i].x + dh[i].y) + (dh[i].z + dh[i].w) : 0.f;
-        s2 += i < nv ? (dh[i].x * xh[i].x + dh[i].y * xh[i].y) + (dh[i].z * xh[i].z + dh[i].w * xh[i].w) : 0.f;
+        s1 += ln_own<RAG>(i, nv, lane, C) ? (dh[i].x + dh[i].y) + (dh[i].z + dh[i].w) : 0.f;
+        s2 += ln_own<RAG>(i, nv, lane, C) ? (dh[i].x * xh[i].x + dh[i].y * xh[i].y) + (dh[i].z * xh[i].z + dh[i].w * xh[i].w) : 0.f;
     }
     const float m1 = wave_sum(s1) / (float)C;
     const float m2 = wave_sum(s2) / (float)C;
 #pragma unroll
     for (int i = 0; i < MAXV; ++i)
-        if (i < nv) {
+        if (ln_own<RAG>(i, nv, lane, C)) {
             const int c4 = i * 64 + lane;
             float4 o = make_float4(rstd * (dh[i].x - m1 - xh[i].x * m2), rstd * (dh[i].y - m1 - xh[i].y * m2),
                                    rstd * (dh[i].z - m1 - xh[i].z * m2), rstd * (dh[i].w - m1 - xh[i].w * m2));
@@ -427,9 +433,18 @@ int prx_groupnorm_bwd(const void* g, const void* x, const float* gamma, const fl
 }
 
 int prx_layernorm_fwd(const void* x, long long ldx, const float* gamma, const float* beta, bf16_t* out_bf16,
-                      float* out_f32, float* mean, float* rstd, int rows, int C, float eps, hipStream_t s, int h16, int s16) {
-    PRX_REQUIRE(C % 256 == 0 && C <= 2048 && ldx % 4 == 0, "layernorm: C must be a multiple of 256 and <= 2048 (C=%d), ldx a multiple of 4", C);
+                      float* out_f32, float* mean, float* rstd, int rows, int C, float eps, hipStream_t s, int h16, int s16, int ragged) {
+    PRX_REQUIRE((C % 256 == 0 || (ragged && C % 128 == 0 && C <= 1024)) && C <= 2048 && ldx % 4 == 0,
+                "layernorm: C must be a multiple of 256 and <= 2048 (C=%d), ldx a multiple of 4", C);
     dim3 grid(ceil_div(rows, 4));
+    if (C % 256 != 0) {      // ragged last vector: its own instances, the others are untouched
+#define PRX_LN_FWD_R(S16) hipLaunchKernelGGL((ln_fwd_kernel<4, S16, true>), grid, dim3(256), 0, s, x, gamma, beta, out_bf16, out_f32, mean, rstd, \
+                                             rows, C, ldx, eps, prx_xcd_local(), h16)
+        if (s16) PRX_LN_FWD_R(true); else PRX_LN_FWD_R(false);
+#undef PRX_LN_FWD_R
+        PRX_LAUNCH_CHECK();
+        return 0;
+    }
 #define PRX_LN_FWD(MAXV, S16) hipLaunchKernelGGL((ln_fwd_kernel<MAXV, S16>), grid, dim3(256), 0, s, x, gamma, beta, out_bf16, out_f32, mean, rstd, \
                                                  rows, C, ldx, eps, prx_xcd_local(), h16)
     if (C <= 1024) { if (s16) PRX_LN_FWD(4, true); else PRX_LN_FWD(4, false); }
@@ -441,11 +456,19 @@ int prx_layernorm_fwd(const void* x, long long ldx, const float* gamma, const fl
 
 int prx_layernorm_bwd(const void* g, long long ldg, const void* x, long long ldx, const float* gamma,
                       const float* mean, const float* rstd, const void* add, long long ldadd, float* dx,
-                      long long lddx, bf16_t* dx_bf16, long long lddxb, int rows, int C, hipStream_t s, int h16, int add_every, int s16) {
-    PRX_REQUIRE(C % 256 == 0 && C <= 2048, "layernorm bwd: C must be a multiple of 256 and <= 2048 (C=%d)", C);
+                      long long lddx, bf16_t* dx_bf16, long long lddxb, int rows, int C, hipStream_t s, int h16, int add_every, int s16, int ragged) {
+    PRX_REQUIRE((C % 256 == 0 || (ragged && C % 128 == 0 && C <= 1024)) && C <= 2048, "layernorm bwd: C must be a multiple of 256 and <= 2048 (C=%d)", C);
     PRX_REQUIRE(ldg % 4 == 0 && ldx % 4 == 0 && ldadd % 4 == 0 && (dx || dx_bf16), "layernorm bwd: leading dimensions must be multiples of 4, one output is needed");
     PRX_REQUIRE(s16 == 0 || s16 == 1 || s16 == 2 || s16 == 7, "layernorm bwd: stream layouts in use are 0, 1 (x), 2 (g), 7 (x, g, add): got %d", s16);
     dim3 grid(ceil_div(rows, 4));
+    if (C % 256 != 0) {      // ragged last vector: its own instances
+#define PRX_LN_BWD_R(S16) hipLaunchKernelGGL((ln_bwd_kernel<4, S16, true>), grid, dim3(256), 0, s, g, ldg, x, ldx, gamma, mean, rstd, add, ldadd, dx, \
+                                             lddx, dx_bf16, lddxb, rows, C, prx_xcd_local(), h16, add_every)
+        if (s16 == 0) PRX_LN_BWD_R(0); else if (s16 == 1) PRX_LN_BWD_R(1); else if (s16 == 2) PRX_LN_BWD_R(2); else PRX_LN_BWD_R(7);
+#undef PRX_LN_BWD_R
+        PRX_LAUNCH_CHECK();
+        return 0;
+    }
 #define PRX_LN_BWD(MAXV, S16) hipLaunchKernelGGL((ln_bwd_kernel<MAXV, S16>), grid, dim3(256), 0, s, g, ldg, x, ldx, gamma, mean, rstd, add, ldadd, dx, \
                                                  lddx, dx_bf16, lddxb, rows, C, prx_xcd_local(), h16, add_every)
 #define PRX_LN_BWD_S(MAXV) do { if (s16 == 0) PRX_LN_BWD(MAXV, 0); else if (s16 == 1) PRX_LN_BWD(MAXV, 1); else if (s16 == 2) PRX_LN_BWD(MAXV, 2); \

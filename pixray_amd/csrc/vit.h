@@ -1,6 +1,19 @@
 #pragma once
 #include "common.h"
+#include "cutouts.h"
 struct PrxVit;
+// What differs between the tower families this runner serves.  CLIP (clip.model.VisionTransformer): no patch-embed bias, ln_pre,
+// eps 1e-5, QuickGELU, CLIP's preprocessing constants.  SLIP (timm VisionTransformer): a bias, no ln_pre, eps 1e-6, exact GELU,
+// the ImageNet constants.
+struct VitFamily {
+    int patch_bias;     // the patch-embed convolution has a bias (bias_n epilogue of its product)
+    int ln_pre;         // a LayerNorm between the token embedding and the first block
+    float eps;          // every LayerNorm's eps
+    int act, dact;      // PRX_ACT_* of the c_fc product and of its dgrad
+    PatchNorm norm;     // channel mean / std of the fused preprocessing
+    int head_dim;       // 0 / 64, or 32 / 16: narrower heads are zero-padded to 64 at weight-packing time (vit.hip PrxVit::hd)
+};
+VitFamily prx_vit_family_clip();
 struct GemmCtx;
 int prx_pack_bf16(const float* in, bf16_t* out, size_t n, hipStream_t s);
 int prx_pack_transpose_bf16(const float* in, bf16_t* out, int R, int C, hipStream_t s);
@@ -8,8 +21,9 @@ int prx_pack_transpose_bf16(const float* in, bf16_t* out, int R, int C, hipStrea
 int prx_pack_op(const float* in, void* out, size_t n, int prec, hipStream_t s);
 int prx_pack_transpose_op(const float* in, void* out, int R, int C, int prec, hipStream_t s);
 int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers, int heads, int out_dim, int max_n,
-                        int precision, const float* const* w, int n_w, hipStream_t s);
+                        int precision, const float* const* w, int n_w, hipStream_t s, const VitFamily* family = nullptr);
 GemmCtx* prx_vit_gemm_ctx_impl(PrxVit* v);
+long long prx_vit_debug_dqkv_impl(PrxVit* v, void* dst, long long max_bytes, hipStream_t s);
 void prx_vit_destroy_impl(PrxVit* v);
 int prx_vit_minmax_impl(PrxVit* v, const float* cutouts, int n, float* mm, hipStream_t s);
 int prx_vit_forward_impl(PrxVit* v, const float* cutouts, int n, const float* mm, float* embeds, hipStream_t s);

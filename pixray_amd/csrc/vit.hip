@@ -1,6 +1,8 @@
 // CLIP visual tower runner (clip.model.VisionTransformer [UPSTREAM openai/CLIP], as called by
 // CLIP_Base.encode_image, slip.py:62-66): forward and activation-gradient backward on the
-// MFMA engine.  Residual stream and LayerNorm statistics stay fp32; every GEMM operand
+// MFMA engine.  The same runner serves the SLIP family (SLIP_Base.encode_image, slip.py:151-157: a timm VisionTransformer
+// [UPSTREAM facebookresearch/SLIP models.py, timm]) through the four switches of VitFamily (vit.h): a patch-embed bias, no
+// ln_pre, LayerNorm eps 1e-6, the exact GELU -- and the preprocessing constants of the first kernel.  Residual stream and LayerNorm statistics stay fp32; every GEMM operand
 // (LN outputs, qkv, attention output, MLP hidden) is bf16; weights are packed once to bf16 in
 // both orientations (forward Bt = W[out,in], dgrad Bt = W^T[in,out]) because they are frozen
 // (slip.py:176).  With precision == PRX_PREC_F32 the same operand buffers hold fp32, the GEMMs run on
@@ -49,6 +51,38 @@ __global__ __launch_bounds__(256) void add_cls_pos_kernel(float* __restrict__ x,
     }
 }
 
+// the family without ln_pre: tokens = [cls + pos[0] ; conv + bias + pos[t]] go straight into the first block's stream (fp32, or the
+// 16-bit stream of the lean layout).  The class-token row of the patch-embed product holds the bias alone (its A row is zero) and is
+// not read.
+template <typename TOut>
+__global__ __launch_bounds__(256) void embed_tokens_kernel(const float* __restrict__ x, const float* __restrict__ cls,
+                                                           const float* __restrict__ pos, TOut* __restrict__ out, int N, int T, int W) {
+    const size_t total = (size_t)N * T * W;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % W);
+        const int t = (int)((i / W) % T);
+        const float p = pos[(size_t)t * W + c];
+        op_st(out, i, t == 0 ? cls[c] + p : x[i] + p);
+    }
+}
+
+// The exact mode's GELU: the fp32-operand 4-wave kernel has the scalar epilogue only, which carries no erff (gemm_epi.h), so the
+// parity mode of the SLIP family applies the activation in a pass of its own -- out = gelu(t), or io *= gelu'(t) in the backward
+// (the same expressions as the fused epilogues of the 16-bit modes; at 1/16 of the MFMA rate the extra pass is not the cost)
+__global__ __launch_bounds__(256) void scale_f32_kernel(float* __restrict__ x, size_t n, float s) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) x[i] *= s;
+}
+
+template <bool BWD>
+__global__ __launch_bounds__(256) void gelu_f32_kernel(const float* __restrict__ t, float* __restrict__ io, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const float x = t[i];
+        const float cdf = 0.5f * (1.f + erff(x * 0.70710678f));
+        if (BWD) io[i] *= cdf + x * (0.39894228f * expf(-0.5f * x * x));
+        else io[i] = x * cdf;
+    }
+}
+
 }  // namespace
 
 int prx_pack_op(const float* in, void* out, size_t n, int prec, hipStream_t s) {
@@ -79,6 +113,13 @@ struct VitLayer {
 
 struct PrxVit {
     int res, patch, width, layers, heads, out_dim, T, max_n, KP;
+    // Padded heads (SLIP's ViT-S/16: 12 heads of 32 on width 384): the attention kernels are head-dim-64, so every head's q, k and v
+    // rows of the qkv projection (weight and bias) are zero-padded to 64 at packing time, and so are the matching input columns of the
+    // out-projection; sqrt(64 / head dim) is folded into the q rows before they are rounded to the operand format, because the
+    // kernels' softmax scale is fixed at 1 / sqrt(64).  The padded lanes carry exact zeros forward (zero weights, zero bias) and
+    // backward (dQ_pad = dS K_pad, dK_pad = dS^T Q_pad, dV_pad = P^T dO_pad with dO_pad = dx Wo_pad^T = 0), so values and gradients
+    // are those of the narrow heads; the price is 64 / head dim times the qkv, attention and out-projection work.
+    int hd, aw;        // head dim of the weights; attention width = heads * 64 (== width when hd == 64)
     int prec;         // PRX_PREC_*: element type of every operand buffer below (void*)
     int f32, h16;     // derived: operands are fp32 / the 16-bit operand format is IEEE half
     float* gs;        // half mode: device {S, 1/S} = the power-of-two scale of the backward in flight (common.h) + 64 partials; else null
@@ -95,6 +136,8 @@ struct PrxVit {
     // GPU arithmetic for this tower (slip.py:175: the CLIP model runs in fp16, residual adds included).  One 16-bit tensor is
     // the saved activation, the LayerNorm input and the residual operand of the next product; dx / dh have no fp32 copy.
     int lean;
+    VitFamily fam;     // what differs between the CLIP and the SLIP towers (vit.h)
+    float* bp;         // patch-embed bias (fam.patch_bias), else null
     int cls_tail;      // 1 (default): the class-token tail below; PRX_VIT_CLS_TAIL=0 runs the last block on every token row (A/B, bisection)
     float* ws; size_t ws_bytes;
     int cur_n;
@@ -138,17 +181,38 @@ int pack_both(PrxVit* v, void** W, void** WT, const float* src, int out, int in,
 }
 }  // namespace
 
+VitFamily prx_vit_family_clip() {
+    VitFamily f;
+    f.patch_bias = 0; f.ln_pre = 1; f.eps = 1e-5f; f.act = PRX_ACT_QUICKGELU; f.dact = PRX_ACT_MUL_DQUICKGELU;
+    f.norm = prx_patch_norm_clip(); f.head_dim = 64;
+    return f;
+}
+
 int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers, int heads, int out_dim, int max_n,
-                        int precision, const float* const* w, int n_w, hipStream_t s) {
+                        int precision, const float* const* w, int n_w, hipStream_t s, const VitFamily* family) {
+    const VitFamily fam = family ? *family : prx_vit_family_clip();
+    // weights ahead of the blocks: conv weight [, conv bias], class token, positions [, ln_pre gamma, beta]
+    const int n_head = 3 + (fam.patch_bias ? 1 : 0) + (fam.ln_pre ? 2 : 0);
     PRX_REQUIRE(prec_valid(precision), "vit_create: unknown precision %d", precision);
-    PRX_REQUIRE(n_w == 5 + 12 * layers + 3, "vit_create: expected %d weight tensors, got %d", 5 + 12 * layers + 3, n_w);
-    PRX_REQUIRE(res % patch == 0 && width == heads * 64 && width % 256 == 0, "vit_create: unsupported geometry");
+    PRX_REQUIRE(n_w == n_head + 12 * layers + 3, "vit_create: expected %d weight tensors, got %d", n_head + 12 * layers + 3, n_w);
+    const int hd = fam.head_dim > 0 ? fam.head_dim : 64;
+    PRX_REQUIRE(res % patch == 0 && width == heads * hd && width % 128 == 0 && (hd == 64 || hd == 32 || hd == 16),
+                "vit_create: unsupported geometry (width %d, %d heads of %d)", width, heads, hd);
+    PRX_REQUIRE(fam.ln_pre || layers >= 1, "vit_create: a tower without ln_pre needs at least one block");
+    PRX_REQUIRE(fam.eps > 0.f && fam.norm.std[0] > 0.f && fam.norm.std[1] > 0.f && fam.norm.std[2] > 0.f,
+                "vit_create: LayerNorm eps and the channel std must be positive");
     const int G = res / patch;
     const int T = G * G + 1;
     PrxVit* v = new PrxVit();
     v->res = res; v->patch = patch; v->width = width; v->layers = layers; v->heads = heads; v->out_dim = out_dim;
     v->prec = precision; v->f32 = prec_is_f32(precision); v->h16 = prec_is_h16(precision);
-    v->gs = nullptr;
+    v->gs = nullptr; v->fam = fam; v->bp = nullptr; v->hd = hd; v->aw = heads * 64;
+    const int AW = v->aw;
+    float *pad_w = nullptr, *pad_b = nullptr;       // fp32 staging of the padded qkv / out-projection weights, reused by every block (stream order)
+    if (hd != 64) {
+        if (int r_ = dev_alloc(v, &pad_w, (size_t)3 * AW * width)) return r_;
+        if (int r_ = dev_alloc(v, &pad_b, (size_t)3 * AW)) return r_;
+    }
     { const char* e = getenv("PRX_LEAN"); v->lean = (v->h16 && !(e && atoi(e) == 0)) ? 1 : 0; }
     { const char* e = getenv("PRX_VIT_CLS_TAIL"); v->cls_tail = (e && atoi(e) == 0) ? 0 : 1; }
     v->T = T; v->max_n = max_n; v->KP = (3 * patch * patch + 7) / 8 * 8; v->cur_n = 0;   // K padded to x8 (L/14: 588 -> 592)
@@ -163,20 +227,48 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
                                        hipMemcpyDeviceToDevice, s));
         if ((r = pack_both(v, &v->Wp, &v->WpT, padded, W, KP, s))) return r;
     }
-    if ((r = copy_f32(v, &v->cls, w[1], W, s))) return r;
-    if ((r = copy_f32(v, &v->pos, w[2], (size_t)T * W, s))) return r;
-    if ((r = copy_f32(v, &v->lnpre_g, w[3], W, s))) return r;
-    if ((r = copy_f32(v, &v->lnpre_b, w[4], W, s))) return r;
+    const float* const* wh = w + 1;
+    if (fam.patch_bias) { if ((r = copy_f32(v, &v->bp, *wh++, W, s))) return r; }
+    if ((r = copy_f32(v, &v->cls, *wh++, W, s))) return r;
+    if ((r = copy_f32(v, &v->pos, *wh++, (size_t)T * W, s))) return r;
+    v->lnpre_g = v->lnpre_b = nullptr;
+    if (fam.ln_pre) {
+        if ((r = copy_f32(v, &v->lnpre_g, *wh++, W, s))) return r;
+        if ((r = copy_f32(v, &v->lnpre_b, *wh++, W, s))) return r;
+    }
     v->L.resize(layers);
     const size_t R = (size_t)max_n * T;
     for (int l = 0; l < layers; ++l) {
-        const float* const* q = w + 5 + 12 * l;
+        const float* const* q = w + n_head + 12 * l;
         VitLayer& y = v->L[l];
         if ((r = copy_f32(v, &y.ln1_g, q[0], W, s))) return r;
         if ((r = copy_f32(v, &y.ln1_b, q[1], W, s))) return r;
-        if ((r = pack_both(v, &y.Wqkv, &y.WqkvT, q[2], 3 * W, W, s))) return r;
-        if ((r = copy_f32(v, &y.bqkv, q[3], 3 * W, s))) return r;
-        if ((r = pack_both(v, &y.Wo, &y.WoT, q[4], W, W, s))) return r;
+        if (hd == 64) {
+            if ((r = pack_both(v, &y.Wqkv, &y.WqkvT, q[2], 3 * W, W, s))) return r;
+            if ((r = copy_f32(v, &y.bqkv, q[3], 3 * W, s))) return r;
+            if ((r = pack_both(v, &y.Wo, &y.WoT, q[4], W, W, s))) return r;
+        } else {
+            const float qs = sqrtf(64.f / (float)hd);
+            // qkv rows: section (q | k | v) x head x hd rows of W floats -> the first hd of every head's 64 rows
+            PRX_CHECK_HIP(hipMemsetAsync(pad_w, 0, sizeof(float) * (size_t)3 * AW * W, s));
+            PRX_CHECK_HIP(hipMemsetAsync(pad_b, 0, sizeof(float) * (size_t)3 * AW, s));
+            for (int sect = 0; sect < 3; ++sect) {
+                PRX_CHECK_HIP(hipMemcpy2DAsync(pad_w + (size_t)sect * AW * W, sizeof(float) * 64 * W, q[2] + (size_t)sect * W * W, sizeof(float) * hd * W,
+                                               sizeof(float) * hd * W, heads, hipMemcpyDeviceToDevice, s));
+                PRX_CHECK_HIP(hipMemcpy2DAsync(pad_b + (size_t)sect * AW, sizeof(float) * 64, q[3] + (size_t)sect * W, sizeof(float) * hd,
+                                               sizeof(float) * hd, heads, hipMemcpyDeviceToDevice, s));
+            }
+            hipLaunchKernelGGL(scale_f32_kernel, dim3(256), dim3(256), 0, s, pad_w, (size_t)AW * W, qs);
+            hipLaunchKernelGGL(scale_f32_kernel, dim3(1), dim3(256), 0, s, pad_b, (size_t)AW, qs);
+            PRX_LAUNCH_CHECK();
+            if ((r = pack_both(v, &y.Wqkv, &y.WqkvT, pad_w, 3 * AW, W, s))) return r;
+            if ((r = copy_f32(v, &y.bqkv, pad_b, 3 * AW, s))) return r;
+            // out-projection [W, W]: input columns head x hd -> the first hd of every head's 64 columns of [W, AW]
+            PRX_CHECK_HIP(hipMemsetAsync(pad_w, 0, sizeof(float) * (size_t)W * AW, s));
+            PRX_CHECK_HIP(hipMemcpy2DAsync(pad_w, sizeof(float) * 64, q[4], sizeof(float) * hd, sizeof(float) * hd, (size_t)W * heads,
+                                           hipMemcpyDeviceToDevice, s));
+            if ((r = pack_both(v, &y.Wo, &y.WoT, pad_w, W, AW, s))) return r;
+        }
         if ((r = copy_f32(v, &y.bo, q[5], W, s))) return r;
         if ((r = copy_f32(v, &y.ln2_g, q[6], W, s))) return r;
         if ((r = copy_f32(v, &y.ln2_b, q[7], W, s))) return r;
@@ -187,17 +279,17 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
         if (v->lean) { ALLOC_OP(y.x_in, R * W); ALLOC_OP(y.x_mid, R * W); }
         else { float *a_, *b_; ALLOC(a_, R * W); ALLOC(b_, R * W); y.x_in = a_; y.x_mid = b_; }
         ALLOC(y.mean1, R); ALLOC(y.rstd1, R); ALLOC(y.mean2, R); ALLOC(y.rstd2, R);
-        ALLOC_OP(y.qkv, R * 3 * W); ALLOC_OP(y.t, R * 4 * W);
+        ALLOC_OP(y.qkv, R * 3 * AW); ALLOC_OP(y.t, R * 4 * W);
         y.o_save = nullptr; y.lse = nullptr;
-        if (T > 64 || v->f32) { ALLOC_OP(y.o_save, R * W); ALLOC(y.lse, (size_t)max_n * heads * T); }
+        if (T > 64 || v->f32) { ALLOC_OP(y.o_save, R * AW); ALLOC(y.lse, (size_t)max_n * heads * T); }
     }
-    const float* const* q = w + 5 + 12 * layers;
+    const float* const* q = w + n_head + 12 * layers;
     if ((r = copy_f32(v, &v->lnpost_g, q[0], W, s))) return r;
     if ((r = copy_f32(v, &v->lnpost_b, q[1], W, s))) return r;
     // proj is [width, out]: forward Bt = proj^T [out, width]; dgrad Bt = proj [width, out]
     if ((r = pack_both(v, &v->proj, &v->projT, q[2], W, out_dim, s))) return r;
-    ALLOC_OP(v->A0, R * KP); ALLOC_OP(v->h, R * W); ALLOC_OP(v->att_o, R * W); ALLOC_OP(v->u, R * 4 * W);
-    ALLOC_OP(v->hpost, (size_t)max_n * W); ALLOC_OP(v->de16, (size_t)max_n * out_dim); ALLOC_OP(v->dt, R * 4 * W); ALLOC_OP(v->do_, R * W); ALLOC_OP(v->dqkv, R * 3 * W);
+    ALLOC_OP(v->A0, R * KP); ALLOC_OP(v->h, R * W); ALLOC_OP(v->att_o, R * AW); ALLOC_OP(v->u, R * 4 * W);
+    ALLOC_OP(v->hpost, (size_t)max_n * W); ALLOC_OP(v->de16, (size_t)max_n * out_dim); ALLOC_OP(v->dt, R * 4 * W); ALLOC_OP(v->do_, R * AW); ALLOC_OP(v->dqkv, R * 3 * AW);
     ALLOC(v->xpre, R * W); ALLOC(v->mean_pre, R); ALLOC(v->rstd_pre, R);
     if (v->lean) ALLOC_OP(v->x_final, R * W);
     else { float* a_; ALLOC(a_, R * W); v->x_final = a_; }
@@ -229,12 +321,18 @@ static int vit_gemm(PrxVit* v, GemmDesc& d, hipStream_t s) {
     return prx_gemm_launch(d, v->ws, v->ws_bytes, s, &v->gctx);
 }
 GemmCtx* prx_vit_gemm_ctx_impl(PrxVit* v) { return v ? &v->gctx : nullptr; }
+long long prx_vit_debug_dqkv_impl(PrxVit* v, void* dst, long long max_bytes, hipStream_t s) {
+    if (!v || v->cur_n < 1) return -1;
+    const long long bytes = (long long)op_esz(v->f32) * v->cur_n * v->T * 3 * v->aw;
+    if (bytes > max_bytes || hipMemcpyAsync(dst, v->dqkv, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) return -1;
+    return bytes;
+}
 
 // LayerNorm whose output is a GEMM operand: bf16, or fp32 in the exact mode (the kernel has both outputs)
 static int ln_op(PrxVit* v, const void* x, long long ldx, const float* g, const float* b, void* out, float* mean, float* rstd,
                  int rows, hipStream_t s) {
     return prx_layernorm_fwd(x, ldx, g, b, v->f32 ? nullptr : (bf16_t*)out, v->f32 ? (float*)out : nullptr, mean, rstd, rows,
-                             v->width, 1e-5f, s, v->h16, v->lean);
+                             v->width, v->fam.eps, s, v->h16, v->lean, 1);
 }
 // LayerNorm backward producing the fp32 gradient stream + its operand twin (the same buffer in the exact mode)
 // `s16`: which of x (1), g (2), add (4) are 16-bit streams (the lean layout; dx is then null and dx_op the only output)
@@ -242,7 +340,7 @@ static int ln_bwd_op(PrxVit* v, const void* g, long long ldg, const void* x, lon
                      const float* rstd, const void* add, long long ldadd, float* dx, long long lddx, void* dx_op, int rows,
                      hipStream_t s, int add_every = 0, int s16 = 0) {
     return prx_layernorm_bwd(g, ldg, x, ldx, gamma, mean, rstd, add, ldadd, dx, lddx, v->f32 ? nullptr : (bf16_t*)dx_op, lddx, rows,
-                             v->width, s, v->h16, add_every, s16);
+                             v->width, s, v->h16, add_every, s16, 1);
 }
 
 int prx_vit_minmax_impl(PrxVit* v, const float* cutouts, int n, float* mm, hipStream_t s) {
@@ -252,46 +350,59 @@ int prx_vit_minmax_impl(PrxVit* v, const float* cutouts, int n, float* mm, hipSt
 
 int prx_vit_forward_impl(PrxVit* v, const float* cutouts, int n, const float* mm, float* embeds, hipStream_t s) {
     PRX_REQUIRE(n >= 1 && n <= v->max_n, "vit: batch %d exceeds handle capacity %d", n, v->max_n);
-    const int W = v->width, T = v->T, R = n * T, KP = v->KP;
+    const int W = v->width, T = v->T, R = n * T, KP = v->KP, AW = v->aw;
     int r;
     v->cur_n = n;
-    if ((r = prx_patchify_fwd(cutouts, mm, v->A0, v->prec, n, v->res, v->patch, T, s))) return r;
+    if ((r = prx_patchify_fwd(cutouts, mm, v->A0, v->prec, n, v->res, v->patch, T, s, v->fam.norm))) return r;
     {   // conv1 (patch embed) as GEMM
         GemmDesc d; d.A = v->A0; d.lda = KP; d.B = v->Wp; d.ldb = KP; d.M = R; d.N = W; d.K = KP;
+        d.bias_n = v->bp;
         d.out_f32 = v->xpre; d.ldc_f32 = W;
         if ((r = vit_gemm(v, d, s))) return r;
     }
-    hipLaunchKernelGGL(add_cls_pos_kernel, dim3(2048), dim3(256), 0, s, v->xpre, v->cls, v->pos, n, T, W);
-    PRX_LAUNCH_CHECK();
     const int lean = v->lean;
     void* x0 = v->layers > 0 ? v->L[0].x_in : v->x_final;
-    if ((r = prx_layernorm_fwd(v->xpre, W, v->lnpre_g, v->lnpre_b, lean ? (bf16_t*)x0 : nullptr, lean ? nullptr : (float*)x0, v->mean_pre,
-                               v->rstd_pre, R, W, 1e-5f, s, v->h16))) return r;
+    if (v->fam.ln_pre) {
+        hipLaunchKernelGGL(add_cls_pos_kernel, dim3(2048), dim3(256), 0, s, v->xpre, v->cls, v->pos, n, T, W);
+        PRX_LAUNCH_CHECK();
+        if ((r = prx_layernorm_fwd(v->xpre, W, v->lnpre_g, v->lnpre_b, lean ? (bf16_t*)x0 : nullptr, lean ? nullptr : (float*)x0, v->mean_pre,
+                                   v->rstd_pre, R, W, v->fam.eps, s, v->h16, 0, 1))) return r;
+    } else {
+        if (lean) hipLaunchKernelGGL(embed_tokens_kernel<half_t>, dim3(2048), dim3(256), 0, s, v->xpre, v->cls, v->pos, (half_t*)x0, n, T, W);   // lean implies IEEE half
+        else hipLaunchKernelGGL(embed_tokens_kernel<float>, dim3(2048), dim3(256), 0, s, v->xpre, v->cls, v->pos, (float*)x0, n, T, W);
+        PRX_LAUNCH_CHECK();
+    }
     for (int l = 0; l < v->layers; ++l) {
         VitLayer& y = v->L[l];
         void* x_next = (l + 1 < v->layers) ? v->L[l + 1].x_in : v->x_final;
         if ((r = ln_op(v, y.x_in, W, y.ln1_g, y.ln1_b, v->h, y.mean1, y.rstd1, R, s))) return r;
-        {   GemmDesc d; d.A = v->h; d.lda = W; d.B = y.Wqkv; d.ldb = W; d.M = R; d.N = 3 * W; d.K = W;
-            d.bias_n = y.bqkv; d.out_bf16 = y.qkv; d.ldc_bf16 = 3 * W;
+        {   GemmDesc d; d.A = v->h; d.lda = W; d.B = y.Wqkv; d.ldb = W; d.M = R; d.N = 3 * AW; d.K = W;
+            d.bias_n = y.bqkv; d.out_bf16 = y.qkv; d.ldc_bf16 = 3 * AW;
             if ((r = vit_gemm(v, d, s))) return r; }
         const void* att = v->att_o;
-        if (v->f32) { if ((r = prx_mha_fwd_f32((const float*)y.qkv, (float*)y.o_save, y.lse, n, T, W, v->heads, s))) return r; att = y.o_save; }
-        else if (T <= 64) { if ((r = prx_mha_fwd((const bf16_t*)y.qkv, (bf16_t*)v->att_o, n, T, W, v->heads, s, v->h16))) return r; }
-        else { if ((r = prx_mha_fwd_gen((const bf16_t*)y.qkv, (bf16_t*)y.o_save, y.lse, n, T, W, v->heads, s, v->h16))) return r; att = y.o_save; }
+        if (v->f32) { if ((r = prx_mha_fwd_f32((const float*)y.qkv, (float*)y.o_save, y.lse, n, T, AW, v->heads, s))) return r; att = y.o_save; }
+        else if (T <= 64) { if ((r = prx_mha_fwd((const bf16_t*)y.qkv, (bf16_t*)v->att_o, n, T, AW, v->heads, s, v->h16))) return r; }
+        else { if ((r = prx_mha_fwd_gen((const bf16_t*)y.qkv, (bf16_t*)y.o_save, y.lse, n, T, AW, v->heads, s, v->h16))) return r; att = y.o_save; }
         // the class-token tail: rows = the n class tokens, reached through a row stride of T * W in the token-major buffers;
         // LN / MLP intermediates of those rows are stored densely ([n][...]) at the start of their buffers
         const bool tail = v->cls_tail && l == v->layers - 1;
         const int rows = tail ? n : R;
         const int ldt = tail ? T * W : W;            // row stride of the token-major fp32 / 16-bit [R, W] buffers
-        {   GemmDesc d; d.A = att; d.lda = ldt; d.B = y.Wo; d.ldb = W; d.M = rows; d.N = W; d.K = W;
+        {   GemmDesc d; d.A = att; d.lda = tail ? T * AW : AW; d.B = y.Wo; d.ldb = AW; d.M = rows; d.N = W; d.K = AW;
             d.bias_n = y.bo; d.ldr = ldt;
             if (lean) { d.resid = (const float*)y.x_in; d.row16 = 1; d.out_bf16 = y.x_mid; d.ldc_bf16 = ldt; }
             else { d.resid = (const float*)y.x_in; d.out_f32 = (float*)y.x_mid; d.ldc_f32 = ldt; }
             if ((r = vit_gemm(v, d, s))) return r; }
         if ((r = ln_op(v, y.x_mid, ldt, y.ln2_g, y.ln2_b, v->h, y.mean2, y.rstd2, rows, s))) return r;
         {   GemmDesc d; d.A = v->h; d.lda = W; d.B = y.W1; d.ldb = W; d.M = rows; d.N = 4 * W; d.K = W;
-            d.bias_n = y.b1; d.act = PRX_ACT_QUICKGELU; d.out_bf16 = v->u; d.out_bf16_pre = y.t; d.ldc_bf16 = 4 * W;
-            if ((r = vit_gemm(v, d, s))) return r; }
+            d.bias_n = y.b1; d.act = v->fam.act; d.out_bf16 = v->u; d.out_bf16_pre = y.t; d.ldc_bf16 = 4 * W;
+            const bool own_pass = v->f32 && v->fam.act == PRX_ACT_GELU;      // see gelu_f32_kernel
+            if (own_pass) { d.act = PRX_ACT_NONE; d.out_bf16 = y.t; d.out_bf16_pre = nullptr; }
+            if ((r = vit_gemm(v, d, s))) return r;
+            if (own_pass) {
+                hipLaunchKernelGGL(gelu_f32_kernel<false>, dim3(2048), dim3(256), 0, s, (const float*)y.t, (float*)v->u, (size_t)rows * 4 * W);
+                PRX_LAUNCH_CHECK();
+            } }
         {   GemmDesc d; d.A = v->u; d.lda = 4 * W; d.B = y.W2; d.ldb = 4 * W; d.M = rows; d.N = W; d.K = 4 * W;
             d.bias_n = y.b2; d.ldr = ldt;
             if (lean) { d.resid = (const float*)y.x_mid; d.row16 = 1; d.out_bf16 = x_next; d.ldc_bf16 = ldt; }
@@ -313,7 +424,7 @@ int prx_vit_backward_a_impl(PrxVit* v, const float* cutouts, const float* mm, co
                             hipStream_t s) {
     const int n = v->cur_n;
     PRX_REQUIRE(n >= 1, "vit backward: no forward in flight on this handle");
-    const int W = v->width, T = v->T, R = n * T, KP = v->KP;
+    const int W = v->width, T = v->T, R = n * T, KP = v->KP, AW = v->aw;
     int r;
     if ((r = prx_l2norm_bwd(v->e, d_embeds, v->de, n, v->out_dim, s))) return r;
     {   GemmDesc d; d.A = v->de; d.a_is_f32 = 1; d.lda = v->out_dim; d.B = v->proj; d.ldb = v->out_dim;
@@ -346,41 +457,49 @@ int prx_vit_backward_a_impl(PrxVit* v, const float* cutouts, const float* mm, co
         const bool tail = v->cls_tail && l == v->layers - 1;
         const int rows = tail ? n : R;
         const int ldt = tail ? T * W : W;
-        // MLP: x_next = x_mid + c_proj(quickgelu(c_fc(ln_2(x_mid))))
+        // MLP: x_next = x_mid + c_proj(act(c_fc(ln_2(x_mid)))), act = QuickGELU (CLIP) | GELU (SLIP)
         {   GemmDesc d; d.A = v->dx_bf; d.lda = ldt; d.B = y.W2T; d.ldb = W; d.M = rows; d.N = 4 * W; d.K = W;
-            d.act = PRX_ACT_MUL_DQUICKGELU; d.aux = y.t; d.ldaux = 4 * W; d.out_bf16 = v->dt; d.ldc_bf16 = 4 * W;
-            if ((r = vit_gemm(v, d, s))) return r; }
+            d.act = v->fam.dact; d.aux = y.t; d.ldaux = 4 * W; d.out_bf16 = v->dt; d.ldc_bf16 = 4 * W;
+            const bool own_pass = v->f32 && v->fam.dact == PRX_ACT_MUL_DGELU;      // see gelu_f32_kernel
+            if (own_pass) { d.act = PRX_ACT_NONE; d.aux = nullptr; }
+            if ((r = vit_gemm(v, d, s))) return r;
+            if (own_pass) {
+                hipLaunchKernelGGL(gelu_f32_kernel<true>, dim3(2048), dim3(256), 0, s, (const float*)y.t, (float*)v->dt, (size_t)rows * 4 * W);
+                PRX_LAUNCH_CHECK();
+            } }
         {   GemmDesc d; d.A = v->dt; d.lda = 4 * W; d.B = y.W1T; d.ldb = 4 * W; d.M = rows; d.N = W; d.K = 4 * W;
             if (lean) { d.out_bf16 = v->dh_bf; d.ldc_bf16 = W; } else { d.out_f32 = v->dh; d.ldc_f32 = W; }
             if ((r = vit_gemm(v, d, s))) return r; }
         if ((r = ln_bwd_op(v, dhs, W, y.x_mid, ldt, y.ln2_g, y.mean2, y.rstd2, dxs, ldt, v->dx, ldt, v->dx_bf, rows, s, 0, lean ? 7 : 0))) return r;
         // attention: x_mid = x_in + out_proj(mha(ln_1(x_in)))
         if (tail)       // d(attention output) is written on the class-token rows only: the other rows must read as zero
-            PRX_CHECK_HIP(hipMemsetAsync(v->do_, 0, op_esz(v->f32) * (size_t)R * W, s));
-        {   GemmDesc d; d.A = v->dx_bf; d.lda = ldt; d.B = y.WoT; d.ldb = W; d.M = rows; d.N = W; d.K = W;
-            d.out_bf16 = v->do_; d.ldc_bf16 = ldt;
+            PRX_CHECK_HIP(hipMemsetAsync(v->do_, 0, op_esz(v->f32) * (size_t)R * AW, s));
+        {   GemmDesc d; d.A = v->dx_bf; d.lda = ldt; d.B = y.WoT; d.ldb = W; d.M = rows; d.N = AW; d.K = W;
+            d.out_bf16 = v->do_; d.ldc_bf16 = tail ? T * AW : AW;
             if ((r = vit_gemm(v, d, s))) return r; }
-        if (v->f32) { if ((r = prx_mha_bwd_f32((const float*)y.qkv, (const float*)y.o_save, (const float*)v->do_, y.lse, (float*)v->dqkv, n, T, W, v->heads, s))) return r; }
-        else if (T <= 64) { if ((r = prx_mha_bwd((const bf16_t*)y.qkv, (const bf16_t*)v->do_, (bf16_t*)v->dqkv, n, T, W, v->heads, s, v->h16))) return r; }
-        else { if ((r = prx_mha_bwd_gen((const bf16_t*)y.qkv, (const bf16_t*)y.o_save, (const bf16_t*)v->do_, y.lse, (bf16_t*)v->dqkv, n, T, W, v->heads, s, v->h16))) return r; }
-        {   GemmDesc d; d.A = v->dqkv; d.lda = 3 * W; d.B = y.WqkvT; d.ldb = 3 * W; d.M = R; d.N = W; d.K = 3 * W;
+        if (v->f32) { if ((r = prx_mha_bwd_f32((const float*)y.qkv, (const float*)y.o_save, (const float*)v->do_, y.lse, (float*)v->dqkv, n, T, AW, v->heads, s))) return r; }
+        else if (T <= 64) { if ((r = prx_mha_bwd((const bf16_t*)y.qkv, (const bf16_t*)v->do_, (bf16_t*)v->dqkv, n, T, AW, v->heads, s, v->h16))) return r; }
+        else { if ((r = prx_mha_bwd_gen((const bf16_t*)y.qkv, (const bf16_t*)y.o_save, (const bf16_t*)v->do_, y.lse, (bf16_t*)v->dqkv, n, T, AW, v->heads, s, v->h16))) return r; }
+        {   GemmDesc d; d.A = v->dqkv; d.lda = 3 * AW; d.B = y.WqkvT; d.ldb = 3 * AW; d.M = R; d.N = W; d.K = 3 * AW;
             if (lean) { d.out_bf16 = v->dh_bf; d.ldc_bf16 = W; } else { d.out_f32 = v->dh; d.ldc_f32 = W; }
             if ((r = vit_gemm(v, d, s))) return r; }
         if ((r = ln_bwd_op(v, dhs, W, y.x_in, W, y.ln1_g, y.mean1, y.rstd1, dxs, W, v->dx, W, v->dx_bf, R, s, tail ? T : 0, lean ? 7 : 0))) return r;
     }
-    // ln_pre backward (in place on dx), then patch-embed dgrad
-    if ((r = ln_bwd_op(v, dxs, W, v->xpre, W, v->lnpre_g, v->mean_pre, v->rstd_pre, nullptr, 0, v->dh, W, v->dh_bf, R, s, 0, lean ? 2 : 0))) return r;
-    {   GemmDesc d; d.A = v->dh_bf; d.lda = W; d.B = v->WpT; d.ldb = W; d.M = R; d.N = KP; d.K = W;
+    // ln_pre backward (in place on dx), then patch-embed dgrad; without ln_pre the stream's gradient is the token gradient itself and
+    // its operand twin (dx_bf, written by the first block's ln_1 backward) feeds the dgrad directly -- the bias takes no gradient
+    // (frozen weights) and the class-token row of d(tokens) meets a zero row of A
+    if (v->fam.ln_pre) { if ((r = ln_bwd_op(v, dxs, W, v->xpre, W, v->lnpre_g, v->mean_pre, v->rstd_pre, nullptr, 0, v->dh, W, v->dh_bf, R, s, 0, lean ? 2 : 0))) return r; }
+    {   GemmDesc d; d.A = v->fam.ln_pre ? v->dh_bf : v->dx_bf; d.lda = W; d.B = v->WpT; d.ldb = W; d.M = R; d.N = KP; d.K = W;
         d.out_f32 = v->dA0; d.ldc_f32 = KP;
         if (v->h16) d.alpha_dev = v->gs + 1;      // ... and is unscaled (1/S) here, before the (rank-summed) renormalisation sums
         if ((r = vit_gemm(v, d, s))) return r; }
-    return prx_patchify_bwd_reduce(cutouts, mm, v->dA0, acc, n, v->res, v->patch, T, s);
+    return prx_patchify_bwd_reduce(cutouts, mm, v->dA0, acc, n, v->res, v->patch, T, s, v->fam.norm);
 }
 
 int prx_vit_backward_b_impl(PrxVit* v, const float* cutouts, const float* mm, const double* acc, float* g_cutouts,
                             hipStream_t s) {
     const int n = v->cur_n;
     PRX_REQUIRE(n >= 1, "vit backward: no forward in flight on this handle");
-    int r = prx_patchify_bwd_apply(cutouts, mm, v->dA0, acc, g_cutouts, n, v->res, v->patch, v->T, s);
+    int r = prx_patchify_bwd_apply(cutouts, mm, v->dA0, acc, g_cutouts, n, v->res, v->patch, v->T, s, v->fam.norm);
     return r;
 }

@@ -14,7 +14,7 @@ pixray drives this package unchanged:
     pixray.do_init(settings); pixray.do_run(settings)
 
 Not carried over (outside SURVEY.md section 8): the notebook display calls, the `--transparent_weight`
-parsing helper of util.py, the SLIP perceptors, ffmpeg video / gif assembly (the frame files are written;
+parsing helper of util.py, the SIMCLR_VITS16 perceptor (it has no text side; refused by name), ffmpeg video / gif assembly (the frame files are written;
 `make_video` / animation gif need ffmpeg and are skipped with a message when it is absent), the per-frame target-image prompt
 table of the animation mode (`pmsTargetTable`, pixray.py:772-795: target images score every frame here), the vdiff drawer (its
 source is not in the reference checkout), and the super_resolution drawer (it needs RealESRGAN weights).
@@ -228,9 +228,15 @@ CORE_OPTIONS = [
 # options of this package only: operand precision of the HIP runners (include/prx.h PRX_PREC_*; "ref" = f32 decoder + fp16 towers)
 EXTRA_OPTIONS = [(None, "--precision", "precision", _S, None, {})]
 
-QUALITY_CLIP_MODELS = {            # pixray.py:1824-1832 (the 'clip' family; the SLIP families need the SLIP checkpoints' code)
+QUALITY_CLIP_MODELS = {            # pixray.py:1824-1832 (the 'clip' family)
     "draft": "ViT-B/16", "normal": "ViT-B/32,ViT-B/16", "better": "RN50,ViT-B/32,ViT-B/16",
     "best": "RN50x4,ViT-B/32,ViT-B/16", "supreme": "RN50x4,RN101,ViT-B/32,ViT-B/16"}
+PERCEPTOR_TABLES = {               # pixray.py:1824-1846: --perceptors -> quality -> --clip_models
+    "clip": QUALITY_CLIP_MODELS,
+    "slip": {"draft": "SLIP_VITB16", "normal": "SLIP_VITB16,SLIP_CC3M", "better": "SLIP_VITB16,SLIP_CC3M,SLIP_CC12M",
+             "best": "SLIP_VITB16,SLIP_CC3M,SLIP_CC12M,SLIP_VITS16", "supreme": "SLIP_VITB16,SLIP_CC3M,SLIP_CC12M,SLIP_VITS16,SLIP_VITL16"},
+    "mixed": {"draft": "ViT-B/16", "normal": "ViT-B/16,SLIP_VITB16", "better": "RN50,ViT-B/16,SLIP_VITB16",
+              "best": "RN50x4,ViT-B/16,SLIP_VITB16", "supreme": "RN50x4,RN101,ViT-B/16,SLIP_VITB16"}}
 QUALITY_TABLES = {                 # pixray.py:1849-1879: iterations, size scale, cutouts per batch, batches
     "draft": (200, 1, 24, 1), "normal": (250, 2, 30, 1), "better": (300, 3, 36, 1), "best": (350, 4, 12, 2), "supreme": (400, 5, 8, 4)}
 EZSIZE_SCALE = {"small": 1, "medium": 2, "large": 4}                                       # pixray.py:1896-1900
@@ -281,14 +287,14 @@ def process_args(parser: argparse.ArgumentParser, namespace=None, argv=None, run
     if args.outdir != "" and not os.path.exists(args.outdir):
         os.makedirs(args.outdir)
     _initialize_logging(args, given)
-    if args.perceptors != "clip":
-        raise ValueError(f"perceptors={args.perceptors!r}: only the OpenAI CLIP family is provided (SURVEY.md section 8 f2)")
+    if args.perceptors not in PERCEPTOR_TABLES:
+        raise ValueError(f"perceptors={args.perceptors!r}: want one of {sorted(PERCEPTOR_TABLES)} (pixray.py:1763)")
     if args.quality not in QUALITY_TABLES:
         print("Qualitfy setting not understood, aborting -> ", args.quality)
         sys.exit(1)
     q_iter, q_scale, q_cuts, q_batches = QUALITY_TABLES[args.quality]
     if args.clip_models is None:
-        args.clip_models = QUALITY_CLIP_MODELS[args.quality]
+        args.clip_models = PERCEPTOR_TABLES[args.perceptors][args.quality]
     if args.iterations is None:
         args.iterations = q_iter
     if args.num_cuts is None:

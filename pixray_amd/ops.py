@@ -152,6 +152,36 @@ class ClipVitHandle:
             self.h = None
 
 
+class _VitTowerCfg(ctypes.Structure):
+    """mirror of `prx_vit_tower_config` (include/prx.h)"""
+    _fields_ = [(n, ctypes.c_int) for n in ("input_resolution", "patch_size", "width", "layers", "heads", "output_dim", "max_batch",
+                                            "precision", "family", "head_dim")] + \
+               [("ln_eps", ctypes.c_float), ("mean", ctypes.c_float * 3), ("std", ctypes.c_float * 3)]
+
+
+VIT_FAMILY_CLIP, VIT_FAMILY_SLIP = 0, 1
+
+
+class SlipVitHandle(ClipVitHandle):
+    """A `prx_clip_vit` made by `prx_vit_tower_create` for the SLIP family (timm VisionTransformer + image_projection): the same
+    handle type and protocol as ClipVitHandle (minmax / encode / backward_reduce / backward_finish / gemm_ctx / destroy)."""
+
+    def __init__(self, cfg, params, max_batch: int, device, precision=None):
+        from .weights import IMAGENET_MEAN, IMAGENET_STD, slip_vit_param_shapes
+        ws = _weights_in_abi_order(params, slip_vit_param_shapes(cfg), device, f"SLIP ViT {getattr(cfg, 'name', '')}")
+        self.precision = precision_code(precision)
+        c = _VitTowerCfg(cfg.input_resolution, cfg.patch_size, cfg.width, cfg.layers, cfg.heads, cfg.output_dim, max_batch, self.precision,
+                         VIT_FAMILY_SLIP, cfg.head_dim, cfg.ln_eps, (ctypes.c_float * 3)(*IMAGENET_MEAN), (ctypes.c_float * 3)(*IMAGENET_STD))
+        h = ctypes.c_void_p()
+        call("prx_vit_tower_create", ctypes.addressof(h), ctypes.addressof(c), _keep(self, _weight_array(ws)), len(ws), _stream())
+        torch.cuda.synchronize(device)   # weight tensors may now be released
+        self.h = h
+        self.cfg = cfg
+        self.max_batch = max_batch
+        self.device = device
+        self.generation = 0
+
+
 def _keep(obj, arr):
     obj._arr = arr   # keep the ctypes array alive for the duration of the call
     return ctypes.addressof(arr)

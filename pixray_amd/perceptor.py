@@ -1,11 +1,13 @@
 """Perceptor wrapper with the reference's `CLIP_Base` surface (/root/reference/slip.py:44-74): attributes
 `input_resolution`, `output_dim`; `encode_image(imgs) -> [N, D]` L2-normalised and differentiable; frozen
 weights; `encode_text(text) -> [n, D]` (raw projection, as slip.py:68-70); `encode_texts`.  The arithmetic is the HIP
-CLIP ViT runner (pixray_amd/csrc/vit.hip) and the HIP text tower (pixray_amd/csrc/clip_text.hip, built on first use)."""
+CLIP ViT runner (pixray_amd/csrc/vit.hip) and the HIP text tower (pixray_amd/csrc/clip_text.hip, built on first use).
+`SlipPerceptor` is the same for the reference's other family, `SLIP_Base` (slip.py:84-170), on the runner's SLIP switches."""
 import torch
 
 from . import ops
-from .weights import (CLIP_CONFIGS, CLIP_RESNET_CONFIGS, CLIP_TEXT_CONFIGS, ClipResNetConfig, synthetic_clip_resnet_params, ClipTextConfig, ClipVitConfig, clip_text_param_shapes,
+from .weights import (IMAGENET_MEAN, IMAGENET_STD, SLIP_CONFIGS, SLIP_REFUSED, SlipVitConfig, synthetic_slip_vit_params,
+                      CLIP_CONFIGS, CLIP_RESNET_CONFIGS, CLIP_TEXT_CONFIGS, ClipResNetConfig, synthetic_clip_resnet_params, ClipTextConfig, ClipVitConfig, clip_text_param_shapes,
                       synthetic_clip_text_params, synthetic_clip_vit_params)
 
 
@@ -22,7 +24,9 @@ class ClipVitPerceptor:
         self.input_resolution = cfg.input_resolution
         self.output_dim = cfg.output_dim
         self.group = group          # torch.distributed group when the cutout batch is sharded
-        if isinstance(cfg, ClipResNetConfig):       # ModifiedResNet family (RN50x4, ...): same protocol, different runner
+        if isinstance(cfg, SlipVitConfig):          # SLIP family: the ViT runner through its tower-family constructor
+            self.handle = ops.SlipVitHandle(cfg, params, max_batch, self.device, precision=precision)
+        elif isinstance(cfg, ClipResNetConfig):     # ModifiedResNet family (RN50x4, ...): same protocol, different runner
             self.handle = ops.ClipResNetHandle(cfg, params, max_batch, self.device, precision=precision)
         else:
             self.handle = ops.ClipVitHandle(cfg, params, max_batch, self.device, precision=precision)
@@ -104,6 +108,42 @@ class ClipVitPerceptor:
         return e / e.norm(dim=-1, keepdim=True)
 
 
+class SlipPerceptor(ClipVitPerceptor):
+    """The reference's `SLIP_Base` surface (slip.py:84-170) on the HIP ViT runner's SLIP family: `input_resolution` 224,
+    `output_dim`, `preprocess` (Resize(224) + CenterCrop(224) + Normalize with the ImageNet constants, slip.py:117-121,147-149),
+    `encode_image(imgs, input_range=None, apply_preprocess=True)` L2-normalised, `encode_text` (raw projection) and
+    `encode_texts` (normalised rows with `unsqueeze(1)`, slip.py:165-170 -- NOT `CLIP_Base.encode_texts`' stack).  The text side is
+    CLIP's text transformer (csrc/clip_text.hip) and CLIP's BPE tokenizer.  On a GPU the reference runs this family in fp32
+    (`model.cuda()`, no `.half()`): `precision="f32"` is its arithmetic, the product default (IEEE-half operands, fp32
+    accumulation) a stated difference."""
+    CLIP_MEAN = IMAGENET_MEAN        # the constants `preprocess` / `encode_image(apply_preprocess=False)` of the base class use
+    CLIP_STD = IMAGENET_STD
+
+    def encode_image(self, imgs, input_range=None, apply_preprocess=True):
+        """slip.py:151-157.  `input_range` reaches `adjust_range` here (slip.py:153), unlike CLIP_Base's; the loop never gives one."""
+        if apply_preprocess and input_range is not None:
+            if imgs.shape[0] > self.handle.max_batch:
+                raise ValueError(f"batch {imgs.shape[0]} exceeds the perceptor capacity {self.handle.max_batch}")
+            return ops.clip_encode_image(imgs, self.handle, fixed_range=(float(input_range[0]), float(input_range[1])))
+        return super().encode_image(imgs, None, apply_preprocess)
+
+    def encode_texts(self, texts):
+        """slip.py:165-170: one tokenizer call over the list, normalised rows, `unsqueeze(1)` -> [n, 1, D]"""
+        e = self.encode_text(list(texts) if not torch.is_tensor(texts) else texts).detach().clone()
+        e = e / e.norm(dim=-1, keepdim=True)
+        return e.unsqueeze(1)
+
+
+def slip_checkpoint_path(name, root="models"):
+    """models/<file> of slip.py:90-112 when it exists, else None (nothing is ever fetched)"""
+    import os
+    cfg = SLIP_CONFIGS.get(name)
+    if cfg is None or not cfg.checkpoint:
+        return None
+    path = os.path.join(root, cfg.checkpoint)
+    return path if os.path.exists(path) else None
+
+
 def get_clip_perceptor(clip_model_name, device, params=None, max_batch=64, seed=0, group=None, text_params=None,
                        tokenizer=None, precision=None):
     """slip.py:173-186 equivalent for the ViT family; `params` is an OpenAI `visual.*` state dict and `text_params` the
@@ -115,9 +155,23 @@ def get_clip_perceptor(clip_model_name, device, params=None, max_batch=64, seed=
             params = synthetic_clip_resnet_params(cfg, seed)
         return ClipVitPerceptor(cfg, params, device, max_batch=max_batch, group=group, text_cfg=CLIP_TEXT_CONFIGS.get(clip_model_name),
                                 text_params=text_params, tokenizer=tokenizer, seed=seed, precision=precision)
+    if clip_model_name in SLIP_REFUSED:
+        raise ValueError(SLIP_REFUSED[clip_model_name])
+    if clip_model_name in SLIP_CONFIGS:           # slip.py:183-184: every name that is not an OpenAI CLIP model is a SLIP_Base
+        cfg = SLIP_CONFIGS[clip_model_name]
+        if params is None:
+            ckpt = slip_checkpoint_path(clip_model_name)
+            if ckpt is not None:
+                from .checkpoints import load_slip
+                params, ckpt_text = load_slip(ckpt, cfg, CLIP_TEXT_CONFIGS[clip_model_name])
+                text_params = text_params if text_params is not None else ckpt_text
+            else:
+                params = synthetic_slip_vit_params(cfg, seed)
+        return SlipPerceptor(cfg, params, device, max_batch=max_batch, group=group, text_cfg=CLIP_TEXT_CONFIGS.get(clip_model_name),
+                             text_params=text_params, tokenizer=tokenizer, seed=seed, precision=precision)
     if clip_model_name not in CLIP_CONFIGS:
         raise KeyError(f"unknown / unsupported perceptor {clip_model_name!r} "
-                       f"(supported: {sorted(CLIP_CONFIGS) + sorted(CLIP_RESNET_CONFIGS)})")
+                       f"(supported: {sorted(CLIP_CONFIGS) + sorted(CLIP_RESNET_CONFIGS) + sorted(SLIP_CONFIGS)})")
     cfg = CLIP_CONFIGS[clip_model_name]
     if params is None:
         params = synthetic_clip_vit_params(cfg, seed)

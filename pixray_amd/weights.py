@@ -270,6 +270,103 @@ def synthetic_clip_vit_params(cfg: ClipVitConfig, seed: int = 0) -> "OrderedDict
     return out
 
 
+# --------------------------------------------------------------------------- SLIP image towers (timm VisionTransformer)
+# [UPSTREAM facebookresearch/SLIP models.py + timm vision_transformer.py; the SLIP/ submodule of the reference checkout is empty, so
+# this is restated from the published sources, parity unpinned]: `timm.create_model(vit_*_patch16_224, num_classes=0)` followed by
+# `@ image_projection`.  Against the CLIP tower: a patch-embed bias, no ln_pre, LayerNorm eps 1e-6, exact GELU, ImageNet Normalize.
+@dataclass
+class SlipVitConfig:
+    name: str = "SLIP_VITB16"
+    input_resolution: int = 224
+    patch_size: int = 16
+    width: int = 768
+    layers: int = 12
+    heads: int = 12
+    output_dim: int = 512
+    ln_eps: float = 1e-6
+    seed_offset: int = 0            # the names that share a configuration keep their own synthetic weights
+    checkpoint: str = ""            # file name under models/ (slip.py:90-107)
+
+    @property
+    def tokens(self) -> int:
+        return (self.input_resolution // self.patch_size) ** 2 + 1
+
+    @property
+    def head_dim(self) -> int:
+        return self.width // self.heads
+
+
+IMAGENET_MEAN = (0.485, 0.456, 0.406)       # slip.py:120
+IMAGENET_STD = (0.229, 0.224, 0.225)
+
+SLIP_CONFIGS = {
+    "SLIP_VITB16": SlipVitConfig("SLIP_VITB16", seed_offset=0, checkpoint="slip_base_100ep.pt"),
+    # the same model on other training data (slip.py:133-135)
+    "SLIP_CC3M": SlipVitConfig("SLIP_CC3M", seed_offset=1, checkpoint="slip_base_cc3m_40ep.pt"),
+    "SLIP_CC12M": SlipVitConfig("SLIP_CC12M", seed_offset=2, checkpoint="slip_base_cc12m_35ep.pt"),
+    "CLIP_VITB16": SlipVitConfig("CLIP_VITB16", seed_offset=3, checkpoint="clip_base_25ep.pt"),
+    "SLIP_VITL16": SlipVitConfig("SLIP_VITL16", width=1024, layers=24, heads=16, seed_offset=4, checkpoint="slip_large_100ep.pt"),
+    "CLIP_VITL16": SlipVitConfig("CLIP_VITL16", width=1024, layers=24, heads=16, seed_offset=5, checkpoint="clip_large_25ep.pt"),
+    # SLIP's vit_small_mocov3_patch16_224: 12 heads of 32 on width 384; the runner pads the heads to 64 when it packs the weights
+    "SLIP_VITS16": SlipVitConfig("SLIP_VITS16", width=384, layers=12, heads=12, seed_offset=6, checkpoint="slip_small_100ep.pt"),
+    "CLIP_VITS16": SlipVitConfig("CLIP_VITS16", width=384, layers=12, heads=12, seed_offset=7, checkpoint="clip_small_25ep.pt"),
+    # reduced 197-token tower (same operators, 2 layers) for fast parity tests
+    "tiny-SLIP/16": SlipVitConfig("tiny-SLIP/16", width=256, layers=2, heads=4, output_dim=128, seed_offset=8),
+    "tiny-SLIP32/16": SlipVitConfig("tiny-SLIP32/16", width=128, layers=2, heads=4, output_dim=128, seed_offset=9),    # heads of 32
+}
+SLIP_REFUSED = {"SIMCLR_VITS16": "SIMCLR_VITS16 has no text side (a SimCLR image encoder only): it cannot score prompts and is not provided"}
+
+
+def slip_vit_param_shapes(cfg: SlipVitConfig) -> "OrderedDict[str, Tuple[int, ...]]":
+    """timm state-dict names of the image side (`visual.` stripped) + SLIP's `image_projection`, in the order the C ABI expects
+    (include/prx.h, prx_vit_tower_create)."""
+    w = cfg.width
+    sh: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    sh["patch_embed.proj.weight"] = (w, 3, cfg.patch_size, cfg.patch_size)
+    sh["patch_embed.proj.bias"] = (w,)
+    sh["cls_token"] = (1, 1, w)
+    sh["pos_embed"] = (1, cfg.tokens, w)
+    for i in range(cfg.layers):
+        p = f"blocks.{i}."
+        sh[p + "norm1.weight"] = (w,); sh[p + "norm1.bias"] = (w,)
+        sh[p + "attn.qkv.weight"] = (3 * w, w); sh[p + "attn.qkv.bias"] = (3 * w,)
+        sh[p + "attn.proj.weight"] = (w, w); sh[p + "attn.proj.bias"] = (w,)
+        sh[p + "norm2.weight"] = (w,); sh[p + "norm2.bias"] = (w,)
+        sh[p + "mlp.fc1.weight"] = (4 * w, w); sh[p + "mlp.fc1.bias"] = (4 * w,)
+        sh[p + "mlp.fc2.weight"] = (w, 4 * w); sh[p + "mlp.fc2.bias"] = (w,)
+    sh["norm.weight"] = (w,); sh["norm.bias"] = (w,)
+    sh["image_projection"] = (w, cfg.output_dim)
+    return sh
+
+
+def synthetic_slip_vit_params(cfg: SlipVitConfig, seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
+    """Seeded random weights of the real architecture, scaled as `synthetic_clip_vit_params` scales the CLIP tower's (the residual
+    stream stays O(1) through every block)."""
+    g = torch.Generator().manual_seed(seed + 15485863 + cfg.seed_offset)
+    w = cfg.width
+    proj_std = (w ** -0.5) * ((2 * cfg.layers) ** -0.5)
+    attn_std = w ** -0.5
+    fc_std = (2 * w) ** -0.5
+    out: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    for name, shape in slip_vit_param_shapes(cfg).items():
+        if name == "patch_embed.proj.weight":
+            t = torch.randn(shape, generator=g) / math.sqrt(3 * cfg.patch_size ** 2)
+        elif name in ("cls_token", "pos_embed", "image_projection"):
+            t = torch.randn(shape, generator=g) * (w ** -0.5)
+        elif name.endswith("attn.qkv.weight"):
+            t = torch.randn(shape, generator=g) * attn_std
+        elif name.endswith("attn.proj.weight") or name.endswith("fc2.weight"):
+            t = torch.randn(shape, generator=g) * proj_std
+        elif name.endswith("fc1.weight"):
+            t = torch.randn(shape, generator=g) * fc_std
+        elif name.endswith(".weight"):       # LayerNorm gamma
+            t = 1.0 + 0.05 * torch.randn(shape, generator=g)
+        else:                                # biases / LayerNorm beta
+            t = 0.02 * torch.randn(shape, generator=g)
+        out[name] = t
+    return out
+
+
 # --------------------------------------------------------------------------- CLIP text tower config
 @dataclass
 class ClipTextConfig:
@@ -292,6 +389,11 @@ CLIP_TEXT_CONFIGS = {
     "RN50": ClipTextConfig("RN50", width=512, heads=8, output_dim=1024),
     "RN101": ClipTextConfig("RN101", width=512, heads=8, output_dim=512),
 }
+# every SLIP model size carries CLIP's text transformer at width 512 / 8 heads / 12 layers [UPSTREAM SLIP models.py]
+CLIP_TEXT_CONFIGS.update({n: ClipTextConfig(n) for n in ("SLIP_VITS16", "SLIP_VITB16", "SLIP_VITL16", "SLIP_CC3M", "SLIP_CC12M",
+                                                         "CLIP_VITS16", "CLIP_VITB16", "CLIP_VITL16")})
+for _n in ("tiny-SLIP/16", "tiny-SLIP32/16"):
+    CLIP_TEXT_CONFIGS[_n] = ClipTextConfig(_n, vocab_size=1000, context_length=77, width=256, layers=2, heads=4, output_dim=128)
 
 
 def clip_text_param_shapes(cfg: ClipTextConfig) -> "OrderedDict[str, Tuple[int, ...]]":
