@@ -213,6 +213,59 @@ int prx_k_scale_dev(float* x, size_t n, const float* scale, void* out16, int h16
 int prx_k_f32_to_op16(const float* in, void* out16, size_t n, int h16, prx_stream_t s);
 int prx_k_add_f32(const float* a, const float* b, float* out, size_t n, prx_stream_t s);
 
+/* ---- the runners' own kernels, each through the host launcher its runner calls (csrc/resnet.h, cutouts.h, vgg.h, vit.h,
+   clip_text.h, prompt_vq.h, vqgan.h, vqgan_enc.h), one kernel at a time (tests/test_kernels_runner_gpu.py).  `prec` = PRX_PREC_*
+   selects the operand element type of the `void*` buffers.  Test surface only: the product's Python never calls them. ---- */
+/* CLIP ModifiedResNet (resnet.hip) */
+int prx_k_rn_pack_conv3x3(const float* w, void* Wf, void* Wd, int Cout, int Cin, int prec, prx_stream_t s);
+int prx_k_stem1_fwd(const float* cut, const float* mm, const float* w, const float* b, void* out, int N, int S, int CO, int prec,
+                    prx_stream_t s);
+int prx_k_stem1_bwd(const void* g, const float* w, float* dY, int N, int S, int CO, const float* oscale_dev, int prec, prx_stream_t s);
+int prx_k_avgpool2_fwd(const void* x, void* out, int N, int H, int W, int C, int prec, prx_stream_t s);
+int prx_k_avgpool2_bwd(const float* g, const void* mask, float* dx_f32, void* dx_op, int N, int H, int W, int C, int prec,
+                       prx_stream_t s);
+int prx_k_relu_mask(float* g, const void* out, void* g_op, size_t n, int prec, prx_stream_t s);
+int prx_k_tokens_fwd(const float* x, const float* pos, void* t, int N, int P, int C, int prec, prx_stream_t s);
+int prx_k_tokens_bwd(const float* dt, float* dx, int N, int P, int C, int prec, prx_stream_t s);
+int prx_k_tok0_gather(const void* t, void* out, int N, int T, int C, int prec, prx_stream_t s);
+int prx_k_tok0_scatter(const void* g0, void* dt, int N, int T, int C, int prec, prx_stream_t s);
+/* batch min / max, patchify and the min/max renormalisation backward (cutouts.hip); m0..s2: the channel means / stds */
+int prx_k_minmax(const float* x, size_t n, float* part, int nparts, float* mm, prx_stream_t s);
+int prx_k_patchify_fwd(const float* cut, const float* mm, void* A, int prec, int N, int S, int P, int T, float m0, float m1, float m2,
+                       float s0, float s1, float s2, prx_stream_t s);
+int prx_k_patchify_bwd_reduce(const float* cut, const float* mm, const float* dA, double* acc, int N, int S, int P, int T, float m0,
+                              float m1, float m2, float s0, float s1, float s2, prx_stream_t s);
+int prx_k_patchify_bwd_apply(const float* cut, const float* mm, const float* dA, const double* acc, float* gcut, int N, int S, int P,
+                             int T, float m0, float m1, float m2, float s0, float s1, float s2, prx_stream_t s);
+int prx_k_preproc_bwd_reduce(const float* cut, const float* mm, const float* dY, double* acc, int N, int S, prx_stream_t s);
+int prx_k_preproc_bwd_apply(const float* cut, const float* mm, const float* dY, const double* acc, float* gcut, int N, int S,
+                            prx_stream_t s);
+/* VGG16 extractor (vgg.hip) */
+int prx_k_vgg_pack(const float* w, void* Wf, void* Wd, int Cout, int Cin, int CiP, int prec, prx_stream_t s);
+int prx_k_vgg_input(const float* x, void* out, int HW, int prec, prx_stream_t s);
+int prx_k_vgg_input_grad(const float* d, float* gx, int HW, const float* unscale, prx_stream_t s);
+int prx_k_vgg_maxpool(const void* x, void* out, void* arg, int H, int W, int C, int prec, prx_stream_t s);
+int prx_k_vgg_combine(const float* above, const void* arg, const float* gcap, const void* act, void* gpre, int H, int W, int C,
+                      const float* gscale, int prec, prx_stream_t s);
+/* ViT runner (vit.hip) */
+int prx_k_pack_transpose_op(const float* in, void* out, int R, int C, int prec, prx_stream_t s);
+int prx_k_vit_add_cls_pos(float* x, const float* cls, const float* pos, int N, int T, int W, prx_stream_t s);
+int prx_k_vit_embed_tokens(const float* x, const float* cls, const float* pos, void* out, int out16, int N, int T, int W,
+                           prx_stream_t s);
+int prx_k_vit_gelu_f32(const float* t, float* io, size_t n, int bwd, prx_stream_t s);
+int prx_k_vit_scale_f32(float* x, size_t n, float scale, int blocks, prx_stream_t s);
+/* CLIP text tower (clip_text.hip) */
+int prx_k_text_embed(const int* tokens, const float* emb, const float* pos, float* x, int* eot, int n, int ctx, int W, int vocab,
+                     prx_stream_t s);
+int prx_k_gather_rows(const float* x, const int* eot, float* out, int n, int ctx, int W, prx_stream_t s);
+/* prompt_vq.hip (prx_k_sqnorm_rows: above) */
+int prx_k_l2norm_fwd(const float* e, float* out, int n, int D, prx_stream_t s);
+int prx_k_l2norm_bwd(const float* e, const float* g, float* de, int n, int D, prx_stream_t s);
+/* VQGAN decoder / encoder weight packs and the codebook's column bounds (vqgan.hip, vqgan_enc.hip) */
+int prx_k_vqgan_pack_conv3x3(const float* w, void* Wf, void* Wd, int Cout, int Cin, int CoP, int prec, prx_stream_t s);
+int prx_k_vqgan_enc_pack_conv3x3(const float* w, void* Wf, int Cout, int Cin, int CiP, prx_stream_t s);
+int prx_k_colminmax(const float* w, float* mn, float* mx, int rows, int D, prx_stream_t s);
+
 /* ------------------------------------------------------------------------ */
 /* Path-level operators: the drop-in boundary of the hot path                */
 /* ------------------------------------------------------------------------ */

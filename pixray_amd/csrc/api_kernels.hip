@@ -8,6 +8,14 @@
 #include "norms.h"
 #include "elementwise.h"
 #include "attention.h"
+#include "resnet.h"
+#include "cutouts.h"
+#include "vgg.h"
+#include "vit.h"
+#include "clip_text.h"
+#include "prompt_vq.h"
+#include "vqgan.h"
+#include "vqgan_enc.h"
 #include "../../include/prx.h"
 
 #define S_(x) ((hipStream_t)(x))
@@ -166,6 +174,107 @@ int prx_k_f32_to_op16(const float* in, void* out16, size_t n, int h16, prx_strea
 }
 int prx_k_add_f32(const float* a, const float* b, float* out, size_t n, prx_stream_t s) {
     return prx_add_f32(a, b, out, n, S_(s));
+}
+
+// ---- the runners' own kernels through the launchers the runners call (tests/test_kernels_runner_gpu.py) -----------------------
+int prx_k_rn_pack_conv3x3(const float* w, void* Wf, void* Wd, int Cout, int Cin, int prec, prx_stream_t s) {
+    return prx_rn_pack_conv3x3(w, Wf, Wd, Cout, Cin, prec, S_(s));
+}
+int prx_k_stem1_fwd(const float* cut, const float* mm, const float* w, const float* b, void* out, int N, int S, int CO, int prec, prx_stream_t s) {
+    return prx_stem1_fwd(cut, mm, w, b, out, N, S, CO, prec, S_(s));
+}
+int prx_k_stem1_bwd(const void* g, const float* w, float* dY, int N, int S, int CO, const float* oscale_dev, int prec, prx_stream_t s) {
+    return prx_stem1_bwd(g, w, dY, N, S, CO, oscale_dev, prec, S_(s));
+}
+int prx_k_avgpool2_fwd(const void* x, void* out, int N, int H, int W, int C, int prec, prx_stream_t s) {
+    return prx_avgpool2_fwd(x, out, N, H, W, C, prec, S_(s));
+}
+int prx_k_avgpool2_bwd(const float* g, const void* mask, float* dx_f32, void* dx_op, int N, int H, int W, int C, int prec, prx_stream_t s) {
+    return prx_avgpool2_bwd(g, mask, dx_f32, dx_op, N, H, W, C, prec, S_(s));
+}
+int prx_k_relu_mask(float* g, const void* out, void* g_op, size_t n, int prec, prx_stream_t s) {
+    return prx_relu_mask(g, out, g_op, n, prec, S_(s));
+}
+int prx_k_tokens_fwd(const float* x, const float* pos, void* t, int N, int P, int C, int prec, prx_stream_t s) {
+    return prx_tokens_fwd(x, pos, t, N, P, C, prec, S_(s));
+}
+int prx_k_tokens_bwd(const float* dt, float* dx, int N, int P, int C, int prec, prx_stream_t s) {
+    return prx_tokens_bwd(dt, dx, N, P, C, prec, S_(s));
+}
+int prx_k_tok0_gather(const void* t, void* out, int N, int T, int C, int prec, prx_stream_t s) {
+    return prx_tok0_gather(t, out, N, T, C, prec, S_(s));
+}
+int prx_k_tok0_scatter(const void* g0, void* dt, int N, int T, int C, int prec, prx_stream_t s) {
+    return prx_tok0_scatter(g0, dt, N, T, C, prec, S_(s));
+}
+int prx_k_minmax(const float* x, size_t n, float* part, int nparts, float* mm, prx_stream_t s) {
+    return prx_minmax(x, n, part, nparts, mm, S_(s));
+}
+int prx_k_patchify_fwd(const float* cut, const float* mm, void* A, int prec, int N, int S, int P, int T, float m0, float m1, float m2, float s0, float s1, float s2, prx_stream_t s) {
+    return prx_patchify_fwd(cut, mm, A, prec, N, S, P, T, S_(s), PatchNorm{{m0, m1, m2}, {s0, s1, s2}});
+}
+int prx_k_patchify_bwd_reduce(const float* cut, const float* mm, const float* dA, double* acc, int N, int S, int P, int T, float m0, float m1, float m2, float s0, float s1, float s2, prx_stream_t s) {
+    return prx_patchify_bwd_reduce(cut, mm, dA, acc, N, S, P, T, S_(s), PatchNorm{{m0, m1, m2}, {s0, s1, s2}});
+}
+int prx_k_patchify_bwd_apply(const float* cut, const float* mm, const float* dA, const double* acc, float* gcut, int N, int S, int P, int T, float m0, float m1, float m2, float s0, float s1, float s2, prx_stream_t s) {
+    return prx_patchify_bwd_apply(cut, mm, dA, acc, gcut, N, S, P, T, S_(s), PatchNorm{{m0, m1, m2}, {s0, s1, s2}});
+}
+int prx_k_preproc_bwd_reduce(const float* cut, const float* mm, const float* dY, double* acc, int N, int S, prx_stream_t s) {
+    return prx_preproc_bwd_reduce(cut, mm, dY, acc, N, S, S_(s));
+}
+int prx_k_preproc_bwd_apply(const float* cut, const float* mm, const float* dY, const double* acc, float* gcut, int N, int S, prx_stream_t s) {
+    return prx_preproc_bwd_apply(cut, mm, dY, acc, gcut, N, S, S_(s));
+}
+int prx_k_vgg_pack(const float* w, void* Wf, void* Wd, int Cout, int Cin, int CiP, int prec, prx_stream_t s) {
+    return prx_vgg_pack(w, Wf, Wd, Cout, Cin, CiP, prec, S_(s));
+}
+int prx_k_vgg_input(const float* x, void* out, int HW, int prec, prx_stream_t s) {
+    return prx_vgg_input(x, out, HW, prec, S_(s));
+}
+int prx_k_vgg_input_grad(const float* d, float* gx, int HW, const float* unscale, prx_stream_t s) {
+    return prx_vgg_input_grad(d, gx, HW, unscale, S_(s));
+}
+int prx_k_vgg_maxpool(const void* x, void* out, void* arg, int H, int W, int C, int prec, prx_stream_t s) {
+    return prx_vgg_maxpool(x, out, (unsigned char*)arg, H, W, C, prec, S_(s));
+}
+int prx_k_vgg_combine(const float* above, const void* arg, const float* gcap, const void* act, void* gpre, int H, int W, int C, const float* gscale, int prec, prx_stream_t s) {
+    return prx_vgg_combine(above, (const unsigned char*)arg, gcap, act, gpre, H, W, C, gscale, prec, S_(s));
+}
+int prx_k_pack_transpose_op(const float* in, void* out, int R, int C, int prec, prx_stream_t s) {
+    return prx_pack_transpose_op(in, out, R, C, prec, S_(s));
+}
+int prx_k_vit_add_cls_pos(float* x, const float* cls, const float* pos, int N, int T, int W, prx_stream_t s) {
+    return prx_vit_add_cls_pos(x, cls, pos, N, T, W, S_(s));
+}
+int prx_k_vit_embed_tokens(const float* x, const float* cls, const float* pos, void* out, int out16, int N, int T, int W, prx_stream_t s) {
+    return prx_vit_embed_tokens(x, cls, pos, out, out16, N, T, W, S_(s));
+}
+int prx_k_vit_gelu_f32(const float* t, float* io, size_t n, int bwd, prx_stream_t s) {
+    return prx_vit_gelu_f32(t, io, n, bwd, S_(s));
+}
+int prx_k_vit_scale_f32(float* x, size_t n, float scale, int blocks, prx_stream_t s) {
+    return prx_vit_scale_f32(x, n, scale, blocks, S_(s));
+}
+int prx_k_text_embed(const int* tokens, const float* emb, const float* pos, float* x, int* eot, int n, int ctx, int W, int vocab, prx_stream_t s) {
+    return prx_text_embed(tokens, emb, pos, x, eot, n, ctx, W, vocab, S_(s));
+}
+int prx_k_gather_rows(const float* x, const int* eot, float* out, int n, int ctx, int W, prx_stream_t s) {
+    return prx_gather_rows(x, eot, out, n, ctx, W, S_(s));
+}
+int prx_k_l2norm_fwd(const float* e, float* out, int n, int D, prx_stream_t s) {
+    return prx_l2norm_fwd(e, out, n, D, S_(s));
+}
+int prx_k_l2norm_bwd(const float* e, const float* g, float* de, int n, int D, prx_stream_t s) {
+    return prx_l2norm_bwd(e, g, de, n, D, S_(s));
+}
+int prx_k_vqgan_pack_conv3x3(const float* w, void* Wf, void* Wd, int Cout, int Cin, int CoP, int prec, prx_stream_t s) {
+    return prx_vqgan_pack_conv3x3(w, Wf, Wd, Cout, Cin, CoP, prec, S_(s));
+}
+int prx_k_vqgan_enc_pack_conv3x3(const float* w, void* Wf, int Cout, int Cin, int CiP, prx_stream_t s) {
+    return prx_vqgan_enc_pack_conv3x3(w, Wf, Cout, Cin, CiP, S_(s));
+}
+int prx_k_colminmax(const float* w, float* mn, float* mx, int rows, int D, prx_stream_t s) {
+    return prx_colminmax(w, mn, mx, rows, D, S_(s));
 }
 
 }  // extern "C"

@@ -7,3 +7,9 @@ int prx_clip_text_create_impl(PrxClipText** out, int vocab, int ctx, int width, 
                               const float* const* w, int n_w, hipStream_t s);
 void prx_clip_text_destroy_impl(PrxClipText* t);
 int prx_clip_text_encode_impl(PrxClipText* t, const int* tokens, int n, float* embeds, hipStream_t s);
+// launchers of the runner's own kernels (the runner calls these; exported as prx_k_* for the kernel-level tests)
+// x[i][j] = emb[tokens[i][j]] + pos[j]; eot[i] = first index of the largest token id of sequence i
+int prx_text_embed(const int* tokens, const float* emb, const float* pos, float* x, int* eot, int n, int ctx, int W, int vocab,
+                   hipStream_t s);
+// out[i] = x[i][eot[i]]
+int prx_gather_rows(const float* x, const int* eot, float* out, int n, int ctx, int W, hipStream_t s);

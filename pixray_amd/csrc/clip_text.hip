@@ -48,6 +48,19 @@ struct TextLayer {
 
 }  // namespace
 
+// launchers of the two kernels above (clip_text.h): one workgroup per sequence; shared by the runner and the kernel-level tests
+int prx_text_embed(const int* tokens, const float* emb, const float* pos, float* x, int* eot, int n, int ctx, int W, int vocab,
+                   hipStream_t s) {
+    hipLaunchKernelGGL(text_embed_kernel, dim3(n), dim3(256), 0, s, tokens, emb, pos, x, eot, ctx, W, vocab);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+int prx_gather_rows(const float* x, const int* eot, float* out, int n, int ctx, int W, hipStream_t s) {
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(n), dim3(256), 0, s, x, eot, out, ctx, W);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+
 struct PrxClipText {
     int vocab, ctx, width, layers, heads, out_dim, max_n;
     std::vector<void*> allocs;
@@ -139,8 +152,7 @@ int prx_clip_text_encode_impl(PrxClipText* t, const int* tokens, int n, float* e
     PRX_REQUIRE(n >= 1 && n <= t->max_n, "clip_text: batch %d exceeds handle capacity %d", n, t->max_n);
     const int W = t->width, T = t->ctx, R = n * T;
     int r;
-    hipLaunchKernelGGL(text_embed_kernel, dim3(n), dim3(256), 0, s, tokens, t->tok, t->pos, t->x, t->eot, T, W, t->vocab);
-    PRX_LAUNCH_CHECK();
+    if ((r = prx_text_embed(tokens, t->tok, t->pos, t->x, t->eot, n, T, W, t->vocab, s))) return r;
     for (int l = 0; l < t->layers; ++l) {
         TextLayer& y = t->L[l];
         if ((r = prx_layernorm_fwd(t->x, W, y.ln1_g, y.ln1_b, t->h, nullptr, t->mean, t->rstd, R, W, 1e-5f, s))) return r;
@@ -159,8 +171,7 @@ int prx_clip_text_encode_impl(PrxClipText* t, const int* tokens, int n, float* e
             d.bias_n = y.b2; d.resid = t->x_mid; d.ldr = W; d.out_f32 = t->x; d.ldc_f32 = W;
             if ((r = tg(t, d, s))) return r; }
     }
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(n), dim3(256), 0, s, t->x, t->eot, t->rows, T, W);
-    PRX_LAUNCH_CHECK();
+    if ((r = prx_gather_rows(t->x, t->eot, t->rows, n, T, W, s))) return r;
     if ((r = prx_layernorm_fwd(t->rows, W, t->lnf_g, t->lnf_b, t->hpost, nullptr, t->mean, t->rstd, n, W, 1e-5f, s))) return r;
     GemmDesc d; d.A = t->hpost; d.lda = W; d.B = t->projT; d.ldb = W; d.M = n; d.N = t->out_dim; d.K = W;
     d.out_f32 = embeds; d.ldc_f32 = t->out_dim;

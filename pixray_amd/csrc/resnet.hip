@@ -298,6 +298,80 @@ struct RBlock {
 
 }  // namespace
 
+// ---- one host launcher per kernel (resnet.h): grid computation and the operand-type / CO dispatch.  The runner below and the
+// kernel-level tests (prx_k_*, csrc/api_kernels.hip) go through these same functions.
+#define RLAUNCH(prec, kernel, total, ...)                                                                                \
+    do {                                                                                                                 \
+        PRX_REQUIRE(prec_valid(prec), #kernel ": unknown precision %d", prec);                                           \
+        PRX_OP_DISPATCH(prec_is_f32(prec), prec_is_h16(prec), TO_,                                                       \
+                        hipLaunchKernelGGL(kernel<TO_>, dim3(rgrid(total)), dim3(256), 0, s, __VA_ARGS__));              \
+        PRX_LAUNCH_CHECK();                                                                                              \
+    } while (0)
+// the stem kernels keep all CO = width/2 output channels of a pixel in one thread: CO is a template parameter
+// (RN50: 32, RN50x4: 40, RN50x16: 48, RN50x64: 64)
+#define STEM_CASE(prec, kernel, CO_, total, ...)                                                                         \
+    case CO_:                                                                                                            \
+        PRX_OP_DISPATCH(prec_is_f32(prec), prec_is_h16(prec), TO_,                                                       \
+                        hipLaunchKernelGGL((kernel<TO_, CO_>), dim3(rgrid(total)), dim3(256), 0, s, __VA_ARGS__));       \
+        break;
+#define STEM_LAUNCH(prec, kernel, total, co, ...)                                                                        \
+    do {                                                                                                                 \
+        PRX_REQUIRE(prec_valid(prec), #kernel ": unknown precision %d", prec);                                           \
+        switch (co) {                                                                                                    \
+            STEM_CASE(prec, kernel, 8, total, __VA_ARGS__) STEM_CASE(prec, kernel, 16, total, __VA_ARGS__)               \
+            STEM_CASE(prec, kernel, 32, total, __VA_ARGS__) STEM_CASE(prec, kernel, 40, total, __VA_ARGS__)              \
+            STEM_CASE(prec, kernel, 48, total, __VA_ARGS__) STEM_CASE(prec, kernel, 64, total, __VA_ARGS__)              \
+            default: PRX_REQUIRE(false, "resnet stem: width/2 = %d is not one of 8, 16, 32, 40, 48, 64", co);            \
+        }                                                                                                                \
+        PRX_LAUNCH_CHECK();                                                                                              \
+    } while (0)
+
+int prx_rn_pack_conv3x3(const float* w, void* Wf, void* Wd, int Cout, int Cin, int prec, hipStream_t s) {
+    RLAUNCH(prec, rn_pack_conv3x3_kernel, (size_t)1024 * 256, w, Wf, Wd, Cout, Cin);
+    return 0;
+}
+int prx_stem1_fwd(const float* cut, const float* mm, const float* w, const float* b, void* out, int N, int S, int CO, int prec,
+                  hipStream_t s) {
+    PRX_REQUIRE(N >= 1 && S >= 2, "resnet stem: %d cutouts of side %d", N, S);
+    STEM_LAUNCH(prec, stem1_fwd_kernel, (size_t)N * (S / 2) * (S / 2), CO, cut, mm, w, b, out, N, S);
+    return 0;
+}
+int prx_stem1_bwd(const void* g, const float* w, float* dY, int N, int S, int CO, const float* oscale_dev, int prec, hipStream_t s) {
+    PRX_REQUIRE(N >= 1 && S >= 2, "resnet stem: %d cutouts of side %d", N, S);
+    STEM_LAUNCH(prec, stem1_bwd_kernel, (size_t)N * S * S, CO, g, w, dY, N, S, oscale_dev);
+    return 0;
+}
+int prx_avgpool2_fwd(const void* x, void* out, int N, int H, int W, int C, int prec, hipStream_t s) {
+    PRX_REQUIRE(C % 4 == 0, "avgpool2: C = %d is not a multiple of 4", C);
+    RLAUNCH(prec, avgpool2_fwd_kernel, (size_t)N * (H / 2) * (W / 2) * C / 4, x, out, N, H, W, C);
+    return 0;
+}
+int prx_avgpool2_bwd(const float* g, const void* mask, float* dx_f32, void* dx_op, int N, int H, int W, int C, int prec, hipStream_t s) {
+    PRX_REQUIRE(C % 4 == 0, "avgpool2: C = %d is not a multiple of 4", C);
+    RLAUNCH(prec, avgpool2_bwd_kernel, (size_t)N * (H / 2) * (W / 2) * C / 4, g, mask, dx_f32, dx_op, N, H, W, C);
+    return 0;
+}
+int prx_relu_mask(float* g, const void* out, void* g_op, size_t n, int prec, hipStream_t s) {
+    RLAUNCH(prec, relu_mask_kernel, n, g, out, g_op, n);
+    return 0;
+}
+int prx_tokens_fwd(const float* x, const float* pos, void* t, int N, int P, int C, int prec, hipStream_t s) {
+    RLAUNCH(prec, tokens_fwd_kernel, (size_t)N * C, x, pos, t, N, P, C);
+    return 0;
+}
+int prx_tokens_bwd(const float* dt, float* dx, int N, int P, int C, int prec, hipStream_t s) {
+    RLAUNCH(prec, tokens_bwd_kernel, (size_t)N * P * C, dt, dx, N, P, C);
+    return 0;
+}
+int prx_tok0_gather(const void* t, void* out, int N, int T, int C, int prec, hipStream_t s) {
+    RLAUNCH(prec, tok0_gather_kernel, (size_t)N * C, t, out, N, T, C);
+    return 0;
+}
+int prx_tok0_scatter(const void* g0, void* dt, int N, int T, int C, int prec, hipStream_t s) {
+    RLAUNCH(prec, tok0_scatter_kernel, (size_t)N * T * C, g0, dt, N, T, C);
+    return 0;
+}
+
 struct PrxResNet {
     int res, width, heads, out_dim, max_n, C, G, T, cur_n;
     int prec;         // PRX_PREC_*
@@ -341,28 +415,6 @@ int ralloc_op(PrxResNet* r, void** p, size_t count) {   // `count` operand eleme
     return 0;
 }
 #define RALLOC_OP(ptr, count) do { int _e = ralloc_op(r, &(ptr), (count)); if (_e) return _e; } while (0)
-// launch an operand-typed kernel template for this handle's precision
-#define RLAUNCH(kernel, total, ...)                                                                                      \
-    do {                                                                                                                 \
-        PRX_OP_DISPATCH(r->f32, r->h16, TO_, hipLaunchKernelGGL(kernel<TO_>, dim3(rgrid(total)), dim3(256), 0, s, __VA_ARGS__)); \
-        PRX_LAUNCH_CHECK();                                                                                              \
-    } while (0)
-// the stem kernels keep all CO = width/2 output channels of a pixel in one thread: CO is a template parameter
-// (RN50: 32, RN50x4: 40, RN50x16: 48, RN50x64: 64)
-#define STEM_CASE(kernel, CO_, total, ...)                                                                               \
-    case CO_:                                                                                                            \
-        PRX_OP_DISPATCH(r->f32, r->h16, TO_, hipLaunchKernelGGL((kernel<TO_, CO_>), dim3(rgrid(total)), dim3(256), 0, s, __VA_ARGS__)); \
-        break;
-#define STEM_LAUNCH(kernel, total, co, ...)                                                                              \
-    do {                                                                                                                 \
-        switch (co) {                                                                                                    \
-            STEM_CASE(kernel, 8, total, __VA_ARGS__) STEM_CASE(kernel, 16, total, __VA_ARGS__)                           \
-            STEM_CASE(kernel, 32, total, __VA_ARGS__) STEM_CASE(kernel, 40, total, __VA_ARGS__)                          \
-            STEM_CASE(kernel, 48, total, __VA_ARGS__) STEM_CASE(kernel, 64, total, __VA_ARGS__)                          \
-            default: PRX_REQUIRE(false, "resnet stem: width/2 = %d is not one of 8, 16, 32, 40, 48, 64", co);            \
-        }                                                                                                                \
-        PRX_LAUNCH_CHECK();                                                                                              \
-    } while (0)
 struct RCur { const float* const* w; int n, pos; };
 #define RNEXT(cur, dst) do { PRX_REQUIRE((cur).pos < (cur).n, "resnet_create: weight list too short"); (dst) = (cur).w[(cur).pos++]; } while (0)
 
@@ -384,7 +436,8 @@ int mk3(PrxResNet* r, RConv3& c, int Cin, int Cout, RCur& cur, hipStream_t s) {
     const float *w, *b; RNEXT(cur, w); RNEXT(cur, b);
     c.Cin = Cin; c.Cout = Cout;
     RALLOC_OP(c.Wf, (size_t)Cout * 9 * Cin); RALLOC_OP(c.Wd, (size_t)Cout * 9 * Cin);
-    RLAUNCH(rn_pack_conv3x3_kernel, (size_t)1024 * 256, w, c.Wf, c.Wd, Cout, Cin);
+    int e;
+    if ((e = prx_rn_pack_conv3x3(w, c.Wf, c.Wd, Cout, Cin, r->prec, s))) return e;
     return rcopy(r, &c.b, b, Cout, s);
 }
 int rg(PrxResNet* r, GemmDesc& d, hipStream_t s) {
@@ -506,10 +559,10 @@ int prx_resnet_forward_impl(PrxResNet* r, const float* cutouts, int n, const flo
     const int S = r->res, S2 = S / 2, S4 = S / 4, w = r->width, wh = w / 2;
     int e;
     r->cur_n = n;
-    STEM_LAUNCH(stem1_fwd_kernel, (size_t)n * S2 * S2, wh, cutouts, mm, r->w1, r->b1, r->s1, n, S);
+    if ((e = prx_stem1_fwd(cutouts, mm, r->w1, r->b1, r->s1, n, S, wh, r->prec, s))) return e;
     if ((e = conv3(r, r->s1, n, S2, wh, r->s2.Wf, wh, r->s2.b, PRX_ACT_RELU, nullptr, nullptr, r->s2a, s))) return e;
     if ((e = conv3(r, r->s2a, n, S2, wh, r->s3.Wf, w, r->s3.b, PRX_ACT_RELU, nullptr, nullptr, r->s3a, s))) return e;
-    RLAUNCH(avgpool2_fwd_kernel, (size_t)n * S4 * S4 * w / 4, r->s3a, r->s0_bf, n, S2, S2, w);
+    if ((e = prx_avgpool2_fwd(r->s3a, r->s0_bf, n, S2, S2, w, r->prec, s))) return e;
     // the identity path of layer1.0 goes through its downsample conv, so no fp32 copy of the stem output is needed
     const void* x_bf = r->s0_bf; const float* x_f32 = nullptr;
     const int lean = r->lean;
@@ -519,14 +572,14 @@ int prx_resnet_forward_impl(PrxResNet* r, const float* cutouts, int n, const flo
         if ((e = lin(r, x_bf, Min, k.Cin, k.c1.W, p, k.c1.b, nullptr, PRX_ACT_RELU, nullptr, nullptr, k.a1, s))) return e;
         if ((e = conv3(r, k.a1, n, H, p, k.c2.Wf, p, k.c2.b, PRX_ACT_RELU, nullptr, nullptr, k.a2, s))) return e;
         if (k.stride > 1) {
-            RLAUNCH(avgpool2_fwd_kernel, (size_t)Mout * p / 4, k.a2, k.p2, n, H, H, p);
+            if ((e = prx_avgpool2_fwd(k.a2, k.p2, n, H, H, p, r->prec, s))) return e;
         }
         // the identity: fp32, or (lean) the 16-bit stream itself -- tb1 holds the downsample output (free in the forward)
         const float* idn = lean ? (const float*)x_bf : x_f32;
         if (k.has_ds) {
             const void* xi = x_bf;
             if (k.stride > 1) {
-                RLAUNCH(avgpool2_fwd_kernel, (size_t)Mout * k.Cin / 4, x_bf, k.xp, n, H, H, k.Cin);
+                if ((e = prx_avgpool2_fwd(x_bf, k.xp, n, H, H, k.Cin, r->prec, s))) return e;
                 xi = k.xp;
             }
             if ((e = lin(r, xi, Mout, k.Cin, k.ds.W, 4 * p, k.ds.b, nullptr, PRX_ACT_NONE, nullptr, lean ? nullptr : r->tf,
@@ -539,11 +592,11 @@ int prx_resnet_forward_impl(PrxResNet* r, const float* cutouts, int n, const flo
     }
     // attention pool
     const int C = r->C, T = r->T, P = T - 1;
-    RLAUNCH(tokens_fwd_kernel, (size_t)n * C, x_f32, r->pos, r->tok, n, P, C);
+    if ((e = prx_tokens_fwd(x_f32, r->pos, r->tok, n, P, C, r->prec, s))) return e;
     if ((e = lin(r, r->tok, n * T, C, r->Win, 3 * C, r->bin, nullptr, PRX_ACT_NONE, nullptr, nullptr, r->qkv, s))) return e;
     if (r->f32) { if ((e = prx_mha_fwd_f32((const float*)r->qkv, (float*)r->att, r->lse, n, T, C, r->heads, s))) return e; }
     else if ((e = prx_mha_fwd_gen((const bf16_t*)r->qkv, (bf16_t*)r->att, r->lse, n, T, C, r->heads, s, r->h16))) return e;
-    RLAUNCH(tok0_gather_kernel, (size_t)n * C, r->att, r->o0, n, T, C);
+    if ((e = prx_tok0_gather(r->att, r->o0, n, T, C, r->prec, s))) return e;
     if ((e = lin(r, r->o0, n, C, r->Wc, r->out_dim, r->bc, nullptr, PRX_ACT_NONE, nullptr, r->e, nullptr, s))) return e;
     return prx_l2norm_fwd(r->e, embeds, n, r->out_dim, s);
 }
@@ -567,14 +620,14 @@ int prx_resnet_backward_a_impl(PrxResNet* r, const float* cutouts, const float* 
             if ((e = prx_scale_dev(r->de, (size_t)n * r->out_dim, r->gs, s))) return e;
         }
         if ((e = rg(r, d, s))) return e; }
-    RLAUNCH(tok0_scatter_kernel, (size_t)n * T * C, r->do0, r->dtok, n, T, C);
+    if ((e = prx_tok0_scatter(r->do0, r->dtok, n, T, C, r->prec, s))) return e;
     if (r->f32) { if ((e = prx_mha_bwd_f32((const float*)r->qkv, (const float*)r->att, (const float*)r->dtok, r->lse, (float*)r->dqkv, n, T, C, r->heads, s))) return e; }
     else if ((e = prx_mha_bwd_gen((const bf16_t*)r->qkv, (const bf16_t*)r->att, (const bf16_t*)r->dtok, r->lse, (bf16_t*)r->dqkv, n, T, C, r->heads, s, r->h16))) return e;
     if ((e = lin(r, r->dqkv, n * T, 3 * C, r->WinT, C, nullptr, nullptr, PRX_ACT_NONE, nullptr, r->dtokf, nullptr, s))) return e;
     float* g = r->gA; float* g2 = r->gB;
     const int lean = r->lean;
     void* gb = r->gbf; void* gb_alt = r->gb2;     // lean layout: the 16-bit gradient stream and the buffer its successor goes to
-    RLAUNCH(tokens_bwd_kernel, (size_t)n * P * C, r->dtokf, g, n, P, C);
+    if ((e = prx_tokens_bwd(r->dtokf, g, n, P, C, r->prec, s))) return e;
     for (int bi = (int)r->blocks.size() - 1; bi >= 0; --bi) {
         RBlock& k = r->blocks[bi];
         const int H = k.Hin, Ho = H / k.stride, Min = n * H * H, Mout = n * Ho * Ho, p = k.planes;
@@ -582,12 +635,11 @@ int prx_resnet_backward_a_impl(PrxResNet* r, const float* cutouts, const float* 
         // own; for every other block the GEMM that formed g (conv1 dgrad + identity gradient of the block after it) applied
         // this block's mask in its epilogue and wrote both copies (PRX_ACT_RELUMASK_POST below): 25 of RN50x4's 26 passes
         // over the residual-stream gradient (12 bytes per element each) are gone.
-        if (bi == (int)r->blocks.size() - 1)
-            RLAUNCH(relu_mask_kernel, (size_t)Mout * 4 * p, g, k.out_bf, gb, (size_t)Mout * 4 * p);
+        if (bi == (int)r->blocks.size() - 1 && (e = prx_relu_mask(g, k.out_bf, gb, (size_t)Mout * 4 * p, r->prec, s))) return e;
         // main branch: conv3 (1x1) dgrad [-> avgpool bwd] -> ReLU mask of a2
         if (k.stride > 1) {
             if ((e = lin(r, gb, Mout, 4 * p, k.c3.WT, p, nullptr, nullptr, PRX_ACT_NONE, nullptr, r->tf, nullptr, s))) return e;
-            RLAUNCH(avgpool2_bwd_kernel, (size_t)Min * p / 16, r->tf, k.a2, (float*)nullptr, r->tb1, n, H, H, p);
+            if ((e = prx_avgpool2_bwd(r->tf, k.a2, nullptr, r->tb1, n, H, H, p, r->prec, s))) return e;
         } else {
             if ((e = lin(r, gb, Mout, 4 * p, k.c3.WT, p, nullptr, nullptr, PRX_ACT_MUL_RELUMASK, k.a2, nullptr, r->tb1, s))) return e;
         }
@@ -598,8 +650,8 @@ int prx_resnet_backward_a_impl(PrxResNet* r, const float* cutouts, const float* 
         if (k.has_ds) {
             if (k.stride > 1) {
                 if ((e = lin(r, gb, Mout, 4 * p, k.ds.WT, k.Cin, nullptr, nullptr, PRX_ACT_NONE, nullptr, r->tf, nullptr, s))) return e;
-                RLAUNCH(avgpool2_bwd_kernel, (size_t)Min * k.Cin / 16, r->tf, (const void*)nullptr, lean ? (float*)nullptr : g2,
-                                   lean ? r->gb3 : (void*)nullptr, n, H, H, k.Cin);
+                if ((e = prx_avgpool2_bwd(r->tf, nullptr, lean ? (float*)nullptr : g2, lean ? r->gb3 : (void*)nullptr, n, H, H, k.Cin,
+                                          r->prec, s))) return e;
                 gid = lean ? (const float*)r->gb3 : g2;
             } else {
                 if ((e = lin(r, gb, Mout, 4 * p, k.ds.WT, k.Cin, nullptr, nullptr, PRX_ACT_NONE, nullptr, lean ? nullptr : r->tf,
@@ -628,10 +680,10 @@ int prx_resnet_backward_a_impl(PrxResNet* r, const float* cutouts, const float* 
     }
     // stem: avgpool -> relu3 mask -> conv3 dgrad -> relu2 mask -> conv2 dgrad -> relu1 mask -> conv1 input gradient
     const int S = r->res, S2 = S / 2, w = r->width, wh = w / 2;
-    RLAUNCH(avgpool2_bwd_kernel, (size_t)n * S2 * S2 * w / 16, g, r->s3a, (float*)nullptr, r->tb1, n, S2, S2, w);
+    if ((e = prx_avgpool2_bwd(g, r->s3a, nullptr, r->tb1, n, S2, S2, w, r->prec, s))) return e;
     if ((e = conv3(r, r->tb1, n, S2, w, r->s3.Wd, wh, nullptr, PRX_ACT_MUL_RELUMASK, r->s2a, nullptr, r->tb2, s))) return e;
     if ((e = conv3(r, r->tb2, n, S2, wh, r->s2.Wd, wh, nullptr, PRX_ACT_MUL_RELUMASK, r->s1, nullptr, r->tb1, s))) return e;
-    STEM_LAUNCH(stem1_bwd_kernel, (size_t)n * S * S, wh, r->tb1, r->w1, r->dY, n, S, (const float*)(r->h16 ? r->gs + 1 : nullptr));
+    if ((e = prx_stem1_bwd(r->tb1, r->w1, r->dY, n, S, wh, r->h16 ? r->gs + 1 : nullptr, r->prec, s))) return e;
     return prx_preproc_bwd_reduce(cutouts, mm, r->dY, acc, n, S, s);
 }
 

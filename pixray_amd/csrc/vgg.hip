@@ -153,6 +153,38 @@ struct VConv { int Cin, CiP, Cout; void *Wf, *Wd; float* b; };   // weight packs
 
 }  // namespace
 
+// ---- one host launcher per kernel (vgg.h): grid computation and the operand-type dispatch, shared by the runner below and the
+// kernel-level tests (prx_k_*, csrc/api_kernels.hip)
+#define VLAUNCH(prec, kernel, total, ...)                                                                                \
+    do {                                                                                                                 \
+        PRX_REQUIRE(prec_valid(prec), #kernel ": unknown precision %d", prec);                                           \
+        PRX_OP_DISPATCH(prec_is_f32(prec), prec_is_h16(prec), TV,                                                        \
+                        hipLaunchKernelGGL(kernel<TV>, dim3(vgrid(total)), dim3(256), 0, s, __VA_ARGS__));               \
+        PRX_LAUNCH_CHECK();                                                                                              \
+    } while (0)
+int prx_vgg_pack(const float* w, void* Wf, void* Wd, int Cout, int Cin, int CiP, int prec, hipStream_t s) {
+    VLAUNCH(prec, vgg_pack_kernel, (size_t)1024 * 256, w, Wf, Wd, Cout, Cin, CiP);
+    return 0;
+}
+int prx_vgg_input(const float* x, void* out, int HW, int prec, hipStream_t s) {
+    VLAUNCH(prec, vgg_input_kernel, (size_t)HW, x, out, HW);
+    return 0;
+}
+int prx_vgg_input_grad(const float* d, float* gx, int HW, const float* unscale, hipStream_t s) {
+    hipLaunchKernelGGL(vgg_input_grad_kernel, dim3(vgrid((size_t)HW)), dim3(256), 0, s, d, gx, HW, unscale);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+int prx_vgg_maxpool(const void* x, void* out, unsigned char* arg, int H, int W, int C, int prec, hipStream_t s) {
+    VLAUNCH(prec, vgg_maxpool_kernel, (size_t)(H / 2) * (W / 2) * C, x, out, arg, H, W, C);
+    return 0;
+}
+int prx_vgg_combine(const float* above, const unsigned char* arg, const float* gcap, const void* act, void* gpre, int H, int W, int C,
+                    const float* gscale, int prec, hipStream_t s) {
+    VLAUNCH(prec, vgg_combine_kernel, (size_t)H * W * C, above, arg, gcap, act, gpre, H, W, C, gscale);
+    return 0;
+}
+
 struct PrxVgg16 {
     int max_h, max_w;
     int prec;         // PRX_PREC_*
@@ -183,8 +215,6 @@ int valloc_op(PrxVgg16* v, void** p, size_t count) {
     *p = q;
     return 0;
 }
-#define VLAUNCH(kernel, total, ...)                                                                                      \
-    PRX_OP_DISPATCH(v->f32, v->h16, TV, hipLaunchKernelGGL(kernel<TV>, dim3(vgrid(total)), dim3(256), 0, s, __VA_ARGS__))
 
 int vconv(PrxVgg16* v, const void* x, int H, int W, int Cin, const void* Bt, int Cout, const float* bias, int act,
           float* of, void* ob, hipStream_t s) {
@@ -222,8 +252,7 @@ int prx_vgg16_create_impl(PrxVgg16** out, const float* const* weights, int n_wei
         const size_t n = (size_t)c.Cout * 9 * c.CiP;
         int e;
         if ((e = valloc_op(v, &c.Wf, n)) || (e = valloc_op(v, &c.Wd, n)) || (e = valloc(v, &c.b, (size_t)c.Cout))) return fail(e);
-        VLAUNCH(vgg_pack_kernel, (size_t)1024 * 256, weights[2 * l], c.Wf, c.Wd, c.Cout, c.Cin, c.CiP);
-        if (hipGetLastError() != hipSuccess) return fail(-1);
+        if ((e = prx_vgg_pack(weights[2 * l], c.Wf, c.Wd, c.Cout, c.Cin, c.CiP, v->prec, s))) return fail(e);
         if (hipMemcpyAsync(c.b, weights[2 * l + 1], sizeof(float) * c.Cout, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(-1);
     }
     const size_t big = (size_t)max_h * max_w * 64;
@@ -249,21 +278,19 @@ int prx_vgg16_forward_impl(PrxVgg16* v, const float* x, int H, int W, void* work
     const VLayout L = vlayout(H, W, v->f32);
     char* base = (char*)workspace;
     void* cur = base + L.x0;
-    VLAUNCH(vgg_input_kernel, (size_t)H * W, x, cur, H * W);
-    PRX_LAUNCH_CHECK();
+    int e;
+    if ((e = prx_vgg_input(x, cur, H * W, v->prec, s))) return e;
     for (int l = 0; l < NCONV; ++l) {
         const VConv& c = v->conv[l];
         const int st = kStage[l];
         if (l > 0 && kStage[l - 1] != st) {      // pool the previous activation
             const int p = st - 1;
             void* pooled = base + L.pooled[p];
-            VLAUNCH(vgg_maxpool_kernel, (size_t)L.h[st] * L.w[st] * c.Cin, (const void*)cur, pooled,
-                    (unsigned char*)(base + L.arg[p]), L.h[st - 1], L.w[st - 1], c.Cin);
-            PRX_LAUNCH_CHECK();
+            if ((e = prx_vgg_maxpool(cur, pooled, (unsigned char*)(base + L.arg[p]), L.h[st - 1], L.w[st - 1], c.Cin, v->prec, s))) return e;
             cur = pooled;
         }
         void* act = base + L.act[l];
-        int e = vconv(v, cur, L.h[st], L.w[st], c.CiP, c.Wf, c.Cout, c.b, PRX_ACT_RELU, kFeat[l] >= 0 ? feats[kFeat[l]] : nullptr, act, s);
+        e = vconv(v, cur, L.h[st], L.w[st], c.CiP, c.Wf, c.Cout, c.b, PRX_ACT_RELU, kFeat[l] >= 0 ? feats[kFeat[l]] : nullptr, act, s);
         if (e) return e;
         cur = act;
     }
@@ -298,18 +325,16 @@ int prx_vgg16_backward_impl(PrxVgg16* v, int H, int W, const void* workspace, co
         const bool pooled_above = above && l + 1 < NCONV && kStage[l + 1] != st;
         const unsigned char* arg = pooled_above ? (const unsigned char*)(base + L.arg[st]) : nullptr;
         const size_t n = (size_t)L.h[st] * L.w[st] * c.Cout;
-        VLAUNCH(vgg_combine_kernel, n, above, arg, gcap, (const void*)(base + L.act[l]), v->gpre, L.h[st], L.w[st], c.Cout,
-                (const float*)v->gs);
-        PRX_LAUNCH_CHECK();
+        int e = prx_vgg_combine(above, arg, gcap, base + L.act[l], v->gpre, L.h[st], L.w[st], c.Cout, v->gs, v->prec, s);
+        if (e) return e;
         float* dst = bufs[flip]; flip ^= 1;
-        int e = vconv(v, v->gpre, L.h[st], L.w[st], c.Cout, c.Wd, c.CiP, nullptr, PRX_ACT_NONE, dst, nullptr, s);
+        e = vconv(v, v->gpre, L.h[st], L.w[st], c.Cout, c.Wd, c.CiP, nullptr, PRX_ACT_NONE, dst, nullptr, s);
         if (e) return e;
         above = dst;
     }
     if (above) {
-        hipLaunchKernelGGL(vgg_input_grad_kernel, dim3(vgrid((size_t)H * W)), dim3(256), 0, s, above, g_x, H * W,
-                           (const float*)(v->gs ? v->gs + 1 : nullptr));
-        PRX_LAUNCH_CHECK();
+        int e = prx_vgg_input_grad(above, g_x, H * W, v->gs ? v->gs + 1 : nullptr, s);
+        if (e) return e;
     } else {
         PRX_CHECK_HIP(hipMemsetAsync(g_x, 0, sizeof(float) * 3 * (size_t)H * W, s));
     }

@@ -31,3 +31,9 @@ int prx_vit_backward_a_impl(PrxVit* v, const float* cutouts, const float* mm, co
                             hipStream_t s);
 int prx_vit_backward_b_impl(PrxVit* v, const float* cutouts, const float* mm, const double* acc, float* g_cutouts,
                             hipStream_t s);
+// launchers of the runner's own token-embedding / exact-mode activation kernels (the runner calls these; exported as prx_k_* for
+// the kernel-level tests).  embed_tokens: `out` is IEEE half when out16, else fp32; scale_f32: x *= scale on `blocks` workgroups
+int prx_vit_add_cls_pos(float* x, const float* cls, const float* pos, int N, int T, int W, hipStream_t s);
+int prx_vit_embed_tokens(const float* x, const float* cls, const float* pos, void* out, int out16, int N, int T, int W, hipStream_t s);
+int prx_vit_gelu_f32(const float* t, float* io, size_t n, int bwd, hipStream_t s);
+int prx_vit_scale_f32(float* x, size_t n, float scale, int blocks, hipStream_t s);

@@ -99,6 +99,30 @@ int prx_pack_transpose_op(const float* in, void* out, int R, int C, int prec, hi
 }
 int prx_pack_bf16(const float* in, bf16_t* out, size_t n, hipStream_t s) { return prx_pack_op(in, out, n, 0, s); }
 int prx_pack_transpose_bf16(const float* in, bf16_t* out, int R, int C, hipStream_t s) { return prx_pack_transpose_op(in, out, R, C, 0, s); }
+// launchers of the token-embedding and exact-mode activation kernels (vit.h): shared by the runner below and the kernel-level tests
+int prx_vit_add_cls_pos(float* x, const float* cls, const float* pos, int N, int T, int W, hipStream_t s) {
+    hipLaunchKernelGGL(add_cls_pos_kernel, dim3(2048), dim3(256), 0, s, x, cls, pos, N, T, W);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+int prx_vit_embed_tokens(const float* x, const float* cls, const float* pos, void* out, int out16, int N, int T, int W, hipStream_t s) {
+    if (out16) hipLaunchKernelGGL(embed_tokens_kernel<half_t>, dim3(2048), dim3(256), 0, s, x, cls, pos, (half_t*)out, N, T, W);   // lean implies IEEE half
+    else hipLaunchKernelGGL(embed_tokens_kernel<float>, dim3(2048), dim3(256), 0, s, x, cls, pos, (float*)out, N, T, W);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+int prx_vit_gelu_f32(const float* t, float* io, size_t n, int bwd, hipStream_t s) {
+    if (bwd) hipLaunchKernelGGL(gelu_f32_kernel<true>, dim3(2048), dim3(256), 0, s, t, io, n);
+    else hipLaunchKernelGGL(gelu_f32_kernel<false>, dim3(2048), dim3(256), 0, s, t, io, n);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+int prx_vit_scale_f32(float* x, size_t n, float scale, int blocks, hipStream_t s) {
+    PRX_REQUIRE(blocks >= 1, "scale_f32: %d workgroups", blocks);
+    hipLaunchKernelGGL(scale_f32_kernel, dim3(blocks), dim3(256), 0, s, x, n, scale);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
 
 struct VitLayer {
     float *ln1_g, *ln1_b, *bqkv, *bo, *ln2_g, *ln2_b, *b1, *b2;
@@ -258,9 +282,8 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
                 PRX_CHECK_HIP(hipMemcpy2DAsync(pad_b + (size_t)sect * AW, sizeof(float) * 64, q[3] + (size_t)sect * W, sizeof(float) * hd,
                                                sizeof(float) * hd, heads, hipMemcpyDeviceToDevice, s));
             }
-            hipLaunchKernelGGL(scale_f32_kernel, dim3(256), dim3(256), 0, s, pad_w, (size_t)AW * W, qs);
-            hipLaunchKernelGGL(scale_f32_kernel, dim3(1), dim3(256), 0, s, pad_b, (size_t)AW, qs);
-            PRX_LAUNCH_CHECK();
+            if ((r = prx_vit_scale_f32(pad_w, (size_t)AW * W, qs, 256, s))) return r;
+            if ((r = prx_vit_scale_f32(pad_b, (size_t)AW, qs, 1, s))) return r;
             if ((r = pack_both(v, &y.Wqkv, &y.WqkvT, pad_w, 3 * AW, W, s))) return r;
             if ((r = copy_f32(v, &y.bqkv, pad_b, 3 * AW, s))) return r;
             // out-projection [W, W]: input columns head x hd -> the first hd of every head's 64 columns of [W, AW]
@@ -363,14 +386,11 @@ int prx_vit_forward_impl(PrxVit* v, const float* cutouts, int n, const float* mm
     const int lean = v->lean;
     void* x0 = v->layers > 0 ? v->L[0].x_in : v->x_final;
     if (v->fam.ln_pre) {
-        hipLaunchKernelGGL(add_cls_pos_kernel, dim3(2048), dim3(256), 0, s, v->xpre, v->cls, v->pos, n, T, W);
-        PRX_LAUNCH_CHECK();
+        if ((r = prx_vit_add_cls_pos(v->xpre, v->cls, v->pos, n, T, W, s))) return r;
         if ((r = prx_layernorm_fwd(v->xpre, W, v->lnpre_g, v->lnpre_b, lean ? (bf16_t*)x0 : nullptr, lean ? nullptr : (float*)x0, v->mean_pre,
                                    v->rstd_pre, R, W, v->fam.eps, s, v->h16, 0, 1))) return r;
     } else {
-        if (lean) hipLaunchKernelGGL(embed_tokens_kernel<half_t>, dim3(2048), dim3(256), 0, s, v->xpre, v->cls, v->pos, (half_t*)x0, n, T, W);   // lean implies IEEE half
-        else hipLaunchKernelGGL(embed_tokens_kernel<float>, dim3(2048), dim3(256), 0, s, v->xpre, v->cls, v->pos, (float*)x0, n, T, W);
-        PRX_LAUNCH_CHECK();
+        if ((r = prx_vit_embed_tokens(v->xpre, v->cls, v->pos, x0, lean, n, T, W, s))) return r;
     }
     for (int l = 0; l < v->layers; ++l) {
         VitLayer& y = v->L[l];
@@ -400,8 +420,7 @@ int prx_vit_forward_impl(PrxVit* v, const float* cutouts, int n, const float* mm
             if (own_pass) { d.act = PRX_ACT_NONE; d.out_bf16 = y.t; d.out_bf16_pre = nullptr; }
             if ((r = vit_gemm(v, d, s))) return r;
             if (own_pass) {
-                hipLaunchKernelGGL(gelu_f32_kernel<false>, dim3(2048), dim3(256), 0, s, (const float*)y.t, (float*)v->u, (size_t)rows * 4 * W);
-                PRX_LAUNCH_CHECK();
+                if ((r = prx_vit_gelu_f32((const float*)y.t, (float*)v->u, (size_t)rows * 4 * W, 0, s))) return r;
             } }
         {   GemmDesc d; d.A = v->u; d.lda = 4 * W; d.B = y.W2; d.ldb = 4 * W; d.M = rows; d.N = W; d.K = 4 * W;
             d.bias_n = y.b2; d.ldr = ldt;
@@ -464,8 +483,7 @@ int prx_vit_backward_a_impl(PrxVit* v, const float* cutouts, const float* mm, co
             if (own_pass) { d.act = PRX_ACT_NONE; d.aux = nullptr; }
             if ((r = vit_gemm(v, d, s))) return r;
             if (own_pass) {
-                hipLaunchKernelGGL(gelu_f32_kernel<true>, dim3(2048), dim3(256), 0, s, (const float*)y.t, (float*)v->dt, (size_t)rows * 4 * W);
-                PRX_LAUNCH_CHECK();
+                if ((r = prx_vit_gelu_f32((const float*)y.t, (float*)v->dt, (size_t)rows * 4 * W, 1, s))) return r;
             } }
         {   GemmDesc d; d.A = v->dt; d.lda = 4 * W; d.B = y.W1T; d.ldb = 4 * W; d.M = rows; d.N = W; d.K = 4 * W;
             if (lean) { d.out_bf16 = v->dh_bf; d.ldc_bf16 = W; } else { d.out_f32 = v->dh; d.ldc_f32 = W; }

@@ -56,6 +56,20 @@ __global__ __launch_bounds__(256) void colminmax_kernel(const float* __restrict_
 
 }  // namespace
 
+// launchers of the two kernels above (vqgan.h): shared by the runner and the kernel-level tests
+int prx_vqgan_pack_conv3x3(const float* w, void* Wf, void* Wd, int Cout, int Cin, int CoP, int prec, hipStream_t s) {
+    PRX_REQUIRE(prec_valid(prec), "vqgan pack_conv3x3: unknown precision %d", prec);
+    PRX_OP_DISPATCH(prec_is_f32(prec), prec_is_h16(prec), TO,
+                    hipLaunchKernelGGL(pack_conv3x3_kernel<TO>, dim3(1024), dim3(256), 0, s, w, (TO*)Wf, (TO*)Wd, Cout, Cin, CoP));
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+int prx_colminmax(const float* w, float* mn, float* mx, int rows, int D, hipStream_t s) {
+    hipLaunchKernelGGL(colminmax_kernel, dim3(ceil_div(D, 256)), dim3(256), 0, s, w, mn, mx, rows, D);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+
 static inline int pad8(int P) { return (P + 7) & ~7; }   // row pitch of [*, P] GEMM operands (see zero_if_padded)
 
 // `void*` members are operand-precision buffers: bf16, or fp32 when the handle was created with PRX_PREC_F32
@@ -163,9 +177,7 @@ int make_conv3(PrxVqgan* v, Conv3& c, int Cin, int Cout, WCursor& cur, hipStream
     VALLOC_OP(c.Wf, (size_t)c.CoP * 9 * Cin);
     if (c.CoP != Cout) PRX_CHECK_HIP(hipMemsetAsync(c.Wf, 0, (size_t)c.CoP * 9 * Cin * op_esz(v->f32), s));
     VALLOC_OP(c.Wd, (size_t)Cin * 9 * c.CoP);
-    PRX_OP_DISPATCH(v->f32, v->h16, TO,
-                    hipLaunchKernelGGL(pack_conv3x3_kernel<TO>, dim3(1024), dim3(256), 0, s, w, (TO*)c.Wf, (TO*)c.Wd, Cout, Cin, c.CoP));
-    PRX_LAUNCH_CHECK();
+    { int e_ = prx_vqgan_pack_conv3x3(w, c.Wf, c.Wd, Cout, Cin, c.CoP, v->prec, s); if (e_) return e_; }
     VALLOC(c.b, c.CoP);
     if (c.CoP != Cout) PRX_CHECK_HIP(hipMemsetAsync(c.b, 0, sizeof(float) * c.CoP, s));
     PRX_CHECK_HIP(hipMemcpyAsync(c.b, b, sizeof(float) * Cout, hipMemcpyDeviceToDevice, s));
@@ -259,9 +271,7 @@ int prx_vqgan_create_impl(PrxVqgan** out, int ch, const int* ch_mult, int n_mult
     if ((r = copyf(v, &v->codebook, cb, (size_t)n_embed * embed_dim, s))) return r;
     VALLOC(v->cnorm, n_embed); VALLOC(v->zmin, embed_dim); VALLOC(v->zmax, embed_dim);
     if ((r = prx_sqnorm_rows(v->codebook, v->cnorm, n_embed, embed_dim, s))) return r;
-    hipLaunchKernelGGL(colminmax_kernel, dim3(ceil_div(embed_dim, 256)), dim3(256), 0, s, v->codebook, v->zmin, v->zmax,
-                       n_embed, embed_dim);
-    PRX_LAUNCH_CHECK();
+    if ((r = prx_colminmax(v->codebook, v->zmin, v->zmax, n_embed, embed_dim, s))) return r;
     if ((r = make_conv1(v, v->pq, embed_dim, z_channels, cur, s))) return r;
     int block_in = ch * ch_mult[n_mult - 1];
     int rh = h0, rw = w0;

@@ -40,6 +40,13 @@ struct EOp { int kind; int idx; int H, W; };   // 0 res, 1 attn, 2 downsample co
 
 }  // namespace
 
+// launcher of the kernel above (vqgan_enc.h): shared by the runner and the kernel-level tests; the encoder runs in bf16 only
+int prx_vqgan_enc_pack_conv3x3(const float* w, void* Wf, int Cout, int Cin, int CiP, hipStream_t s) {
+    hipLaunchKernelGGL(pack_conv3x3_fwd_kernel, dim3(512), dim3(256), 0, s, w, (bf16_t*)Wf, Cout, Cin, CiP);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+
 struct PrxVqganEnc {
     int in_ch, zc, D, NC, H, W, h0, w0;
     std::vector<void*> allocs;
@@ -82,8 +89,7 @@ int e_conv3(PrxVqganEnc* e, EConv3& c, int Cin, int Cout, ECursor& cur, hipStrea
     const float *w, *b; ENEXT(cur, w); ENEXT(cur, b);
     c.Cin = Cin; c.CiP = (Cin + 7) / 8 * 8; c.Cout = Cout;
     EALLOC(c.W, (size_t)Cout * 9 * c.CiP);
-    hipLaunchKernelGGL(pack_conv3x3_fwd_kernel, dim3(512), dim3(256), 0, s, w, c.W, Cout, Cin, c.CiP);
-    PRX_LAUNCH_CHECK();
+    { int r_ = prx_vqgan_enc_pack_conv3x3(w, c.W, Cout, Cin, c.CiP, s); if (r_) return r_; }
     return ecopy(e, &c.b, b, Cout, s);
 }
 int e_conv1(PrxVqganEnc* e, EConv1& c, int Cin, int Cout, ECursor& cur, hipStream_t s) {

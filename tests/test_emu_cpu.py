@@ -33,11 +33,12 @@ def emu():
     with _emu.enable() as lib:
         import test_kernels_gpu as tk
         import test_kernels_half_gpu as th
+        import test_kernels_runner_gpu as tr
         import test_path_gpu as tp
-        for m in (tk, th, tp):
+        for m in (tk, th, tr, tp):
             m.DEV = "cpu"
-        yield types_ns(lib=lib, tk=tk, th=th, tp=tp)
-        for m in (tk, th, tp):
+        yield types_ns(lib=lib, tk=tk, th=th, tr=tr, tp=tp)
+        for m in (tk, th, tr, tp):
             m.DEV = "cuda"
 
 
@@ -216,6 +217,13 @@ def test_half_mode_and_lean_layout_kernel_variants(emu):
     each against float64 at the gates that file derives; every variant flag at least once"""
     figs = emu.th.emu_subset()
     assert len(figs[0]) == len(figs[1]) == 4
+
+
+def test_runner_private_kernels_one_at_a_time(emu):
+    """tests/test_kernels_runner_gpu.py at CPU sizes: the stem, pool, token, min/max, patchify, renormalisation-backward, VGG, embedding,
+    l2norm kernels and the weight packers, each through the launcher its runner calls and against float64; and the renormalisation
+    sums bit for bit under the reversed workgroup order"""
+    emu.tr.emu_subset(emu.lib)
 
 
 def test_strotss_and_hypercolumn_kernels(emu):
