@@ -240,6 +240,22 @@ int prx_k_patchify_bwd_apply(const float* cut, const float* mm, const float* dA,
 int prx_k_preproc_bwd_reduce(const float* cut, const float* mm, const float* dY, double* acc, int N, int S, prx_stream_t s);
 int prx_k_preproc_bwd_apply(const float* cut, const float* mm, const float* dY, const double* acc, float* gcut, int N, int S,
                             prx_stream_t s);
+/* the cutout stages one at a time (cutouts.hip; tests/test_kernels_cutouts_gpu.py).  desc: n_cut descriptors of 36 doubles (layout: at
+ * prx_cutouts_forward).  uv: [n_cut][dst pixels][2] floats of scratch; gsrc_priv: [n_cut][3][Hs][Ws] scratch, gsrc: [3][Hs][Ws] their sum;
+ * grgb: [n_cut][3][S][S], the incoming gradient pulled back through the colour jitter (written for jittered cutouts only);
+ * maps_scratch: >= 64 bytes per cutout (forms 0 and 1).  form: -1 = the PRX_CUTOUT_BWD environment switch decides (the product),
+ * 0 = workgroup scatter, 1 = one-wave scatter, 2 = per-pixel gather */
+int prx_k_pool_fwd(const float* img, float* pooled, int* argmax, const unsigned char* mask, int C, int H, int W, int S, prx_stream_t s);
+int prx_k_pool_bwd(const float* g, const int* argmax, const unsigned char* mask, float* gimg, int C, int H, int W, int S, prx_stream_t s);
+int prx_k_rescale_fwd(const float* pooled, float* base, int C, int S, int Hb, int Wb, prx_stream_t s);
+int prx_k_rescale_bwd(const float* g_base, float* g_pooled, int C, int S, int Hb, int Wb, prx_stream_t s);
+int prx_k_warp_a_fwd(const float* src, int Hs, int Ws, const double* desc, float* out, int n_cut, int Ha, int Wa, prx_stream_t s);
+int prx_k_warp_a_bwd(const float* g, int Hs, int Ws, const double* desc, float* uv, float* gsrc_priv, float* gsrc, int n_cut, int Ha,
+                     int Wa, int form, prx_stream_t s);
+int prx_k_warp_b_fwd(const float* a, int Ha, int Wa, const double* desc, const float* noise, float* out, int n_cut, int S,
+                     prx_stream_t s);
+int prx_k_warp_b_bwd(const float* a, int Ha, int Wa, const double* desc, const float* g, float* grgb, float* uv, float* ga, int n_cut,
+                     int S, float* maps_scratch, size_t maps_scratch_bytes, int form, prx_stream_t s);
 /* VGG16 extractor (vgg.hip) */
 int prx_k_vgg_pack(const float* w, void* Wf, void* Wd, int Cout, int Cin, int CiP, int prec, prx_stream_t s);
 int prx_k_vgg_input(const float* x, void* out, int HW, int prec, prx_stream_t s);

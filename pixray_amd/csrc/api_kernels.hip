@@ -225,6 +225,49 @@ int prx_k_preproc_bwd_reduce(const float* cut, const float* mm, const float* dY,
 int prx_k_preproc_bwd_apply(const float* cut, const float* mm, const float* dY, const double* acc, float* gcut, int N, int S, prx_stream_t s) {
     return prx_preproc_bwd_apply(cut, mm, dY, acc, gcut, N, S, S_(s));
 }
+// the cutout stages one at a time (tests/test_kernels_cutouts_gpu.py); `form` of the two backward launchers: cutouts.h
+int prx_k_pool_fwd(const float* img, float* pooled, int* argmax, const unsigned char* mask, int C, int H, int W, int S, prx_stream_t s) {
+    PRX_REQUIRE(img && pooled && argmax, "prx_k_pool_fwd: null argument");
+    PRX_REQUIRE(C > 0 && H > 0 && W > 0 && S > 0, "prx_k_pool_fwd: sizes must be positive (C=%d H=%d W=%d S=%d)", C, H, W, S);
+    return prx_pool_fwd(img, pooled, argmax, mask, C, H, W, S, S_(s));
+}
+int prx_k_pool_bwd(const float* g, const int* argmax, const unsigned char* mask, float* gimg, int C, int H, int W, int S, prx_stream_t s) {
+    PRX_REQUIRE(g && argmax && gimg, "prx_k_pool_bwd: null argument");
+    PRX_REQUIRE(C > 0 && H > 0 && W > 0 && S > 0, "prx_k_pool_bwd: sizes must be positive (C=%d H=%d W=%d S=%d)", C, H, W, S);
+    return prx_pool_bwd(g, argmax, mask, gimg, C, H, W, S, S_(s));
+}
+int prx_k_rescale_fwd(const float* pooled, float* base, int C, int S, int Hb, int Wb, prx_stream_t s) {
+    PRX_REQUIRE(pooled && base, "prx_k_rescale_fwd: null argument");
+    PRX_REQUIRE(C > 0 && S > 0 && Hb > 0 && Wb > 0, "prx_k_rescale_fwd: sizes must be positive (C=%d S=%d Hb=%d Wb=%d)", C, S, Hb, Wb);
+    return prx_rescale_fwd(pooled, base, C, S, Hb, Wb, S_(s));
+}
+int prx_k_rescale_bwd(const float* g_base, float* g_pooled, int C, int S, int Hb, int Wb, prx_stream_t s) {
+    PRX_REQUIRE(g_base && g_pooled, "prx_k_rescale_bwd: null argument");
+    PRX_REQUIRE(C > 0 && S > 0 && Hb > 0 && Wb > 0, "prx_k_rescale_bwd: sizes must be positive (C=%d S=%d Hb=%d Wb=%d)", C, S, Hb, Wb);
+    return prx_rescale_bwd(g_base, g_pooled, C, S, Hb, Wb, S_(s));
+}
+int prx_k_warp_a_fwd(const float* src, int Hs, int Ws, const double* desc, float* out, int n_cut, int Ha, int Wa, prx_stream_t s) {
+    PRX_REQUIRE(src && desc && out, "prx_k_warp_a_fwd: null argument");
+    PRX_REQUIRE(n_cut > 0 && Hs > 1 && Ws > 1 && Ha > 1 && Wa > 1, "prx_k_warp_a_fwd: n_cut=%d source %dx%d destination %dx%d", n_cut, Hs, Ws, Ha, Wa);
+    return prx_warp_a_fwd(src, Hs, Ws, desc, out, n_cut, Ha, Wa, S_(s));
+}
+int prx_k_warp_a_bwd(const float* g, int Hs, int Ws, const double* desc, float* uv, float* gsrc_priv, float* gsrc, int n_cut, int Ha, int Wa,
+                     int form, prx_stream_t s) {
+    PRX_REQUIRE(g && desc && uv && gsrc_priv && gsrc, "prx_k_warp_a_bwd: null argument");
+    PRX_REQUIRE(n_cut > 0 && Hs > 1 && Ws > 1 && Ha > 1 && Wa > 1, "prx_k_warp_a_bwd: n_cut=%d source %dx%d destination %dx%d", n_cut, Hs, Ws, Ha, Wa);
+    return prx_warp_a_bwd(g, Hs, Ws, desc, uv, gsrc_priv, gsrc, n_cut, Ha, Wa, S_(s), form);
+}
+int prx_k_warp_b_fwd(const float* a, int Ha, int Wa, const double* desc, const float* noise, float* out, int n_cut, int S, prx_stream_t s) {
+    PRX_REQUIRE(a && desc && out, "prx_k_warp_b_fwd: null argument");
+    PRX_REQUIRE(n_cut > 0 && Ha > 1 && Wa > 1 && S > 1, "prx_k_warp_b_fwd: n_cut=%d stage-A image %dx%d S=%d", n_cut, Ha, Wa, S);
+    return prx_warp_b_fwd(a, Ha, Wa, desc, noise, out, n_cut, S, S_(s));
+}
+int prx_k_warp_b_bwd(const float* a, int Ha, int Wa, const double* desc, const float* g, float* grgb, float* uv, float* ga, int n_cut, int S,
+                     float* maps_scratch, size_t maps_scratch_bytes, int form, prx_stream_t s) {
+    PRX_REQUIRE(a && desc && g && grgb && uv && ga, "prx_k_warp_b_bwd: null argument");
+    PRX_REQUIRE(n_cut > 0 && Ha > 1 && Wa > 1 && S > 1, "prx_k_warp_b_bwd: n_cut=%d stage-A image %dx%d S=%d", n_cut, Ha, Wa, S);
+    return prx_warp_b_bwd(a, Ha, Wa, desc, g, grgb, uv, ga, n_cut, S, S_(s), maps_scratch, maps_scratch_bytes, form);
+}
 int prx_k_vgg_pack(const float* w, void* Wf, void* Wd, int Cout, int Cin, int CiP, int prec, prx_stream_t s) {
     return prx_vgg_pack(w, Wf, Wd, Cout, Cin, CiP, prec, S_(s));
 }

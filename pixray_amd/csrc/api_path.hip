@@ -102,9 +102,9 @@ int prx_cutouts_backward(const float* g_out, const double* desc, const unsigned 
     // g_base_priv doubles as the [n_cut,3,S,S] scratch of the ColorJitter pull-back (S <= Hb, Wb) before stage A overwrites it
     // g_pooled is written only at the very end of this call: until then it holds the per-cutout stage maps of stage B
     if ((r = prx_warp_b_bwd(stage_a, Hb, Wb, desc, g_out, g_base_priv, uv_scratch, g_stage_a, n_cut, S, S_(s), g_pooled,
-                            sizeof(float) * 3 * (size_t)S * S))) return r;
+                            sizeof(float) * 3 * (size_t)S * S, -1))) return r;
     const bool rect = Hb != S || Wb != S;
-    if ((r = prx_warp_a_bwd(g_stage_a, Hb, Wb, desc, uv_scratch, g_base_priv, rect ? g_base : g_pooled, n_cut, Hb, Wb, S_(s)))) return r;
+    if ((r = prx_warp_a_bwd(g_stage_a, Hb, Wb, desc, uv_scratch, g_base_priv, rect ? g_base : g_pooled, n_cut, Hb, Wb, S_(s), -1))) return r;
     if (rect && (r = prx_rescale_bwd(g_base, g_pooled, 3, S, Hb, Wb, S_(s)))) return r;
     return prx_pool_bwd(g_pooled, argmax, spot_mask, g_img, 3, H, W, S, S_(s));
 }

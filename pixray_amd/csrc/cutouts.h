@@ -6,11 +6,13 @@ int prx_pool_bwd(const float* g, const int* argmax, const unsigned char* mask, f
 // stage A renders Ha x Wa images from the shared Hs x Ws source; stage B reads them through the descriptor's window
 int prx_warp_a_fwd(const float* src, int Hs, int Ws, const double* desc, float* out, int n_cut, int Ha, int Wa, hipStream_t s);
 int prx_warp_a_bwd(const float* g, int Hs, int Ws, const double* desc, float* uv, float* gsrc_priv, float* gsrc, int n_cut, int Ha,
-                   int Wa, hipStream_t s);   // uv: [n_cut,Ha*Wa,2] scratch
+                   int Wa, hipStream_t s, int form);   // uv: [n_cut,Ha*Wa,2] scratch
+// form (both backward launchers): -1 = PRX_CUTOUT_BWD decides, read once per process (what the product passes); 0 = workgroup
+// scatter, 1 = one-wave scatter, 2 = per-pixel gather (the kernel tests run all three)
 int prx_warp_b_fwd(const float* a, int Ha, int Wa, const double* desc, const float* noise, float* out, int n_cut, int S,
                    hipStream_t s);
 int prx_warp_b_bwd(const float* a, int Ha, int Wa, const double* desc, const float* g, float* grgb, float* uv, float* ga, int n_cut,
-                   int S, hipStream_t s, float* maps_scratch, size_t maps_scratch_bytes);
+                   int S, hipStream_t s, float* maps_scratch, size_t maps_scratch_bytes, int form);
 // grgb: [n_cut,3,S,S], uv: [n_cut,S*S,2] scratch; maps_scratch: >= 64 bytes per cutout, untouched by anything else until the
 // launch has finished (the per-cutout inverse stage maps of the tile-owned scatter)
 // bilinear resize of the pooled [C,S,S] image to the canvas aspect [C,Hb,Wb] (pixray.py:468-472) and its gradient

@@ -862,6 +862,7 @@ __device__ __forceinline__ void scatter_tile_wave(const GatherStage& st, const S
         ts.cnt[lane] = cnt;
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0): the wave's LDS writes above are visible to its reads below
+    __builtin_amdgcn_wave_barrier();             // no instruction: keeps the compiler from moving LDS traffic across (the attention kernels' idiom)
     const size_t plane = (size_t)st.Hd * st.Wd;
     constexpr int U = 4;
     for (int r = 0; r < MAXR * MAXR; ++r) {
@@ -891,6 +892,7 @@ __device__ __forceinline__ void scatter_tile_wave(const GatherStage& st, const S
         }
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -1539,21 +1541,27 @@ int prx_warp_a_fwd(const float* src, int Hs, int Ws, const double* desc, float* 
     return 0;
 }
 int prx_warp_a_bwd(const float* g, int Hs, int Ws, const double* desc, float* uv, float* gsrc_priv, float* gsrc, int n_cut, int Ha,
-                   int Wa, hipStream_t s) {
+                   int Wa, hipStream_t s, int form) {
     // uv: [n_cut][Ha*Wa][2] scratch
     // gsrc_priv: [n_cut][3][Hs][Ws] per-cutout private planes (scratch, every element written); gsrc: [3][Hs][Ws] their sum
+    // form: -1 = PRX_CUTOUT_BWD decides (the product), 0 = workgroup scatter, 1 = one-wave scatter, 2 = per-pixel gather
+    PRX_REQUIRE(form >= -1 && form <= 2, "warp_a_bwd: form is not one of -1, 0, 1, 2");
+    const bool gather = form < 0 ? cutout_bwd_gather() : form == 2;
+    const bool block = form < 0 ? cutout_bwd_block() : form == 0;
+    // the per-cutout stage maps (16 floats each) live in `gsrc` until reduce_planes_kernel overwrites it with the result
+    // (refused before anything is launched: a refusal writes nothing)
+    if (!gather)
+        PRX_REQUIRE((size_t)n_cut * sizeof(StageMap) <= (size_t)3 * Hs * Ws * sizeof(float), "warp_a_bwd: too many cutouts for the stage-map scratch");
     const int tx = (Ws + TILE_W - 1) / TILE_W, ty = (Hs + TILE_W - 1) / TILE_W;
     hipLaunchKernelGGL(uv_kernel, dim3(std::min(ew_grid((size_t)Ha * Wa), 64), n_cut), dim3(256), 0, s, desc, 1, (float2*)uv, Wa, Ha, Ws, Hs);
     PRX_LAUNCH_CHECK();
-    if (cutout_bwd_gather())
+    if (gather)
         hipLaunchKernelGGL(warp_a_bwd_kernel, dim3(tx * ty, n_cut), dim3(256), 0, s, g, Hs, Ws, desc, (const float2*)uv, gsrc_priv, n_cut,
                            Ha, Wa);
     else {
-        // the per-cutout stage maps (16 floats each) live in `gsrc` until reduce_planes_kernel overwrites it with the result
-        PRX_REQUIRE((size_t)n_cut * sizeof(StageMap) <= (size_t)3 * Hs * Ws * sizeof(float), "warp_a_bwd: too many cutouts for the stage-map scratch");
         hipLaunchKernelGGL(stage_map_kernel, dim3(ceil_div(n_cut, 64)), dim3(64), 0, s, desc, 1, (StageMap*)gsrc, n_cut, Wa, Ha, Ws, Hs);
         PRX_LAUNCH_CHECK();
-        if (cutout_bwd_block())
+        if (block)
             hipLaunchKernelGGL(warp_a_bwd2_kernel, dim3(tx * ty, n_cut), dim3(256), 0, s, g, Hs, Ws, desc, (const float2*)uv, (const StageMap*)gsrc,
                                gsrc_priv, n_cut, Ha, Wa, cutout_dbg());
         else
@@ -1574,23 +1582,28 @@ int prx_warp_b_fwd(const float* a, int Ha, int Wa, const double* desc, const flo
     return 0;
 }
 int prx_warp_b_bwd(const float* a, int Ha, int Wa, const double* desc, const float* g, float* grgb, float* uv, float* ga, int n_cut,
-                   int S, hipStream_t s, float* maps_scratch, size_t maps_scratch_bytes) {
+                   int S, hipStream_t s, float* maps_scratch, size_t maps_scratch_bytes, int form) {
     // grgb: [n_cut][3][S][S] scratch (the gradient pulled back through the ColorJitter); uv: [n_cut][S*S][2] scratch;
-    // ga: [n_cut][3][Ha][Wa], every element written
+    // ga: [n_cut][3][Ha][Wa], every element written; form: as for prx_warp_a_bwd
+    PRX_REQUIRE(form >= -1 && form <= 2, "warp_b_bwd: form is not one of -1, 0, 1, 2");
+    const bool gather = form < 0 ? cutout_bwd_gather() : form == 2;
+    const bool block = form < 0 ? cutout_bwd_block() : form == 0;
+    // maps_scratch: any buffer of >= n_cut stage maps that nothing else touches until this launch has finished
+    // (refused before anything is launched: a refusal writes nothing)
+    if (!gather)
+        PRX_REQUIRE(maps_scratch != nullptr && (size_t)n_cut * sizeof(StageMap) <= maps_scratch_bytes, "warp_b_bwd: stage-map scratch too small");
     hipLaunchKernelGGL(uv_kernel, dim3(std::min(ew_grid((size_t)S * S), 64), n_cut), dim3(256), 0, s, desc, 2, (float2*)uv, S, S, 0, 0);
     PRX_LAUNCH_CHECK();
     hipLaunchKernelGGL(warp_b_jac_kernel, dim3(std::min(ew_grid((size_t)S * S), 64), n_cut), dim3(256), 0, s, a, Ha, Wa, desc, g, grgb,
                        n_cut, S);
     PRX_LAUNCH_CHECK();
     const int tx = (Wa + TILE_W - 1) / TILE_W, ty = (Ha + TILE_W - 1) / TILE_W;
-    if (cutout_bwd_gather())
+    if (gather)
         hipLaunchKernelGGL(warp_b_bwd_kernel, dim3(tx * ty, n_cut), dim3(256), 0, s, Ha, Wa, desc, g, grgb, (const float2*)uv, ga, n_cut, S);
     else {
-        // maps_scratch: any buffer of >= n_cut stage maps that nothing else touches until this launch has finished
-        PRX_REQUIRE(maps_scratch != nullptr && (size_t)n_cut * sizeof(StageMap) <= maps_scratch_bytes, "warp_b_bwd: stage-map scratch too small");
         hipLaunchKernelGGL(stage_map_kernel, dim3(ceil_div(n_cut, 64)), dim3(64), 0, s, desc, 2, (StageMap*)maps_scratch, n_cut, S, S, 0, 0);
         PRX_LAUNCH_CHECK();
-        if (cutout_bwd_block())
+        if (block)
             hipLaunchKernelGGL(warp_b_bwd2_kernel, dim3(tx * ty, n_cut), dim3(256), 0, s, Ha, Wa, desc, g, grgb, (const float2*)uv,
                                (const StageMap*)maps_scratch, ga, n_cut, S, cutout_dbg());
         else

@@ -34,11 +34,12 @@ def emu():
         import test_kernels_gpu as tk
         import test_kernels_half_gpu as th
         import test_kernels_runner_gpu as tr
+        import test_kernels_cutouts_gpu as tc
         import test_path_gpu as tp
-        for m in (tk, th, tr, tp):
+        for m in (tk, th, tr, tc, tp):
             m.DEV = "cpu"
-        yield types_ns(lib=lib, tk=tk, th=th, tr=tr, tp=tp)
-        for m in (tk, th, tr, tp):
+        yield types_ns(lib=lib, tk=tk, th=th, tr=tr, tc=tc, tp=tp)
+        for m in (tk, th, tr, tc, tp):
             m.DEV = "cuda"
 
 
@@ -224,6 +225,15 @@ def test_runner_private_kernels_one_at_a_time(emu):
     l2norm kernels and the weight packers, each through the launcher its runner calls and against float64; and the renormalisation
     sums bit for bit under the reversed workgroup order"""
     emu.tr.emu_subset(emu.lib)
+
+
+def test_cutout_stages_one_at_a_time_all_three_backward_forms(emu):
+    """tests/test_kernels_cutouts_gpu.py on the emulated kernels: pool, rescale, stage A and stage B against float64 -- every padding mode
+    x grid flavour at the small shapes, the search fallbacks (x6 magnification, x0.2 minification under border padding, 45 degrees,
+    perspectives, far reflection, fully outside, singular), each with the workgroup scatter, the one-wave scatter and the per-pixel
+    gather, the colour-jitter Jacobian, the explicit noise and the refusals"""
+    figs = emu.tc.emu_subset()
+    assert any(k.startswith("bwd-el/") and k.endswith("form2") for k in figs) and any(k.startswith("colour-grgb/") for k in figs)
 
 
 def test_strotss_and_hypercolumn_kernels(emu):
