@@ -373,7 +373,7 @@ __global__ __launch_bounds__(256) void warp_a_fwd_kernel(const float* __restrict
     }
 }
 
-// ---- backward in GATHER form ----------------------------------------------------------------------------------------
+// ---- backward: source-owned sums (the geometry all three forms of warp_bwd_kernel share; the forms are described there) --
 // The reference differentiates its warps with grid_sampler_2d_backward: float atomics, run-to-run different bits
 // (pixray.py:29 documents the non-determinism).  Here every SOURCE pixel collects its own contributions in a fixed order:
 // bit-reproducible, no atomics, no memsets.  For source pixel s the destination pixels whose bilinear footprint touches
@@ -440,17 +440,18 @@ __device__ void build_stage_map(StageMap& sm, const double* m, int gtype, int Wd
     sm.ulo = ulo - 1.5f; sm.uhi = uhi + 1.5f; sm.vlo = vlo - 1.5f; sm.vhi = vhi + 1.5f;
 }
 
-// Raw-coordinate intervals [a, b) whose padded coordinate can produce a tap on source index s (size W), clipped to
-// [lo, hi].  Returns the count (<= MAXI); intervals come out sorted, merged and pairwise disjoint.
-constexpr int MAXI = 3;
-__device__ __forceinline__ int tap_intervals(int mode, int s, int W, float lo, float hi, float* ia, float* ib) {
+// Raw-coordinate intervals [a, b) whose padded coordinate can produce a tap on a source index in [s0, s1] (one pixel: s0 == s1;
+// a tile: its range clipped to the image) of an axis of size W, clipped to [lo, hi].  Returns the count (<= MAXR); intervals
+// come out sorted, merged and pairwise disjoint.
+constexpr int MAXR = 3;
+__device__ __forceinline__ int tile_intervals(int mode, int s0, int s1, int W, float lo, float hi, float* ia, float* ib) {
     const float eps = 2e-3f;       // slack against the fp32 rounding of the forward's own coordinate arithmetic
-    const float fs = (float)s, fW = (float)W;
+    const float f0 = (float)s0, f1 = (float)s1, fW = (float)W;
     // the direct image: every mode has it (the upright copy of the source inside its own domain)
-    float a = fs - 1.f - eps, b = fs + 1.f + eps;
+    float a = f0 - 1.f - eps, b = f1 + 1.f + eps;
     if (mode == MODE_BORDER) {                      // clamping folds everything beyond the edge onto the edge pixel
-        if (s == 0) a = -INFINITY;
-        if (s == W - 1) b = INFINITY;
+        if (s0 == 0) a = -INFINITY;
+        if (s1 == W - 1) b = INFINITY;
     }
     a = fmaxf(a, lo); b = fminf(b, hi);
     int n = 0;
@@ -459,12 +460,12 @@ __device__ __forceinline__ int tap_intervals(int mode, int s, int W, float lo, f
     // first-order mirror images (reflection about the low and the high edge); a raw range that reaches past them
     // (|excursion| > one image size: never with pixray's distortion scales) falls back to the whole range
     float m0a, m0b, m1a, m1b, dlo, dhi;
-    if (mode == MODE_REFLECT) {                     // align_corners=False: mirrors about -0.5 and W-0.5
-        m0a = -fs - 2.f; m0b = -fs; m1a = 2.f * fW - fs - 2.f; m1b = 2.f * fW - fs;
+    if (mode == MODE_REFLECT) {                     // align_corners=False: mirrors about -0.5 and W - 0.5: t -> -1 - t, t -> 2W - 1 - t
+        m0a = -f1 - 2.f; m0b = -f0; m1a = 2.f * fW - f1 - 2.f; m1b = 2.f * fW - f0;
         dlo = -fW - 0.5f; dhi = 2.f * fW - 0.5f;
-    } else {                                        // align_corners=True: mirrors about 0 and W-1
+    } else {                                        // align_corners=True: mirrors about 0 and W - 1
         const float span = fW - 1.f;
-        m0a = -fs - 1.f; m0b = -fs + 1.f; m1a = 2.f * span - fs - 1.f; m1b = 2.f * span - fs + 1.f;
+        m0a = -f1 - 1.f; m0b = -f0 + 1.f; m1a = 2.f * span - f1 - 1.f; m1b = 2.f * span - f0 + 1.f;
         dlo = -span; dhi = 2.f * span;
     }
     if (lo < dlo || hi > dhi) { ia[0] = lo; ib[0] = hi; return 1; }
@@ -507,14 +508,13 @@ __device__ __forceinline__ bool preimage_box(const StageMap& sm, float ua, float
     return x0 <= x1 && y0 <= y1;
 }
 
-// what one stage's gather needs to know
+// what the tile helpers need to know of one stage (warp_bwd_kernel builds it in registers)
 struct GatherStage {
-    const double* m; int gtype, mode;
+    int mode;
     int Wd, Hd;            // destination plane
     int Ws, Hs;            // source image the taps index (the stage-B window, or the whole stage-A source)
     const float* g;        // destination-side gradient planes of this cutout, [3][Hd][Wd]
     const float2* uv;      // the forward's raw source coordinate of every destination pixel of this cutout, [Hd][Wd] (uv_kernel)
-    unsigned long long* dbg = nullptr;   // PRX_CUTOUT_DBG=1: {candidates visited, rectangles, candidates inside their rectangle, with a tap in the tile}
 };
 
 // LDS staging of one block's candidates: neighbouring source pixels share almost all of their destination candidates, so
@@ -574,9 +574,9 @@ constexpr int HEAVY = 96;        // candidates above which a pixel is handed to 
 template <bool COOP>
 __device__ __forceinline__ int gather_pixel(const GatherStage& st, const StageMap& sm, const TileStage& ts, int sx, int sy,
                                             float (&acc)[3], int budget) {
-    float xa[MAXI], xb[MAXI], ya[MAXI], yb[MAXI];
-    const int nx = tap_intervals(st.mode, sx, st.Ws, sm.ulo, sm.uhi, xa, xb);
-    const int ny = tap_intervals(st.mode, sy, st.Hs, sm.vlo, sm.vhi, ya, yb);
+    float xa[MAXR], xb[MAXR], ya[MAXR], yb[MAXR];
+    const int nx = tile_intervals(st.mode, sx, sx, st.Ws, sm.ulo, sm.uhi, xa, xb);
+    const int ny = tile_intervals(st.mode, sy, sy, st.Hs, sm.vlo, sm.vhi, ya, yb);
     const int lane = threadIdx.x & 63;
     int total = 0;
     // Only border padding creates unbounded rectangles (an edge pixel owns the whole strip of padded area beside it); under
@@ -664,78 +664,31 @@ __device__ __forceinline__ void gather_tile(const GatherStage& st, const StageMa
     out[0] = acc[0]; out[1] = acc[1]; out[2] = acc[2];
 }
 
-// ---- backward, tile-owned scatter form (round 3) ----------------------------------------------------------------------
-// The per-PIXEL gather above spends ~1-2 k instructions of pre-image geometry per source pixel before it touches a candidate
-// (0.54 ms per iteration at the headline: 10x its HBM bound).  Same ownership, coarser granularity: a workgroup owns a
-// 16 x 16 tile of SOURCE pixels, works out the raw-coordinate rectangles / destination boxes ONCE for the tile, and then runs
-// DESTINATION-parallel over the candidates -- each lane takes one destination pixel, rebuilds the forward's own four taps
-// (make_taps on the stored raw coordinate: same roundings, exact adjoint) and adds the taps that fall inside the tile into an
-// LDS accumulator.  No global atomics, no memsets, every gradient element written exactly once, and still bit-reproducible:
-//   * candidates are visited in a fixed order (rectangle by rectangle, k = thread id + 256 j);
-//   * each of the block's 4 waves has its OWN accumulator plane, so no two waves ever add to the same word; within a wave the
-//     additions of one ds_add_f32 instruction are serialised by the LDS in a fixed lane order, and instructions retire in
-//     program order;
-//   * the four planes are summed in wave order at the end.
-// Uniqueness / completeness as in the gather: the tile's raw rectangles are pairwise disjoint and a candidate is counted in
-// the rectangle that contains its raw coordinate; acceptance is by the exact taps, the boxes only bound the search.
-constexpr int MAXR = 3;
-// raw-coordinate intervals whose padded coordinate can produce a tap on a source index in [s0, s1] (tile range, clipped to
-// the image), clipped to [lo, hi]: the tile-level version of tap_intervals
-__device__ __forceinline__ int tile_intervals(int mode, int s0, int s1, int W, float lo, float hi, float* ia, float* ib) {
-    const float eps = 2e-3f;
-    const float f0 = (float)s0, f1 = (float)s1, fW = (float)W;
-    float a = f0 - 1.f - eps, b = f1 + 1.f + eps;
-    if (mode == MODE_BORDER) {
-        if (s0 == 0) a = -INFINITY;
-        if (s1 == W - 1) b = INFINITY;
-    }
-    a = fmaxf(a, lo); b = fminf(b, hi);
-    int n = 0;
-    if (b > a) { ia[0] = a; ib[0] = b; n = 1; }
-    if (mode != MODE_REFLECT && mode != MODE_REFLECT_AC) return n;
-    float m0a, m0b, m1a, m1b, dlo, dhi;
-    if (mode == MODE_REFLECT) {                     // mirrors about -0.5 and W - 0.5: t -> -1 - t, t -> 2W - 1 - t
-        m0a = -f1 - 2.f; m0b = -f0; m1a = 2.f * fW - f1 - 2.f; m1b = 2.f * fW - f0;
-        dlo = -fW - 0.5f; dhi = 2.f * fW - 0.5f;
-    } else {                                        // mirrors about 0 and W - 1
-        const float span = fW - 1.f;
-        m0a = -f1 - 1.f; m0b = -f0 + 1.f; m1a = 2.f * span - f1 - 1.f; m1b = 2.f * span - f0 + 1.f;
-        dlo = -span; dhi = 2.f * span;
-    }
-    if (lo < dlo || hi > dhi) { ia[0] = lo; ib[0] = hi; return 1; }       // beyond the first-order mirrors: search the whole range
-    m0a = fmaxf(m0a - eps, lo); m0b = fminf(m0b + eps, hi);
-    m1a = fmaxf(m1a - eps, lo); m1b = fminf(m1b + eps, hi);
-    int cnt = 0;
-    float ra[3], rb[3];
-    if (m0b > m0a) { ra[cnt] = m0a; rb[cnt] = m0b; ++cnt; }
-    if (n) {
-        if (cnt && ia[0] <= rb[cnt - 1]) rb[cnt - 1] = fmaxf(rb[cnt - 1], ib[0]);
-        else { ra[cnt] = ia[0]; rb[cnt] = ib[0]; ++cnt; }
-    }
-    if (m1b > m1a) {
-        if (cnt && m1a <= rb[cnt - 1]) rb[cnt - 1] = fmaxf(rb[cnt - 1], m1b);
-        else { ra[cnt] = m1a; rb[cnt] = m1b; ++cnt; }
-    }
-    for (int i = 0; i < cnt; ++i) { ia[i] = ra[i]; ib[i] = rb[i]; }
-    return cnt;
-}
-
-struct TileScatter {
+// ---- tile-owned scatter: forms 0 and 1 of warp_bwd_kernel (described there) ---------------------------------------------
+// the disjoint raw rectangles of a tile and their destination boxes
+struct TileRects {
+    float ua[MAXR * MAXR], ub[MAXR * MAXR], va[MAXR * MAXR], vb[MAXR * MAXR];
+    int x0[MAXR * MAXR], y0[MAXR * MAXR], bw[MAXR * MAXR], cnt[MAXR * MAXR];
+};
+struct TileScatter {                         // form 0: rectangles compacted to the first nrect slots
     int nrect;
-    float ua[MAXR * MAXR], ub[MAXR * MAXR], va[MAXR * MAXR], vb[MAXR * MAXR];     // disjoint raw rectangles of the tile
-    int x0[MAXR * MAXR], y0[MAXR * MAXR], bw[MAXR * MAXR], cnt[MAXR * MAXR];      // their destination boxes
-    float acc[4][3][TILE_W * TILE_W];                                                 // one accumulator plane set per wave
+    TileRects rect;
+    float acc[4][3][TILE_W * TILE_W];        // one accumulator plane set per wave
+};
+struct WaveScatter {                         // form 1: rectangle (i, j) in slot 3 j + i, cnt == 0 where there is none
+    TileRects rect;
+    float acc[3][TILE_W * TILE_W];
 };
 
 // one candidate: destination pixel with raw coordinate q and gradient (g0, g1, g2) -> LDS accumulator of the tile
-__device__ __forceinline__ int scatter_candidate(const GatherStage& st, float* __restrict__ a0, float* __restrict__ a1, float* __restrict__ a2,
-                                                 int tx0, int ty0, float ua, float ub, float va, float vb, float2 q, float g0, float g1, float g2) {
-    if (!(q.x >= ua && q.x < ub && q.y >= va && q.y < vb)) return 0;
+__device__ __forceinline__ void scatter_candidate(const GatherStage& st, float* __restrict__ a0, float* __restrict__ a1, float* __restrict__ a2,
+                                                  int tx0, int ty0, float ua, float ub, float va, float vb, float2 q, float g0, float g1, float g2) {
+    if (!(q.x >= ua && q.x < ub && q.y >= va && q.y < vb)) return;
     const Taps t = make_taps(q.x, q.y, st.Ws, st.Hs, st.mode);          // the forward's own taps
     const int lx = t.x0 - tx0, ly = t.y0 - ty0;                          // north-west tap inside the tile?
     const bool cx0 = t.vx0 && lx >= 0 && lx < TILE_W, cx1 = t.vx1 && lx + 1 >= 0 && lx + 1 < TILE_W;
     const bool cy0 = t.vy0 && ly >= 0 && ly < TILE_W, cy1 = t.vy1 && ly + 1 >= 0 && ly + 1 < TILE_W;
-    if (!((cx0 || cx1) && (cy0 || cy1))) return 1;
+    if (!((cx0 || cx1) && (cy0 || cy1))) return;
     const float e = 1.f - t.wx, s_ = 1.f - t.wy;                        // sample_plane's weights, same products
     const float w00 = s_ * e, w01 = s_ * t.wx, w10 = t.wy * e, w11 = t.wy * t.wx;
     const int p00 = ly * TILE_W + lx;
@@ -743,11 +696,41 @@ __device__ __forceinline__ int scatter_candidate(const GatherStage& st, float* _
     if (cx1 && cy0) { atomicAdd(&a0[p00 + 1], g0 * w01); atomicAdd(&a1[p00 + 1], g1 * w01); atomicAdd(&a2[p00 + 1], g2 * w01); }
     if (cx0 && cy1) { atomicAdd(&a0[p00 + TILE_W], g0 * w10); atomicAdd(&a1[p00 + TILE_W], g1 * w10); atomicAdd(&a2[p00 + TILE_W], g2 * w10); }
     if (cx1 && cy1) { atomicAdd(&a0[p00 + TILE_W + 1], g0 * w11); atomicAdd(&a1[p00 + TILE_W + 1], g1 * w11); atomicAdd(&a2[p00 + TILE_W + 1], g2 * w11); }
-    return 2;
 }
 
-// all contributions to the 16 x 16 source tile at (tx0, ty0) (source-window coordinates); thread t returns the sums of its own
-// source pixel (tx0 + (t & 15), ty0 + (t >> 4)).  Must be called by all 256 threads of the block.
+// the candidates of rectangle r into the accumulator planes a0 / a1 / a2: thread `tid` of the STRIDE that share the tile takes
+// k = tid + STRIDE j, j ascending
+template <int STRIDE>
+__device__ __forceinline__ void scatter_rect(const GatherStage& st, const TileRects& tr, int r, int tid, float* __restrict__ a0,
+                                             float* __restrict__ a1, float* __restrict__ a2, int tx0, int ty0) {
+    constexpr int U = 4;                 // candidates per thread per trip: their 16 loads are in flight together
+    const size_t plane = (size_t)st.Hd * st.Wd;
+    const float ua = tr.ua[r], ub = tr.ub[r], va = tr.va[r], vb = tr.vb[r];
+    const int bx0 = tr.x0[r], by0 = tr.y0[r], bw = tr.bw[r], cnt = tr.cnt[r];
+    const float ibw = 1.f / (float)bw;
+    for (int k0 = tid; k0 < cnt; k0 += STRIDE * U) {
+        float2 q[U]; float g0[U], g1[U], g2[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const int k = k0 + STRIDE * j;
+            q[j] = make_float2(-INFINITY, -INFINITY);         // fails every rectangle test
+            g0[j] = g1[j] = g2[j] = 0.f;
+            if (k < cnt) {
+                int ky = (int)((float)k * ibw);                // k / bw without the integer division (cnt < 2^23; corrected below)
+                int kx = k - ky * bw;
+                if (kx < 0) { --ky; kx += bw; } else if (kx >= bw) { ++ky; kx -= bw; }
+                const size_t o = (size_t)(by0 + ky) * st.Wd + (bx0 + kx);
+                q[j] = st.uv[o];
+                g0[j] = st.g[o]; g1[j] = st.g[plane + o]; g2[j] = st.g[2 * plane + o];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < U; ++j) scatter_candidate(st, a0, a1, a2, tx0, ty0, ua, ub, va, vb, q[j], g0[j], g1[j], g2[j]);
+    }
+}
+
+// form 0: all contributions to the 16 x 16 source tile at (tx0, ty0) (source-window coordinates); thread t returns the sums of
+// its own source pixel (tx0 + (t & 15), ty0 + (t >> 4)).  Must be called by all 256 threads of the block.
 __device__ __forceinline__ void scatter_tile(const GatherStage& st, const StageMap& sm, TileScatter& ts, int tx0, int ty0, float (&out)[3]) {
     const int tid = threadIdx.x, wave = tid >> 6;
     if (tid == 0) {
@@ -762,76 +745,26 @@ __device__ __forceinline__ void scatter_tile(const GatherStage& st, const StageM
                 for (int i = 0; i < nx; ++i) {
                     int x0, x1, y0, y1;
                     if (!preimage_box(sm, xa[i], xb[i], ya[j], yb[j], st.Wd, st.Hd, x0, x1, y0, y1)) continue;
-                    ts.ua[n] = xa[i]; ts.ub[n] = xb[i]; ts.va[n] = ya[j]; ts.vb[n] = yb[j];
-                    ts.x0[n] = x0; ts.y0[n] = y0; ts.bw[n] = x1 - x0 + 1; ts.cnt[n] = (x1 - x0 + 1) * (y1 - y0 + 1);
+                    ts.rect.ua[n] = xa[i]; ts.rect.ub[n] = xb[i]; ts.rect.va[n] = ya[j]; ts.rect.vb[n] = yb[j];
+                    ts.rect.x0[n] = x0; ts.rect.y0[n] = y0; ts.rect.bw[n] = x1 - x0 + 1; ts.rect.cnt[n] = (x1 - x0 + 1) * (y1 - y0 + 1);
                     ++n;
                 }
         }
         ts.nrect = n;
-        if (st.dbg) {
-            unsigned long long tot = 0;
-            for (int r = 0; r < n; ++r) tot += (unsigned long long)ts.cnt[r];
-            atomicAdd(&st.dbg[0], tot);
-            atomicAdd(&st.dbg[1], (unsigned long long)n);
-        }
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c)
 #pragma unroll
         for (int w = 0; w < 4; ++w) ts.acc[w][c][tid] = 0.f;
     __syncthreads();
-    const size_t plane = (size_t)st.Hd * st.Wd;
     const int nrect = ts.nrect;
-    float* a0 = ts.acc[wave][0]; float* a1 = ts.acc[wave][1]; float* a2 = ts.acc[wave][2];
-    constexpr int U = 4;                 // candidates per thread per trip: their 16 loads are in flight together
-    int n_in = 0, n_tap = 0;
-    for (int r = 0; r < nrect; ++r) {
-        const float ua = ts.ua[r], ub = ts.ub[r], va = ts.va[r], vb = ts.vb[r];
-        const int bx0 = ts.x0[r], by0 = ts.y0[r], bw = ts.bw[r], cnt = ts.cnt[r];
-        const float ibw = 1.f / (float)bw;
-        for (int k0 = tid; k0 < cnt; k0 += 256 * U) {
-            float2 q[U]; float g0[U], g1[U], g2[U];
-#pragma unroll
-            for (int j = 0; j < U; ++j) {
-                const int k = k0 + 256 * j;
-                q[j] = make_float2(-INFINITY, -INFINITY);         // fails every rectangle test
-                g0[j] = g1[j] = g2[j] = 0.f;
-                if (k < cnt) {
-                    int ky = (int)((float)k * ibw);                // k / bw without the integer division (cnt < 2^23; corrected below)
-                    int kx = k - ky * bw;
-                    if (kx < 0) { --ky; kx += bw; } else if (kx >= bw) { ++ky; kx -= bw; }
-                    const size_t o = (size_t)(by0 + ky) * st.Wd + (bx0 + kx);
-                    q[j] = st.uv[o];
-                    g0[j] = st.g[o]; g1[j] = st.g[plane + o]; g2[j] = st.g[2 * plane + o];
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < U; ++j) {
-                const int code = scatter_candidate(st, a0, a1, a2, tx0, ty0, ua, ub, va, vb, q[j], g0[j], g1[j], g2[j]);
-                n_in += code >= 1; n_tap += code == 2;
-            }
-        }
-    }
-    if (st.dbg) { atomicAdd(&st.dbg[2], (unsigned long long)n_in); atomicAdd(&st.dbg[3], (unsigned long long)n_tap); }
+    for (int r = 0; r < nrect; ++r) scatter_rect<256>(st, ts.rect, r, tid, ts.acc[wave][0], ts.acc[wave][1], ts.acc[wave][2], tx0, ty0);
     __syncthreads();
 #pragma unroll
     for (int c = 0; c < 3; ++c) out[c] = ((ts.acc[0][c][tid] + ts.acc[1][c][tid]) + ts.acc[2][c][tid]) + ts.acc[3][c][tid];
 }
 
-// ---- the same, ONE WAVE per tile ---------------------------------------------------------------------------------------
-// Measured (profiles/r03_cfg1_kernel_stats.csv): with 256-thread blocks the two scatter kernels still took 170-190 us, the
-// same with and without precomputed stage maps and unrolled loads -- a tile has only ~350 candidates (1.4 trips of 256
-// lanes), so a block's life is its serial chain: descriptor words -> rectangles by one lane -> barrier -> loads -> LDS adds ->
-// barrier -> store, ~10 us, with 6 blocks resident per CU.  One wave per tile quadruples the tiles in flight per CU, needs
-// no workgroup barrier at all (the wave's own LDS traffic is ordered), computes the <= 9 rectangle boxes on 9 lanes in
-// parallel, and is reproducible by construction: one accumulator, fixed candidate order, in-order LDS.
-struct WaveScatter {
-    float ua[MAXR * MAXR], ub[MAXR * MAXR], va[MAXR * MAXR], vb[MAXR * MAXR];
-    int x0[MAXR * MAXR], y0[MAXR * MAXR], bw[MAXR * MAXR], cnt[MAXR * MAXR];
-    float acc[3][TILE_W * TILE_W];
-};
-
-// lane l returns the sums of source pixels l, l + 64, l + 128, l + 192 of the tile (row-major 16 x 16)
+// form 1: lane l returns the sums of source pixels l, l + 64, l + 128, l + 192 of the tile (row-major 16 x 16)
 __device__ __forceinline__ void scatter_tile_wave(const GatherStage& st, const StageMap& sm, WaveScatter& ts, int tx0, int ty0, float (&out)[4][3]) {
     const int lane = threadIdx.x & 63;
 #pragma unroll
@@ -853,43 +786,19 @@ __device__ __forceinline__ void scatter_tile_wave(const GatherStage& st, const S
                 const float va = j == 0 ? ya[0] : (j == 1 ? ya[1] : ya[2]), vb = j == 0 ? yb[0] : (j == 1 ? yb[1] : yb[2]);
                 int x0, x1, y0, y1;
                 if (preimage_box(sm, ua, ub, va, vb, st.Wd, st.Hd, x0, x1, y0, y1)) {
-                    ts.ua[lane] = ua; ts.ub[lane] = ub; ts.va[lane] = va; ts.vb[lane] = vb;
-                    ts.x0[lane] = x0; ts.y0[lane] = y0; ts.bw[lane] = x1 - x0 + 1;
+                    ts.rect.ua[lane] = ua; ts.rect.ub[lane] = ub; ts.rect.va[lane] = va; ts.rect.vb[lane] = vb;
+                    ts.rect.x0[lane] = x0; ts.rect.y0[lane] = y0; ts.rect.bw[lane] = x1 - x0 + 1;
                     cnt = (x1 - x0 + 1) * (y1 - y0 + 1);
                 }
             }
         }
-        ts.cnt[lane] = cnt;
+        ts.rect.cnt[lane] = cnt;
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0): the wave's LDS writes above are visible to its reads below
     __builtin_amdgcn_wave_barrier();             // no instruction: keeps the compiler from moving LDS traffic across (the attention kernels' idiom)
-    const size_t plane = (size_t)st.Hd * st.Wd;
-    constexpr int U = 4;
     for (int r = 0; r < MAXR * MAXR; ++r) {
-        const int cnt = ts.cnt[r];
-        if (cnt == 0) continue;
-        const float ua = ts.ua[r], ub = ts.ub[r], va = ts.va[r], vb = ts.vb[r];
-        const int bx0 = ts.x0[r], by0 = ts.y0[r], bw = ts.bw[r];
-        const float ibw = 1.f / (float)bw;
-        for (int k0 = lane; k0 < cnt; k0 += 64 * U) {
-            float2 q[U]; float g0[U], g1[U], g2[U];
-#pragma unroll
-            for (int j = 0; j < U; ++j) {
-                const int k = k0 + 64 * j;
-                q[j] = make_float2(-INFINITY, -INFINITY);
-                g0[j] = g1[j] = g2[j] = 0.f;
-                if (k < cnt) {
-                    int ky = (int)((float)k * ibw);
-                    int kx = k - ky * bw;
-                    if (kx < 0) { --ky; kx += bw; } else if (kx >= bw) { ++ky; kx -= bw; }
-                    const size_t o = (size_t)(by0 + ky) * st.Wd + (bx0 + kx);
-                    q[j] = st.uv[o];
-                    g0[j] = st.g[o]; g1[j] = st.g[plane + o]; g2[j] = st.g[2 * plane + o];
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < U; ++j) scatter_candidate(st, ts.acc[0], ts.acc[1], ts.acc[2], tx0, ty0, ua, ub, va, vb, q[j], g0[j], g1[j], g2[j]);
-        }
+        if (ts.rect.cnt[r] == 0) continue;
+        scatter_rect<64>(st, ts.rect, r, lane, ts.acc[0], ts.acc[1], ts.acc[2], tx0, ty0);
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();
@@ -928,113 +837,6 @@ __global__ __launch_bounds__(256) void uv_kernel(const double* __restrict__ desc
         float u, v;
         project(m, gtype, (int)(pix % Wd), (int)(pix / Wd), Wd, Hd, Ws, Hs, u, v);
         uv[(size_t)n * plane + pix] = make_float2(u, v);
-    }
-}
-
-// Stage A backward: g[n][3][Ha][Wa] -> per-cutout private source-gradient planes gsrc[n][3][Hs][Ws] (every element written;
-// summed over n afterwards by reduce_planes_kernel in a fixed order)
-__global__ __launch_bounds__(256) void warp_a_bwd_kernel(const float* __restrict__ g, int Hs, int Ws,
-                                                         const double* __restrict__ desc, const float2* __restrict__ uv,
-                                                         float* __restrict__ gsrc, int n_cut, int Ha, int Wa) {
-    __shared__ StageMap sm;
-    __shared__ TileStage ts;
-    const int tiles = (Ws + TILE_W - 1) / TILE_W;
-    const int n = blockIdx.y;
-    const int tx0 = (blockIdx.x % tiles) * TILE_W, ty0 = (blockIdx.x / tiles) * TILE_W;
-    const int sx = tx0 + (threadIdx.x & 15);
-    const int sy = ty0 + (threadIdx.x >> 4);
-    const bool live = sx < Ws && sy < Hs;
-    const double* d = desc + (size_t)n * DESC_WORDS;
-    const int mode = (int)d[D_MODE1];
-    const size_t plane = (size_t)Ha * Wa, splane = (size_t)Hs * Ws;
-    const float* gi = g + (size_t)n * 3 * plane;
-    float* gs = gsrc + (size_t)n * 3 * splane + (size_t)sy * Ws + sx;
-    if (mode == MODE_IDENT) {      // 1:1 copy (Ha x Wa == Hs x Ws)
-        if (live) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) gs[(size_t)c * splane] = gi[(size_t)c * plane + (size_t)sy * Wa + sx];
-        }
-        return;
-    }
-    if (threadIdx.x == 0) build_stage_map(sm, d + D_M1, (int)d[D_GRID1], Wa, Ha, Ws, Hs);
-    __syncthreads();
-    GatherStage st{d + D_M1, (int)d[D_GRID1], mode, Wa, Ha, Ws, Hs, gi, uv + (size_t)n * plane};
-    float o[3];
-    gather_tile(st, sm, ts, tx0, ty0, sx, sy, live, o);
-    if (live) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) gs[(size_t)c * splane] = o[c];
-    }
-}
-
-// the same in the tile-owned scatter form (scatter_tile)
-__global__ __launch_bounds__(256) void warp_a_bwd2_kernel(const float* __restrict__ g, int Hs, int Ws,
-                                                          const double* __restrict__ desc, const float2* __restrict__ uv,
-                                                          const StageMap* __restrict__ maps, float* __restrict__ gsrc, int n_cut, int Ha, int Wa,
-                                                          unsigned long long* dbg) {
-    __shared__ TileScatter ts;
-    const int tiles = (Ws + TILE_W - 1) / TILE_W;
-    const int n = blockIdx.y;
-    const int tx0 = (blockIdx.x % tiles) * TILE_W, ty0 = (blockIdx.x / tiles) * TILE_W;
-    const int sx = tx0 + (threadIdx.x & 15);
-    const int sy = ty0 + (threadIdx.x >> 4);
-    const bool live = sx < Ws && sy < Hs;
-    const double* d = desc + (size_t)n * DESC_WORDS;
-    const int mode = (int)d[D_MODE1];
-    const size_t plane = (size_t)Ha * Wa, splane = (size_t)Hs * Ws;
-    const float* gi = g + (size_t)n * 3 * plane;
-    float* gs = gsrc + (size_t)n * 3 * splane + (size_t)sy * Ws + sx;
-    if (mode == MODE_IDENT) {
-        if (live) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) gs[(size_t)c * splane] = gi[(size_t)c * plane + (size_t)sy * Wa + sx];
-        }
-        return;
-    }
-    const StageMap sm = maps[n];          // uniform address: scalar loads
-    GatherStage st{d + D_M1, (int)d[D_GRID1], mode, Wa, Ha, Ws, Hs, gi, uv + (size_t)n * plane, dbg};
-    float o[3];
-    scatter_tile(st, sm, ts, tx0, ty0, o);
-    if (live) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) gs[(size_t)c * splane] = o[c];
-    }
-}
-
-// one wave per tile (scatter_tile_wave)
-__global__ __launch_bounds__(64) void warp_a_bwd3_kernel(const float* __restrict__ g, int Hs, int Ws,
-                                                         const double* __restrict__ desc, const float2* __restrict__ uv,
-                                                         const StageMap* __restrict__ maps, float* __restrict__ gsrc, int n_cut, int Ha, int Wa) {
-    __shared__ WaveScatter ts;
-    const int tiles = (Ws + TILE_W - 1) / TILE_W;
-    const int n = blockIdx.y;
-    const int tx0 = (blockIdx.x % tiles) * TILE_W, ty0 = (blockIdx.x / tiles) * TILE_W;
-    const int lane = threadIdx.x;
-    const double* d = desc + (size_t)n * DESC_WORDS;
-    const int mode = (int)d[D_MODE1];
-    const size_t plane = (size_t)Ha * Wa, splane = (size_t)Hs * Ws;
-    const float* gi = g + (size_t)n * 3 * plane;
-    float* gs = gsrc + (size_t)n * 3 * splane;
-    if (mode == MODE_IDENT) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int p = lane + 64 * j, sx = tx0 + (p & 15), sy = ty0 + (p >> 4);
-            if (sx < Ws && sy < Hs)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) gs[(size_t)c * splane + (size_t)sy * Ws + sx] = gi[(size_t)c * plane + (size_t)sy * Wa + sx];
-        }
-        return;
-    }
-    const StageMap sm = maps[n];
-    GatherStage st{d + D_M1, (int)d[D_GRID1], mode, Wa, Ha, Ws, Hs, gi, uv + (size_t)n * plane};
-    float o[4][3];
-    scatter_tile_wave(st, sm, ts, tx0, ty0, o);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int p = lane + 64 * j, sx = tx0 + (p & 15), sy = ty0 + (p >> 4);
-        if (sx < Ws && sy < Hs)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) gs[(size_t)c * splane + (size_t)sy * Ws + sx] = o[j][c];
     }
 }
 
@@ -1155,118 +957,99 @@ __global__ __launch_bounds__(256) void warp_b_jac_kernel(const float* __restrict
     }
 }
 
-// pass 2 (source-parallel gather): ga[n][3][Ha][Wa], every element written (zero outside the stage-B source window)
-__global__ __launch_bounds__(256) void warp_b_bwd_kernel(int Ha, int Wa, const double* __restrict__ desc, const float* __restrict__ g,
-                                                         const float* __restrict__ grgb, const float2* __restrict__ uv,
-                                                         float* __restrict__ ga, int n_cut, int S) {
-    __shared__ StageMap sm;
-    __shared__ TileStage ts;
-    const size_t plane = (size_t)S * S, aplane = (size_t)Ha * Wa;
-    const int tiles = (Wa + TILE_W - 1) / TILE_W;
+// ---- warp backward: one kernel, three forms, two stages ----------------------------------------------------------------
+// A block owns a 16 x 16 tile of SOURCE pixels of one cutout (grid: tiles of the output image x cutouts) and writes every
+// gradient element of it exactly once; how the tile collects its contributions is the FORM:
+//
+//   FORM 2, per-pixel gather (round 2): every source pixel enumerates its own pre-image boxes (gather_pixel) and sums in a
+//     fixed order; the block stages its tile's direct pre-image in LDS once (TileStage).  It spends ~1-2 k instructions of
+//     pre-image geometry per source pixel before it touches a candidate (0.54 ms per iteration at the headline: 10x its HBM
+//     bound).  Builds its stage map in LDS on thread 0; needs no maps buffer.
+//
+//   FORM 0, workgroup scatter (round 3, what the product runs): same ownership, coarser granularity.  The workgroup works out
+//     the raw-coordinate rectangles / destination boxes ONCE for the tile (one lane, compacted) and then runs
+//     DESTINATION-parallel over the candidates -- each lane takes one destination pixel, rebuilds the forward's own four taps
+//     (make_taps on the stored raw coordinate: same roundings, exact adjoint) and adds the taps that fall inside the tile into
+//     an LDS accumulator.  No global atomics, no memsets, and still bit-reproducible:
+//       * candidates are visited in a fixed order (rectangle by rectangle, k = thread id + 256 j);
+//       * each of the block's 4 waves has its OWN accumulator plane, so no two waves ever add to the same word; within a wave
+//         the additions of one ds_add_f32 instruction are serialised by the LDS in a fixed lane order, and instructions
+//         retire in program order;
+//       * the four planes are summed in wave order at the end.
+//     Uniqueness / completeness as in the gather: the tile's raw rectangles are pairwise disjoint and a candidate is counted
+//     in the rectangle that contains its raw coordinate; acceptance is by the exact taps, the boxes only bound the search.
+//
+//   FORM 1, one WAVE per tile.  Measured (profiles/r03_cfg1_kernel_stats.csv): with 256-thread blocks the two scatter kernels
+//     still took 170-190 us, the same with and without precomputed stage maps and unrolled loads -- a tile has only ~350
+//     candidates (1.4 trips of 256 lanes), so a block's life is its serial chain: descriptor words -> rectangles by one lane ->
+//     barrier -> loads -> LDS adds -> barrier -> store, ~10 us, with 6 blocks resident per CU.  One wave per tile quadruples
+//     the tiles in flight per CU, needs no workgroup barrier at all (the wave's own LDS traffic is ordered), computes the <= 9
+//     rectangle boxes on 9 lanes in parallel, and is reproducible by construction: one accumulator, fixed candidate order,
+//     in-order LDS.  It did not move the time either (the figures stand above the host launcher).
+//
+// Forms 0 and 1 read the cutout's stage map from maps[n] (stage_map_kernel) through a uniform address.
+//
+// The STAGE picks the descriptor words, the planes and the source window; the two stages are the same computation:
+//   STAGE 1 (A): g[n][3][Hd][Wd] on the stage-A plane -> per-cutout private source-gradient planes out[n][3][Ho][Wo] (summed
+//     over n afterwards by reduce_planes_kernel in a fixed order); the window is the whole source image; grgb is not read.
+//   STAGE 2 (B): the gradient on the S x S cutout (Wd = Hd = S; grgb where the cutout has ColorJitter, its Jacobian already
+//     applied by warp_b_jac_kernel, else g) -> out[n][3][Ho][Wo] on the stage-A plane, through the descriptor's source window;
+//     in-image elements outside the window are written as zeros.
+template <int FORM, int STAGE>
+__global__ __launch_bounds__(FORM == 1 ? 64 : 256) void warp_bwd_kernel(const double* __restrict__ desc, const float* __restrict__ g,
+                                                                        const float* __restrict__ grgb, const float2* __restrict__ uv,
+                                                                        const StageMap* __restrict__ maps, float* __restrict__ out,
+                                                                        int Wd, int Hd, int Wo, int Ho) {
+    constexpr int NT = FORM == 1 ? 64 : 256;       // threads of the block
+    constexpr int PPT = TILE_W * TILE_W / NT;      // tile pixels a thread owns: p = threadIdx.x + NT j
     const int n = blockIdx.y;
-    const int ax0 = (blockIdx.x % tiles) * TILE_W, ay0 = (blockIdx.x / tiles) * TILE_W;
-    const int ax = ax0 + (threadIdx.x & 15);      // stage-A image coordinates
-    const int ay = ay0 + (threadIdx.x >> 4);
-    const bool inimg = ax < Wa && ay < Ha;
     const double* d = desc + (size_t)n * DESC_WORDS;
-    const int mode = (int)d[D_MODE2];
-    const SrcWin q = src_window(d);
-    const int sx = ax - q.ox, sy = ay - q.oy;                                // coordinates inside the source window
-    const bool live = inimg && sx >= 0 && sx < q.ww && sy >= 0 && sy < q.wh;
-    const float* gi = (d[D_JIT] != 0.0 ? grgb : g) + (size_t)n * 3 * plane;
-    float* go = ga + (size_t)n * 3 * aplane + (size_t)ay * Wa + ax;
-    float o[3] = {0.f, 0.f, 0.f};
-    if (mode == MODE_IDENT) {      // output pixel (x, y) copies window pixel (x, y)
-        if (live && sx < S && sy < S) {
+    const int mode = (int)d[STAGE == 1 ? D_MODE1 : D_MODE2];
+    // source window inside the output image (stage A: all of it, so the window tests below are compile-time true)
+    const int ox = STAGE == 1 ? 0 : (int)d[D_WOX], oy = STAGE == 1 ? 0 : (int)d[D_WOY];
+    const int ww = STAGE == 1 ? Wo : (int)d[D_WW], wh = STAGE == 1 ? Ho : (int)d[D_WH];
+    const auto in_window = [&](int sx, int sy) { return STAGE == 1 || (sx >= 0 && sx < ww && sy >= 0 && sy < wh); };
+    const size_t plane = (size_t)Hd * Wd, oplane = (size_t)Ho * Wo;
+    const float* gi = (STAGE == 2 && d[D_JIT] != 0.0 ? grgb : g) + (size_t)n * 3 * plane;
+    float* go = out + (size_t)n * 3 * oplane;
+    const int tiles = (Wo + TILE_W - 1) / TILE_W;
+    const int ax0 = (blockIdx.x % tiles) * TILE_W, ay0 = (blockIdx.x / tiles) * TILE_W;     // the tile, output-image coordinates
+    float o[PPT][3];
+    if (mode == MODE_IDENT) {      // destination pixel (x, y) copied window pixel (x, y)
 #pragma unroll
-            for (int c = 0; c < 3; ++c) o[c] = gi[(size_t)c * plane + (size_t)sy * S + sx];
+        for (int j = 0; j < PPT; ++j) {
+            const int p = threadIdx.x + NT * j, ax = ax0 + (p & 15), ay = ay0 + (p >> 4), sx = ax - ox, sy = ay - oy;
+            const bool live = ax < Wo && ay < Ho && in_window(sx, sy) && sx < Wd && sy < Hd;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[j][c] = live ? gi[(size_t)c * plane + (size_t)sy * Wd + sx] : 0.f;
         }
     } else {
-        if (threadIdx.x == 0) build_stage_map(sm, d + D_M2, (int)d[D_GRID2], S, S, q.ww, q.wh);
-        __syncthreads();
-        GatherStage st{d + D_M2, (int)d[D_GRID2], mode, S, S, q.ww, q.wh, gi, uv + (size_t)n * plane};
-        gather_tile(st, sm, ts, ax0 - q.ox, ay0 - q.oy, sx, sy, live, o);
-    }
-    if (inimg) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) go[(size_t)c * aplane] = o[c];
-    }
-}
-
-// pass 2 in the tile-owned scatter form (scatter_tile)
-__global__ __launch_bounds__(256) void warp_b_bwd2_kernel(int Ha, int Wa, const double* __restrict__ desc, const float* __restrict__ g,
-                                                          const float* __restrict__ grgb, const float2* __restrict__ uv,
-                                                          const StageMap* __restrict__ maps, float* __restrict__ ga, int n_cut, int S,
-                                                          unsigned long long* dbg) {
-    __shared__ TileScatter ts;
-    const size_t plane = (size_t)S * S, aplane = (size_t)Ha * Wa;
-    const int tiles = (Wa + TILE_W - 1) / TILE_W;
-    const int n = blockIdx.y;
-    const int ax0 = (blockIdx.x % tiles) * TILE_W, ay0 = (blockIdx.x / tiles) * TILE_W;
-    const int ax = ax0 + (threadIdx.x & 15);
-    const int ay = ay0 + (threadIdx.x >> 4);
-    const bool inimg = ax < Wa && ay < Ha;
-    const double* d = desc + (size_t)n * DESC_WORDS;
-    const int mode = (int)d[D_MODE2];
-    const SrcWin q = src_window(d);
-    const int sx = ax - q.ox, sy = ay - q.oy;
-    const bool live = inimg && sx >= 0 && sx < q.ww && sy >= 0 && sy < q.wh;
-    const float* gi = (d[D_JIT] != 0.0 ? grgb : g) + (size_t)n * 3 * plane;
-    float* go = ga + (size_t)n * 3 * aplane + (size_t)ay * Wa + ax;
-    float o[3] = {0.f, 0.f, 0.f};
-    if (mode == MODE_IDENT) {
-        if (live && sx < S && sy < S) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) o[c] = gi[(size_t)c * plane + (size_t)sy * S + sx];
+        const GatherStage st{mode, Wd, Hd, ww, wh, gi, uv + (size_t)n * plane};
+        const int tx0 = ax0 - ox, ty0 = ay0 - oy;                                             // the tile, window coordinates
+        if constexpr (FORM == 2) {
+            __shared__ StageMap sm;
+            __shared__ TileStage ts;
+            if (threadIdx.x == 0) build_stage_map(sm, d + (STAGE == 1 ? D_M1 : D_M2), (int)d[STAGE == 1 ? D_GRID1 : D_GRID2], Wd, Hd, ww, wh);
+            __syncthreads();
+            const int ax = ax0 + (threadIdx.x & 15), ay = ay0 + (threadIdx.x >> 4), sx = ax - ox, sy = ay - oy;
+            gather_tile(st, sm, ts, tx0, ty0, sx, sy, ax < Wo && ay < Ho && in_window(sx, sy), o[0]);
+        } else if constexpr (FORM == 0) {
+            __shared__ TileScatter ts;
+            const StageMap sm = maps[n];          // uniform address: scalar loads
+            scatter_tile(st, sm, ts, tx0, ty0, o[0]);
+        } else {
+            __shared__ WaveScatter ts;
+            const StageMap sm = maps[n];
+            scatter_tile_wave(st, sm, ts, tx0, ty0, o);
         }
-    } else {
-        const StageMap sm = maps[n];
-        GatherStage st{d + D_M2, (int)d[D_GRID2], mode, S, S, q.ww, q.wh, gi, uv + (size_t)n * plane, dbg ? dbg + 4 : nullptr};
-        scatter_tile(st, sm, ts, ax0 - q.ox, ay0 - q.oy, o);
-        if (!live) { o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; }
-    }
-    if (inimg) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) go[(size_t)c * aplane] = o[c];
-    }
-}
-
-// one wave per tile (scatter_tile_wave)
-__global__ __launch_bounds__(64) void warp_b_bwd3_kernel(int Ha, int Wa, const double* __restrict__ desc, const float* __restrict__ g,
-                                                         const float* __restrict__ grgb, const float2* __restrict__ uv,
-                                                         const StageMap* __restrict__ maps, float* __restrict__ ga, int n_cut, int S) {
-    __shared__ WaveScatter ts;
-    const size_t plane = (size_t)S * S, aplane = (size_t)Ha * Wa;
-    const int tiles = (Wa + TILE_W - 1) / TILE_W;
-    const int n = blockIdx.y;
-    const int ax0 = (blockIdx.x % tiles) * TILE_W, ay0 = (blockIdx.x / tiles) * TILE_W;
-    const int lane = threadIdx.x;
-    const double* d = desc + (size_t)n * DESC_WORDS;
-    const int mode = (int)d[D_MODE2];
-    const SrcWin q = src_window(d);
-    const float* gi = (d[D_JIT] != 0.0 ? grgb : g) + (size_t)n * 3 * plane;
-    float* go = ga + (size_t)n * 3 * aplane;
-    float o[4][3];
-    if (mode == MODE_IDENT) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int p = lane + 64 * j, ax = ax0 + (p & 15), ay = ay0 + (p >> 4), sx = ax - q.ox, sy = ay - q.oy;
-            const bool live = ax < Wa && ay < Ha && sx >= 0 && sx < q.ww && sy >= 0 && sy < q.wh && sx < S && sy < S;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) o[j][c] = live ? gi[(size_t)c * plane + (size_t)sy * S + sx] : 0.f;
-        }
-    } else {
-        const StageMap sm = maps[n];
-        GatherStage st{d + D_M2, (int)d[D_GRID2], mode, S, S, q.ww, q.wh, gi, uv + (size_t)n * plane};
-        scatter_tile_wave(st, sm, ts, ax0 - q.ox, ay0 - q.oy, o);
     }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int p = lane + 64 * j, ax = ax0 + (p & 15), ay = ay0 + (p >> 4), sx = ax - q.ox, sy = ay - q.oy;
-        if (!(ax < Wa && ay < Ha)) continue;
-        const bool live = sx >= 0 && sx < q.ww && sy >= 0 && sy < q.wh;
+    for (int j = 0; j < PPT; ++j) {
+        const int p = threadIdx.x + NT * j, ax = ax0 + (p & 15), ay = ay0 + (p >> 4);
+        if (!(ax < Wo && ay < Ho)) continue;
+        const bool live = in_window(ax - ox, ay - oy);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) go[(size_t)c * aplane + (size_t)ay * Wa + ax] = live ? o[j][c] : 0.f;
+        for (int c = 0; c < 3; ++c) go[(size_t)c * oplane + (size_t)ay * Wo + ax] = live ? o[j][c] : 0.f;
     }
 }
 
@@ -1488,40 +1271,36 @@ __global__ __launch_bounds__(256) void patchify_bwd_apply_kernel(const float* __
 
 }  // namespace
 
-// PRX_CUTOUT_BWD=gather: the round-2 per-pixel gather kernels instead of the tile-owned scatter (A/B measurements)
-static bool cutout_bwd_gather() {
-    static const bool v = [] { const char* e = getenv("PRX_CUTOUT_BWD"); return e && e[0] == 'g'; }();
-    return v;
-}
-
-// PRX_CUTOUT_DBG=1: count the scatter's work (candidates visited / inside their rectangle / contributing) per stage and print
-// the totals when the process exits (diagnostic; adds global atomics, so do not time with it on)
-static unsigned long long* cutout_dbg() {
-    static unsigned long long* buf = [] () -> unsigned long long* {
-        const char* e = getenv("PRX_CUTOUT_DBG");
-        if (!(e && e[0] == '1')) return nullptr;
-        void* p = nullptr;
-        if (hipMalloc(&p, 8 * sizeof(unsigned long long)) != hipSuccess || hipMemset(p, 0, 8 * sizeof(unsigned long long)) != hipSuccess) return nullptr;
-        static unsigned long long* keep = (unsigned long long*)p;
-        atexit([] {
-            unsigned long long h[8];
-            if (hipMemcpy(h, keep, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess)
-                fprintf(stderr, "[prx cutout scatter] stage A: visited %llu rects %llu in-rect %llu contributing %llu | stage B: visited %llu rects %llu in-rect %llu contributing %llu\n",
-                        h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
-        });
-        return keep;
-    }();
-    return buf;
-}
-
+// The form of the warp backward, 0 = workgroup scatter, 1 = one-wave scatter, 2 = per-pixel gather: what the caller names, or
+// for -1 (the product) what PRX_CUTOUT_BWD says, read once per process: g... = gather, w... = wave, else the workgroup scatter.
 // The scatter runs one tile per 256-thread workgroup (per-wave accumulator planes) by default; PRX_CUTOUT_BWD=wave selects the
 // one-wave-per-tile form.  Measured at the headline (profiles/r03_cfg1_kernel_stats.csv, r03b): stage B / stage A
 // 187 / 170 us (workgroup), 209 / 184 us (wave), 150 / 255 us (round-2 gather): neither more tiles in flight nor the removed
 // barriers and serial set-up moved it -- what is left is the ~12 conflicting ds_add_f32 per candidate (4 taps x 3 channels,
 // neighbouring destination pixels share taps), i.e. the LDS atomic rate.
-static bool cutout_bwd_block() {
-    static const bool v = [] { const char* e = getenv("PRX_CUTOUT_BWD"); return !(e && e[0] == 'w'); }();
-    return v;
+static int cutout_bwd_form(int form) {
+    static const int env = [] { const char* e = getenv("PRX_CUTOUT_BWD"); return !e ? 0 : e[0] == 'g' ? 2 : e[0] == 'w' ? 1 : 0; }();
+    return form < 0 ? env : form;
+}
+
+// the tile pass of one stage in the resolved form (0, 1, 2): the destination plane is Wd x Hd, the output image Wo x Ho;
+// `maps` holds n_cut stage maps for forms 0 and 1 (written here) and is not touched by form 2
+template <int STAGE>
+static int launch_warp_bwd(int form, const double* desc, const float* g, const float* grgb, const float2* uv, StageMap* maps, float* out,
+                           int n_cut, int Wd, int Hd, int Wo, int Ho, hipStream_t s) {
+    const dim3 grid(((Wo + TILE_W - 1) / TILE_W) * ((Ho + TILE_W - 1) / TILE_W), n_cut);
+    if (form == 2)
+        hipLaunchKernelGGL((warp_bwd_kernel<2, STAGE>), grid, dim3(256), 0, s, desc, g, grgb, uv, nullptr, out, Wd, Hd, Wo, Ho);
+    else {
+        hipLaunchKernelGGL(stage_map_kernel, dim3(ceil_div(n_cut, 64)), dim3(64), 0, s, desc, STAGE, maps, n_cut, Wd, Hd, Wo, Ho);
+        PRX_LAUNCH_CHECK();
+        if (form == 0)
+            hipLaunchKernelGGL((warp_bwd_kernel<0, STAGE>), grid, dim3(256), 0, s, desc, g, grgb, uv, maps, out, Wd, Hd, Wo, Ho);
+        else
+            hipLaunchKernelGGL((warp_bwd_kernel<1, STAGE>), grid, dim3(64), 0, s, desc, g, grgb, uv, maps, out, Wd, Hd, Wo, Ho);
+    }
+    PRX_LAUNCH_CHECK();
+    return 0;
 }
 
 int prx_pool_fwd(const float* img, float* pooled, int* argmax, const unsigned char* mask, int C, int H, int W, int S, hipStream_t s) {
@@ -1546,29 +1325,14 @@ int prx_warp_a_bwd(const float* g, int Hs, int Ws, const double* desc, float* uv
     // gsrc_priv: [n_cut][3][Hs][Ws] per-cutout private planes (scratch, every element written); gsrc: [3][Hs][Ws] their sum
     // form: -1 = PRX_CUTOUT_BWD decides (the product), 0 = workgroup scatter, 1 = one-wave scatter, 2 = per-pixel gather
     PRX_REQUIRE(form >= -1 && form <= 2, "warp_a_bwd: form is not one of -1, 0, 1, 2");
-    const bool gather = form < 0 ? cutout_bwd_gather() : form == 2;
-    const bool block = form < 0 ? cutout_bwd_block() : form == 0;
+    form = cutout_bwd_form(form);
     // the per-cutout stage maps (16 floats each) live in `gsrc` until reduce_planes_kernel overwrites it with the result
     // (refused before anything is launched: a refusal writes nothing)
-    if (!gather)
+    if (form != 2)
         PRX_REQUIRE((size_t)n_cut * sizeof(StageMap) <= (size_t)3 * Hs * Ws * sizeof(float), "warp_a_bwd: too many cutouts for the stage-map scratch");
-    const int tx = (Ws + TILE_W - 1) / TILE_W, ty = (Hs + TILE_W - 1) / TILE_W;
     hipLaunchKernelGGL(uv_kernel, dim3(std::min(ew_grid((size_t)Ha * Wa), 64), n_cut), dim3(256), 0, s, desc, 1, (float2*)uv, Wa, Ha, Ws, Hs);
     PRX_LAUNCH_CHECK();
-    if (gather)
-        hipLaunchKernelGGL(warp_a_bwd_kernel, dim3(tx * ty, n_cut), dim3(256), 0, s, g, Hs, Ws, desc, (const float2*)uv, gsrc_priv, n_cut,
-                           Ha, Wa);
-    else {
-        hipLaunchKernelGGL(stage_map_kernel, dim3(ceil_div(n_cut, 64)), dim3(64), 0, s, desc, 1, (StageMap*)gsrc, n_cut, Wa, Ha, Ws, Hs);
-        PRX_LAUNCH_CHECK();
-        if (block)
-            hipLaunchKernelGGL(warp_a_bwd2_kernel, dim3(tx * ty, n_cut), dim3(256), 0, s, g, Hs, Ws, desc, (const float2*)uv, (const StageMap*)gsrc,
-                               gsrc_priv, n_cut, Ha, Wa, cutout_dbg());
-        else
-            hipLaunchKernelGGL(warp_a_bwd3_kernel, dim3(tx * ty, n_cut), dim3(64), 0, s, g, Hs, Ws, desc, (const float2*)uv, (const StageMap*)gsrc,
-                               gsrc_priv, n_cut, Ha, Wa);
-    }
-    PRX_LAUNCH_CHECK();
+    if (int rc = launch_warp_bwd<1>(form, desc, g, nullptr, (const float2*)uv, (StageMap*)gsrc, gsrc_priv, n_cut, Wa, Ha, Ws, Hs, s)) return rc;
     hipLaunchKernelGGL(reduce_planes_kernel, dim3(ew_grid((size_t)3 * Hs * Ws)), dim3(256), 0, s, gsrc_priv, gsrc, n_cut,
                        (size_t)3 * Hs * Ws);
     PRX_LAUNCH_CHECK();
@@ -1586,32 +1350,17 @@ int prx_warp_b_bwd(const float* a, int Ha, int Wa, const double* desc, const flo
     // grgb: [n_cut][3][S][S] scratch (the gradient pulled back through the ColorJitter); uv: [n_cut][S*S][2] scratch;
     // ga: [n_cut][3][Ha][Wa], every element written; form: as for prx_warp_a_bwd
     PRX_REQUIRE(form >= -1 && form <= 2, "warp_b_bwd: form is not one of -1, 0, 1, 2");
-    const bool gather = form < 0 ? cutout_bwd_gather() : form == 2;
-    const bool block = form < 0 ? cutout_bwd_block() : form == 0;
+    form = cutout_bwd_form(form);
     // maps_scratch: any buffer of >= n_cut stage maps that nothing else touches until this launch has finished
     // (refused before anything is launched: a refusal writes nothing)
-    if (!gather)
+    if (form != 2)
         PRX_REQUIRE(maps_scratch != nullptr && (size_t)n_cut * sizeof(StageMap) <= maps_scratch_bytes, "warp_b_bwd: stage-map scratch too small");
     hipLaunchKernelGGL(uv_kernel, dim3(std::min(ew_grid((size_t)S * S), 64), n_cut), dim3(256), 0, s, desc, 2, (float2*)uv, S, S, 0, 0);
     PRX_LAUNCH_CHECK();
     hipLaunchKernelGGL(warp_b_jac_kernel, dim3(std::min(ew_grid((size_t)S * S), 64), n_cut), dim3(256), 0, s, a, Ha, Wa, desc, g, grgb,
                        n_cut, S);
     PRX_LAUNCH_CHECK();
-    const int tx = (Wa + TILE_W - 1) / TILE_W, ty = (Ha + TILE_W - 1) / TILE_W;
-    if (gather)
-        hipLaunchKernelGGL(warp_b_bwd_kernel, dim3(tx * ty, n_cut), dim3(256), 0, s, Ha, Wa, desc, g, grgb, (const float2*)uv, ga, n_cut, S);
-    else {
-        hipLaunchKernelGGL(stage_map_kernel, dim3(ceil_div(n_cut, 64)), dim3(64), 0, s, desc, 2, (StageMap*)maps_scratch, n_cut, S, S, 0, 0);
-        PRX_LAUNCH_CHECK();
-        if (block)
-            hipLaunchKernelGGL(warp_b_bwd2_kernel, dim3(tx * ty, n_cut), dim3(256), 0, s, Ha, Wa, desc, g, grgb, (const float2*)uv,
-                               (const StageMap*)maps_scratch, ga, n_cut, S, cutout_dbg());
-        else
-            hipLaunchKernelGGL(warp_b_bwd3_kernel, dim3(tx * ty, n_cut), dim3(64), 0, s, Ha, Wa, desc, g, grgb, (const float2*)uv,
-                               (const StageMap*)maps_scratch, ga, n_cut, S);
-    }
-    PRX_LAUNCH_CHECK();
-    return 0;
+    return launch_warp_bwd<2>(form, desc, g, grgb, (const float2*)uv, (StageMap*)maps_scratch, ga, n_cut, S, S, Wa, Ha, s);
 }
 int prx_rescale_fwd(const float* pooled, float* base, int C, int S, int Hb, int Wb, hipStream_t s) {
     hipLaunchKernelGGL(rescale_fwd_kernel, dim3(ew_grid((size_t)C * Hb * Wb)), dim3(256), 0, s, pooled, base, C, S, Hb, Wb);

@@ -688,10 +688,11 @@ def test_clip_torchscript_archive_adapter(tmp_path):
     assert set(checkpoints.clip_state_dict_from_archive(plain)) == {"visual." + k for k in vis}
 
 
-def _kernel_scratch(src: str, obj: str = None):
+def _kernel_scratch(src: str, obj: str = None, flags=()):
     """[(kernel name, scratch bytes per lane)] of every gfx950 kernel of a .hip source.  Read from the object file the build
     left beside it (the AMDGPU metadata note of the device code object inside its fat binary: a second or two) when that object
-    is newer than the source and every header; otherwise the source is compiled with the resource remarks on (minutes)."""
+    is newer than the source and every header; otherwise the source is compiled with the resource remarks on (minutes) and
+    `flags`, the extra flags csrc/Makefile gives this file."""
     import glob
     import re
     import shutil
@@ -718,7 +719,7 @@ def _kernel_scratch(src: str, obj: str = None):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
-    out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", src, "-o", os.devnull,
+    out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", *flags, "-c", src, "-o", os.devnull,
                           "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     names = re.findall(r"Function Name: (\S+)", out.stderr)
@@ -739,6 +740,17 @@ def test_gemm_engine_kernels_have_no_scratch():
         assert len(kernels) >= at_least
         bad = [(n, s) for n, s in kernels if s != 0]
         assert not bad, bad
+
+
+def test_cutout_warp_backward_kernels_have_no_scratch():
+    """warp_bwd_kernel<FORM, STAGE> builds its per-stage view (descriptor words, planes, source window) in registers and hands
+    it to the tile helpers by reference; a view that went to memory would cost the product kernels their speed with every
+    parity test green.  All six instances (three forms x two stages) must come out of the compiler without scratch."""
+    src = os.path.join(os.path.dirname(HERE), "pixray_amd", "csrc", "cutouts.hip")
+    kernels = [(n, s) for n, s in _kernel_scratch(src, flags=("-ffp-contract=off", "-fno-slp-vectorize")) if "warp_bwd" in n]
+    assert len(kernels) >= 6, kernels
+    bad = [(n, s) for n, s in kernels if s != 0]
+    assert not bad, bad
 
 
 def test_custom_backward_last_is_the_same_gradient():
