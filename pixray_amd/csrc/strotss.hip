@@ -328,7 +328,7 @@ int prx_strotss_remd_bwd(const float* G, int ldg, const float* X, int ldx, const
                          const float* g_out, void* workspace, long long workspace_bytes, float* dX, int lddx, hipStream_t s) {
     PRX_REQUIRE(G && X && Y && xs && ys && rowpack && colpack && stats && g_out && dX && workspace, "strotss remd bwd: NULL argument");
     PRX_REQUIRE(n >= 1 && m >= 1 && d >= 1 && d <= REMD_DMAX && ldg >= m && ldx >= d && ldy >= d && lddx >= d,
-                "strotss remd bwd: bad shape n=%d m=%d d=%d (d <= %d)", n, m, d, REMD_DMAX);
+                "strotss remd bwd: bad shape n=%d m=%d d=%d (d <= %d) ldg=%d ldx=%d ldy=%d lddx=%d", n, m, d, REMD_DMAX, ldg, ldx, ldy, lddx);
     PRX_REQUIRE(workspace_bytes >= prx_strotss_remd_bwd_workspace_bytes(n, m, d) && ((uintptr_t)workspace & 15) == 0,
                 "strotss remd bwd: workspace of %lld bytes, 16-byte aligned, needed", prx_strotss_remd_bwd_workspace_bytes(n, m, d));
     int* cnt = (int*)workspace;

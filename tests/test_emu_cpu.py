@@ -35,11 +35,12 @@ def emu():
         import test_kernels_half_gpu as th
         import test_kernels_runner_gpu as tr
         import test_kernels_cutouts_gpu as tc
+        import test_kernels_strotss_gpu as ts
         import test_path_gpu as tp
-        for m in (tk, th, tr, tc, tp):
+        for m in (tk, th, tr, tc, ts, tp):
             m.DEV = "cpu"
-        yield types_ns(lib=lib, tk=tk, th=th, tr=tr, tc=tc, tp=tp)
-        for m in (tk, th, tr, tc, tp):
+        yield types_ns(lib=lib, tk=tk, th=th, tr=tr, tc=tc, ts=ts, tp=tp)
+        for m in (tk, th, tr, tc, ts, tp):
             m.DEV = "cuda"
 
 
@@ -240,6 +241,15 @@ def test_strotss_and_hypercolumn_kernels(emu):
     emu.tk.test_strotss_relaxed_emd_kernels_match_the_composed_torch_expression(300, 777, False)
     emu.tk.test_strotss_relaxed_emd_kernels_match_the_composed_torch_expression(640, 200, True)
     emu.tk.test_hypercolumns_match_the_composed_torch_expression()
+
+
+def test_strotss_and_hypercolumn_kernels_one_stage_at_a_time(emu):
+    """tests/test_kernels_strotss_gpu.py on the emulated kernels: the chunk-edge selection of the relaxed-EMD backward (cosine and cosine + L2
+    with pairs below, above and on the clamp bounds), the match scan across column 16384, the scan carry at n = 2085, the worst-case
+    workspace at exactly its documented size, the minima pass with planted gaps and exact ties, the refusals, one self-similarity case and
+    the 12-map hyper-column case, each against float64"""
+    figs = emu.ts.emu_subset()
+    assert any(k.startswith("remd-bwd/straddle") for k in figs) and any(k.startswith("hypercol-bwd/") for k in figs)
 
 
 # ------------------------------------------------------------------------------------------------ the path's own ops
