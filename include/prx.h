@@ -717,6 +717,17 @@ int prx_symmetry_fwd_bwd(const float* x, int planes, int h, int w, float weight,
 int prx_edge_fwd_bwd(const float* x, int planes, int h, int w, float r, float g, float b, int left, int right, int upper, int lower,
                      float inv_l, float inv_r, float inv_u, float inv_d, float inv_all, float edge_weight, double* partials, float* grad,
                      float* loss, unsigned* ticket, prx_stream_t s);
+/* edge with a target image and / or a mask: as prx_edge_fwd_bwd, but the per-element target is target [3][h][w] (null: the flat
+ * colour), and with mask [h][w] (null: none) the bands are ignored and every element where mask <= 0 weighs inv_mask */
+int prx_edge_target_fwd_bwd(const float* x, int planes, int h, int w, const float* target, float r, float g, float b, const float* mask,
+                            int left, int right, int upper, int lower, float inv_l, float inv_r, float inv_u, float inv_d, float inv_mask,
+                            float inv_all, float edge_weight, double* partials, float* grad, float* loss, unsigned* ticket, prx_stream_t s);
+/* gaussian: x [planes = 3k][h][w] against colour (r, g, b), weighed |1 - gy[y] gx[c]|: loss = scale * sum a |d|, grad = scale a sign(d) */
+int prx_gaussian_fwd_bwd(const float* x, int planes, int h, int w, const float* gy, const float* gx, float r, float g, float b, float scale,
+                         double* partials, float* grad, float* loss, unsigned* ticket, prx_stream_t s);
+/* aesthetic: embeds [n][d], head w [d] + bias on the L2-normalised rows (eps 1e-12); loss = 0.02 / n * sum (rating - target)^2 */
+int prx_aesthetic_fwd_bwd(const float* embeds, int n, int d, const float* w, float bias, float target, double* partials, float* grad,
+                          float* loss, unsigned* ticket, prx_stream_t s);
 /* palette: x [n][3][hw], palette [np <= 256][3]; loss = scale * sum over pixels of |pixel - nearest entry| */
 int prx_palette_fwd_bwd(const float* x, int n, int hw, const float* palette, int np, float scale, double* partials, float* grad,
                         float* loss, unsigned* ticket, prx_stream_t s);

@@ -1,6 +1,6 @@
 // Built-in custom losses of pixray (Losses/SaturationLoss.py, SymmetryLoss.py, SmoothnessLoss.py, PaletteLoss.py,
-// EdgeLoss.py) in fp32 with fp64 accumulators.  Each loss scalar leaves its launch through plug_reduce (fixed summation order,
-// no float atomics).  Where the gradient is local (symmetry, edge, palette) the forward launch writes it too; saturation needs
+// EdgeLoss.py, GaussianLoss.py, AestheticLoss.py) in fp32 with fp64 accumulators.  Each loss scalar leaves its launch through plug_reduce (fixed summation order,
+// no float atomics).  Where the gradient is local (symmetry, edge, gaussian, aesthetic, palette) the forward launch writes it too; saturation needs
 // the batch statistics first and smoothness a neighbourhood of per-pixel factors, so they take a second, elementwise launch.
 #include "plugin_losses.h"
 #include "../../include/prx.h"
@@ -100,6 +100,103 @@ __global__ __launch_bounds__(PLUG_THREADS) void edge_kernel(const float* __restr
         grad[e] = 2.f * edge_weight * a * d;
     }
     if (plug_reduce<1>(v, partials, ticket)) *loss = (float)(v[0] * (double)edge_weight);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- edge, target image / mask
+// edge_kernel with a per-element target (target [3][h][w], or the flat colour where it is null) and an optional mask [h][w]:
+// with a mask the bands are ignored and every element where mask <= 0 weighs inv_mask (EdgeLoss.py:100-103: the masked-in part
+// is replaced by the target, so it adds nothing).  Both pointers are kernel arguments: wave-uniform branches.
+__global__ __launch_bounds__(PLUG_THREADS) void edge_target_kernel(const float* __restrict__ x, int planes, int h, int w,
+                                                                   const float* __restrict__ target, float cr, float cg, float cb,
+                                                                   const float* __restrict__ mask, int left, int right, int upper,
+                                                                   int lower, float inv_l, float inv_r, float inv_u, float inv_d,
+                                                                   float inv_mask, float inv_all, float edge_weight,
+                                                                   double* __restrict__ partials, float* __restrict__ grad,
+                                                                   float* __restrict__ loss, unsigned* __restrict__ ticket) {
+    const long long N = (long long)planes * h * w;
+    const long long hw = (long long)h * w;
+    double v[1] = {0.0};
+    for (long long e = (long long)blockIdx.x * PLUG_THREADS + threadIdx.x; e < N; e += (long long)gridDim.x * PLUG_THREADS) {
+        const long long pl = e / hw;
+        const int rem = (int)(e - pl * hw), y = rem / w, c = rem - y * w;
+        const int ch = (int)(pl % 3);
+        const float tgt = target ? target[(size_t)ch * hw + rem] : (ch == 0 ? cr : (ch == 1 ? cg : cb));
+        float a = inv_all;
+        if (mask) {
+            if (mask[rem] <= 0.f) a += inv_mask;
+        } else {
+            if (c < left) a += inv_l;
+            if (c >= w - right) a += inv_r;
+            if (c >= left && c < w - right) {
+                if (y < upper) a += inv_u;
+                if (y >= h - lower) a += inv_d;
+            }
+        }
+        const float d = x[e] - tgt;
+        v[0] += (double)a * ((double)d * d);
+        grad[e] = 2.f * edge_weight * a * d;
+    }
+    if (plug_reduce<1>(v, partials, ticket)) *loss = (float)(v[0] * (double)edge_weight);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- gaussian
+// GaussianLoss.py: x [planes = 3k][h][w] against a flat colour, each element weighed a = |1 - gy[y] gx[c]| (the outer product of
+// two 1-D gaussian tables, rounded to fp32 before the subtraction as torch.outer does): loss = scale * sum a |d|,
+// grad = scale a sign(d), sign(0) = 0 (torch.abs's subgradient)
+__global__ __launch_bounds__(PLUG_THREADS) void gaussian_kernel(const float* __restrict__ x, int planes, int h, int w,
+                                                                const float* __restrict__ gy, const float* __restrict__ gx, float cr,
+                                                                float cg, float cb, float scale, double* __restrict__ partials,
+                                                                float* __restrict__ grad, float* __restrict__ loss,
+                                                                unsigned* __restrict__ ticket) {
+    const long long N = (long long)planes * h * w;
+    const long long hw = (long long)h * w;
+    double v[1] = {0.0};
+    for (long long e = (long long)blockIdx.x * PLUG_THREADS + threadIdx.x; e < N; e += (long long)gridDim.x * PLUG_THREADS) {
+        const long long pl = e / hw;
+        const int rem = (int)(e - pl * hw), y = rem / w, c = rem - y * w;
+        const int ch = (int)(pl % 3);
+        const float col = ch == 0 ? cr : (ch == 1 ? cg : cb);
+        const float a = fabsf(1.f - __fmul_rn(gy[y], gx[c]));
+        const float d = x[e] - col;
+        v[0] += (double)a * (double)fabsf(d);
+        grad[e] = d > 0.f ? scale * a : (d < 0.f ? -(scale * a) : 0.f);
+    }
+    if (plug_reduce<1>(v, partials, ticket)) *loss = (float)(v[0] * (double)scale);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- aesthetic
+// AestheticLoss.py: a linear head on the normalised embeddings, r_i = w . e_i / max(|e_i|, 1e-12) + bias (F.normalize's eps),
+// loss = 0.02 / n * sum_i (r_i - target)^2.  One wave per row, lanes stride over d; both row sums in double through wave_sum_d.
+// grad[i][j] = 0.04 / n * diff_i * (w[j] inv_i - e[i][j] dot_i inv_i^3) above the eps floor; at or below it the divisor is the
+// constant 1e-12 and only the first term remains.  The row loop is wave-uniform and every thread reaches plug_reduce.
+__global__ __launch_bounds__(PLUG_THREADS) void aesthetic_kernel(const float* __restrict__ embeds, int n, int d,
+                                                                 const float* __restrict__ w, float bias, float target,
+                                                                 double* __restrict__ partials, float* __restrict__ grad,
+                                                                 float* __restrict__ loss, unsigned* __restrict__ ticket) {
+    constexpr int ROWS = PLUG_THREADS / 64;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const double gs = 0.04 / (double)n;
+    double v[1] = {0.0};
+    for (long long row = (long long)blockIdx.x * ROWS + wid; row < n; row += (long long)gridDim.x * ROWS) {
+        const float* e = embeds + (size_t)row * d;
+        double ss = 0.0, dot = 0.0;
+        for (int j = lane; j < d; j += 64) {
+            const double ej = (double)e[j];
+            ss += ej * ej;
+            dot += (double)w[j] * ej;
+        }
+        ss = wave_sum_d(ss);
+        dot = wave_sum_d(dot);
+        const double nrm = sqrt(ss);
+        const bool floor_ = nrm <= 1e-12;
+        const double inv = 1.0 / (floor_ ? 1e-12 : nrm);
+        const double diff = dot * inv + (double)bias - (double)target;
+        const double ga = gs * diff * inv, gb = floor_ ? 0.0 : gs * diff * dot * inv * inv * inv;
+        float* g = grad + (size_t)row * d;
+        for (int j = lane; j < d; j += 64) g[j] = (float)(ga * (double)w[j] - gb * (double)e[j]);
+        if (lane == 0) v[0] += diff * diff;
+    }
+    if (plug_reduce<1>(v, partials, ticket)) *loss = (float)(v[0] * 0.02 / (double)n);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- palette
@@ -306,6 +403,32 @@ int plug_edge(const float* x, int planes, int h, int w, float r, float g, float 
     PRX_LAUNCH_CHECK();
     return 0;
 }
+int plug_edge_target(const float* x, int planes, int h, int w, const float* target, float r, float g, float b, const float* mask,
+                     int left, int right, int upper, int lower, float inv_l, float inv_r, float inv_u, float inv_d, float inv_mask,
+                     float inv_all, float edge_weight, double* partials, float* grad, float* loss, unsigned* ticket, hipStream_t s) {
+    PRX_REQUIRE(x && partials && grad && loss && ticket && planes > 0 && planes % 3 == 0 && h > 0 && w > 0, "edge (target): bad arguments");
+    PRX_REQUIRE(left >= 0 && right >= 0 && upper >= 0 && lower >= 0, "edge (target): negative margins");
+    hipLaunchKernelGGL(edge_target_kernel, dim3(plug_blocks((long long)planes * h * w)), dim3(PLUG_THREADS), 0, s, x, planes, h, w, target, r, g, b, mask,
+                       left, right, upper, lower, inv_l, inv_r, inv_u, inv_d, inv_mask, inv_all, edge_weight, partials, grad, loss, ticket);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+int plug_gaussian(const float* x, int planes, int h, int w, const float* gy, const float* gx, float r, float g, float b, float scale,
+                  double* partials, float* grad, float* loss, unsigned* ticket, hipStream_t s) {
+    PRX_REQUIRE(x && gy && gx && partials && grad && loss && ticket && planes > 0 && planes % 3 == 0 && h > 0 && w > 0, "gaussian: bad arguments");
+    hipLaunchKernelGGL(gaussian_kernel, dim3(plug_blocks((long long)planes * h * w)), dim3(PLUG_THREADS), 0, s, x, planes, h, w, gy, gx, r, g, b, scale,
+                       partials, grad, loss, ticket);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+int plug_aesthetic(const float* embeds, int n, int d, const float* w, float bias, float target, double* partials, float* grad, float* loss,
+                   unsigned* ticket, hipStream_t s) {
+    PRX_REQUIRE(embeds && w && partials && grad && loss && ticket && n >= 1 && d >= 1, "aesthetic: bad arguments");
+    hipLaunchKernelGGL(aesthetic_kernel, dim3(plug_blocks((long long)n * 64)), dim3(PLUG_THREADS), 0, s, embeds, n, d, w, bias, target, partials, grad,
+                       loss, ticket);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
 int plug_palette(const float* x, int n, int hw, const float* palette, int np, float scale, double* partials, float* grad, float* loss,
                  unsigned* ticket, hipStream_t s) {
     PRX_REQUIRE(x && palette && partials && grad && loss && ticket && n > 0 && hw > 0, "palette: bad arguments");
@@ -364,6 +487,20 @@ int prx_edge_fwd_bwd(const float* x, int planes, int h, int w, float r, float g,
                      float* loss, unsigned* ticket, prx_stream_t s) {
     return plug_edge(x, planes, h, w, r, g, b, left, right, upper, lower, inv_l, inv_r, inv_u, inv_d, inv_all, edge_weight, partials,
                      grad, loss, ticket, S_(s));
+}
+int prx_edge_target_fwd_bwd(const float* x, int planes, int h, int w, const float* target, float r, float g, float b, const float* mask,
+                            int left, int right, int upper, int lower, float inv_l, float inv_r, float inv_u, float inv_d, float inv_mask,
+                            float inv_all, float edge_weight, double* partials, float* grad, float* loss, unsigned* ticket, prx_stream_t s) {
+    return plug_edge_target(x, planes, h, w, target, r, g, b, mask, left, right, upper, lower, inv_l, inv_r, inv_u, inv_d, inv_mask, inv_all,
+                            edge_weight, partials, grad, loss, ticket, S_(s));
+}
+int prx_gaussian_fwd_bwd(const float* x, int planes, int h, int w, const float* gy, const float* gx, float r, float g, float b, float scale,
+                         double* partials, float* grad, float* loss, unsigned* ticket, prx_stream_t s) {
+    return plug_gaussian(x, planes, h, w, gy, gx, r, g, b, scale, partials, grad, loss, ticket, S_(s));
+}
+int prx_aesthetic_fwd_bwd(const float* embeds, int n, int d, const float* w, float bias, float target, double* partials, float* grad,
+                          float* loss, unsigned* ticket, prx_stream_t s) {
+    return plug_aesthetic(embeds, n, d, w, bias, target, partials, grad, loss, ticket, S_(s));
 }
 int prx_palette_fwd_bwd(const float* x, int n, int hw, const float* palette, int np, float scale, double* partials, float* grad,
                         float* loss, unsigned* ticket, prx_stream_t s) {

@@ -967,6 +967,18 @@ def symmetry_loss(out, weight=1.0):
     return _LocalGradLossFn.apply(out, launch)
 
 
+def _edge_bands(n, c, h, w, margins, what):
+    """(left, right, upper, lower) pixel margins -> (ints, 1 / band elements per band, 0 where the band is off)"""
+    left, right, upper, lower = (int(m) for m in margins)
+    inner = max(0, (w - right) - left)
+    bands = (n * c * h * max(0, min(left, w)), n * c * h * max(0, min(right, w)), n * c * max(0, min(upper, h)) * inner,
+             n * c * max(0, min(lower, h)) * inner)
+    for m, cnt in zip((left, right, upper, lower), bands):
+        if m != 0 and cnt == 0:
+            raise PrxError(f"{what}: margins {margins} leave an empty band on a {h} x {w} image")
+    return (left, right, upper, lower), [1.0 / cnt if m != 0 else 0.0 for m, cnt in zip((left, right, upper, lower), bands)]
+
+
 def edge_loss(out, color, margins, edge_weight, global_weight):
     """EdgeLoss (flat colour, no mask image): `margins` = (left, right, upper, lower) in PIXELS"""
     _need_cuda(out)
@@ -974,14 +986,7 @@ def edge_loss(out, color, margins, edge_weight, global_weight):
     n, c, h, w = x.shape
     if c != 3:
         raise PrxError("edge_loss: expected 3 channels")
-    left, right, upper, lower = (int(m) for m in margins)
-    inner = max(0, (w - right) - left)
-    bands = (n * c * h * max(0, min(left, w)), n * c * h * max(0, min(right, w)), n * c * max(0, min(upper, h)) * inner,
-             n * c * max(0, min(lower, h)) * inner)
-    for m, cnt in zip((left, right, upper, lower), bands):
-        if m != 0 and cnt == 0:
-            raise PrxError(f"edge_loss: margins {margins} leave an empty band on a {h} x {w} image")
-    inv = [1.0 / cnt if m != 0 else 0.0 for m, cnt in zip((left, right, upper, lower), bands)]
+    (left, right, upper, lower), inv = _edge_bands(n, c, h, w, margins, "edge_loss")
     inv_all = float(global_weight) / x.numel() if global_weight else 0.0
 
     def launch():
@@ -990,6 +995,79 @@ def edge_loss(out, color, margins, edge_weight, global_weight):
              *[float(v) for v in inv], inv_all, float(edge_weight), _partials(x.device), grad, loss, _ticket(x.device), _stream())
         return loss, grad
     return _LocalGradLossFn.apply(out, launch)
+
+
+def edge_target_loss(out, target, color, mask, margins, edge_weight, global_weight):
+    """EdgeLoss with `--edge_input_image` / `--edge_mask_image`: `target` a [1, 3, H, W] (or [3, H, W]) fp32 device tensor or
+    None (then the flat `color`), `mask` a [H, W] (any leading 1s) fp32 device tensor or None.  Without a mask the four margin
+    bands (`margins` in PIXELS) are scored against the target; with one they are skipped and every element where mask <= 0 is
+    scored, mean over ALL elements.  Plus global_weight * MSE over the image, all times edge_weight."""
+    _need_cuda(out)
+    x = _f32_nchw(out, "edge_target_loss")
+    n, c, h, w = x.shape
+    if c != 3:
+        raise PrxError("edge_target_loss: expected 3 channels")
+    for t, name, numel in ((target, "target", 3 * h * w), (mask, "mask", h * w)):
+        if t is None:
+            continue
+        _need_cuda(t)
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel or tuple(t.shape[-2:]) != (h, w) or t.device != x.device:
+            raise PrxError(f"edge_target_loss: {name} must be a contiguous fp32 tensor of {numel} elements ending in ({h}, {w}) on "
+                           f"{x.device}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+    if mask is None:
+        (left, right, upper, lower), inv = _edge_bands(n, c, h, w, margins, "edge_target_loss")
+    else:
+        (left, right, upper, lower), inv = (0, 0, 0, 0), [0.0, 0.0, 0.0, 0.0]
+    inv_mask = 1.0 / x.numel() if mask is not None else 0.0
+    inv_all = float(global_weight) / x.numel() if global_weight else 0.0
+
+    def launch():
+        grad, loss = torch.empty_like(x), torch.empty((), device=x.device)
+        call("prx_edge_target_fwd_bwd", x, n * c, h, w, target, float(color[0]), float(color[1]), float(color[2]), mask, left, right,
+             upper, lower, *[float(v) for v in inv], inv_mask, inv_all, float(edge_weight), _partials(x.device), grad, loss,
+             _ticket(x.device), _stream())
+        return loss, grad
+    return _LocalGradLossFn.apply(out, launch)
+
+
+def gaussian_loss(out, gy, gx, color01, weight=1.0):
+    """GaussianLoss: mean(|out - colour| * |1 - gy (x) gx|) * weight.  `gy` [H], `gx` [W]: fp32 device tables; `color01` in [0, 1]"""
+    _need_cuda(out, gy, gx)
+    x = _f32_nchw(out, "gaussian_loss")
+    n, c, h, w = x.shape
+    if c != 3:
+        raise PrxError("gaussian_loss: expected 3 channels")
+    for t, name, numel in ((gy, "gy", h), (gx, "gx", w)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (numel,) or t.device != x.device:
+            raise PrxError(f"gaussian_loss: {name} must be a contiguous fp32 [{numel}] tensor on {x.device}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+    scale = float(weight) / x.numel()
+
+    def launch():
+        grad, loss = torch.empty_like(x), torch.empty((), device=x.device)
+        call("prx_gaussian_fwd_bwd", x, n * c, h, w, gy, gx, float(color01[0]), float(color01[1]), float(color01[2]), scale,
+             _partials(x.device), grad, loss, _ticket(x.device), _stream())
+        return loss, grad
+    return _LocalGradLossFn.apply(out, launch)
+
+
+def aesthetic_loss(embeds, weight, bias, target):
+    """AestheticLoss: 0.02 * mean((linear(normalize(embeds), weight, bias) - target)^2).  `embeds` [n, d] fp32, `weight` a
+    [d] (or [1, d]) fp32 device tensor, `bias` and `target` floats"""
+    _need_cuda(embeds, weight)
+    if embeds.dim() != 2 or embeds.dtype != torch.float32 or embeds.shape[0] < 1 or embeds.shape[1] < 1:
+        raise PrxError(f"aesthetic_loss: expected an fp32 [n, d] tensor, got {tuple(embeds.shape)} {embeds.dtype}")
+    x = embeds.contiguous()
+    n, d = x.shape
+    if weight.dtype != torch.float32 or not weight.is_contiguous() or weight.numel() != d or weight.device != x.device:
+        raise PrxError(f"aesthetic_loss: weight must be a contiguous fp32 tensor of {d} elements on {x.device}, got "
+                       f"{tuple(weight.shape)} {weight.dtype} on {weight.device}")
+
+    def launch():
+        grad, loss = torch.empty_like(x), torch.empty((), device=x.device)
+        call("prx_aesthetic_fwd_bwd", x, n, d, weight, float(bias), float(target), _partials(x.device), grad, loss,
+             _ticket(x.device), _stream())
+        return loss, grad
+    return _LocalGradLossFn.apply(embeds, launch)
 
 
 def palette_loss(cutouts, palette, weight=1.0):

@@ -11,8 +11,10 @@ as `custom_losses=` and the `lossGlobals` dict handed to every `get_loss` call.
 reference's `pixel` drawer on the HIP rasteriser, the nearest-upsampled pixel grid that stands in for its `fast_pixel`, and its
 `line_sketch` and `clipdraw` stroke drawers on the HIP stroke rasteriser); `filters_class_table` holds the reference's three
 filters (`lookup`, `tiler`, `wallpaper`: builtin_filters.py) and `loss_class_table` its losses (`style`: style_loss.py;
-`palette`, `saturation`, `symmetry`, `smoothness`, `edge`: builtin_losses.py), all on HIP kernels.  `resmem` and
-`aesthetic` are registered so that asking for them says why they are unavailable (their model weights are not shipped).
+`palette`, `saturation`, `symmetry`, `smoothness`, `edge` -- with `--edge_input_image` / `--edge_mask_image` -- and `aesthetic`,
+whose linear head is read from the file `--aesthetic_model` names: builtin_losses.py), all on HIP kernels.  `resmem` is
+registered so that asking for it says why it is unavailable (its network is not shipped and cannot be loaded here).
+`builtin_losses.GaussianLoss` has no registry name, as in the reference: `add_custom_loss("gaussian", GaussianLoss)`.
 Further plugins register through `add_custom_filter` / `add_custom_loss`; the reference's own plain-torch plugin files drop
 in unchanged that way (see tests/test_host_logic.py::test_unmodified_reference_plugins_drop_in)."""
 from typing import Dict, List, Tuple
