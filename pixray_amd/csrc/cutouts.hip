@@ -219,9 +219,32 @@ __device__ __forceinline__ float coverage(const Taps& t) {
 // gray fill of the uncovered part of the bilinear footprint (kornia's `padding_mode="fill"`: zeros padding + (1 - warp(ones)) * fill).
 // Branch-free on purpose: hipcc miscompiled the `mode == MODE_FILL ? ... : 0` form of this inside warp_b_fwd_kernel (the
 // divergent select clobbered live tap-pointer registers; MODE_ZEROS was fine, MODE_FILL returned garbage).
-__device__ __forceinline__ float fill_term(const Taps& t, int mode, const double* d) {
-    const float fillv = (mode == MODE_FILL) ? (float)d[D_FILL] : 0.f;
+// `fillv` is the cutout's gray level under MODE_FILL and 0 otherwise (StageWords below: block-uniform, read once per block).
+__device__ __forceinline__ float fill_term(const Taps& t, float fillv) {
     return (1.f - coverage(t)) * fillv;
+}
+// the words of one stage that depend only on the cutout, read ONCE per block through a block-uniform address (the cutout index
+// is blockIdx.y in every destination-parallel kernel below): scalar loads into scalar registers, instead of ~20 fp64 loads per
+// pixel through a per-lane address
+struct StageWords {
+    double m[9];         // the stage's matrix
+    int mode, gtype;
+    float fillv;         // fill_term's factor: the gray level under MODE_FILL, else 0 (a uniform select, outside the pixel loop)
+};
+__device__ __forceinline__ StageWords stage_words(const double* d, int stage) {
+    StageWords w;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) w.m[k] = d[(stage == 1 ? D_M1 : D_M2) + k];
+    w.mode = (int)d[stage == 1 ? D_MODE1 : D_MODE2];
+    w.gtype = (int)d[stage == 1 ? D_GRID1 : D_GRID2];
+    w.fillv = (w.mode == MODE_FILL) ? (float)d[D_FILL] : 0.f;
+    return w;
+}
+// the in-plane pixel index of a destination-parallel kernel: 32 bits (the hosts refuse planes of 2^31 elements or more), one
+// division per pixel -- the flat size_t index over all cutouts cost three 64-bit divisions per pixel
+__device__ __forceinline__ void pixel_xy(unsigned pix, unsigned W, int& x, int& y) {
+    const unsigned yy = pix / W;
+    y = (int)yy; x = (int)(pix - yy * W);
 }
 // ------------------------------------------------------------------ ColorJitter (HSV) with duals
 template <int ND>
@@ -351,25 +374,30 @@ __device__ __forceinline__ void jitter_d(Dual<ND> (&rgb)[3], float sat, float hu
 __global__ __launch_bounds__(256) void warp_a_fwd_kernel(const float* __restrict__ src, int Hs, int Ws,
                                                          const double* __restrict__ desc, float* __restrict__ out,
                                                          int n_cut, int Ha, int Wa) {
-    const size_t plane = (size_t)Ha * Wa;
-    const size_t total = (size_t)n_cut * plane;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (size_t)gridDim.x * blockDim.x) {
-        const int x = (int)(idx % Wa), y = (int)((idx / Wa) % Ha), n = (int)(idx / plane);
-        const double* d = desc + (size_t)n * DESC_WORDS;
-        const int mode = (int)d[D_MODE1];
-        float* o = out + ((size_t)n * 3) * plane + (size_t)y * Wa + x;
-        if (mode == MODE_IDENT) {
+    // grid: (blocks over the plane, cutouts).  The cutout's words are block-uniform and read once (stage_words); the pixel index
+    // runs inside the plane in 32 bits (the host refuses planes of 2^31 elements or more)
+    const int n = blockIdx.y;
+    const StageWords w = stage_words(desc + (size_t)n * DESC_WORDS, 1);
+    const unsigned plane = (unsigned)Ha * (unsigned)Wa, splane = (unsigned)Hs * (unsigned)Ws, stride = gridDim.x * blockDim.x;
+    float* on = out + (size_t)n * 3 * plane;
+    if (w.mode == MODE_IDENT) {
+        for (unsigned pix = blockIdx.x * blockDim.x + threadIdx.x; pix < plane; pix += stride) {
+            int x, y;
+            pixel_xy(pix, (unsigned)Wa, x, y);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) o[(size_t)c * plane] = src[(size_t)c * Hs * Ws + (size_t)y * Ws + x];
-            continue;
+            for (int c = 0; c < 3; ++c) on[(size_t)c * plane + pix] = src[(size_t)c * splane + (size_t)y * Ws + x];
         }
+        return;
+    }
+    for (unsigned pix = blockIdx.x * blockDim.x + threadIdx.x; pix < plane; pix += stride) {
+        int x, y;
+        pixel_xy(pix, (unsigned)Wa, x, y);
         float u, v;
-        project(d + D_M1, (int)d[D_GRID1], x, y, Wa, Ha, Ws, Hs, u, v);
-        Taps t = make_taps(u, v, Ws, Hs, mode);
-        const float fillc = fill_term(t, mode, d);
+        project(w.m, w.gtype, x, y, Wa, Ha, Ws, Hs, u, v);
+        const Taps t = make_taps(u, v, Ws, Hs, w.mode);
+        const float fillc = fill_term(t, w.fillv);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) o[(size_t)c * plane] = sample_plane(src + (size_t)c * Hs * Ws, Ws, t) + fillc;
+        for (int c = 0; c < 3; ++c) on[(size_t)c * plane + pix] = sample_plane(src + (size_t)c * splane, Ws, t) + fillc;
     }
 }
 
@@ -808,44 +836,54 @@ __device__ __forceinline__ void scatter_tile_wave(const GatherStage& st, const S
         for (int c = 0; c < 3; ++c) out[j][c] = ts.acc[c][lane + 64 * j];
 }
 
-// the stage map of every cutout, once per stage (it is the same for all tiles of a cutout; built from fp64 it costs a single
-// lane ~3 us, which every one of the 196 tile blocks of a cutout used to spend on its own): maps[n] for stage 1 / 2
-__global__ void stage_map_kernel(const double* __restrict__ desc, int stage, StageMap* __restrict__ maps, int n_cut, int Wd, int Hd, int Ws, int Hs) {
-    const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= n_cut) return;
-    const double* d = desc + (size_t)n * DESC_WORDS;
+// The stage map of a cutout is the same for all of its tiles; built from fp64 it costs a single lane ~3 us, which every one of
+// the 196 tile blocks of a cutout used to spend on its own.  It is written once per stage by the stage's destination-parallel
+// pre-pass (uv_kernel for stage A, warp_b_jac_kernel for stage B): thread 0 of the cutout's first block, maps[n]; all zeros for
+// a MODE_IDENT cutout.  `maps == nullptr` (form 2, which builds its own in LDS): not written.
+__device__ __forceinline__ void write_stage_map(StageMap* __restrict__ maps, int n, const StageWords& w, int Wd, int Hd, int Ws, int Hs) {
+    if (maps == nullptr || blockIdx.x != 0 || threadIdx.x != 0) return;
     StageMap sm{};
-    if ((int)d[stage == 1 ? D_MODE1 : D_MODE2] != MODE_IDENT) {
-        if (stage == 2) { Ws = (int)d[D_WW]; Hs = (int)d[D_WH]; }
-        build_stage_map(sm, d + (stage == 1 ? D_M1 : D_M2), (int)d[stage == 1 ? D_GRID1 : D_GRID2], Wd, Hd, Ws, Hs);
-    }
+    if (w.mode != MODE_IDENT) build_stage_map(sm, w.m, w.gtype, Wd, Hd, Ws, Hs);
     maps[n] = sm;
 }
 
-// destination-parallel pre-pass of a gather stage: the raw source coordinate of every destination pixel, exactly as the
-// forward computed it (stage 1: D_M1 / D_GRID1 / D_MODE1 on the Ha x Wa stage-A plane; stage 2: the stage-B words on S x S)
-__global__ __launch_bounds__(256) void uv_kernel(const double* __restrict__ desc, int stage, float2* __restrict__ uv, int Wd, int Hd,
-                                                 int Ws, int Hs) {
+// destination-parallel pre-pass of the stage-A gather: the raw source coordinate of every destination pixel of the Ha x Wa stage-A
+// plane, exactly as the forward computed it (D_M1 / D_GRID1 / D_MODE1; MODE_IDENT cutouts: not written), and the cutout's stage
+// map.  Stage B's pre-pass is warp_b_jac_kernel.
+__global__ __launch_bounds__(256) void uv_kernel(const double* __restrict__ desc, float2* __restrict__ uv, StageMap* __restrict__ maps,
+                                                 int Wd, int Hd, int Ws, int Hs) {
     const int n = blockIdx.y;
-    const double* d = desc + (size_t)n * DESC_WORDS;
-    if ((int)d[stage == 1 ? D_MODE1 : D_MODE2] == MODE_IDENT) return;
-    const double* m = d + (stage == 1 ? D_M1 : D_M2);
-    const int gtype = (int)d[stage == 1 ? D_GRID1 : D_GRID2];
-    if (stage == 2) { Ws = (int)d[D_WW]; Hs = (int)d[D_WH]; }
-    const size_t plane = (size_t)Hd * Wd;
-    for (size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x; pix < plane; pix += (size_t)gridDim.x * blockDim.x) {
+    const StageWords w = stage_words(desc + (size_t)n * DESC_WORDS, 1);
+    write_stage_map(maps, n, w, Wd, Hd, Ws, Hs);
+    if (w.mode == MODE_IDENT) return;
+    const unsigned plane = (unsigned)Hd * (unsigned)Wd, stride = gridDim.x * blockDim.x;
+    float2* uvn = uv + (size_t)n * plane;
+    for (unsigned pix = blockIdx.x * blockDim.x + threadIdx.x; pix < plane; pix += stride) {
+        int x, y;
+        pixel_xy(pix, (unsigned)Wd, x, y);
         float u, v;
-        project(m, gtype, (int)(pix % Wd), (int)(pix / Wd), Wd, Hd, Ws, Hs, u, v);
-        uv[(size_t)n * plane + pix] = make_float2(u, v);
+        project(w.m, w.gtype, x, y, Wd, Hd, Ws, Hs, u, v);
+        uvn[pix] = make_float2(u, v);
     }
 }
 
-// out[i] = sum_n planes[n][i]
+// out[i] = sum_n planes[n][i], summed left to right over n: ((p0 + p1) + p2) + ...  One element per lane; the loads of RP_UNROLL
+// planes are issued before the first of their additions, so that a lane keeps RP_UNROLL requests in flight instead of one
+constexpr int RP_UNROLL = 16;
 __global__ __launch_bounds__(256) void reduce_planes_kernel(const float* __restrict__ planes, float* __restrict__ out,
                                                             int n, size_t plane_elems) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < plane_elems; i += (size_t)gridDim.x * blockDim.x) {
+        const float* p = planes + i;
         float acc = 0.f;
-        for (int k = 0; k < n; ++k) acc += planes[(size_t)k * plane_elems + i];
+        int k = 0;
+        for (; k + RP_UNROLL <= n; k += RP_UNROLL) {
+            float v[RP_UNROLL];
+#pragma unroll
+            for (int j = 0; j < RP_UNROLL; ++j) v[j] = p[(size_t)(k + j) * plane_elems];
+#pragma unroll
+            for (int j = 0; j < RP_UNROLL; ++j) acc += v[j];
+        }
+        for (; k < n; ++k) acc += p[(size_t)k * plane_elems];
         out[i] = acc;
     }
 }
@@ -887,73 +925,106 @@ __device__ __forceinline__ void philox_normal3(unsigned long long seed, unsigned
 __global__ __launch_bounds__(256) void warp_b_fwd_kernel(const float* __restrict__ a, int Ha, int Wa, const double* __restrict__ desc,
                                                          const float* __restrict__ noise, float* __restrict__ out,
                                                          int n_cut, int S) {
-    const size_t total = (size_t)n_cut * S * S;
-    const size_t plane = (size_t)S * S, aplane = (size_t)Ha * Wa;
-    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        const int x = (int)(idx % S), y = (int)((idx / S) % S), n = (int)(idx / plane);
-        const double* d = desc + (size_t)n * DESC_WORDS;
-        const int mode = (int)d[D_MODE2];
-        const SrcWin q = src_window(d);
-        const float* an = a + (size_t)n * 3 * aplane + (size_t)q.oy * Wa + q.ox;     // window origin
-        const size_t pix = (size_t)y * S + x;
+    // grid: (blocks over the S x S plane, cutouts); everything that depends only on the cutout -- padding mode, grid flavour,
+    // matrix, source window, jitter constants, noise factor, seed -- is block-uniform and read once, the pixel index is 32-bit
+    const int n = blockIdx.y;
+    const double* d = desc + (size_t)n * DESC_WORDS;
+    const StageWords w = stage_words(d, 2);
+    const SrcWin q = src_window(d);
+    const bool jit = d[D_JIT] != 0.0, sat_first = d[D_SATFIRST] != 0.0;
+    const float sat = (float)d[D_SAT], hue = (float)d[D_HUE], nf = (float)d[D_NOISE];
+    const unsigned long long seed = (unsigned long long)d[D_SEED];
+    const bool draw = !noise && nf != 0.f && d[D_SEED] != 0.0;
+    const unsigned plane = (unsigned)S * (unsigned)S, stride = gridDim.x * blockDim.x;
+    const size_t aplane = (size_t)Ha * Wa;
+    const float* an = a + (size_t)n * 3 * aplane + (size_t)q.oy * Wa + q.ox;     // window origin
+    const float* nz = noise ? noise + (size_t)n * 3 * plane : nullptr;
+    float* on = out + (size_t)n * 3 * plane;
+    for (unsigned pix = blockIdx.x * blockDim.x + threadIdx.x; pix < plane; pix += stride) {
+        int x, y;
+        pixel_xy(pix, (unsigned)S, x, y);
         Dual<0> rgb[3];
         Taps t = ident_taps(x, y);                 // MODE_IDENT: one tap of weight 1 (same code path, no divergent select)
-        if (mode != MODE_IDENT) {
+        if (w.mode != MODE_IDENT) {
             float u, v;
-            project(d + D_M2, (int)d[D_GRID2], x, y, S, S, q.ww, q.wh, u, v);
-            t = make_taps(u, v, q.ww, q.wh, mode);
+            project(w.m, w.gtype, x, y, S, S, q.ww, q.wh, u, v);
+            t = make_taps(u, v, q.ww, q.wh, w.mode);
         }
-        const float fillc = fill_term(t, mode, d);
+        const float fillc = fill_term(t, w.fillv);
 #pragma unroll
         for (int c = 0; c < 3; ++c) rgb[c].v = sample_plane(an + c * aplane, Wa, t) + fillc;
-        if (d[D_JIT] != 0.0) jitter_d<0>(rgb, (float)d[D_SAT], (float)d[D_HUE], d[D_SATFIRST] != 0.0);
-        const float nf = (float)d[D_NOISE];
-        float* o = out + (size_t)n * 3 * plane + pix;
+        if (jit) jitter_d<0>(rgb, sat, hue, sat_first);
         float zn[3] = {0.f, 0.f, 0.f};
-        if (!noise && nf != 0.f && d[D_SEED] != 0.0) philox_normal3((unsigned long long)d[D_SEED], (unsigned)pix, zn);
+        if (draw) philox_normal3(seed, pix, zn);    // counter = the pixel index y * S + x, key = the seed word
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             float v = rgb[c].v;
-            if (noise) v += nf * noise[(size_t)n * 3 * plane + c * plane + pix];
+            if (noise) v += nf * nz[(size_t)c * plane + pix];
             else v += nf * zn[c];
-            o[c * plane] = v;
+            on[(size_t)c * plane + pix] = v;
         }
     }
 }
 
-// Stage B backward, pass 1 (destination-parallel): the gradient w.r.t. the SAMPLED rgb of every output pixel, i.e. the
-// incoming gradient pulled back through the ColorJitter (forward-mode duals of kornia's rgb -> hsv -> rgb round trips).
-// Cutouts without jitter are skipped (pass 2 reads their incoming gradient directly).
+// Stage B backward, the destination-parallel pre-pass (one launch per iteration; it used to be three):
+//   * uv[n][pix] = the raw source coordinate of every destination pixel of every cutout that is not MODE_IDENT, from the same
+//     project() call with the same arguments as the forward's -- the scatter's exact-adjoint property rests on these bits;
+//   * grgb = the gradient w.r.t. the SAMPLED rgb of every output pixel of a cutout WITH ColorJitter, i.e. the incoming gradient
+//     pulled back through the jitter (forward-mode duals of kornia's rgb -> hsv -> rgb round trips), from the taps of that same
+//     coordinate: one fp64 projection per pixel serves both.  Cutouts without jitter write uv only (pass 2 reads their
+//     incoming gradient directly);
+//   * maps[n] = the cutout's stage map (write_stage_map; not for form 2).
 __global__ __launch_bounds__(256) void warp_b_jac_kernel(const float* __restrict__ a, int Ha, int Wa, const double* __restrict__ desc,
-                                                         const float* __restrict__ g, float* __restrict__ grgb, int n_cut, int S) {
-    const size_t plane = (size_t)S * S, aplane = (size_t)Ha * Wa;
+                                                         const float* __restrict__ g, float* __restrict__ grgb, float2* __restrict__ uv,
+                                                         StageMap* __restrict__ maps, int n_cut, int S) {
     const int n = blockIdx.y;
     const double* d = desc + (size_t)n * DESC_WORDS;
-    if (d[D_JIT] == 0.0) return;
-    const int mode = (int)d[D_MODE2];
+    const StageWords w = stage_words(d, 2);
     const SrcWin q = src_window(d);
-    const float* an = a + (size_t)n * 3 * aplane + (size_t)q.oy * Wa + q.ox;
-    for (size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x; pix < plane; pix += (size_t)gridDim.x * blockDim.x) {
-        const int x = (int)(pix % S), y = (int)(pix / S);
-        Taps t = ident_taps(x, y);
-        if (mode != MODE_IDENT) {
+    write_stage_map(maps, n, w, S, S, q.ww, q.wh);
+    const bool jit = d[D_JIT] != 0.0;
+    if (w.mode == MODE_IDENT && !jit) return;
+    const unsigned plane = (unsigned)S * (unsigned)S, stride = gridDim.x * blockDim.x;
+    float2* uvn = uv + (size_t)n * plane;
+    if (!jit) {
+        for (unsigned pix = blockIdx.x * blockDim.x + threadIdx.x; pix < plane; pix += stride) {
+            int x, y;
+            pixel_xy(pix, (unsigned)S, x, y);
             float u, v;
-            project(d + D_M2, (int)d[D_GRID2], x, y, S, S, q.ww, q.wh, u, v);
-            t = make_taps(u, v, q.ww, q.wh, mode);
+            project(w.m, w.gtype, x, y, S, S, q.ww, q.wh, u, v);
+            uvn[pix] = make_float2(u, v);
         }
-        const float fillc = fill_term(t, mode, d);
+        return;
+    }
+    const bool sat_first = d[D_SATFIRST] != 0.0;
+    const float sat = (float)d[D_SAT], hue = (float)d[D_HUE];
+    const size_t aplane = (size_t)Ha * Wa;
+    const float* an = a + (size_t)n * 3 * aplane + (size_t)q.oy * Wa + q.ox;
+    const float* gn = g + (size_t)n * 3 * plane;
+    float* grn = grgb + (size_t)n * 3 * plane;
+    for (unsigned pix = blockIdx.x * blockDim.x + threadIdx.x; pix < plane; pix += stride) {
+        int x, y;
+        pixel_xy(pix, (unsigned)S, x, y);
+        Taps t = ident_taps(x, y);
+        if (w.mode != MODE_IDENT) {
+            float u, v;
+            project(w.m, w.gtype, x, y, S, S, q.ww, q.wh, u, v);
+            uvn[pix] = make_float2(u, v);
+            t = make_taps(u, v, q.ww, q.wh, w.mode);
+        }
+        const float fillc = fill_term(t, w.fillv);
         Dual<3> rgb[3];
         float gin[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             rgb[c] = cst<3>(sample_plane(an + c * aplane, Wa, t) + fillc);
             rgb[c].d[c] = 1.f;
-            gin[c] = g[(size_t)n * 3 * plane + c * plane + pix];
+            gin[c] = gn[(size_t)c * plane + pix];
         }
-        jitter_d<3>(rgb, (float)d[D_SAT], (float)d[D_HUE], d[D_SATFIRST] != 0.0);
+        jitter_d<3>(rgb, sat, hue, sat_first);
 #pragma unroll
         for (int i = 0; i < 3; ++i)
-            grgb[(size_t)n * 3 * plane + i * plane + pix] = gin[0] * rgb[0].d[i] + gin[1] * rgb[1].d[i] + gin[2] * rgb[2].d[i];
+            grn[(size_t)i * plane + pix] = gin[0] * rgb[0].d[i] + gin[1] * rgb[1].d[i] + gin[2] * rgb[2].d[i];
     }
 }
 
@@ -987,7 +1058,7 @@ __global__ __launch_bounds__(256) void warp_b_jac_kernel(const float* __restrict
 //     rectangle boxes on 9 lanes in parallel, and is reproducible by construction: one accumulator, fixed candidate order,
 //     in-order LDS.  It did not move the time either (the figures stand above the host launcher).
 //
-// Forms 0 and 1 read the cutout's stage map from maps[n] (stage_map_kernel) through a uniform address.
+// Forms 0 and 1 read the cutout's stage map from maps[n] (write_stage_map, in the stage's pre-pass) through a uniform address.
 //
 // The STAGE picks the descriptor words, the planes and the source window; the two stages are the same computation:
 //   STAGE 1 (A): g[n][3][Hd][Wd] on the stage-A plane -> per-cutout private source-gradient planes out[n][3][Ho][Wo] (summed
@@ -1203,31 +1274,80 @@ __global__ __launch_bounds__(256) void patchify_fwd_kernel(const float* __restri
     }
 }
 
-// Reduction for the min/max renorm backward: acc = {sum g_y, sum g_y*y, count(x==min), count(x==max)} (double)
+// ---- min/max renorm backward (slip.py:21-36), two passes over cut[N][3][S][S] and the patch-layout gradient dA ----
+// Both kernels run on the grid (blocks over one plane, planes): the plane index n*3 + c is block-uniform, so the channel, its
+// std and the plane's row bases cost nothing per element, and the index inside the plane is 32-bit (the host refuses totals of
+// 2^31 or more).  VEC: a lane takes FOUR consecutive x with 16-byte loads / stores; the host selects it when P % 4 == 0 and
+// S % 4 == 0 (the four x then lie in one patch row, so their dA words are contiguous and 16-byte aligned: Kp % 8 == 0, every
+// term of k a multiple of 4) and the three base pointers are 16-byte aligned.  The index decode happens once per quad.  The
+// scalar form serves every other geometry.  The per-element arithmetic is the same in both, division by std included
+// (a * (1 / b) does not round like a / b).
+struct RenormQuad {
+    unsigned idx;        // element index of the first x inside cut / gcut
+    size_t ia;           // its index inside dA
+};
+template <bool VEC>
+__device__ __forceinline__ RenormQuad renorm_decode(unsigned e, unsigned pl, int n, int c, int S, int P, int G, int T, int K) {
+    constexpr unsigned W = VEC ? 4 : 1;
+    const unsigned Sq = (unsigned)S / W;
+    const unsigned yy = e / Sq;
+    const int y = (int)yy, x = (int)((e - yy * Sq) * W);
+    const int ty = y / P, tx = x / P;
+    const int tok = 1 + ty * G + tx;
+    const int k = c * P * P + (y - ty * P) * P + (x - tx * P);
+    RenormQuad r;
+    r.idx = pl * (unsigned)S * (unsigned)S + e * W;
+    r.ia = ((size_t)n * T + tok) * K + k;
+    return r;
+}
+
+// Reduction: acc = {sum g_y, sum g_y*y, count(x==min), count(x==max)} (double); g_y = dA / std_c
+constexpr int RR_UNROLL = 4;
+template <bool VEC>
 __global__ __launch_bounds__(256) void patchify_bwd_reduce_kernel(const float* __restrict__ cut,
                                                                   const float* __restrict__ mm,
                                                                   const float* __restrict__ dA, double* __restrict__ acc,
                                                                   int N, int S, int P, int T, int K, PatchNorm nm) {
+    constexpr int W = VEC ? 4 : 1;
     const int G = S / P;
-    const size_t total = (size_t)N * 3 * S * S;
     const float mn = mm[0], mx = mm[1];
     const float range = mx - mn;
     const float inv = range != 0.f ? 1.f / range : 1.f;
     double s1 = 0, s2 = 0, cmin = 0, cmax = 0;
-    // 32-bit index arithmetic (the host checks total < 2^31): the size_t div/mod chain of the first version cost more than
-    // the memory traffic
-    const unsigned S2 = (unsigned)S * S, total32 = (unsigned)total, stride = gridDim.x * blockDim.x;
-    for (unsigned idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total32; idx += stride) {
-        const unsigned pl = idx / S2, rem = idx - pl * S2;
-        const int y = (int)(rem / (unsigned)S), x = (int)(rem - (unsigned)y * S);
+    const unsigned per_plane = (unsigned)S * (unsigned)S / W, stride = gridDim.x * blockDim.x;
+    // RR_UNROLL trips at a time, their loads issued before the first sum: few blocks (every block ends in four double atomics on
+    // the same four words) still keep enough requests in flight
+    for (unsigned pl = blockIdx.y; pl < (unsigned)N * 3u; pl += gridDim.y) {
         const int n = (int)(pl / 3u), c = (int)(pl - 3u * n);
-        const int ty = y / P, tx = x / P;
-        const int tok = 1 + ty * G + tx;
-        const int k = c * P * P + (y - ty * P) * P + (x - tx * P);
-        const float gy = dA[((size_t)n * T + tok) * K + k] / nm.std[c];
-        const float xv = cut[idx];
-        s1 += gy; s2 += gy * ((xv - mn) * inv);
-        cmin += (xv == mn); cmax += (xv == mx);
+        const float sd = nm.std[c];
+        for (unsigned e0 = blockIdx.x * blockDim.x + threadIdx.x; e0 < per_plane; e0 += RR_UNROLL * stride) {
+            float xv[RR_UNROLL][W], ga[RR_UNROLL][W];
+            bool on[RR_UNROLL];
+#pragma unroll
+            for (int t = 0; t < RR_UNROLL; ++t) {
+                const unsigned e = e0 + t * stride;
+                on[t] = e < per_plane;
+                if (!on[t]) continue;
+                const RenormQuad r = renorm_decode<VEC>(e, pl, n, c, S, P, G, T, K);
+                if constexpr (VEC) {
+                    const float4 x4 = *reinterpret_cast<const float4*>(cut + r.idx), g4 = *reinterpret_cast<const float4*>(dA + r.ia);
+                    xv[t][0] = x4.x; xv[t][1] = x4.y; xv[t][2] = x4.z; xv[t][3] = x4.w;
+                    ga[t][0] = g4.x; ga[t][1] = g4.y; ga[t][2] = g4.z; ga[t][3] = g4.w;
+                } else {
+                    xv[t][0] = cut[r.idx]; ga[t][0] = dA[r.ia];
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < RR_UNROLL; ++t) {
+                if (!on[t]) continue;
+#pragma unroll
+                for (int j = 0; j < W; ++j) {
+                    const float gy = ga[t][j] / sd;
+                    s1 += gy; s2 += gy * ((xv[t][j] - mn) * inv);
+                    cmin += (xv[t][j] == mn); cmax += (xv[t][j] == mx);
+                }
+            }
+        }
     }
     s1 = wave_sum_d(s1); s2 = wave_sum_d(s2); cmin = wave_sum_d(cmin); cmax = wave_sum_d(cmax);
     __shared__ double red[4][4];
@@ -1239,33 +1359,45 @@ __global__ __launch_bounds__(256) void patchify_bwd_reduce_kernel(const float* _
 }
 
 // g_cut = g_y/range + [x==min]*gmin/cnt_min + [x==max]*gmax/cnt_max   (slip.py:21-36 backward)
+template <bool VEC>
 __global__ __launch_bounds__(256) void patchify_bwd_apply_kernel(const float* __restrict__ cut,
                                                                  const float* __restrict__ mm,
                                                                  const float* __restrict__ dA,
                                                                  const double* __restrict__ acc, float* __restrict__ gcut,
                                                                  int N, int S, int P, int T, int K, PatchNorm nm) {
+    constexpr int W = VEC ? 4 : 1;
     const int G = S / P;
-    const size_t total = (size_t)N * 3 * S * S;
     const float mn = mm[0], mx = mm[1];
     const float range = mx - mn;
     const bool live = range != 0.f;
     const float inv = live ? 1.f / range : 1.f;
     const float gmin = live ? (float)((acc[1] - acc[0]) * inv / fmax(acc[2], 1.0)) : 0.f;
     const float gmax = live ? (float)(-acc[1] * inv / fmax(acc[3], 1.0)) : 0.f;
-    const unsigned S2 = (unsigned)S * S, total32 = (unsigned)total, stride = gridDim.x * blockDim.x;
-    for (unsigned idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total32; idx += stride) {
-        const unsigned pl = idx / S2, rem = idx - pl * S2;
-        const int y = (int)(rem / (unsigned)S), x = (int)(rem - (unsigned)y * S);
+    const unsigned per_plane = (unsigned)S * (unsigned)S / W, stride = gridDim.x * blockDim.x;
+    for (unsigned pl = blockIdx.y; pl < (unsigned)N * 3u; pl += gridDim.y) {
         const int n = (int)(pl / 3u), c = (int)(pl - 3u * n);
-        const int ty = y / P, tx = x / P;
-        const int tok = 1 + ty * G + tx;
-        const int k = c * P * P + (y - ty * P) * P + (x - tx * P);
-        const float gy = dA[((size_t)n * T + tok) * K + k] / nm.std[c];
-        const float xv = cut[idx];
-        float g = gy * inv;
-        if (xv == mn) g += gmin;
-        if (xv == mx) g += gmax;
-        gcut[idx] = g;
+        const float sd = nm.std[c];
+        for (unsigned e = blockIdx.x * blockDim.x + threadIdx.x; e < per_plane; e += stride) {
+            const RenormQuad r = renorm_decode<VEC>(e, pl, n, c, S, P, G, T, K);
+            float xv[W], ga[W], go[W];
+            if constexpr (VEC) {
+                const float4 x4 = *reinterpret_cast<const float4*>(cut + r.idx), g4 = *reinterpret_cast<const float4*>(dA + r.ia);
+                xv[0] = x4.x; xv[1] = x4.y; xv[2] = x4.z; xv[3] = x4.w;
+                ga[0] = g4.x; ga[1] = g4.y; ga[2] = g4.z; ga[3] = g4.w;
+            } else {
+                xv[0] = cut[r.idx]; ga[0] = dA[r.ia];
+            }
+#pragma unroll
+            for (int j = 0; j < W; ++j) {
+                const float gy = ga[j] / sd;
+                float g = gy * inv;
+                if (xv[j] == mn) g += gmin;
+                if (xv[j] == mx) g += gmax;
+                go[j] = g;
+            }
+            if constexpr (VEC) *reinterpret_cast<float4*>(gcut + r.idx) = make_float4(go[0], go[1], go[2], go[3]);
+            else gcut[r.idx] = go[0];
+        }
     }
 }
 
@@ -1284,21 +1416,18 @@ static int cutout_bwd_form(int form) {
 }
 
 // the tile pass of one stage in the resolved form (0, 1, 2): the destination plane is Wd x Hd, the output image Wo x Ho;
-// `maps` holds n_cut stage maps for forms 0 and 1 (written here) and is not touched by form 2
+// `maps` holds n_cut stage maps for forms 0 and 1 (written by the stage's pre-pass, which the caller has launched) and is not
+// touched by form 2
 template <int STAGE>
 static int launch_warp_bwd(int form, const double* desc, const float* g, const float* grgb, const float2* uv, StageMap* maps, float* out,
                            int n_cut, int Wd, int Hd, int Wo, int Ho, hipStream_t s) {
     const dim3 grid(((Wo + TILE_W - 1) / TILE_W) * ((Ho + TILE_W - 1) / TILE_W), n_cut);
     if (form == 2)
         hipLaunchKernelGGL((warp_bwd_kernel<2, STAGE>), grid, dim3(256), 0, s, desc, g, grgb, uv, nullptr, out, Wd, Hd, Wo, Ho);
-    else {
-        hipLaunchKernelGGL(stage_map_kernel, dim3(ceil_div(n_cut, 64)), dim3(64), 0, s, desc, STAGE, maps, n_cut, Wd, Hd, Wo, Ho);
-        PRX_LAUNCH_CHECK();
-        if (form == 0)
-            hipLaunchKernelGGL((warp_bwd_kernel<0, STAGE>), grid, dim3(256), 0, s, desc, g, grgb, uv, maps, out, Wd, Hd, Wo, Ho);
-        else
-            hipLaunchKernelGGL((warp_bwd_kernel<1, STAGE>), grid, dim3(64), 0, s, desc, g, grgb, uv, maps, out, Wd, Hd, Wo, Ho);
-    }
+    else if (form == 0)
+        hipLaunchKernelGGL((warp_bwd_kernel<0, STAGE>), grid, dim3(256), 0, s, desc, g, grgb, uv, maps, out, Wd, Hd, Wo, Ho);
+    else
+        hipLaunchKernelGGL((warp_bwd_kernel<1, STAGE>), grid, dim3(64), 0, s, desc, g, grgb, uv, maps, out, Wd, Hd, Wo, Ho);
     PRX_LAUNCH_CHECK();
     return 0;
 }
@@ -1313,8 +1442,21 @@ int prx_pool_bwd(const float* g, const int* argmax, const unsigned char* mask, f
     PRX_LAUNCH_CHECK();
     return 0;
 }
+// The destination-parallel warp kernels run on the grid (blocks over one plane, cutouts) with a 32-bit pixel index inside the
+// plane: a plane of 2^31 elements or more (and more cutouts than a grid has rows) is refused before anything is launched.
+#define PRX_REQUIRE_PLANE32(what, n_cut, H, W)                                                                                   \
+    do {                                                                                                                         \
+        PRX_REQUIRE((size_t)(H) * (size_t)(W) < ((size_t)1 << 31), what ": a plane of %dx%d exceeds the 32-bit index range", H, W); \
+        PRX_REQUIRE((n_cut) <= 65535, what ": %d cutouts exceed the 65535 rows of a launch grid", n_cut);                        \
+    } while (0)
+static inline dim3 plane_grid(size_t plane, int n_cut, int max_blocks) {
+    return dim3(std::min(ew_grid(plane), max_blocks), n_cut);
+}
+
 int prx_warp_a_fwd(const float* src, int Hs, int Ws, const double* desc, float* out, int n_cut, int Ha, int Wa, hipStream_t s) {
-    hipLaunchKernelGGL(warp_a_fwd_kernel, dim3(ew_grid((size_t)n_cut * Ha * Wa)), dim3(256), 0, s, src, Hs, Ws, desc, out,
+    PRX_REQUIRE_PLANE32("warp_a_fwd", n_cut, Ha, Wa);
+    PRX_REQUIRE_PLANE32("warp_a_fwd (source)", n_cut, Hs, Ws);
+    hipLaunchKernelGGL(warp_a_fwd_kernel, plane_grid((size_t)Ha * Wa, n_cut, 1024), dim3(256), 0, s, src, Hs, Ws, desc, out,
                        n_cut, Ha, Wa);
     PRX_LAUNCH_CHECK();
     return 0;
@@ -1330,17 +1472,22 @@ int prx_warp_a_bwd(const float* g, int Hs, int Ws, const double* desc, float* uv
     // (refused before anything is launched: a refusal writes nothing)
     if (form != 2)
         PRX_REQUIRE((size_t)n_cut * sizeof(StageMap) <= (size_t)3 * Hs * Ws * sizeof(float), "warp_a_bwd: too many cutouts for the stage-map scratch");
-    hipLaunchKernelGGL(uv_kernel, dim3(std::min(ew_grid((size_t)Ha * Wa), 64), n_cut), dim3(256), 0, s, desc, 1, (float2*)uv, Wa, Ha, Ws, Hs);
+    PRX_REQUIRE_PLANE32("warp_a_bwd", n_cut, Ha, Wa);
+    // ONE pre-pass: the raw coordinates and (forms 0 and 1) the stage maps
+    hipLaunchKernelGGL(uv_kernel, plane_grid((size_t)Ha * Wa, n_cut, 64), dim3(256), 0, s, desc, (float2*)uv,
+                       form != 2 ? (StageMap*)gsrc : nullptr, Wa, Ha, Ws, Hs);
     PRX_LAUNCH_CHECK();
     if (int rc = launch_warp_bwd<1>(form, desc, g, nullptr, (const float2*)uv, (StageMap*)gsrc, gsrc_priv, n_cut, Wa, Ha, Ws, Hs, s)) return rc;
-    hipLaunchKernelGGL(reduce_planes_kernel, dim3(ew_grid((size_t)3 * Hs * Ws)), dim3(256), 0, s, gsrc_priv, gsrc, n_cut,
-                       (size_t)3 * Hs * Ws);
+    // one-wave blocks: the 3 Hs Ws outputs are all the parallelism there is, and waves spread over the CUs more evenly than blocks of four
+    hipLaunchKernelGGL(reduce_planes_kernel, dim3((unsigned)std::min<size_t>(((size_t)3 * Hs * Ws + 63) / 64, 65536)), dim3(64), 0, s,
+                       gsrc_priv, gsrc, n_cut, (size_t)3 * Hs * Ws);
     PRX_LAUNCH_CHECK();
     return 0;
 }
 int prx_warp_b_fwd(const float* a, int Ha, int Wa, const double* desc, const float* noise, float* out, int n_cut, int S,
                    hipStream_t s) {
-    hipLaunchKernelGGL(warp_b_fwd_kernel, dim3(ew_grid((size_t)n_cut * S * S)), dim3(256), 0, s, a, Ha, Wa, desc, noise, out,
+    PRX_REQUIRE_PLANE32("warp_b_fwd", n_cut, S, S);
+    hipLaunchKernelGGL(warp_b_fwd_kernel, plane_grid((size_t)S * S, n_cut, 1024), dim3(256), 0, s, a, Ha, Wa, desc, noise, out,
                        n_cut, S);
     PRX_LAUNCH_CHECK();
     return 0;
@@ -1355,10 +1502,10 @@ int prx_warp_b_bwd(const float* a, int Ha, int Wa, const double* desc, const flo
     // (refused before anything is launched: a refusal writes nothing)
     if (form != 2)
         PRX_REQUIRE(maps_scratch != nullptr && (size_t)n_cut * sizeof(StageMap) <= maps_scratch_bytes, "warp_b_bwd: stage-map scratch too small");
-    hipLaunchKernelGGL(uv_kernel, dim3(std::min(ew_grid((size_t)S * S), 64), n_cut), dim3(256), 0, s, desc, 2, (float2*)uv, S, S, 0, 0);
-    PRX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(warp_b_jac_kernel, dim3(std::min(ew_grid((size_t)S * S), 64), n_cut), dim3(256), 0, s, a, Ha, Wa, desc, g, grgb,
-                       n_cut, S);
+    PRX_REQUIRE_PLANE32("warp_b_bwd", n_cut, S, S);
+    // ONE pre-pass: raw coordinates, the gradient pulled back through the ColorJitter and (forms 0 and 1) the stage maps
+    hipLaunchKernelGGL(warp_b_jac_kernel, plane_grid((size_t)S * S, n_cut, 1024), dim3(256), 0, s, a, Ha, Wa, desc, g, grgb,
+                       (float2*)uv, form != 2 ? (StageMap*)maps_scratch : nullptr, n_cut, S);
     PRX_LAUNCH_CHECK();
     return launch_warp_bwd<2>(form, desc, g, grgb, (const float2*)uv, (StageMap*)maps_scratch, ga, n_cut, S, S, Wa, Ha, s);
 }
@@ -1381,6 +1528,19 @@ int prx_minmax(const float* x, size_t n, float* part, int nparts, float* mm, hip
 }
 static inline int patch_kp(int P) { return (3 * P * P + 7) / 8 * 8; }
 
+// the renorm backward's grid (blocks over one plane, planes) and its choice of the 16-byte form (the kernels' comment): `quads`
+// needs four consecutive x inside one patch row and 16-byte aligned rows in all three arrays
+static inline bool renorm_quads(int S, int P, int K, const void* cut, const void* dA, const void* gcut) {
+    return P % 4 == 0 && S % 4 == 0 && K % 4 == 0 && (((uintptr_t)cut | (uintptr_t)dA | (uintptr_t)gcut) & 15) == 0;
+}
+// blocks per plane of the reduction: about 384 blocks in all.  Measured at the headline (192 planes of 224 x 224, 16-byte form,
+// four trips' loads in flight per lane): 1 / 2 / 8 blocks per plane 29.6 / 23.2 / 28.1 us -- every block ends in a wave reduction
+// of four doubles and four atomics on the same words, and 1.5 blocks per CU already keep the loads in flight
+static inline int renorm_reduce_blocks(int N) { return std::max(1, ceil_div(384, std::max(N, 1) * 3)); }
+static inline dim3 renorm_grid(int N, int S, bool quads, int max_blocks) {
+    return dim3(std::min(ew_grid((size_t)S * S / (quads ? 4 : 1)), max_blocks), std::min(N * 3, 65535));
+}
+
 int prx_patchify_fwd(const float* cut, const float* mm, void* A, int prec, int N, int S, int P, int T, hipStream_t s, const PatchNorm& norm) {
     PRX_REQUIRE(S % P == 0 && T == (S / P) * (S / P) + 1, "patchify: bad geometry S=%d P=%d T=%d", S, P, T);
     const int Kp = patch_kp(P);
@@ -1394,15 +1554,20 @@ int prx_patchify_bwd_reduce(const float* cut, const float* mm, const float* dA, 
                             hipStream_t s, const PatchNorm& norm) {
     PRX_REQUIRE((size_t)N * 3 * S * S < ((size_t)1 << 31), "patchify backward: %d cutouts of %dx%d exceed the 32-bit index range", N, S, S);
     PRX_CHECK_HIP(hipMemsetAsync(acc, 0, sizeof(double) * 4, s));
-    hipLaunchKernelGGL(patchify_bwd_reduce_kernel, dim3(std::min(ew_grid((size_t)N * 3 * S * S), 2048)), dim3(256), 0, s,
-                       cut, mm, dA, acc, N, S, P, T, patch_kp(P), norm);
+    if (renorm_quads(S, P, patch_kp(P), cut, dA, nullptr))
+        hipLaunchKernelGGL(patchify_bwd_reduce_kernel<true>, renorm_grid(N, S, true, renorm_reduce_blocks(N)), dim3(256), 0, s, cut, mm, dA, acc, N, S, P, T, patch_kp(P), norm);
+    else
+        hipLaunchKernelGGL(patchify_bwd_reduce_kernel<false>, renorm_grid(N, S, false, renorm_reduce_blocks(N)), dim3(256), 0, s, cut, mm, dA, acc, N, S, P, T, patch_kp(P), norm);
     PRX_LAUNCH_CHECK();
     return 0;
 }
 int prx_patchify_bwd_apply(const float* cut, const float* mm, const float* dA, const double* acc, float* gcut, int N,
                            int S, int P, int T, hipStream_t s, const PatchNorm& norm) {
-    hipLaunchKernelGGL(patchify_bwd_apply_kernel, dim3(ew_grid((size_t)N * 3 * S * S)), dim3(256), 0, s, cut, mm, dA, acc,
-                       gcut, N, S, P, T, patch_kp(P), norm);
+    PRX_REQUIRE((size_t)N * 3 * S * S < ((size_t)1 << 31), "patchify backward: %d cutouts of %dx%d exceed the 32-bit index range", N, S, S);
+    if (renorm_quads(S, P, patch_kp(P), cut, dA, gcut))
+        hipLaunchKernelGGL(patchify_bwd_apply_kernel<true>, renorm_grid(N, S, true, 64), dim3(256), 0, s, cut, mm, dA, acc, gcut, N, S, P, T, patch_kp(P), norm);
+    else
+        hipLaunchKernelGGL(patchify_bwd_apply_kernel<false>, renorm_grid(N, S, false, 64), dim3(256), 0, s, cut, mm, dA, acc, gcut, N, S, P, T, patch_kp(P), norm);
     PRX_LAUNCH_CHECK();
     return 0;
 }
@@ -1411,19 +1576,24 @@ int prx_patchify_bwd_apply(const float* cut, const float* mm, const float* dA, c
 // consumes the normalised image directly): the patch kernels with one "patch" = the whole image (P = S, one token per
 // image); their token index is 1-based, hence the pointer shifted back by one row of K = 3*S*S.
 int prx_preproc_bwd_reduce(const float* cut, const float* mm, const float* dY, double* acc, int N, int S, hipStream_t s) {
-    PRX_CHECK_HIP(hipMemsetAsync(acc, 0, sizeof(double) * 4, s));
     PRX_REQUIRE((size_t)N * 3 * S * S < ((size_t)1 << 31), "preprocessing backward: %d cutouts of %dx%d exceed the 32-bit index range", N, S, S);
+    PRX_CHECK_HIP(hipMemsetAsync(acc, 0, sizeof(double) * 4, s));
     const int K = 3 * S * S;
-    hipLaunchKernelGGL(patchify_bwd_reduce_kernel, dim3(std::min(ew_grid((size_t)N * 3 * S * S), 2048)), dim3(256), 0, s,
-                       cut, mm, dY - K, acc, N, S, S, 1, K, prx_patch_norm_clip());
+    if (renorm_quads(S, S, K, cut, dY, nullptr))
+        hipLaunchKernelGGL(patchify_bwd_reduce_kernel<true>, renorm_grid(N, S, true, renorm_reduce_blocks(N)), dim3(256), 0, s, cut, mm, dY - K, acc, N, S, S, 1, K, prx_patch_norm_clip());
+    else
+        hipLaunchKernelGGL(patchify_bwd_reduce_kernel<false>, renorm_grid(N, S, false, renorm_reduce_blocks(N)), dim3(256), 0, s, cut, mm, dY - K, acc, N, S, S, 1, K, prx_patch_norm_clip());
     PRX_LAUNCH_CHECK();
     return 0;
 }
 int prx_preproc_bwd_apply(const float* cut, const float* mm, const float* dY, const double* acc, float* gcut, int N, int S,
                           hipStream_t s) {
     const int K = 3 * S * S;
-    hipLaunchKernelGGL(patchify_bwd_apply_kernel, dim3(ew_grid((size_t)N * 3 * S * S)), dim3(256), 0, s, cut, mm, dY - K, acc,
-                       gcut, N, S, S, 1, K, prx_patch_norm_clip());
+    PRX_REQUIRE((size_t)N * 3 * S * S < ((size_t)1 << 31), "preprocessing backward: %d cutouts of %dx%d exceed the 32-bit index range", N, S, S);
+    if (renorm_quads(S, S, K, cut, dY, gcut))
+        hipLaunchKernelGGL(patchify_bwd_apply_kernel<true>, renorm_grid(N, S, true, 64), dim3(256), 0, s, cut, mm, dY - K, acc, gcut, N, S, S, 1, K, prx_patch_norm_clip());
+    else
+        hipLaunchKernelGGL(patchify_bwd_apply_kernel<false>, renorm_grid(N, S, false, 64), dim3(256), 0, s, cut, mm, dY - K, acc, gcut, N, S, S, 1, K, prx_patch_norm_clip());
     PRX_LAUNCH_CHECK();
     return 0;
 }
