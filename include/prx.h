@@ -378,6 +378,47 @@ int prx_fft_drawer_freq_columns(const prx_fft_drawer* h);
 int prx_fft_drawer_synth(prx_fft_drawer* h, const float* params, float contrast, float* image, prx_stream_t stream);
 int prx_fft_drawer_backward(prx_fft_drawer* h, const float* g_image, float* g_params, prx_stream_t stream);
 
+/* --- SuperResolutionDrawer.synth (super_resolution.py:34-102): clamp_with_grad(RRDBNet(z), 0, 1), the RealESRGAN x4 network
+ * [UPSTREAM basicsr/archs/rrdbnet_arch.py] with the drawer's arguments (scale 4, no tiling, no padding, fp32), and its data
+ * gradient (the weights are frozen).  csrc/rrdbnet.hip, layout and memory formula in csrc/rrdbnet.h.
+ *   z / g_z: fp32 [3][h][w] in [0,1];  image / g_image: fp32 [3][4h][4w].
+ *   weights: 2 (15 num_block + 6) fp32 device tensors in torch layout, (weight [Cout][Cin][3][3], bias [Cout]) per convolution,
+ *   in the order conv_first, body.{i}.rdb{1,2,3}.conv{1..5}, conv_body, conv_up1, conv_up2, conv_hr, conv_last; they are
+ *   copied / packed on `stream` at creation (synchronise before releasing them).
+ *   The kernels are built for num_feat = 64, num_grow = 32 and PRX_PREC_F16 / PRX_PREC_F32; anything else is refused by name.
+ * clamp = 0: image = the raw network output and backward is the identity rule (tests).  backward differentiates the handle's
+ * LAST synth.  Everything is allocated at creation; synth / backward only launch on `stream` and never synchronise. */
+typedef struct prx_rrdbnet prx_rrdbnet;
+int prx_rrdbnet_create(prx_rrdbnet** out, int num_feat, int num_grow, int num_block, int h, int w, const float* const* weights,
+                       int n_weights, int precision, prx_stream_t stream);
+void prx_rrdbnet_destroy(prx_rrdbnet* h);
+int prx_rrdbnet_synth(prx_rrdbnet* h, const float* z, float* image, int clamp, prx_stream_t stream);
+int prx_rrdbnet_backward(prx_rrdbnet* h, const float* g_image, float* g_z, prx_stream_t stream);
+/* one 3x3 convolution of the family on caller-owned buffers (synchronises: a test entry).  T = half / float by `prec`.
+ * forward (dgrad = 0): in T [pixels][ld_in], channels in_off .. + Cin -> v = conv + bias, LeakyReLU(0.2) if lrelu, then
+ *   v = alpha v + beta r1 + r2 (r1, r2: fp32 [pixels][ld_r*], first 64 channels, null: absent), written as T into
+ *   out[pixels][ld_out] at out_off and / or as fp32 into out_f32 at of_off.  H x W: the output grid; up: in is [H/2][W/2],
+ *   read nearest-2x.
+ * data gradient (dgrad = 1): in fp32 [pixels][ld_in], the gradient of the Cout outputs at in_off, multiplied on load by the
+ *   LeakyReLU derivative of act (T [pixels][ld_act] at act_off; a > 0: 1, else 0.2; null: none); the Cin results go through the
+ *   same v = alpha v + beta r1 + r2 and are stored (accum = 0) or added (accum = 1) into out_f32 at of_off.
+ * wt: the torch weight [Cout][Cin][3][3] fp32; Cin, Cout multiples of 32. */
+int prx_k_rrdb_conv(int dgrad, const void* in, int ld_in, int in_off, const void* act, int ld_act, int act_off, const float* wt,
+                    const float* bias, int Cin, int Cout, int H, int W, int up, int lrelu, float alpha, float beta, const float* r1,
+                    int ld_r1, const float* r2, int ld_r2, void* out, int ld_out, int out_off, float* out_f32, int ld_of, int of_off,
+                    int accum, int prec, prx_stream_t stream);
+/* the backward of a nearest-2x read: out [h][w][64] = 2 x 2 block sums of in [2h][2w][64] */
+int prx_k_rrdb_sum2x2(const float* in, float* out, int h, int w, int C, prx_stream_t stream);
+/* conv_first (3 -> 64: z NCHW fp32 -> T [pixels][ld_out] and / or fp32 [pixels][64]) and its data gradient of g1 + g2 */
+int prx_k_rrdb_conv_first(const float* z, const float* wt, const float* bias, int h, int w, void* out, int ld_out, float* out_f32, int prec,
+                          prx_stream_t stream);
+int prx_k_rrdb_conv_first_bwd(const float* g1, int ld1, const float* g2, int ld2, const float* wt, int h, int w, float* dz, prx_stream_t stream);
+/* conv_last (64 -> 3: T [pixels][64] -> image NCHW fp32, clamped to [0,1] if clamp; raw: the un-clamped values) and its
+ * backward: g_image through g * ((g * (raw - clamp(raw))) >= 0) if clamp, then the data gradient -> g_out fp32 [pixels][64] */
+int prx_k_rrdb_conv_last(const void* in, const float* wt, const float* bias, int H, int W, int clamp, float* image, float* raw, int prec,
+                         prx_stream_t stream);
+int prx_k_rrdb_conv_last_bwd(const float* g_image, const float* raw, const float* wt, int H, int W, int clamp, float* g_out, prx_stream_t stream);
+
 /* --- STROTSS hyper-column sampling of the StyleLoss plugin (`spatial_feature_extract`, Losses/StyleLoss.py:169-223): n
  * positions, one bilinear sample of each of n_layers NHWC fp32 feature maps per position, concatenated over channels, plus
  * the two coordinate channels -> out [n, ldo] (ldo >= sum(channels) + 2).

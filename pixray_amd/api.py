@@ -157,6 +157,35 @@ def build_fft_clip_session(*, size=(512, 512), clip_model="ViT-L/14", num_cuts=2
                    comm=_maybe_oneshot_comm(group, rank, world_size, size))
 
 
+def build_super_resolution_clip_session(*, size=(256, 256), model="RealESRGAN_x4plus", clip_model="ViT-B/32", num_cuts=64,
+                                        learning_rate=0.2, iterations=250, seed=0, device="cuda", prompt_embeds=None,
+                                        init_image: Optional[torch.Tensor] = None, state_dict=None, custom_losses=(), args=None,
+                                        precision: Optional[str] = None) -> Session:
+    """The super_resolution drawer (`SuperResolutionDrawer`: z is an RGB image at a quarter of the canvas, RRDBNet x4 on the HIP
+    runner) + one CLIP perceptor + MakeCutouts + a Prompt + the fused optimiser on z with the [0,1] clamp in its kernel.
+    `model`: a weights.RRDBNET_CONFIGS name; `state_dict`: basicsr-format parameters when the caller has them (else the
+    checkpoint file under models/, else seeded synthetic weights); `init_image`: [1,3,H,W] in [0,1]; `precision` as in
+    `build_vqgan_clip_session` ("ref": the fp32 network of the reference + fp16 towers)."""
+    from .super_resolution_drawer import SuperResolutionDrawer
+    _lib.load()
+    _lib.require_device()
+    dev = torch.device(device)
+    drawer_precision, precision = _lib.split_precision(precision)
+    st = types.SimpleNamespace(size=tuple(size), super_resolution_model=model, super_resolution_state_dict=state_dict, weight_seed=seed,
+                               precision=drawer_precision)
+    drawer = SuperResolutionDrawer(st)
+    drawer.load_model(st, dev)
+    drawer.init_from_tensor(None if init_image is None else init_image.to(dev) * 2 - 1)
+    size = drawer.size
+    perceptor = get_clip_perceptor(clip_model, dev, max_batch=num_cuts, seed=seed + 1, precision=precision)
+    mk = MakeCutouts(perceptor.input_resolution, num_cuts, generator=torch.Generator().manual_seed(1000 + seed),
+                     aspect_width=size[0] / size[1])
+    pe = prompt_embeds if prompt_embeds is not None else seeded_unit_vectors(1, perceptor.output_dim, seed + 2)
+    pms = {clip_model: [Prompt(pe.to(dev), 1.0, float("-inf")).to(dev)]}
+    return Session(drawer, {clip_model: perceptor}, {perceptor.input_resolution: mk}, pms, learning_rate=learning_rate,
+                   iterations=iterations, custom_losses=list(custom_losses), args=args, seed=seed)
+
+
 # BASELINE.json `configs` as (builder kwargs); configs[0] is the CPU plumbing case (tests/test_host_logic.py), configs[4]
 # (vdiff) has no source in the reference checkout
 WORKLOADS = {

@@ -11,6 +11,8 @@ are exercised in tests with randomly initialised upstream-format state dicts; th
 * facebookresearch/SLIP checkpoints (`models/slip_base_100ep.pt`, ..., slip.py:90-140): `load_slip`.
 * torchvision `vgg16` (`models.vgg16(pretrained=True)`, Losses/StyleLoss.py:27): `features.{0,2,5,...,28}.{weight,bias}`;
   the `classifier.*` tensors are dropped (the StyleLoss extractor stops at relu5_3).
+* RealESRGAN (`models/super_resolution_RealESRGAN_x4plus.ckpt`, super_resolution.py:47-61, real_esrganer.py:54-60): basicsr's
+  RRDBNet state dict under `params_ema`, else `params`: `load_rrdbnet`.
 """
 from collections import OrderedDict
 from typing import Dict
@@ -205,3 +207,23 @@ def vgg16_from_torchvision(state_dict: Dict[str, torch.Tensor]):
     sd = state_dict.get("state_dict", state_dict)
     params = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
     return _check(params, vgg16_param_shapes())
+
+
+def load_rrdbnet(path: str, cfg):
+    """A RealESRGAN checkpoint file -> the RRDBNet runner's parameters (weights.rrdbnet_param_shapes order).  The file keeps
+    basicsr's state dict under `params_ema`, else `params` (real_esrganer.py:54-60); names and shapes are checked strictly and
+    the first missing or mismatching key is named.  Nothing is ever fetched: a file that is not there is an error."""
+    from .weights import rrdbnet_param_shapes
+    loadnet = torch.load(path, map_location="cpu", weights_only=True)
+    if isinstance(loadnet, dict) and "params_ema" in loadnet:
+        sd = loadnet["params_ema"]
+    elif isinstance(loadnet, dict) and "params" in loadnet:
+        sd = loadnet["params"]
+    else:
+        raise KeyError(f"{path}: no `params_ema` / `params` entry (not a RealESRGAN checkpoint)")
+    shapes = rrdbnet_param_shapes(cfg)
+    out = _check(sd, shapes)
+    extra = [k for k in sd if k not in shapes]
+    if extra:
+        raise KeyError(f"{path}: unexpected entry {extra[0]} (the configuration has {cfg.num_block} blocks)")
+    return out

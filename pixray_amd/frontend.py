@@ -16,8 +16,8 @@ pixray drives this package unchanged:
 Not carried over (outside SURVEY.md section 8): the notebook display calls, the `--transparent_weight`
 parsing helper of util.py, the SIMCLR_VITS16 perceptor (it has no text side; refused by name), ffmpeg video / gif assembly (the frame files are written;
 `make_video` / animation gif need ffmpeg and are skipped with a message when it is absent), the per-frame target-image prompt
-table of the animation mode (`pmsTargetTable`, pixray.py:772-795: target images score every frame here), the vdiff drawer (its
-source is not in the reference checkout), and the super_resolution drawer (it needs RealESRGAN weights).
+table of the animation mode (`pmsTargetTable`, pixray.py:772-795: target images score every frame here), and the vdiff drawer
+(its source is not in the reference checkout).
 """
 from __future__ import annotations
 

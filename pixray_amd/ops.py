@@ -884,6 +884,72 @@ def fft_synth(params: torch.Tensor, handle: FftDrawerHandle, contrast: float = 0
     return _FftSynthFn.apply(params, handle, contrast)
 
 
+# --------------------------------------------------------------------------------------- RRDBNet x4 (super_resolution drawer)
+class RrdbNetHandle:
+    """Owns a `prx_rrdbnet` (csrc/rrdbnet.hip): weight packs and every activation / gradient buffer of one latent size,
+    allocated here and never afterwards.  `precision`: "fp16" (default) | "f32"; "bf16" is refused by name."""
+
+    def __init__(self, cfg, params, latent_hw, device, precision=None):
+        from .weights import rrdbnet_param_shapes
+        ws = _weights_in_abi_order(params, rrdbnet_param_shapes(cfg), device, f"RRDBNet {getattr(cfg, 'name', '')}")
+        self.precision = precision_code(precision)
+        hh, ww = int(latent_hw[0]), int(latent_hw[1])
+        h = ctypes.c_void_p()
+        call("prx_rrdbnet_create", ctypes.addressof(h), cfg.num_feat, cfg.num_grow_ch, cfg.num_block, hh, ww, _keep(self, _weight_array(ws)),
+             len(ws), self.precision, _stream())
+        torch.cuda.synchronize(device)   # the weights are copied / packed: the tensors may now be released
+        self.h = h
+        self.cfg = cfg
+        self.latent_hw = (hh, ww)
+        self.device = device
+        self.generation = 0              # see _ClipEncodeFn: one forward's activations per handle
+
+    def __del__(self):
+        h = getattr(self, "h", None)
+        if h is not None and h.value:
+            try:
+                _destroy_handle("prx_rrdbnet_destroy", h)
+            except Exception:
+                pass
+            self.h = None
+
+
+class _RrdbNetSynthFn(torch.autograd.Function):
+    """SuperResolutionDrawer.synth (super_resolution.py:81-83).  One forward's activations per handle: a backward whose
+    generation is stale (a second `synth()` ran in between) fails by name instead of differentiating the wrong forward."""
+
+    @staticmethod
+    def forward(ctx, z, handle, clamp):
+        _need_cuda(z)
+        z = z.contiguous().float()
+        hh, ww = handle.latent_hw
+        if tuple(z.shape) != (1, 3, hh, ww):
+            raise PrxError(f"rrdbnet_synth: z must be [1,3,{hh},{ww}], got {tuple(z.shape)}")
+        img = torch.empty(1, 3, 4 * hh, 4 * ww, device=z.device)
+        call("prx_rrdbnet_synth", handle.h, z, img, int(bool(clamp)), _stream())
+        handle.generation += 1
+        ctx.generation = handle.generation
+        ctx.handle = handle
+        return img
+
+    @staticmethod
+    def backward(ctx, g):
+        handle = ctx.handle
+        if handle.generation != ctx.generation:
+            raise PrxError("rrdbnet_synth: stale backward -- the handle has run another synth since this forward "
+                           "(it keeps ONE forward's activations; use one handle per live graph)")
+        g = g.contiguous().float()
+        hh, ww = handle.latent_hw
+        dz = torch.empty(1, 3, hh, ww, device=g.device)
+        call("prx_rrdbnet_backward", handle.h, g, dz, _stream())
+        return dz, None, None
+
+
+def rrdbnet_synth(z, handle: RrdbNetHandle, clamp: bool = True):
+    """clamp_with_grad(RRDBNet(z), 0, 1) [1,3,4h,4w]; `clamp=False`: the raw network output (tests)"""
+    return _RrdbNetSynthFn.apply(z, handle, clamp)
+
+
 # --------------------------------------------------------------------------------------- built-in losses and filters
 # (csrc/plugin_losses.hip, plugin_filters.hip).  Every loss scalar comes out of its launch through the same fixed-order
 # "partials, then the last workgroup" reduction as the Prompt loss: `partials` is a scratch of 1024 rows x 4 doubles.

@@ -9,7 +9,8 @@ as `custom_losses=` and the `lossGlobals` dict handed to every `get_loss` call.
 
 `class_table` maps `--drawer` names to drawer classes (the HIP VQGAN drawer, the fft spectrum drawer, the polygon grid of the
 reference's `pixel` drawer on the HIP rasteriser, the nearest-upsampled pixel grid that stands in for its `fast_pixel`, and its
-`line_sketch` and `clipdraw` stroke drawers on the HIP stroke rasteriser); `filters_class_table` holds the reference's three
+`line_sketch` and `clipdraw` stroke drawers on the HIP stroke rasteriser, and its `super_resolution` drawer on the HIP RRDBNet
+x4 runner); `filters_class_table` holds the reference's three
 filters (`lookup`, `tiler`, `wallpaper`: builtin_filters.py) and `loss_class_table` its losses (`style`: style_loss.py;
 `palette`, `saturation`, `symmetry`, `smoothness`, `edge` -- with `--edge_input_image` / `--edge_mask_image` -- and `aesthetic`,
 whose linear head is read from the file `--aesthetic_model` names: builtin_losses.py), all on HIP kernels.  `resmem` is
@@ -28,10 +29,11 @@ from .pixel_grid_drawer import PixelGridDrawer
 from .prompt import parse_prompt
 from .stroke_drawer import ClipDrawer, LineDrawer
 from .style_loss import StyleLoss
+from .super_resolution_drawer import SuperResolutionDrawer
 from .vqgan_drawer import VqganDrawer
 
 class_table: Dict[str, type] = {"vqgan": VqganDrawer, "pixel": PixelDrawer, "fft": FftDrawer, "fast_pixel": PixelGridDrawer,
-                               "line_sketch": LineDrawer, "clipdraw": ClipDrawer}
+                               "line_sketch": LineDrawer, "clipdraw": ClipDrawer, "super_resolution": SuperResolutionDrawer}
 filters_class_table: Dict[str, type] = dict(BUILTIN_FILTERS)
 loss_class_table: Dict[str, type] = {**BUILTIN_LOSSES, "style": StyleLoss, **UNAVAILABLE_LOSSES}
 

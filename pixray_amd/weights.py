@@ -596,3 +596,77 @@ def synthetic_vgg16_params(seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
         else:
             out[name] = torch.randn(shape, generator=g) * math.sqrt(2.0 / (shape[1] * 9))
     return out
+
+
+# ------------------------------------------------------------------------------------------ RRDBNet (super_resolution drawer)
+@dataclass
+class RrdbNetConfig:
+    """basicsr's RRDBNet(num_in_ch=3, num_out_ch=3, scale=4) as RealESRGAN_x4plus uses it (super_resolution.py:60-62)"""
+    num_feat: int = 64
+    num_grow_ch: int = 32
+    num_block: int = 23
+    name: str = "RealESRGAN_x4plus"
+
+
+RRDBNET_CONFIGS = {
+    "RealESRGAN_x4plus": RrdbNetConfig(),
+    # reduced depth with the SAME channel geometry: the kernels are specialised on channels, not on depth
+    "tiny-RRDB": RrdbNetConfig(num_block=1, name="tiny-RRDB"),
+}
+
+
+def rrdbnet_conv_names(cfg: RrdbNetConfig):
+    names = ["conv_first"]
+    for i in range(cfg.num_block):
+        for r in (1, 2, 3):
+            names += [f"body.{i}.rdb{r}.conv{k}" for k in range(1, 6)]
+    return names + ["conv_body", "conv_up1", "conv_up2", "conv_hr", "conv_last"]
+
+
+def rrdbnet_param_shapes(cfg: RrdbNetConfig) -> "OrderedDict[str, Tuple[int, ...]]":
+    """basicsr state-dict names and shapes, in the order the C ABI takes them (include/prx.h prx_rrdbnet_create)"""
+    f, g = cfg.num_feat, cfg.num_grow_ch
+    sh: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    for name in rrdbnet_conv_names(cfg):
+        if name == "conv_first":
+            cin, cout = 3, f
+        elif name == "conv_last":
+            cin, cout = f, 3
+        elif name.startswith("body."):
+            k = int(name[-1])
+            cin, cout = f + g * (k - 1), (f if k == 5 else g)
+        else:
+            cin, cout = f, f
+        sh[name + ".weight"] = (cout, cin, 3, 3)
+        sh[name + ".bias"] = (cout,)
+    return sh
+
+
+RRDBNET_LAST_STD = 0.35          # conv_last weight std * sqrt(fan_in): see synthetic_rrdbnet_params
+
+
+def synthetic_rrdbnet_params(cfg: RrdbNetConfig, seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
+    """Seeded weights of the real architecture (no checkpoint offline) under which a drawer does not start saturated.
+    Kaiming-scaled convolutions with basicsr's x0.1 on the dense blocks put ~90 % of the pre-clamp output outside [0,1] at 23
+    blocks, and the reason is the architecture's skips, not the convolutions: with small dense-block weights rdb3(rdb2(rdb1(x)))
+    is close to x, so every RRDB returns about 0.2 x + x and the trunk grows like 1.2 ** num_block (x66 at 23 blocks).  The
+    network is positively homogeneous in the trunk apart from its small biases, so conv_body is scaled by 1.2 ** -num_block:
+    what it adds to the first features is then O(1) at any depth, and conv_last maps the O(1) features to 0.5 +- ~0.3
+    (tests/test_super_resolution_host.py holds 2 % .. 30 % of the pre-clamp values outside [0,1] at 23 blocks, z ~ U[0,1]
+    16 x 16).  Every bias is non-zero."""
+    g = torch.Generator().manual_seed(seed + 2323)
+    out: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    for name, shape in rrdbnet_param_shapes(cfg).items():
+        base = name.rsplit(".", 1)[0]
+        if name.endswith("bias"):
+            out[name] = 0.02 * torch.randn(shape, generator=g) + (0.5 if base == "conv_last" else 0.0)
+            continue
+        std = math.sqrt(2.0 / (1.0 + 0.2 ** 2) / (shape[1] * 9))          # Kaiming for LeakyReLU(0.2)
+        if base.startswith("body."):
+            std *= 0.1                                                     # basicsr default_init_weights(scale=0.1)
+        elif base == "conv_body":
+            std *= 1.2 ** -cfg.num_block
+        elif base == "conv_last":
+            std = RRDBNET_LAST_STD / math.sqrt(shape[1] * 9)
+        out[name] = torch.randn(shape, generator=g) * std
+    return out
