@@ -501,13 +501,14 @@ int prx_cutouts_backward(const float* g_out, const double* desc, const unsigned 
  *   backward_finish(acc) -> g_cutouts [n,3,R,R] */
 typedef struct prx_clip_vit prx_clip_vit;
 typedef struct prx_clip_vit_config {
-    int input_resolution;  /* 224 */
-    int patch_size;        /* 32 */
-    int width;             /* 768 */
-    int layers;            /* 12 */
-    int heads;             /* 12 */
-    int output_dim;        /* 512 */
-    int max_batch;         /* capacity in cutouts */
+    int input_resolution;  /* 224; 336 (ViT-L/14@336px: 577 tokens) */
+    int patch_size;        /* 32 | 16 | 14 */
+    int width;             /* 768 | 1024 (ViT-L/14, ViT-L/14@336px) */
+    int layers;            /* 12 | 24 */
+    int heads;             /* 12 | 16 */
+    int output_dim;        /* 512 | 768 */
+    int max_batch;         /* capacity in cutouts: create allocates one forward's activations for this many; an allocation that fails
+                              is an error of the call (rc < 0, prx_last_error names the bytes), nothing stays allocated */
     int precision;         /* PRX_PREC_F16 | PRX_PREC_BF16 | PRX_PREC_F32 */
 } prx_clip_vit_config;
 int prx_clip_vit_create(prx_clip_vit** out, const prx_clip_vit_config* cfg, const float* const* weights, int n_weights,
@@ -561,7 +562,7 @@ int prx_clip_vit_backward_reduce(prx_clip_vit* h, const float* cutouts, const fl
 int prx_clip_vit_backward_finish(prx_clip_vit* h, const float* cutouts, const float* mm, const double* acc,
                                  float* g_cutouts, prx_stream_t s);
 
-/* --- CLIP_Base.encode_image for a ModifiedResNet visual tower (RN50x4, RN50, ...) [UPSTREAM clip/model.py: ModifiedResNet,
+/* --- CLIP_Base.encode_image for a ModifiedResNet visual tower (RN50, RN101, RN50x4, RN50x16, RN50x64) [UPSTREAM clip/model.py: ModifiedResNet,
  *     Bottleneck, AttentionPool2d].  Same call sequence and min/max contract as the ViT entry points above.
  * weights[]: fp32 device tensors with the eval-mode BatchNorms folded into their convolutions on the host
  *   (pixray_amd/weights.py::fold_clip_resnet_params, from the `visual.*` state dict):
@@ -571,12 +572,14 @@ int prx_clip_vit_backward_finish(prx_clip_vit* h, const float* cutouts, const fl
  *   attnpool.positional_embedding [(R/32)^2+1, 32w], in_proj {weight [3*32w, 32w] = q|k|v, bias}, c_proj {weight, bias}. */
 typedef struct prx_clip_resnet prx_clip_resnet;
 typedef struct prx_clip_resnet_config {
-    int input_resolution;  /* 288 (RN50x4) */
-    int width;             /* 80 */
-    int layers[4];         /* {4, 6, 10, 6} */
-    int heads;             /* 40 = width * 32 / 64 */
-    int output_dim;        /* 640 */
-    int max_batch;
+    int input_resolution;  /* 224 (RN50, RN101) | 288 (RN50x4) | 384 (RN50x16) | 448 (RN50x64); a multiple of 32 */
+    int width;             /* 64 | 80 | 96 | 128; width / 2 (the stem kernels' channel count) one of 8, 16, 32, 40, 48, 64 */
+    int layers[4];         /* {3,4,6,3} | {3,4,23,3} | {4,6,10,6} | {6,8,18,8} | {3,15,36,10} */
+    int heads;             /* width * 32 / 64: 32 | 40 | 48 | 64 (attention pool over (R/32)^2 + 1 = 50 | 82 | 145 | 197 tokens) */
+    int output_dim;        /* 1024 | 512 | 640 | 768 | 1024 */
+    int max_batch;         /* capacity in cutouts: create allocates one forward's activations for this many (RN50x64 at 448^2: 572 MiB
+                              per cutout with half operands, 1077 MiB with bf16, 1561 MiB in the exact mode); an allocation that fails
+                              is an error of the call (rc < 0, prx_last_error names the bytes), nothing stays allocated */
     int precision;         /* PRX_PREC_F16 | PRX_PREC_BF16 | PRX_PREC_F32 */
 } prx_clip_resnet_config;
 int prx_clip_resnet_create(prx_clip_resnet** out, const prx_clip_resnet_config* cfg, const float* const* weights, int n_weights,
@@ -665,8 +668,13 @@ int prx_k_vq_nearest(const float* z, long long tok_stride, long long ch_stride, 
                      prx_stream_t s);
 int prx_k_sqnorm_rows(const float* w, float* out, int rows, int D, prx_stream_t s);
 
-/* same attention for any sequence length (ViT-B/16: 197 tokens, ViT-L/14: 257): 64-token tiles, online softmax;
- * `out` and `lse` (fp32 [N*heads*T]) are kept for the backward */
+/* same attention for any sequence length T >= 1, head dim 64; `out` and `lse` (fp32 [N*heads*T]) are kept for the backward.  Two kernel
+ * families: workgroups per (image, head) with a wave per 32 tokens for T <= 640 (ViT-B/16 197 tokens, ViT-L/14 257, ViT-L/14@336px 577,
+ * the ModifiedResNet attention pools 50 ... 197), and one wave per 64-token tile with an online softmax for every larger T.
+ * prx_mha_route chooses the family of the following general-T calls of the process: -1 that rule (PRX_MHA_TILES=1 in the environment:
+ * tiles everywhere), 0 the workgroup family wherever it is able (T <= 640), 1 the tile kernels; it returns the previous setting.
+ * Both families are atomic-free and bit-reproducible. */
+int prx_mha_route(int route);
 int prx_k_mha_fwd_gen(const void* qkv, void* out, float* lse, int N, int T, int C, int heads, prx_stream_t s);
 int prx_k_mha_bwd_gen(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int N, int T, int C,
                       int heads, prx_stream_t s);

@@ -3,7 +3,8 @@ are exercised in tests with randomly initialised upstream-format state dicts; th
 
 * OpenAI CLIP (`clip.load(name)` state dict, slip.py:175): keys `visual.conv1.weight`, `visual.class_embedding`,
   `visual.positional_embedding`, `visual.ln_pre.*`, `visual.transformer.resblocks.{i}.*`, `visual.ln_post.*`,
-  `visual.proj` -> strip the `visual.` prefix (weights may be fp16 on CUDA: cast to fp32).
+  `visual.proj` -> strip the `visual.` prefix (weights may be fp16 on CUDA: cast to fp32).  The ModifiedResNet models (RN50 ...
+  RN50x64) carry `visual.conv{1,2,3}`, `visual.bn{1,2,3}.*`, `visual.layer{1..4}.{b}.*` and `visual.attnpool.*` instead.
 * HF `CLIPVisionModelWithProjection` -> the same names (q/k/v projections are concatenated into `in_proj_*`).
 * taming-transformers VQGAN Lightning checkpoint (`vqgan.py:124-140`): `state_dict` with `decoder.*`,
   `post_quant_conv.*`, `quantize.embedding.weight` for the decoder runner, plus `encoder.*` / `quant_conv.*` for the
@@ -19,8 +20,8 @@ from typing import Dict
 
 import torch
 
-from .weights import (ClipTextConfig, ClipVitConfig, VqganConfig, clip_text_param_shapes, clip_vit_param_shapes, slip_vit_param_shapes,
-                      vgg16_param_shapes, vqgan_encoder_param_shapes, vqgan_param_shapes)
+from .weights import (ClipResNetConfig, ClipTextConfig, ClipVitConfig, VqganConfig, clip_resnet_param_shapes, clip_text_param_shapes,
+                      clip_vit_param_shapes, slip_vit_param_shapes, vgg16_param_shapes, vqgan_encoder_param_shapes, vqgan_param_shapes)
 
 
 def _check(params: Dict[str, torch.Tensor], shapes) -> "OrderedDict[str, torch.Tensor]":
@@ -35,8 +36,13 @@ def _check(params: Dict[str, torch.Tensor], shapes) -> "OrderedDict[str, torch.T
     return out
 
 
-def clip_visual_from_openai(state_dict: Dict[str, torch.Tensor], cfg: ClipVitConfig):
+def clip_visual_from_openai(state_dict: Dict[str, torch.Tensor], cfg):
+    """visual side of an OpenAI CLIP state dict: the ViT towers' tensors in the order of `clip_vit_param_shapes`, or -- for a
+    ClipResNetConfig (RN50 ... RN50x64) -- the ModifiedResNet's in the order of `clip_resnet_param_shapes` (BatchNorm un-folded, its
+    `num_batches_tracked` counters dropped: ops.ClipResNetHandle folds)."""
     params = {k[len("visual."):]: v for k, v in state_dict.items() if k.startswith("visual.")}
+    if isinstance(cfg, ClipResNetConfig):
+        return _check(params, clip_resnet_param_shapes(cfg))
     return _check(params, clip_vit_param_shapes(cfg))
 
 
@@ -166,15 +172,34 @@ def clip_state_dict_from_archive(path: str) -> Dict[str, torch.Tensor]:
     return {k: v.detach() for k, v in sd.items()}
 
 
-def clip_config_from_state_dict(sd: Dict[str, torch.Tensor], name: str = "checkpoint") -> ClipVitConfig:
-    """`clip.model.build_model` reads the ViT geometry off the tensors' shapes; so does this (visual tower of the ViT family)."""
-    if "visual.proj" not in sd:
-        raise ValueError("not a CLIP ViT state dict (no visual.proj): ModifiedResNet towers are configured by name")
-    width = sd["visual.conv1.weight"].shape[0]
-    patch = sd["visual.conv1.weight"].shape[-1]
-    layers = len({k.split(".")[3] for k in sd if k.startswith("visual.transformer.resblocks.")})
-    grid = round((sd["visual.positional_embedding"].shape[0] - 1) ** 0.5)
-    return ClipVitConfig(name, patch * grid, patch, width, layers, width // 64, sd["visual.proj"].shape[1])
+def clip_config_from_state_dict(sd: Dict[str, torch.Tensor], name: str = "checkpoint"):
+    """`clip.model.build_model` reads the geometry off the tensors' shapes; so does this: a ClipVitConfig when the state dict has
+    `visual.proj`, else the ClipResNetConfig of a ModifiedResNet (width from `visual.layer1.0.conv1.weight`, blocks per layer counted,
+    resolution from the attention pool's positional embedding, heads = width * 32 // 64)."""
+    if "visual.proj" in sd:
+        width = sd["visual.conv1.weight"].shape[0]
+        patch = sd["visual.conv1.weight"].shape[-1]
+        layers = len({k.split(".")[3] for k in sd if k.startswith("visual.transformer.resblocks.")})
+        grid = round((sd["visual.positional_embedding"].shape[0] - 1) ** 0.5)
+        return ClipVitConfig(name, patch * grid, patch, width, layers, width // 64, sd["visual.proj"].shape[1])
+    for k in ("visual.layer1.0.conv1.weight", "visual.attnpool.positional_embedding", "visual.attnpool.c_proj.weight"):
+        if k not in sd:
+            raise KeyError(f"not a CLIP state dict: neither visual.proj (ViT) nor {k} (ModifiedResNet)")
+    width = sd["visual.layer1.0.conv1.weight"].shape[0]
+    layers = tuple(len({k.split(".")[2] for k in sd if k.startswith(f"visual.layer{b}.")}) for b in (1, 2, 3, 4))
+    grid = round((sd["visual.attnpool.positional_embedding"].shape[0] - 1) ** 0.5)
+    return ClipResNetConfig(name, grid * 32, width, layers, width * 32 // 64, sd["visual.attnpool.c_proj.weight"].shape[0])
+
+
+def clip_text_config_from_state_dict(sd: Dict[str, torch.Tensor], name: str = "checkpoint") -> ClipTextConfig:
+    """the text side of `clip.model.build_model`: width and heads (width // 64) from `ln_final`, layers counted"""
+    for k in ("token_embedding.weight", "positional_embedding", "ln_final.weight", "text_projection"):
+        if k not in sd:
+            raise KeyError(f"checkpoint is missing {k}")
+    width = sd["ln_final.weight"].shape[0]
+    layers = len({k.split(".")[2] for k in sd if k.startswith("transformer.resblocks.")})
+    return ClipTextConfig(name, sd["token_embedding.weight"].shape[0], sd["positional_embedding"].shape[0], width, layers, width // 64,
+                          sd["text_projection"].shape[1])
 
 
 def load_slip(path: str, cfg, text_cfg: ClipTextConfig):

@@ -11,11 +11,21 @@
 // fp16 CLIP towers, slip.py:175); the public entry points pick the instantiation from `h16`.
 #include "attention.h"
 #include <stdlib.h>
+#include <atomic>
 
-// PRX_MHA_TILES=1: route 64 < T <= 512 through the tile kernels as well (A/B measurements; keeps the T > 512 path tested)
-static bool prx_mha_force_tiles() {
-    static const bool v = [] { const char* e = getenv("PRX_MHA_TILES"); return e && e[0] == '1'; }();
-    return v;
+// Which family takes a general-T call.  The workgroup-per-(image, head) kernels (attention_kernels.inc, "blk") split a head over
+// gridDim.z workgroups of <= 5 waves, each streaming the head's whole K / V (or Q / dO), so nothing in them depends on T; they take
+// T <= MHA_BLK_MAX_T = 640 (ViT-L/14@336px: 577 tokens = 19 token blocks on 4 x 5 waves), the tile kernels everything longer.  At N = 32,
+// T = 577, 16 heads they measured 147 us forward / 441 us backward against the tile kernels' 623 / 3269 us.
+// prx_mha_route (include/prx.h) chooses the route of the NEXT calls: -1 the rule above (PRX_MHA_TILES=1 in the environment: tiles
+// everywhere, A/B measurements), 0 the workgroup family wherever it is able, 1 the tile kernels.
+constexpr int MHA_BLK_MAX_T = 640;
+static std::atomic<int> g_mha_route{-1};
+extern "C" int prx_mha_route(int route) { return g_mha_route.exchange(route < 0 ? -1 : (route ? 1 : 0)); }
+static bool prx_mha_blk_route(int T) {
+    static const bool env_tiles = [] { const char* e = getenv("PRX_MHA_TILES"); return e && e[0] == '1'; }();
+    const int route = g_mha_route.load(std::memory_order_relaxed);
+    return T <= MHA_BLK_MAX_T && route != 1 && !(route < 0 && env_tiles);
 }
 
 #define A16_NS att_bf16

@@ -608,12 +608,12 @@ __global__ __launch_bounds__(64) void mha_bwd_dkv_gen_kernel(const a16_t* __rest
 
 
 // ---------------------------------------------------------------------------------------------------------------
-// 64 < T <= 512 (ViT-B/16: 197, ViT-L/14: 257, RN50x4 attention pool: 82): one WORKGROUP per (image, head) with one
+// 64 < T <= 640 (ViT-B/16: 197, ViT-L/14: 257, ViT-L/14@336px: 577, the ModifiedResNet attention pools: 50 ... 197): workgroups per (image, head) with one
 // wave per 32 tokens, the register-resident scheme of the T <= 64 kernels above (scores with the owned tokens on the
 // lane columns, so that the probabilities are already the A operand of the second product) streamed over 128-token LDS
 // chunks of the other operand.  The tile kernels further below (one wave per 64-query tile, every wave re-staging and
 // re-transposing K / V for itself, 36-55 KB of LDS per wave) ran ViT-L/14 at 256 cutouts at 1.5 / 1.9 / 6.0 ms per
-// layer (forward / dQ / dK+dV: 2-3 waves per CU); they remain for T > 512 and for the causal text tower.
+// layer (forward / dQ / dK+dV: 2-3 waves per CU); they remain for T > 640 and for the causal text tower.
 //   forward : online softmax per owned query (running max / sum per lane); the rescale factors reach the O accumulators
 //             (queries on register rows) through a 32-float LDS line per wave
 //   backward: dQ kernel (owned queries, chunks of K / V / K^T) and dK+dV kernel (owned keys, chunks of Q / dO / Q^T /
@@ -968,7 +968,7 @@ inline int mha_bwd(const a16_t* qkv, const a16_t* dout, a16_t* dqkv, int N, int 
 
 inline int mha_fwd_gen(const a16_t* qkv, a16_t* out, float* lse, int N, int T, int C, int heads, hipStream_t s) {
     PRX_REQUIRE(C == heads * 64 && T >= 1, "mha(gen): needs head dim 64 (T=%d C=%d heads=%d)", T, C, heads);
-    if (T <= 512 && !prx_mha_force_tiles()) {       // workgroups of <= 5 waves per (image, head), one wave per 32 tokens
+    if (prx_mha_blk_route(T)) {       // workgroups of <= 5 waves per (image, head), one wave per 32 tokens
         const int nw = ceil_div(T, 32), nsplit = ceil_div(nw, 5), wpb = ceil_div(nw, nsplit);
         hipLaunchKernelGGL(mha_fwd_blk_kernel, dim3(heads, N, nsplit), dim3(64 * wpb), 0, s, qkv, out, lse, T, C, heads, 0.125f, prx_xcd_local());
         PRX_LAUNCH_CHECK();
@@ -988,7 +988,7 @@ inline int mha_fwd_causal(const a16_t* qkv, a16_t* out, int N, int T, int C, int
 inline int mha_bwd_gen(const a16_t* qkv, const a16_t* out, const a16_t* dout, const float* lse, a16_t* dqkv, int N, int T,
                     int C, int heads, hipStream_t s) {
     PRX_REQUIRE(C == heads * 64 && T >= 1, "mha(gen) bwd: needs head dim 64 (T=%d C=%d heads=%d)", T, C, heads);
-    if (T <= 512 && !prx_mha_force_tiles()) {
+    if (prx_mha_blk_route(T)) {
         const int nw = ceil_div(T, 32), nsplit = ceil_div(nw, 5), wpb = ceil_div(nw, nsplit);
         const dim3 g(heads, N, nsplit), b(64 * wpb);
         const int xcd = prx_xcd_local();

@@ -385,6 +385,7 @@ struct PrxResNet {
     float* gs;        // half mode: device {S, 1/S} = the power-of-two scale of the backward in flight (common.h) + 64 partials; else null
     GemmCtx gctx;     // this handle's engine state
     std::vector<void*> allocs;
+    size_t alloc_bytes = 0;              // device bytes this handle holds (weights + one forward's activations for max_n cutouts)
     float *w1, *b1;                      // stem conv1 (fp32, BN folded)
     RConv3 s2, s3;
     std::vector<RBlock> blocks;
@@ -398,21 +399,33 @@ struct PrxResNet {
 };
 
 namespace {
+// an allocation that fails is an error of the call (the handle under construction is freed by its guard), never an abort; the message
+// carries the figure: the runner keeps one forward's activations for max_n cutouts, so a smaller max_batch is the way out
+int ralloc_bytes(PrxResNet* r, void** p, size_t bytes) {
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        prx_set_error("resnet_create: device allocation of %zu bytes failed (%s) with %zu bytes already held by this handle: the runner keeps "
+                      "one forward's activations for max_batch = %d cutouts of %d x %d (width %d)", bytes, hipGetErrorString(e),
+                      r->alloc_bytes, r->max_n, r->res, r->res, r->width);
+        return -1;
+    }
+    r->allocs.push_back(q);
+    r->alloc_bytes += bytes;
+    *p = q;
+    return 0;
+}
 template <typename Tp>
 int ralloc(PrxResNet* r, Tp** p, size_t count) {
     void* q = nullptr;
-    PRX_CHECK_HIP(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(Tp)));
-    r->allocs.push_back(q);
+    if (int e = ralloc_bytes(r, &q, std::max<size_t>(count, 1) * sizeof(Tp))) return e;
     *p = (Tp*)q;
     return 0;
 }
 #define RALLOC(ptr, count) do { int _e = ralloc(r, &(ptr), (count)); if (_e) return _e; } while (0)
 int ralloc_op(PrxResNet* r, void** p, size_t count) {   // `count` operand elements
-    void* q = nullptr;
-    PRX_CHECK_HIP(hipMalloc(&q, std::max<size_t>(count, 1) * op_esz(r->f32)));
-    r->allocs.push_back(q);
-    *p = q;
-    return 0;
+    return ralloc_bytes(r, p, std::max<size_t>(count, 1) * op_esz(r->f32));
 }
 #define RALLOC_OP(ptr, count) do { int _e = ralloc_op(r, &(ptr), (count)); if (_e) return _e; } while (0)
 struct RCur { const float* const* w; int n, pos; };
@@ -473,7 +486,7 @@ int prx_resnet_create_impl(PrxResNet** out, int res, int width, const int* layer
     PRX_REQUIRE(res % 32 == 0 && width % 16 == 0 && max_n >= 1, "resnet_create: unsupported geometry (res %d width %d)", res, width);
     PRX_REQUIRE(width * 32 == heads * 64, "resnet_create: the attention pool needs head dim 64 (width %d heads %d)", width, heads);
     PrxResNet* r = new PrxResNet();
-    std::unique_ptr<PrxResNet> guard(r);
+    std::unique_ptr<PrxResNet, void (*)(PrxResNet*)> guard(r, prx_resnet_destroy_impl);      // a failed create frees what it allocated
     r->prec = precision; r->f32 = prec_is_f32(precision); r->h16 = prec_is_h16(precision);
     r->gs = nullptr;
     { const char* ev = getenv("PRX_RN_LEAN"); r->lean = (r->h16 && !(ev && atoi(ev) == 0)) ? 1 : 0; }

@@ -16,6 +16,7 @@
 #include "prompt_vq.h"
 #include "elementwise.h"
 #include <vector>
+#include <memory>
 
 namespace {
 
@@ -149,6 +150,7 @@ struct PrxVit {
     float* gs;        // half mode: device {S, 1/S} = the power-of-two scale of the backward in flight (common.h) + 64 partials; else null
     GemmCtx gctx;     // this handle's engine state (tile overrides, timing log)
     std::vector<void*> allocs;
+    size_t alloc_bytes = 0;  // device bytes this handle holds (weights + one forward's activations for max_n cutouts)
     void *Wp, *WpT, *projT, *proj;
     float *cls, *pos, *lnpre_g, *lnpre_b, *lnpost_g, *lnpost_b;
     std::vector<VitLayer> L;
@@ -173,21 +175,33 @@ struct PrxVit {
 };
 
 namespace {
+// an allocation that fails is an error of the call (the handle under construction is freed by its guard), never an abort; the message
+// carries the figure: the runner keeps one forward's activations for max_n cutouts, so a smaller max_batch is the way out
+int dev_alloc_bytes(PrxVit* v, void** p, size_t bytes) {
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        prx_set_error("vit_create: device allocation of %zu bytes failed (%s) with %zu bytes already held by this handle: the runner keeps one "
+                      "forward's activations for max_batch = %d cutouts of %d tokens (width %d, %d layers)", bytes, hipGetErrorString(e),
+                      v->alloc_bytes, v->max_n, v->T, v->width, v->layers);
+        return -1;
+    }
+    v->allocs.push_back(q);
+    v->alloc_bytes += bytes;
+    *p = q;
+    return 0;
+}
 template <typename Tp>
 int dev_alloc(PrxVit* v, Tp** p, size_t count) {
     void* q = nullptr;
-    PRX_CHECK_HIP(hipMalloc(&q, count * sizeof(Tp)));
-    v->allocs.push_back(q);
+    if (int e = dev_alloc_bytes(v, &q, count * sizeof(Tp))) return e;
     *p = (Tp*)q;
     return 0;
 }
 #define ALLOC(ptr, count) do { int _r = dev_alloc(v, &(ptr), (count)); if (_r) return _r; } while (0)
 int dev_alloc_op(PrxVit* v, void** p, size_t count) {   // `count` operand elements
-    void* q = nullptr;
-    PRX_CHECK_HIP(hipMalloc(&q, count * op_esz(v->f32)));
-    v->allocs.push_back(q);
-    *p = q;
-    return 0;
+    return dev_alloc_bytes(v, p, count * op_esz(v->f32));
 }
 #define ALLOC_OP(ptr, count) do { int _r = dev_alloc_op(v, &(ptr), (count)); if (_r) return _r; } while (0)
 
@@ -228,6 +242,8 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
     const int G = res / patch;
     const int T = G * G + 1;
     PrxVit* v = new PrxVit();
+    std::unique_ptr<PrxVit, void (*)(PrxVit*)> guard(v, prx_vit_destroy_impl);      // a failed create frees what it allocated
+    v->T = T; v->max_n = max_n;
     v->res = res; v->patch = patch; v->width = width; v->layers = layers; v->heads = heads; v->out_dim = out_dim;
     v->prec = precision; v->f32 = prec_is_f32(precision); v->h16 = prec_is_h16(precision);
     v->gs = nullptr; v->fam = fam; v->bp = nullptr; v->hd = hd; v->aw = heads * 64;
@@ -328,7 +344,7 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
     if (v->h16) ALLOC(v->gs, 2 + 64);
     v->ws_bytes = (size_t)64 << 20;
     ALLOC(v->ws, v->ws_bytes / sizeof(float));
-    *out = v;
+    *out = guard.release();
     return 0;
 }
 

@@ -120,7 +120,8 @@ def _weights_in_abi_order(params, shapes, device, what):
 
 
 class ClipVitHandle:
-    """Owns a `prx_clip_vit` (packed weights + activation workspace for `max_batch` cutouts).
+    """Owns a `prx_clip_vit` (packed weights + activation workspace for `max_batch` cutouts, allocated at create time; an allocation
+    that fails raises PrxError with the bytes asked for and held, and the partly built handle is freed).
     `precision`: "fp16" (default) / "bf16" (fast paths) or "f32" (exact-f32 MFMA parity mode, include/prx.h PRX_PREC_*)."""
     abi = "prx_clip_vit"
 
@@ -193,8 +194,14 @@ class _ClipResNetCfg(ctypes.Structure):
 
 
 class ClipResNetHandle:
-    """Owns a `prx_clip_resnet` (CLIP ModifiedResNet tower: RN50x4, ...); same protocol as ClipVitHandle.  `params` is
-    the OpenAI `visual.*` state dict (BatchNorm un-folded); the fold happens here."""
+    """Owns a `prx_clip_resnet` (CLIP ModifiedResNet tower: RN50, RN101, RN50x4, RN50x16, RN50x64); same protocol as ClipVitHandle.
+    `params` is the OpenAI `visual.*` state dict (BatchNorm un-folded); the fold happens here.
+
+    The runner allocates one forward's activations (and the backward's gradient streams) for `max_batch` cutouts when it is created.
+    For RN50x64 at 448 x 448 that is 599 467 264 bytes (572 MiB) per cutout with IEEE-half operands (the default), 1 129 325 824
+    (1077 MiB) with bf16 and 1 636 394 240 (1561 MiB) in the exact-f32 mode, beside 1.7 GB (half) of packed weights: 35.7 GiB at
+    max_batch = 64 in the default mode.  RN50x16 at 384 x 384 takes 262 / 470 / 683 MiB per cutout.  An allocation that fails raises
+    PrxError with the bytes asked for and the bytes held so far; the partly built handle is freed and the process goes on."""
     abi = "prx_clip_resnet"
 
     def __init__(self, cfg, params, max_batch: int, device, precision=None):

@@ -144,36 +144,42 @@ def slip_checkpoint_path(name, root="models"):
     return path if os.path.exists(path) else None
 
 
-def get_clip_perceptor(clip_model_name, device, params=None, max_batch=64, seed=0, group=None, text_params=None,
-                       tokenizer=None, precision=None):
-    """slip.py:173-186 equivalent for the ViT family; `params` is an OpenAI `visual.*` state dict and `text_params` the
-    text-side entries of the same checkpoint (random-init weights of the real architectures are synthesised when none
-    are given: no checkpoints exist offline).  `precision`: "fp16" (default) | "bf16" (fast paths) | "f32" (exact-f32 MFMA parity mode)."""
-    if clip_model_name in CLIP_RESNET_CONFIGS:
-        cfg = CLIP_RESNET_CONFIGS[clip_model_name]
-        if params is None:
-            params = synthetic_clip_resnet_params(cfg, seed)
-        return ClipVitPerceptor(cfg, params, device, max_batch=max_batch, group=group, text_cfg=CLIP_TEXT_CONFIGS.get(clip_model_name),
-                                text_params=text_params, tokenizer=tokenizer, seed=seed, precision=precision)
+def clip_perceptor_config(clip_model_name):
+    """-> (vision configuration, text configuration or None) of a perceptor name: every `clip.available_models()` name (RN50, RN101,
+    RN50x4, RN50x16, RN50x64, ViT-B/32, ViT-B/16, ViT-L/14, ViT-L/14@336px), the SLIP family and the reduced test towers.  Needs no device:
+    the front end reads the cutout size of a name from here before any tower exists."""
     if clip_model_name in SLIP_REFUSED:
         raise ValueError(SLIP_REFUSED[clip_model_name])
+    for table in (CLIP_RESNET_CONFIGS, SLIP_CONFIGS, CLIP_CONFIGS):
+        if clip_model_name in table:
+            return table[clip_model_name], CLIP_TEXT_CONFIGS.get(clip_model_name)
+    raise KeyError(f"unknown / unsupported perceptor {clip_model_name!r} "
+                   f"(supported: {sorted(CLIP_CONFIGS) + sorted(CLIP_RESNET_CONFIGS) + sorted(SLIP_CONFIGS)})")
+
+
+def get_clip_perceptor(clip_model_name, device, params=None, max_batch=64, seed=0, group=None, text_params=None,
+                       tokenizer=None, precision=None):
+    """slip.py:173-186 equivalent; `params` is an OpenAI `visual.*` state dict and `text_params` the
+    text-side entries of the same checkpoint (random-init weights of the real architectures are synthesised when none
+    are given: no checkpoints exist offline).  `precision`: "fp16" (default) | "bf16" (fast paths) | "f32" (exact-f32 MFMA parity mode)."""
+    cfg, text_cfg = clip_perceptor_config(clip_model_name)
+    if clip_model_name in CLIP_RESNET_CONFIGS:
+        if params is None:
+            params = synthetic_clip_resnet_params(cfg, seed)
+        return ClipVitPerceptor(cfg, params, device, max_batch=max_batch, group=group, text_cfg=text_cfg,
+                                text_params=text_params, tokenizer=tokenizer, seed=seed, precision=precision)
     if clip_model_name in SLIP_CONFIGS:           # slip.py:183-184: every name that is not an OpenAI CLIP model is a SLIP_Base
-        cfg = SLIP_CONFIGS[clip_model_name]
         if params is None:
             ckpt = slip_checkpoint_path(clip_model_name)
             if ckpt is not None:
                 from .checkpoints import load_slip
-                params, ckpt_text = load_slip(ckpt, cfg, CLIP_TEXT_CONFIGS[clip_model_name])
+                params, ckpt_text = load_slip(ckpt, cfg, text_cfg)
                 text_params = text_params if text_params is not None else ckpt_text
             else:
                 params = synthetic_slip_vit_params(cfg, seed)
-        return SlipPerceptor(cfg, params, device, max_batch=max_batch, group=group, text_cfg=CLIP_TEXT_CONFIGS.get(clip_model_name),
+        return SlipPerceptor(cfg, params, device, max_batch=max_batch, group=group, text_cfg=text_cfg,
                              text_params=text_params, tokenizer=tokenizer, seed=seed, precision=precision)
-    if clip_model_name not in CLIP_CONFIGS:
-        raise KeyError(f"unknown / unsupported perceptor {clip_model_name!r} "
-                       f"(supported: {sorted(CLIP_CONFIGS) + sorted(CLIP_RESNET_CONFIGS) + sorted(SLIP_CONFIGS)})")
-    cfg = CLIP_CONFIGS[clip_model_name]
     if params is None:
         params = synthetic_clip_vit_params(cfg, seed)
-    return ClipVitPerceptor(cfg, params, device, max_batch=max_batch, group=group, text_cfg=CLIP_TEXT_CONFIGS.get(clip_model_name),
+    return ClipVitPerceptor(cfg, params, device, max_batch=max_batch, group=group, text_cfg=text_cfg,
                             text_params=text_params, tokenizer=tokenizer, seed=seed, precision=precision)

@@ -218,6 +218,7 @@ CLIP_CONFIGS = {
     "ViT-B/32": ClipVitConfig(),
     "ViT-B/16": ClipVitConfig("ViT-B/16", 224, 16, 768, 12, 12, 512),
     "ViT-L/14": ClipVitConfig("ViT-L/14", 224, 14, 1024, 24, 16, 768),
+    "ViT-L/14@336px": ClipVitConfig("ViT-L/14@336px", 336, 14, 1024, 24, 16, 768),       # 577 tokens
     # reduced tower (same operators, 2 layers) for fast parity tests
     "tiny-B/32": ClipVitConfig("tiny-B/32", 224, 32, 256, 2, 4, 128),
 }
@@ -384,10 +385,13 @@ CLIP_TEXT_CONFIGS = {
     "ViT-B/32": ClipTextConfig(),
     "ViT-B/16": ClipTextConfig("ViT-B/16"),
     "ViT-L/14": ClipTextConfig("ViT-L/14", width=768, heads=12, output_dim=768),
+    "ViT-L/14@336px": ClipTextConfig("ViT-L/14@336px", width=768, heads=12, output_dim=768),
     "tiny-B/32": ClipTextConfig("tiny-B/32", vocab_size=1000, context_length=77, width=256, layers=2, heads=4, output_dim=128),
     "RN50x4": ClipTextConfig("RN50x4", width=640, heads=10, output_dim=640),
     "RN50": ClipTextConfig("RN50", width=512, heads=8, output_dim=1024),
     "RN101": ClipTextConfig("RN101", width=512, heads=8, output_dim=512),
+    "RN50x16": ClipTextConfig("RN50x16", width=768, heads=12, output_dim=768),
+    "RN50x64": ClipTextConfig("RN50x64", width=1024, heads=16, output_dim=1024),
 }
 # every SLIP model size carries CLIP's text transformer at width 512 / 8 heads / 12 layers [UPSTREAM SLIP models.py]
 CLIP_TEXT_CONFIGS.update({n: ClipTextConfig(n) for n in ("SLIP_VITS16", "SLIP_VITB16", "SLIP_VITL16", "SLIP_CC3M", "SLIP_CC12M",
@@ -444,7 +448,7 @@ def synthetic_clip_text_params(cfg: ClipTextConfig, seed: int = 0) -> "OrderedDi
     return out
 
 
-# --------------------------------------------------------------------------- CLIP ModifiedResNet config (RN50x4, ...)
+# --------------------------------------------------------------------------- CLIP ModifiedResNet config (RN50x4, RN50x16, ...)
 @dataclass
 class ClipResNetConfig:
     name: str = "RN50x4"
@@ -467,6 +471,8 @@ CLIP_RESNET_CONFIGS = {
     "RN50x4": ClipResNetConfig(),
     "RN50": ClipResNetConfig("RN50", 224, 64, (3, 4, 6, 3), 32, 1024),
     "RN101": ClipResNetConfig("RN101", 224, 64, (3, 4, 23, 3), 32, 512),      # quality `supreme` names it (pixray.py:1830)
+    "RN50x16": ClipResNetConfig("RN50x16", 384, 96, (6, 8, 18, 8), 48, 768),           # 145 pool tokens, embed 3072
+    "RN50x64": ClipResNetConfig("RN50x64", 448, 128, (3, 15, 36, 10), 64, 1024),      # 197 pool tokens, embed 4096
     # reduced tower with the same operator mix (stem, stride-1 and stride-2 bottlenecks, attention pool)
     "tiny-RN": ClipResNetConfig("tiny-RN", 96, 16, (1, 2, 1, 1), 8, 64),
 }
