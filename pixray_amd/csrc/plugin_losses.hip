@@ -235,17 +235,18 @@ __global__ __launch_bounds__(PLUG_THREADS) void palette_kernel(const float* __re
 // ---------------------------------------------------------------------------------------------------------------- smoothness
 // torch.gradient along an axis of length L (uniform spacing): g[i] = sum_j coef(i, j) f[j], |i - j| <= 2.  Interior: central
 // difference; the two end points one-sided, first or second order.  The backward is the transpose: df[j] = sum_i coef(i, j) u[i].
-__device__ __forceinline__ float grad_coef(int i, int j, int L, int eo, float inv_h) {
+template <typename T>
+__device__ __forceinline__ T grad_coef(int i, int j, int L, int eo, T inv_h) {
     const int d = j - i;
     if (i == 0) {
-        if (eo == 1) return d == 0 ? -inv_h : (d == 1 ? inv_h : 0.f);
-        return d == 0 ? -1.5f * inv_h : (d == 1 ? 2.f * inv_h : (d == 2 ? -0.5f * inv_h : 0.f));
+        if (eo == 1) return d == 0 ? -inv_h : (d == 1 ? inv_h : T(0));
+        return d == 0 ? T(-1.5) * inv_h : (d == 1 ? T(2) * inv_h : (d == 2 ? T(-0.5) * inv_h : T(0)));
     }
     if (i == L - 1) {
-        if (eo == 1) return d == 0 ? inv_h : (d == -1 ? -inv_h : 0.f);
-        return d == 0 ? 1.5f * inv_h : (d == -1 ? -2.f * inv_h : (d == -2 ? 0.5f * inv_h : 0.f));
+        if (eo == 1) return d == 0 ? inv_h : (d == -1 ? -inv_h : T(0));
+        return d == 0 ? T(1.5) * inv_h : (d == -1 ? T(-2) * inv_h : (d == -2 ? T(0.5) * inv_h : T(0)));
     }
-    return d == 1 ? 0.5f * inv_h : (d == -1 ? -0.5f * inv_h : 0.f);
+    return d == 1 ? T(0.5) * inv_h : (d == -1 ? T(-0.5) * inv_h : T(0));
 }
 
 // The reference's view: cutouts [n][3][h][w] -> pixels [n*h][w][3]; rows run through all cutouts (row r is row r % h of cutout
@@ -257,42 +258,47 @@ struct SmoothView {
         const int b = r / h, y = r - b * h;
         return x[(((size_t)b * 3 + ch) * h + y) * w + c];
     }
-    // the two gradients of channel ch at (r, c)
-    __device__ __forceinline__ void grads(int r, int c, int ch, int eo, float inv_h, float& gy, float& gx) const {
+    // the two gradients of channel ch at (r, c), in T = float (backward) or double (forward)
+    template <typename T>
+    __device__ __forceinline__ void grads(int r, int c, int ch, int eo, T inv_h, T& gy, T& gx) const {
         const int R = n * h;
-        gy = 0.f; gx = 0.f;
+        gy = T(0); gx = T(0);
         for (int d = -2; d <= 2; ++d) {
             const int rr = r + d, cc = c + d;
-            if (rr >= 0 && rr < R) { const float k = grad_coef(r, rr, R, eo, inv_h); if (k != 0.f) gy += k * at(rr, c, ch); }
-            if (cc >= 0 && cc < w) { const float k = grad_coef(c, cc, w, eo, inv_h); if (k != 0.f) gx += k * at(r, cc, ch); }
+            if (rr >= 0 && rr < R) { const T k = grad_coef(r, rr, R, eo, inv_h); if (k != T(0)) gy += k * (T)at(rr, c, ch); }
+            if (cc >= 0 && cc < w) { const T k = grad_coef(c, cc, w, eo, inv_h); if (k != T(0)) gx += k * (T)at(r, cc, ch); }
         }
     }
 };
 
 // per pixel: s = |(gy, gx) over 3 channels|, v = s | min(s, 0.5) | log(1 + s); loss = w * mean v.
-// tfac[pixel] = dv/ds / s (0 where s == 0: the zero subgradient at a flat pixel, where the reference's sqrt gives NaN)
+// tfac[pixel] = dv/ds / s (0 where s == 0: the zero subgradient at a flat pixel, where the reference's sqrt gives NaN).
+// The pixel is evaluated in double (stencil with 1 / spacing formed in double, root, logarithm): with fp32 values the scalar was the sum
+// of per-pixel roundings plus its own conversion, up to 1.5 * 2^-24 off on a 3 x 3 cutout; now it is the fp32 rounding of the float64 sum,
+// the best an fp32 result can be, and tfac is rounded once.  15 loads per channel dominate either way.
 __global__ __launch_bounds__(PLUG_THREADS) void smoothness_fwd_kernel(const float* __restrict__ x, int n, int h, int w, int type, int eo,
-                                                                      float inv_h, float weight, double* __restrict__ partials,
+                                                                      float spacing, float weight, double* __restrict__ partials,
                                                                       float* __restrict__ tfac, float* __restrict__ loss,
                                                                       unsigned* __restrict__ ticket) {
     const SmoothView V{x, n, h, w};
     const long long N = (long long)n * h * w;
+    const double inv_h = 1.0 / (double)spacing;
     double v[1] = {0.0};
     for (long long p = (long long)blockIdx.x * PLUG_THREADS + threadIdx.x; p < N; p += (long long)gridDim.x * PLUG_THREADS) {
         const int r = (int)(p / w), c = (int)(p - (long long)r * w);
-        float ss = 0.f;
+        double ss = 0.0;
         for (int ch = 0; ch < 3; ++ch) {
-            float gy, gx;
+            double gy, gx;
             V.grads(r, c, ch, eo, inv_h, gy, gx);
             ss += gy * gy + gx * gx;
         }
-        const float s = sqrtf(ss);
-        float val, dv;
-        if (type == 1) { val = fminf(s, 0.5f); dv = s <= 0.5f ? 1.f : 0.f; }
-        else if (type == 2) { val = logf(1.f + s); dv = 1.f / (1.f + s); }
-        else { val = s; dv = 1.f; }
+        const double s = sqrt(ss);
+        double val, dv;
+        if (type == 1) { val = fmin(s, 0.5); dv = s <= 0.5 ? 1.0 : 0.0; }
+        else if (type == 2) { val = log(1.0 + s); dv = 1.0 / (1.0 + s); }
+        else { val = s; dv = 1.0; }
         v[0] += val;
-        tfac[p] = s > 0.f ? dv / s : 0.f;
+        tfac[p] = s > 0.0 ? (float)(dv / s) : 0.f;
     }
     if (plug_reduce<1>(v, partials, ticket)) *loss = (float)(v[0] / (double)N * (double)weight);
 }
@@ -442,7 +448,7 @@ int plug_smoothness_fwd(const float* x, int n, int h, int w, int type, int edge_
     PRX_REQUIRE(x && partials && tfac && loss && ticket && n > 0, "smoothness: bad arguments");
     PRX_REQUIRE((edge_order == 1 || edge_order == 2) && h > edge_order && w > edge_order && spacing != 0.f && type >= 0 && type <= 2,
                 "smoothness: edge order %d on %d x %d, type %d", edge_order, h, w, type);
-    hipLaunchKernelGGL(smoothness_fwd_kernel, dim3(plug_blocks((long long)n * h * w)), dim3(PLUG_THREADS), 0, s, x, n, h, w, type, edge_order, 1.f / spacing, weight,
+    hipLaunchKernelGGL(smoothness_fwd_kernel, dim3(plug_blocks((long long)n * h * w)), dim3(PLUG_THREADS), 0, s, x, n, h, w, type, edge_order, spacing, weight,
                        partials, tfac, loss, ticket);
     PRX_LAUNCH_CHECK();
     return 0;

@@ -36,11 +36,12 @@ def emu():
         import test_kernels_runner_gpu as tr
         import test_kernels_cutouts_gpu as tc
         import test_kernels_strotss_gpu as ts
+        import test_kernels_select_gpu as tsel
         import test_path_gpu as tp
-        for m in (tk, th, tr, tc, ts, tp):
+        for m in (tk, th, tr, tc, ts, tsel, tp):
             m.DEV = "cpu"
-        yield types_ns(lib=lib, tk=tk, th=th, tr=tr, tc=tc, ts=ts, tp=tp)
-        for m in (tk, th, tr, tc, ts, tp):
+        yield types_ns(lib=lib, tk=tk, th=th, tr=tr, tc=tc, ts=ts, tsel=tsel, tp=tp)
+        for m in (tk, th, tr, tc, ts, tsel, tp):
             m.DEV = "cuda"
 
 
@@ -250,6 +251,15 @@ def test_strotss_and_hypercolumn_kernels_one_stage_at_a_time(emu):
     the 12-map hyper-column case, each against float64"""
     figs = emu.ts.emu_subset()
     assert any(k.startswith("remd-bwd/straddle") for k in figs) and any(k.startswith("hypercol-bwd/") for k in figs)
+
+
+def test_prompt_vq_palette_and_smoothness_kernels_at_their_switch_points(emu):
+    """tests/test_kernels_select_gpu.py on the emulated kernels, every case: the prompt loss on both sides of `stop`, on an exact tie, at
+    planted angles, on a row parallel to the embed and on zero rows; the nearest-code search at ragged shapes in both layouts with planted
+    exact ties inside a thread, across threads, tiles and the select loop; the palette loss and the colour lookup with duplicate and
+    equidistant entries; the smoothness stencils at the smallest size, across cutouts, on a flat patch and around the kink; the refusals"""
+    figs = emu.tsel.emu_subset()
+    assert any(k.startswith("prompt-tie/") for k in figs) and any(k.startswith("smooth-flat-") for k in figs)
 
 
 # ------------------------------------------------------------------------------------------------ the path's own ops
