@@ -508,7 +508,8 @@ typedef struct prx_clip_vit_config {
     int heads;             /* 12 | 16 */
     int output_dim;        /* 512 | 768 */
     int max_batch;         /* capacity in cutouts: create allocates one forward's activations for this many; an allocation that fails
-                              is an error of the call (rc < 0, prx_last_error names the bytes), nothing stays allocated */
+                              is an error of the call (rc < 0, prx_last_error names the bytes asked for and the bytes held), nothing stays
+                              allocated -- as in every prx_*_create: a handle frees its device memory on every path (csrc/dev_arena.h) */
     int precision;         /* PRX_PREC_F16 | PRX_PREC_BF16 | PRX_PREC_F32 */
 } prx_clip_vit_config;
 int prx_clip_vit_create(prx_clip_vit** out, const prx_clip_vit_config* cfg, const float* const* weights, int n_weights,
@@ -579,7 +580,8 @@ typedef struct prx_clip_resnet_config {
     int output_dim;        /* 1024 | 512 | 640 | 768 | 1024 */
     int max_batch;         /* capacity in cutouts: create allocates one forward's activations for this many (RN50x64 at 448^2: 572 MiB
                               per cutout with half operands, 1077 MiB with bf16, 1561 MiB in the exact mode); an allocation that fails
-                              is an error of the call (rc < 0, prx_last_error names the bytes), nothing stays allocated */
+                              is an error of the call (rc < 0, prx_last_error names the bytes asked for and the bytes held), nothing stays
+                              allocated -- as in every prx_*_create (prx_fft_drawer_create returns null) */
     int precision;         /* PRX_PREC_F16 | PRX_PREC_BF16 | PRX_PREC_F32 */
 } prx_clip_resnet_config;
 int prx_clip_resnet_create(prx_clip_resnet** out, const prx_clip_resnet_config* cfg, const float* const* weights, int n_weights,

@@ -10,6 +10,7 @@
 #include "attention.h"
 #include "elementwise.h"
 #include "vit.h"  // prx_pack_* helpers
+#include "dev_arena.h"
 #include <vector>
 #include <memory>
 
@@ -63,7 +64,7 @@ int prx_gather_rows(const float* x, const int* eot, float* out, int n, int ctx, 
 
 struct PrxClipText {
     int vocab, ctx, width, layers, heads, out_dim, max_n;
-    std::vector<void*> allocs;
+    DevArena mem;     // every device buffer below: freed with the handle
     float *tok, *pos, *lnf_g, *lnf_b;
     bf16_t* projT;
     std::vector<TextLayer> L;
@@ -74,22 +75,8 @@ struct PrxClipText {
 };
 
 namespace {
-template <typename Tp>
-int talloc(PrxClipText* t, Tp** p, size_t count) {
-    void* q = nullptr;
-    PRX_CHECK_HIP(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(Tp)));
-    t->allocs.push_back(q);
-    *p = (Tp*)q;
-    return 0;
-}
-#define TALLOC(ptr, count) do { int _r = talloc(t, &(ptr), (count)); if (_r) return _r; } while (0)
-int tcopy(PrxClipText* t, float** dst, const float* src, size_t n, hipStream_t s) {
-    TALLOC(*dst, n);
-    PRX_CHECK_HIP(hipMemcpyAsync(*dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return 0;
-}
 int tpack(PrxClipText* t, bf16_t** W, const float* src, size_t n, hipStream_t s) {
-    TALLOC(*W, n);
+    DEV_ALLOC(t->mem, alloc, *W, n);
     return prx_pack_bf16(src, *W, n, s);
 }
 int tg(PrxClipText* t, GemmDesc& d, hipStream_t s) { return prx_gemm_launch(d, t->ws, t->ws_bytes, s); }
@@ -101,50 +88,51 @@ int prx_clip_text_create_impl(PrxClipText** out, int vocab, int ctx, int width, 
                               const float* const* w, int n_w, hipStream_t s) {
     PRX_REQUIRE(n_w == 2 + 12 * layers + 3, "clip_text_create: expected %d weight tensors, got %d", 2 + 12 * layers + 3, n_w);
     PRX_REQUIRE(width == heads * 64 && width % 256 == 0 && ctx >= 1 && vocab >= 1 && max_n >= 1, "clip_text_create: unsupported geometry");
-    PrxClipText* t = new PrxClipText();
-    std::unique_ptr<PrxClipText> guard(t);
+    std::unique_ptr<PrxClipText> guard(new PrxClipText());      // a failed create frees what it allocated (DevArena)
+    PrxClipText* t = guard.get();
+    DevArena& m = t->mem;
+    m.describe("clip_text_create", ": the text tower keeps one forward's activations for max_batch = %d sequences of %d tokens (width %d, %d layers)",
+                    max_n, ctx, width, layers);
     t->vocab = vocab; t->ctx = ctx; t->width = width; t->layers = layers; t->heads = heads; t->out_dim = out_dim; t->max_n = max_n;
     const int W = width;
     int r;
-    if ((r = tcopy(t, &t->tok, w[0], (size_t)vocab * W, s))) return r;
-    if ((r = tcopy(t, &t->pos, w[1], (size_t)ctx * W, s))) return r;
+    if ((r = m.copy_f32(&t->tok, w[0], (size_t)vocab * W, s))) return r;
+    if ((r = m.copy_f32(&t->pos, w[1], (size_t)ctx * W, s))) return r;
     t->L.resize(layers);
     for (int l = 0; l < layers; ++l) {
         const float* const* q = w + 2 + 12 * l;
         TextLayer& y = t->L[l];
-        if ((r = tcopy(t, &y.ln1_g, q[0], W, s))) return r;
-        if ((r = tcopy(t, &y.ln1_b, q[1], W, s))) return r;
+        if ((r = m.copy_f32(&y.ln1_g, q[0], W, s))) return r;
+        if ((r = m.copy_f32(&y.ln1_b, q[1], W, s))) return r;
         if ((r = tpack(t, &y.Wqkv, q[2], (size_t)3 * W * W, s))) return r;
-        if ((r = tcopy(t, &y.bqkv, q[3], 3 * W, s))) return r;
+        if ((r = m.copy_f32(&y.bqkv, q[3], 3 * W, s))) return r;
         if ((r = tpack(t, &y.Wo, q[4], (size_t)W * W, s))) return r;
-        if ((r = tcopy(t, &y.bo, q[5], W, s))) return r;
-        if ((r = tcopy(t, &y.ln2_g, q[6], W, s))) return r;
-        if ((r = tcopy(t, &y.ln2_b, q[7], W, s))) return r;
+        if ((r = m.copy_f32(&y.bo, q[5], W, s))) return r;
+        if ((r = m.copy_f32(&y.ln2_g, q[6], W, s))) return r;
+        if ((r = m.copy_f32(&y.ln2_b, q[7], W, s))) return r;
         if ((r = tpack(t, &y.W1, q[8], (size_t)4 * W * W, s))) return r;
-        if ((r = tcopy(t, &y.b1, q[9], 4 * W, s))) return r;
+        if ((r = m.copy_f32(&y.b1, q[9], 4 * W, s))) return r;
         if ((r = tpack(t, &y.W2, q[10], (size_t)4 * W * W, s))) return r;
-        if ((r = tcopy(t, &y.b2, q[11], W, s))) return r;
+        if ((r = m.copy_f32(&y.b2, q[11], W, s))) return r;
     }
     const float* const* q = w + 2 + 12 * layers;
-    if ((r = tcopy(t, &t->lnf_g, q[0], W, s))) return r;
-    if ((r = tcopy(t, &t->lnf_b, q[1], W, s))) return r;
-    TALLOC(t->projT, (size_t)W * out_dim);                       // x @ proj[W, out]: Bt = proj^T [out, W]
+    if ((r = m.copy_f32(&t->lnf_g, q[0], W, s))) return r;
+    if ((r = m.copy_f32(&t->lnf_b, q[1], W, s))) return r;
+    DEV_ALLOC(m, alloc, t->projT, (size_t)W * out_dim);                       // x @ proj[W, out]: Bt = proj^T [out, W]
     if ((r = prx_pack_transpose_bf16(q[2], t->projT, W, out_dim, s))) return r;
     const size_t R = (size_t)max_n * ctx;
-    TALLOC(t->x, R * W); TALLOC(t->x_mid, R * W); TALLOC(t->rows, (size_t)max_n * W); TALLOC(t->mean, R); TALLOC(t->rstd, R);
-    TALLOC(t->h, R * W); TALLOC(t->qkv, R * 3 * W); TALLOC(t->att, R * W); TALLOC(t->u, R * 4 * W); TALLOC(t->hpost, (size_t)max_n * W);
-    TALLOC(t->eot, max_n);
+    DEV_ALLOC(m, alloc, t->x, R * W); DEV_ALLOC(m, alloc, t->x_mid, R * W); DEV_ALLOC(m, alloc, t->rows, (size_t)max_n * W);
+    DEV_ALLOC(m, alloc, t->mean, R); DEV_ALLOC(m, alloc, t->rstd, R);
+    DEV_ALLOC(m, alloc, t->h, R * W); DEV_ALLOC(m, alloc, t->qkv, R * 3 * W); DEV_ALLOC(m, alloc, t->att, R * W);
+    DEV_ALLOC(m, alloc, t->u, R * 4 * W); DEV_ALLOC(m, alloc, t->hpost, (size_t)max_n * W);
+    DEV_ALLOC(m, alloc, t->eot, max_n);
     t->ws_bytes = (size_t)16 << 20;
-    TALLOC(t->ws, t->ws_bytes / sizeof(float));
+    DEV_ALLOC(m, alloc, t->ws, t->ws_bytes / sizeof(float));
     *out = guard.release();
     return 0;
 }
 
-void prx_clip_text_destroy_impl(PrxClipText* t) {
-    if (!t) return;
-    for (void* p : t->allocs) (void)hipFree(p);
-    delete t;
-}
+void prx_clip_text_destroy_impl(PrxClipText* t) { delete t; }
 
 // tokens: int32 [n, ctx] (what clip.tokenize returns, zero padded after the EOT token) -> embeds fp32 [n, out_dim],
 // NOT normalised (CLIP_Base.encode_text returns the raw projection, slip.py:68-70; Prompt normalises, pixray.py:276)

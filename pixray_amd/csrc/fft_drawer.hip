@@ -26,7 +26,9 @@
 #include "../../include/prx.h"
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <vector>
+#include "dev_arena.h"
 
 namespace {
 inline int up4(int v) { return (v + 3) & ~3; }
@@ -201,11 +203,12 @@ struct prx_fft_drawer {
     size_t ws_bytes = 0;
     float contrast = 0.9f;
     GemmCtx gctx;
+    DevArena mem;                // every device buffer above: freed with the handle
 };
 
 namespace {
-int upload(float** dst, const std::vector<float>& v) {
-    PRX_CHECK_HIP(hipMalloc(dst, v.size() * sizeof(float)));
+int upload(prx_fft_drawer* h, float** dst, const std::vector<float>& v) {
+    DEV_ALLOC(h->mem, alloc, *dst, v.size());
     PRX_CHECK_HIP(hipMemcpy(*dst, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
     return 0;
 }
@@ -217,13 +220,9 @@ int gemm_f32(prx_fft_drawer* h, const float* A, int lda, const float* B, int ldb
     d.out_f32 = out; d.ldc_f32 = ldc;
     return prx_gemm_launch(d, h->ws, h->ws_bytes, s, &h->gctx);
 }
-}  // namespace
-
-extern "C" {
-
-prx_fft_drawer* prx_fft_drawer_create(int W, int H, float decay, float colors) {
-    if (W < 2 || H < 2) { prx_set_error("fft drawer: canvas %d x %d too small", W, H); return nullptr; }
-    prx_fft_drawer* h = new prx_fft_drawer();
+// the twiddle matrices, the colour matrix and every buffer of one canvas size
+int fft_build(prx_fft_drawer* h, int W, int H, float decay, float colors) {
+    h->mem.describe("fft drawer", ": the drawer keeps its twiddle matrices and one synth's buffers for a %d x %d canvas", W, H);
     h->W = W; h->H = H;
     h->Wh = W / 2 + 1;
     h->Wf = W / 2 + (W % 2 ? 2 : 1);        // the lucid frequency helper keeps one surplus column for an odd width
@@ -266,28 +265,31 @@ prx_fft_drawer* prx_fft_drawer_create(int W, int H, float decay, float colors) {
     std::vector<float> cm(9);
     for (int c = 0; c < 3; ++c)
         for (int d = 0; d < 3; ++d) cm[3 * c + d] = (float)(m[d][c] / mx);       // [c][d] = M^T[c][d]: rgb_d = sum_c y_c M[d][c]
-    bool ok = upload(&h->scale, scale) == 0 && upload(&h->A1, A1) == 0 && upload(&h->A1T, A1T) == 0 && upload(&h->T2, T2) == 0 &&
-              upload(&h->T2T, T2T) == 0 && upload(&h->cm, cm) == 0;
-    auto dev = [&](float** p, size_t n) { if (ok && hipMalloc(p, n * sizeof(float)) != hipSuccess) ok = false; };
-    dev(&h->bt1, (size_t)3 * HP2 * K1p); dev(&h->c1, (size_t)W * 3 * HP2); dev(&h->x, (size_t)3 * H * W); dev(&h->gy, (size_t)3 * H * W);
-    dev(&h->dxT, (size_t)3 * W * HP); dev(&h->dc1t, (size_t)3 * HP2 * WP); dev(&h->dP, (size_t)3 * HP2 * K1p);
+    int r;
+    if ((r = upload(h, &h->scale, scale)) || (r = upload(h, &h->A1, A1)) || (r = upload(h, &h->A1T, A1T)) || (r = upload(h, &h->T2, T2)) ||
+        (r = upload(h, &h->T2T, T2T)) || (r = upload(h, &h->cm, cm))) return r;
+    DEV_ALLOC(h->mem, alloc, h->bt1, (size_t)3 * HP2 * K1p); DEV_ALLOC(h->mem, alloc, h->c1, (size_t)W * 3 * HP2);
+    DEV_ALLOC(h->mem, alloc, h->x, (size_t)3 * H * W); DEV_ALLOC(h->mem, alloc, h->gy, (size_t)3 * H * W);
+    DEV_ALLOC(h->mem, alloc, h->dxT, (size_t)3 * W * HP); DEV_ALLOC(h->mem, alloc, h->dc1t, (size_t)3 * HP2 * WP);
+    DEV_ALLOC(h->mem, alloc, h->dP, (size_t)3 * HP2 * K1p);
     h->ws_bytes = (size_t)32 << 20;
-    dev(&h->ws, h->ws_bytes / sizeof(float));
-    if (ok && hipMalloc(&h->acc, (6 + 3 * FFT_MOM_BLOCKS) * sizeof(double)) != hipSuccess) ok = false;
+    DEV_ALLOC(h->mem, alloc, h->ws, h->ws_bytes / sizeof(float));
+    DEV_ALLOC(h->mem, alloc, h->acc, (size_t)6 + 3 * FFT_MOM_BLOCKS);
     // padding rows of dC1T are an A operand of the last backward GEMM: never written, so zeroed once
-    if (ok && hipMemset(h->dc1t, 0, (size_t)3 * HP2 * WP * sizeof(float)) != hipSuccess) ok = false;
-    if (!ok) { prx_set_error("fft drawer: device allocation failed"); prx_fft_drawer_destroy(h); return nullptr; }
-    return h;
+    PRX_CHECK_HIP(hipMemset(h->dc1t, 0, (size_t)3 * HP2 * WP * sizeof(float)));
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+prx_fft_drawer* prx_fft_drawer_create(int W, int H, float decay, float colors) {
+    if (W < 2 || H < 2) { prx_set_error("fft drawer: canvas %d x %d too small", W, H); return nullptr; }
+    std::unique_ptr<prx_fft_drawer> h(new prx_fft_drawer());      // a failed create frees what it allocated (DevArena)
+    return fft_build(h.get(), W, H, decay, colors) ? nullptr : h.release();
 }
 
-void prx_fft_drawer_destroy(prx_fft_drawer* h) {
-    if (!h) return;
-    float* bufs[] = {h->scale, h->A1, h->A1T, h->T2, h->T2T, h->cm, h->bt1, h->c1, h->x, h->gy, h->dxT, h->dc1t, h->dP, h->ws};
-    for (float* b : bufs)
-        if (b) (void)hipFree(b);
-    if (h->acc) (void)hipFree(h->acc);
-    delete h;
-}
+void prx_fft_drawer_destroy(prx_fft_drawer* h) { delete h; }
 
 int prx_fft_drawer_freq_columns(const prx_fft_drawer* h) { return h ? h->Wf : 0; }
 

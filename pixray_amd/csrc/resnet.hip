@@ -13,6 +13,7 @@
 #include "cutouts.h"
 #include "prompt_vq.h"
 #include "vit.h"  // prx_pack_* helpers
+#include "dev_arena.h"
 #include <cstdlib>
 #include <vector>
 #include <memory>
@@ -384,8 +385,7 @@ struct PrxResNet {
     int lean;
     float* gs;        // half mode: device {S, 1/S} = the power-of-two scale of the backward in flight (common.h) + 64 partials; else null
     GemmCtx gctx;     // this handle's engine state
-    std::vector<void*> allocs;
-    size_t alloc_bytes = 0;              // device bytes this handle holds (weights + one forward's activations for max_n cutouts)
+    DevArena mem;     // every device buffer below (weights + one forward's activations for max_n cutouts): freed with the handle
     float *w1, *b1;                      // stem conv1 (fp32, BN folded)
     RConv3 s2, s3;
     std::vector<RBlock> blocks;
@@ -399,59 +399,25 @@ struct PrxResNet {
 };
 
 namespace {
-// an allocation that fails is an error of the call (the handle under construction is freed by its guard), never an abort; the message
-// carries the figure: the runner keeps one forward's activations for max_n cutouts, so a smaller max_batch is the way out
-int ralloc_bytes(PrxResNet* r, void** p, size_t bytes) {
-    void* q = nullptr;
-    const hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        prx_set_error("resnet_create: device allocation of %zu bytes failed (%s) with %zu bytes already held by this handle: the runner keeps "
-                      "one forward's activations for max_batch = %d cutouts of %d x %d (width %d)", bytes, hipGetErrorString(e),
-                      r->alloc_bytes, r->max_n, r->res, r->res, r->width);
-        return -1;
-    }
-    r->allocs.push_back(q);
-    r->alloc_bytes += bytes;
-    *p = q;
-    return 0;
-}
-template <typename Tp>
-int ralloc(PrxResNet* r, Tp** p, size_t count) {
-    void* q = nullptr;
-    if (int e = ralloc_bytes(r, &q, std::max<size_t>(count, 1) * sizeof(Tp))) return e;
-    *p = (Tp*)q;
-    return 0;
-}
-#define RALLOC(ptr, count) do { int _e = ralloc(r, &(ptr), (count)); if (_e) return _e; } while (0)
-int ralloc_op(PrxResNet* r, void** p, size_t count) {   // `count` operand elements
-    return ralloc_bytes(r, p, std::max<size_t>(count, 1) * op_esz(r->f32));
-}
-#define RALLOC_OP(ptr, count) do { int _e = ralloc_op(r, &(ptr), (count)); if (_e) return _e; } while (0)
 struct RCur { const float* const* w; int n, pos; };
 #define RNEXT(cur, dst) do { PRX_REQUIRE((cur).pos < (cur).n, "resnet_create: weight list too short"); (dst) = (cur).w[(cur).pos++]; } while (0)
 
-int rcopy(PrxResNet* r, float** dst, const float* src, size_t n, hipStream_t s) {
-    RALLOC(*dst, n);
-    PRX_CHECK_HIP(hipMemcpyAsync(*dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return 0;
-}
 int mk1(PrxResNet* r, RConv1& c, int Cin, int Cout, RCur& cur, hipStream_t s) {
     const float *w, *b; RNEXT(cur, w); RNEXT(cur, b);
     c.Cin = Cin; c.Cout = Cout;
-    RALLOC_OP(c.W, (size_t)Cout * Cin); RALLOC_OP(c.WT, (size_t)Cout * Cin);
+    DEV_ALLOC(r->mem, alloc_op, c.W, (size_t)Cout * Cin, r->f32); DEV_ALLOC(r->mem, alloc_op, c.WT, (size_t)Cout * Cin, r->f32);
     int e;
     if ((e = prx_pack_op(w, c.W, (size_t)Cout * Cin, r->prec, s))) return e;
     if ((e = prx_pack_transpose_op(w, c.WT, Cout, Cin, r->prec, s))) return e;
-    return rcopy(r, &c.b, b, Cout, s);
+    return r->mem.copy_f32(&c.b, b, Cout, s);
 }
 int mk3(PrxResNet* r, RConv3& c, int Cin, int Cout, RCur& cur, hipStream_t s) {
     const float *w, *b; RNEXT(cur, w); RNEXT(cur, b);
     c.Cin = Cin; c.Cout = Cout;
-    RALLOC_OP(c.Wf, (size_t)Cout * 9 * Cin); RALLOC_OP(c.Wd, (size_t)Cout * 9 * Cin);
+    DEV_ALLOC(r->mem, alloc_op, c.Wf, (size_t)Cout * 9 * Cin, r->f32); DEV_ALLOC(r->mem, alloc_op, c.Wd, (size_t)Cout * 9 * Cin, r->f32);
     int e;
     if ((e = prx_rn_pack_conv3x3(w, c.Wf, c.Wd, Cout, Cin, r->prec, s))) return e;
-    return rcopy(r, &c.b, b, Cout, s);
+    return r->mem.copy_f32(&c.b, b, Cout, s);
 }
 int rg(PrxResNet* r, GemmDesc& d, hipStream_t s) {
     if (r->f32) { d.f32 = 1; d.a_is_f32 = 0; }
@@ -485,8 +451,13 @@ int prx_resnet_create_impl(PrxResNet** out, int res, int width, const int* layer
     PRX_REQUIRE(prec_valid(precision), "resnet_create: unknown precision %d", precision);
     PRX_REQUIRE(res % 32 == 0 && width % 16 == 0 && max_n >= 1, "resnet_create: unsupported geometry (res %d width %d)", res, width);
     PRX_REQUIRE(width * 32 == heads * 64, "resnet_create: the attention pool needs head dim 64 (width %d heads %d)", width, heads);
-    PrxResNet* r = new PrxResNet();
-    std::unique_ptr<PrxResNet, void (*)(PrxResNet*)> guard(r, prx_resnet_destroy_impl);      // a failed create frees what it allocated
+    std::unique_ptr<PrxResNet> guard(new PrxResNet());      // a failed create frees what it allocated (DevArena)
+    PrxResNet* r = guard.get();
+    DevArena& m = r->mem;
+    const int f32 = prec_is_f32(precision);
+    // the runner keeps one forward's activations for max_n cutouts, so a smaller max_batch is the way out of a failed allocation
+    m.describe("resnet_create", ": the runner keeps one forward's activations for max_batch = %d cutouts of %d x %d (width %d)", max_n, res, res,
+               width);
     r->prec = precision; r->f32 = prec_is_f32(precision); r->h16 = prec_is_h16(precision);
     r->gs = nullptr;
     { const char* ev = getenv("PRX_RN_LEAN"); r->lean = (r->h16 && !(ev && atoi(ev) == 0)) ? 1 : 0; }
@@ -495,8 +466,8 @@ int prx_resnet_create_impl(PrxResNet** out, int res, int width, const int* layer
     RCur cur{w, n_w, 0};
     int e;
     {   const float *ww, *bb; RNEXT(cur, ww); RNEXT(cur, bb);
-        if ((e = rcopy(r, &r->w1, ww, (size_t)(width / 2) * 27, s))) return e;
-        if ((e = rcopy(r, &r->b1, bb, width / 2, s))) return e; }
+        if ((e = m.copy_f32(&r->w1, ww, (size_t)(width / 2) * 27, s))) return e;
+        if ((e = m.copy_f32(&r->b1, bb, width / 2, s))) return e; }
     if ((e = mk3(r, r->s2, width / 2, width / 2, cur, s))) return e;
     if ((e = mk3(r, r->s3, width / 2, width, cur, s))) return e;
     const size_t N = (size_t)max_n;
@@ -513,12 +484,12 @@ int prx_resnet_create_impl(PrxResNet** out, int res, int width, const int* layer
             if ((e = mk1(r, k.c3, planes, planes * 4, cur, s))) return e;
             if (k.has_ds && (e = mk1(r, k.ds, inplanes, planes * 4, cur, s))) return e;
             const size_t Min = N * H * H, Ho = H / k.stride, Mout = N * Ho * Ho;
-            RALLOC_OP(k.a1, Min * planes); RALLOC_OP(k.a2, Min * planes);
+            DEV_ALLOC(m, alloc_op, k.a1, Min * planes, f32); DEV_ALLOC(m, alloc_op, k.a2, Min * planes, f32);
             k.p2 = k.a2; k.xp = nullptr;
-            if (k.stride > 1) { RALLOC_OP(k.p2, Mout * planes); RALLOC_OP(k.xp, Mout * inplanes); }
-            RALLOC_OP(k.out_bf, Mout * planes * 4);
+            if (k.stride > 1) { DEV_ALLOC(m, alloc_op, k.p2, Mout * planes, f32); DEV_ALLOC(m, alloc_op, k.xp, Mout * inplanes, f32); }
+            DEV_ALLOC(m, alloc_op, k.out_bf, Mout * planes * 4, f32);
             k.out_f32 = nullptr;
-            if (!r->lean || (li == 3 && b == layers[li] - 1)) RALLOC(k.out_f32, Mout * planes * 4);
+            if (!r->lean || (li == 3 && b == layers[li] - 1)) DEV_ALLOC(m, alloc, k.out_f32, Mout * planes * 4);
             maxMC = std::max(maxMC, std::max(Min * (size_t)std::max(inplanes, planes), Mout * (size_t)planes * 4));
             r->blocks.push_back(k);
             inplanes = planes * 4; H = (int)Ho;
@@ -529,38 +500,37 @@ int prx_resnet_create_impl(PrxResNet** out, int res, int width, const int* layer
     RNEXT(cur, pos); RNEXT(cur, win); RNEXT(cur, bin); RNEXT(cur, wc); RNEXT(cur, bc);
     PRX_REQUIRE(cur.pos == n_w, "resnet_create: %d weight tensors given, %d consumed", n_w, cur.pos);
     const int C = r->C, T = r->T;
-    if ((e = rcopy(r, &r->pos, pos, (size_t)T * C, s))) return e;
-    RALLOC_OP(r->Win, (size_t)3 * C * C); RALLOC_OP(r->WinT, (size_t)3 * C * C);
+    if ((e = m.copy_f32(&r->pos, pos, (size_t)T * C, s))) return e;
+    DEV_ALLOC(m, alloc_op, r->Win, (size_t)3 * C * C, f32); DEV_ALLOC(m, alloc_op, r->WinT, (size_t)3 * C * C, f32);
     if ((e = prx_pack_op(win, r->Win, (size_t)3 * C * C, r->prec, s))) return e;
     if ((e = prx_pack_transpose_op(win, r->WinT, 3 * C, C, r->prec, s))) return e;
-    if ((e = rcopy(r, &r->bin, bin, 3 * C, s))) return e;
-    RALLOC_OP(r->Wc, (size_t)out_dim * C); RALLOC_OP(r->WcT, (size_t)out_dim * C);
+    if ((e = m.copy_f32(&r->bin, bin, 3 * C, s))) return e;
+    DEV_ALLOC(m, alloc_op, r->Wc, (size_t)out_dim * C, f32); DEV_ALLOC(m, alloc_op, r->WcT, (size_t)out_dim * C, f32);
     if ((e = prx_pack_op(wc, r->Wc, (size_t)out_dim * C, r->prec, s))) return e;
     if ((e = prx_pack_transpose_op(wc, r->WcT, out_dim, C, r->prec, s))) return e;
-    if ((e = rcopy(r, &r->bc, bc, out_dim, s))) return e;
+    if ((e = m.copy_f32(&r->bc, bc, out_dim, s))) return e;
     const size_t S2 = (size_t)(res / 2) * (res / 2), S4 = (size_t)(res / 4) * (res / 4);
-    RALLOC_OP(r->s1, N * S2 * (width / 2)); RALLOC_OP(r->s2a, N * S2 * (width / 2)); RALLOC_OP(r->s3a, N * S2 * width);
-    RALLOC_OP(r->s0_bf, N * S4 * width); RALLOC(r->s0_f32, N * S4 * width);
-    RALLOC_OP(r->tok, N * T * C); RALLOC_OP(r->qkv, N * T * 3 * C); RALLOC_OP(r->att, N * T * C); RALLOC_OP(r->o0, N * C);
-    RALLOC_OP(r->dtok, N * T * C); RALLOC_OP(r->dqkv, N * T * 3 * C); RALLOC_OP(r->do0, N * C); RALLOC(r->dtokf, N * T * C);
-    RALLOC(r->lse, N * heads * T); RALLOC(r->e, N * out_dim); RALLOC(r->de, N * out_dim);
-    RALLOC(r->gA, maxMC); RALLOC(r->tf, maxMC);
+    DEV_ALLOC(m, alloc_op, r->s1, N * S2 * (width / 2), f32); DEV_ALLOC(m, alloc_op, r->s2a, N * S2 * (width / 2), f32);
+    DEV_ALLOC(m, alloc_op, r->s3a, N * S2 * width, f32);
+    DEV_ALLOC(m, alloc_op, r->s0_bf, N * S4 * width, f32); DEV_ALLOC(m, alloc, r->s0_f32, N * S4 * width);
+    DEV_ALLOC(m, alloc_op, r->tok, N * T * C, f32); DEV_ALLOC(m, alloc_op, r->qkv, N * T * 3 * C, f32);
+    DEV_ALLOC(m, alloc_op, r->att, N * T * C, f32); DEV_ALLOC(m, alloc_op, r->o0, N * C, f32);
+    DEV_ALLOC(m, alloc_op, r->dtok, N * T * C, f32); DEV_ALLOC(m, alloc_op, r->dqkv, N * T * 3 * C, f32); DEV_ALLOC(m, alloc_op, r->do0, N * C, f32);
+    DEV_ALLOC(m, alloc, r->dtokf, N * T * C);
+    DEV_ALLOC(m, alloc, r->lse, N * heads * T); DEV_ALLOC(m, alloc, r->e, N * out_dim); DEV_ALLOC(m, alloc, r->de, N * out_dim);
+    DEV_ALLOC(m, alloc, r->gA, maxMC); DEV_ALLOC(m, alloc, r->tf, maxMC);
     r->gB = nullptr; r->gb2 = r->gb3 = nullptr;
-    if (r->lean) { RALLOC_OP(r->gb2, maxMC); RALLOC_OP(r->gb3, maxMC); } else RALLOC(r->gB, maxMC);
-    RALLOC_OP(r->tb1, maxMC); RALLOC_OP(r->tb2, maxMC); RALLOC_OP(r->gbf, maxMC);
-    RALLOC(r->dY, N * 3 * (size_t)res * res); RALLOC(r->mm_part, 2 * 1024);
-    if (r->h16) RALLOC(r->gs, 2 + 64);
+    if (r->lean) { DEV_ALLOC(m, alloc_op, r->gb2, maxMC, f32); DEV_ALLOC(m, alloc_op, r->gb3, maxMC, f32); } else DEV_ALLOC(m, alloc, r->gB, maxMC);
+    DEV_ALLOC(m, alloc_op, r->tb1, maxMC, f32); DEV_ALLOC(m, alloc_op, r->tb2, maxMC, f32); DEV_ALLOC(m, alloc_op, r->gbf, maxMC, f32);
+    DEV_ALLOC(m, alloc, r->dY, N * 3 * (size_t)res * res); DEV_ALLOC(m, alloc, r->mm_part, 2 * 1024);
+    if (r->h16) DEV_ALLOC(m, alloc, r->gs, 2 + 64);
     r->ws_bytes = (size_t)64 << 20;
-    RALLOC(r->ws, r->ws_bytes / sizeof(float));
+    DEV_ALLOC(m, alloc, r->ws, r->ws_bytes / sizeof(float));
     *out = guard.release();
     return 0;
 }
 
-void prx_resnet_destroy_impl(PrxResNet* r) {
-    if (!r) return;
-    for (void* p : r->allocs) (void)hipFree(p);
-    delete r;
-}
+void prx_resnet_destroy_impl(PrxResNet* r) { delete r; }
 
 int prx_resnet_minmax_impl(PrxResNet* r, const float* cutouts, int n, float* mm, hipStream_t s) {
     PRX_REQUIRE(n >= 1 && n <= r->max_n, "resnet: batch %d exceeds handle capacity %d", n, r->max_n);

@@ -19,8 +19,11 @@
 // prefix of an fp32 gradient concat buffer.  Every output element has exactly one owner lane: no atomics, same bits every run.
 #include "rrdbnet.h"
 
+#include <memory>
 #include <new>
 #include <vector>
+
+#include "dev_arena.h"
 
 #include "../../include/prx.h"
 
@@ -341,7 +344,7 @@ struct RrdbConvW { void* wf; void* wd; const float* bias; int cin, cout; };
 struct prx_rrdbnet {
     int nb = 0, h = 0, w = 0, f32 = 0, have_fwd = 0, clamp = 1;
     size_t esz = 2;
-    std::vector<void*> allocs;
+    DevArena mem;                        // every device buffer below: freed with the handle
     float *w_first = nullptr, *b_first = nullptr, *w_last = nullptr, *b_last = nullptr;
     std::vector<RrdbConvW> convs;        // 15 per RRDB (rdb1.conv1 .. rdb3.conv5), then conv_body, conv_up1, conv_up2, conv_hr
     std::vector<void*> cat;              // 3 nb concat buffers [h w][192] T
@@ -353,18 +356,7 @@ struct prx_rrdbnet {
     const float* xin(int j) const { return j == 0 ? feat : X[j & 3]; }
 };
 
-static void* rrdb_alloc(prx_rrdbnet* r, size_t bytes) {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-    r->allocs.push_back(p);
-    return p;
-}
-
-extern "C" void prx_rrdbnet_destroy(prx_rrdbnet* h) {
-    if (!h) return;
-    for (void* p : h->allocs) (void)hipFree(p);
-    delete h;
-}
+extern "C" void prx_rrdbnet_destroy(prx_rrdbnet* h) { delete h; }
 
 extern "C" int prx_rrdbnet_create(prx_rrdbnet** out, int num_feat, int num_grow, int num_block, int h, int w, const float* const* weights,
                                   int n_weights, int precision, prx_stream_t stream) {
@@ -381,48 +373,43 @@ extern "C" int prx_rrdbnet_create(prx_rrdbnet** out, int num_feat, int num_grow,
     int f32 = 0;
     if (int rc = rrdb_prec(precision, &f32)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    prx_rrdbnet* r = new (std::nothrow) prx_rrdbnet();
+    std::unique_ptr<prx_rrdbnet> guard(new (std::nothrow) prx_rrdbnet());      // a failed create frees what it allocated (DevArena)
+    prx_rrdbnet* r = guard.get();
     PRX_REQUIRE(r, "prx_rrdbnet_create: out of host memory");
     r->nb = num_block; r->h = h; r->w = w; r->f32 = f32; r->esz = f32 ? 4 : 2;
-    const size_t hw = (size_t)h * w, e = r->esz;
-    bool ok = true;
-    auto A = [&](size_t bytes) { void* p = rrdb_alloc(r, bytes); ok = ok && p; return p; };
+    const size_t hw = (size_t)h * w;
+    DevArena& m = r->mem;
+    m.describe("prx_rrdbnet_create", ": the runner keeps every activation and gradient buffer of %d blocks at %d x %d (the concat buffers alone take %.0f MB)",
+               num_block, h, w, 3.0 * num_block * 192 * r->esz * hw / 1e6);
+    int rc;
     // the weights are copied: the caller may release its tensors once the stream has run
-    auto copy_f32 = [&](const float* src, size_t n) {
-        float* p = (float*)A(n * 4);
-        if (p && hipMemcpyAsync(p, src, n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) ok = false;
-        return p;
-    };
-    r->w_first = copy_f32(weights[0], 64 * 27);
-    r->b_first = copy_f32(weights[1], 64);
-    r->w_last = copy_f32(weights[2 * (n_conv - 1)], 3 * 64 * 9);
-    r->b_last = copy_f32(weights[2 * (n_conv - 1) + 1], 3);
-    for (int i = 1; i < n_conv - 1 && ok; ++i) {
+    if ((rc = m.copy_f32(&r->w_first, weights[0], 64 * 27, s))) return rc;
+    if ((rc = m.copy_f32(&r->b_first, weights[1], 64, s))) return rc;
+    if ((rc = m.copy_f32(&r->w_last, weights[2 * (n_conv - 1)], 3 * 64 * 9, s))) return rc;
+    if ((rc = m.copy_f32(&r->b_last, weights[2 * (n_conv - 1) + 1], 3, s))) return rc;
+    for (int i = 1; i < n_conv - 1; ++i) {
         const int k = i - 1;
         int cin = 64, cout = 64;
         if (k < 15 * num_block) { const int c = k % 5; cin = 64 + 32 * c; cout = c == 4 ? 64 : 32; }
         RrdbConvW cw;
         cw.cin = cin; cw.cout = cout;
-        cw.wf = A((size_t)cin * cout * 9 * e);
-        cw.wd = A((size_t)cin * cout * 9 * e);
-        cw.bias = copy_f32(weights[2 * i + 1], cout);
-        if (!ok) break;
-        if (rrdb_pack_launch(weights[2 * i], cw.wf, cout, cin, 0, f32, s) || rrdb_pack_launch(weights[2 * i], cw.wd, cout, cin, 1, f32, s)) ok = false;
+        DEV_ALLOC(m, alloc_op, cw.wf, (size_t)cin * cout * 9, f32);
+        DEV_ALLOC(m, alloc_op, cw.wd, (size_t)cin * cout * 9, f32);
+        float* bias;
+        if ((rc = m.copy_f32(&bias, weights[2 * i + 1], cout, s))) return rc;
+        cw.bias = bias;
+        if ((rc = rrdb_pack_launch(weights[2 * i], cw.wf, cout, cin, 0, f32, s)) || (rc = rrdb_pack_launch(weights[2 * i], cw.wd, cout, cin, 1, f32, s))) return rc;
         r->convs.push_back(cw);
     }
-    for (int j = 0; j < 3 * num_block && ok; ++j) r->cat.push_back(A(hw * 192 * e));
-    for (int i = 0; i < 4; ++i) { r->X[i] = (float*)A(hw * 64 * 4); r->G[i] = (float*)A(hw * 192 * 4); }
-    r->feat = (float*)A(hw * 64 * 4);
-    r->tb = A(hw * 64 * e); r->u0 = A(hw * 64 * e); r->u1 = A(4 * hw * 64 * e); r->u2 = A(16 * hw * 64 * e); r->u3 = A(16 * hw * 64 * e);
-    r->raw = (float*)A(48 * hw * 4);
-    r->gA = (float*)A(16 * hw * 64 * 4); r->gB = (float*)A(16 * hw * 64 * 4); r->gC = (float*)A(4 * hw * 64 * 4); r->gD = (float*)A(hw * 64 * 4);
-    if (!ok) {
-        prx_rrdbnet_destroy(r);
-        prx_set_error("prx_rrdbnet_create: device allocation or weight packing failed (%d blocks at %d x %d: the concat buffers alone take %.0f MB)",
-                      num_block, h, w, 3.0 * num_block * 192 * e * hw / 1e6);
-        return -1;
-    }
-    *out = r;
+    for (int j = 0; j < 3 * num_block; ++j) { void* c; DEV_ALLOC(m, alloc_op, c, hw * 192, f32); r->cat.push_back(c); }
+    for (int i = 0; i < 4; ++i) { DEV_ALLOC(m, alloc, r->X[i], hw * 64); DEV_ALLOC(m, alloc, r->G[i], hw * 192); }
+    DEV_ALLOC(m, alloc, r->feat, hw * 64);
+    DEV_ALLOC(m, alloc_op, r->tb, hw * 64, f32); DEV_ALLOC(m, alloc_op, r->u0, hw * 64, f32); DEV_ALLOC(m, alloc_op, r->u1, 4 * hw * 64, f32);
+    DEV_ALLOC(m, alloc_op, r->u2, 16 * hw * 64, f32); DEV_ALLOC(m, alloc_op, r->u3, 16 * hw * 64, f32);
+    DEV_ALLOC(m, alloc, r->raw, 48 * hw);
+    DEV_ALLOC(m, alloc, r->gA, 16 * hw * 64); DEV_ALLOC(m, alloc, r->gB, 16 * hw * 64);
+    DEV_ALLOC(m, alloc, r->gC, 4 * hw * 64); DEV_ALLOC(m, alloc, r->gD, hw * 64);
+    *out = guard.release();
     return 0;
 }
 

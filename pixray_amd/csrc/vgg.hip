@@ -15,6 +15,8 @@
 #include "vgg.h"
 #include "gemm.h"
 #include "elementwise.h"
+#include "dev_arena.h"
+#include <memory>
 #include <vector>
 #include <algorithm>
 
@@ -191,7 +193,7 @@ struct PrxVgg16 {
     int f32, h16;     // derived: operands are fp32 / the 16-bit operand format is IEEE half
     float* gs;        // half mode: device {S, 1/S} of the backward in flight + partial maxima; else null
     GemmCtx gctx;     // this handle's engine state
-    std::vector<void*> allocs;
+    DevArena mem;     // every device buffer below: freed with the handle
     VConv conv[NCONV];
     float *dA, *dB, *ws;       // dgrad ping-pong (fp32), split-K scratch
     void* gpre;       // operand precision
@@ -199,23 +201,6 @@ struct PrxVgg16 {
 };
 
 namespace {
-template <typename Tp>
-int valloc(PrxVgg16* v, Tp** p, size_t count) {
-    void* q = nullptr;
-    PRX_CHECK_HIP(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(Tp)));
-    v->allocs.push_back(q);
-    *p = (Tp*)q;
-    return 0;
-}
-#define VALLOC(ptr, count) do { int _e = valloc(v, &(ptr), (count)); if (_e) return _e; } while (0)
-int valloc_op(PrxVgg16* v, void** p, size_t count) {
-    void* q = nullptr;
-    PRX_CHECK_HIP(hipMalloc(&q, std::max<size_t>(count, 1) * op_esz(v->f32)));
-    v->allocs.push_back(q);
-    *p = q;
-    return 0;
-}
-
 int vconv(PrxVgg16* v, const void* x, int H, int W, int Cin, const void* Bt, int Cout, const float* bias, int act,
           float* of, void* ob, hipStream_t s) {
     GemmDesc d; d.A = x; d.a_mode = PRX_A_CONV3X3; d.lda = Cin; d.B = Bt; d.ldb = 9 * Cin; d.M = H * W; d.N = Cout; d.K = 9 * Cin;
@@ -242,34 +227,30 @@ int prx_vgg16_create_impl(PrxVgg16** out, const float* const* weights, int n_wei
     PRX_REQUIRE(prec_valid(precision), "vgg16_create: unknown precision %d", precision);
     PRX_REQUIRE(out && weights && n_weights == 2 * NCONV, "vgg16_create: expected %d weight tensors, got %d", 2 * NCONV, n_weights);
     PRX_REQUIRE(max_h >= 16 && max_w >= 16, "vgg16_create: the input must be at least 16x16 (got %dx%d)", max_h, max_w);
-    PrxVgg16* v = new PrxVgg16();
+    std::unique_ptr<PrxVgg16> guard(new PrxVgg16());      // a failed create frees what it allocated (DevArena)
+    PrxVgg16* v = guard.get();
     v->max_h = max_h; v->max_w = max_w; v->prec = precision; v->f32 = prec_is_f32(precision); v->h16 = prec_is_h16(precision);
     v->gs = nullptr;
-    auto fail = [&](int e) { prx_vgg16_destroy_impl(v); return e; };
+    v->mem.describe("vgg16_create", ": the extractor keeps its weight packs and the gradient streams of a %d x %d input", max_h, max_w);
     for (int l = 0; l < NCONV; ++l) {
         VConv& c = v->conv[l];
         c.Cin = kCin[l]; c.CiP = cpad(kCin[l]); c.Cout = kCout[l];
         const size_t n = (size_t)c.Cout * 9 * c.CiP;
-        int e;
-        if ((e = valloc_op(v, &c.Wf, n)) || (e = valloc_op(v, &c.Wd, n)) || (e = valloc(v, &c.b, (size_t)c.Cout))) return fail(e);
-        if ((e = prx_vgg_pack(weights[2 * l], c.Wf, c.Wd, c.Cout, c.Cin, c.CiP, v->prec, s))) return fail(e);
-        if (hipMemcpyAsync(c.b, weights[2 * l + 1], sizeof(float) * c.Cout, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(-1);
+        DEV_ALLOC(v->mem, alloc_op, c.Wf, n, v->f32); DEV_ALLOC(v->mem, alloc_op, c.Wd, n, v->f32);
+        DEV_ALLOC(v->mem, alloc, c.b, (size_t)c.Cout);
+        if (int e = prx_vgg_pack(weights[2 * l], c.Wf, c.Wd, c.Cout, c.Cin, c.CiP, v->prec, s)) return e;
+        PRX_CHECK_HIP(hipMemcpyAsync(c.b, weights[2 * l + 1], sizeof(float) * c.Cout, hipMemcpyDeviceToDevice, s));
     }
     const size_t big = (size_t)max_h * max_w * 64;
-    int e;
-    if ((e = valloc(v, &v->dA, big)) || (e = valloc(v, &v->dB, big)) || (e = valloc_op(v, &v->gpre, big))) return fail(e);
+    DEV_ALLOC(v->mem, alloc, v->dA, big); DEV_ALLOC(v->mem, alloc, v->dB, big); DEV_ALLOC(v->mem, alloc_op, v->gpre, big, v->f32);
     v->ws_bytes = (size_t)64 << 20;
-    if ((e = valloc(v, &v->ws, v->ws_bytes / sizeof(float)))) return fail(e);
-    if (v->h16 && (e = valloc(v, &v->gs, (size_t)2 + NFEAT * 256))) return fail(e);
-    *out = v;
+    DEV_ALLOC(v->mem, alloc, v->ws, v->ws_bytes / sizeof(float));
+    if (v->h16) DEV_ALLOC(v->mem, alloc, v->gs, (size_t)2 + NFEAT * 256);
+    *out = guard.release();
     return 0;
 }
 
-void prx_vgg16_destroy_impl(PrxVgg16* v) {
-    if (!v) return;
-    for (void* p : v->allocs) (void)hipFree(p);
-    delete v;
-}
+void prx_vgg16_destroy_impl(PrxVgg16* v) { delete v; }
 
 // x: [3,H,W] fp32 (already in the extractor's input space); feats[k]: fp32 NHWC [h_k*w_k, C_k] or null (not wanted)
 int prx_vgg16_forward_impl(PrxVgg16* v, const float* x, int H, int W, void* workspace, float* const* feats, hipStream_t s) {

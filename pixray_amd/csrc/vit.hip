@@ -15,6 +15,7 @@
 #include "cutouts.h"
 #include "prompt_vq.h"
 #include "elementwise.h"
+#include "dev_arena.h"
 #include <vector>
 #include <memory>
 
@@ -149,8 +150,7 @@ struct PrxVit {
     int f32, h16;     // derived: operands are fp32 / the 16-bit operand format is IEEE half
     float* gs;        // half mode: device {S, 1/S} = the power-of-two scale of the backward in flight (common.h) + 64 partials; else null
     GemmCtx gctx;     // this handle's engine state (tile overrides, timing log)
-    std::vector<void*> allocs;
-    size_t alloc_bytes = 0;  // device bytes this handle holds (weights + one forward's activations for max_n cutouts)
+    DevArena mem;     // every device buffer below (weights + one forward's activations for max_n cutouts): freed with the handle
     void *Wp, *WpT, *projT, *proj;
     float *cls, *pos, *lnpre_g, *lnpre_b, *lnpost_g, *lnpost_b;
     std::vector<VitLayer> L;
@@ -175,44 +175,9 @@ struct PrxVit {
 };
 
 namespace {
-// an allocation that fails is an error of the call (the handle under construction is freed by its guard), never an abort; the message
-// carries the figure: the runner keeps one forward's activations for max_n cutouts, so a smaller max_batch is the way out
-int dev_alloc_bytes(PrxVit* v, void** p, size_t bytes) {
-    void* q = nullptr;
-    const hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        prx_set_error("vit_create: device allocation of %zu bytes failed (%s) with %zu bytes already held by this handle: the runner keeps one "
-                      "forward's activations for max_batch = %d cutouts of %d tokens (width %d, %d layers)", bytes, hipGetErrorString(e),
-                      v->alloc_bytes, v->max_n, v->T, v->width, v->layers);
-        return -1;
-    }
-    v->allocs.push_back(q);
-    v->alloc_bytes += bytes;
-    *p = q;
-    return 0;
-}
-template <typename Tp>
-int dev_alloc(PrxVit* v, Tp** p, size_t count) {
-    void* q = nullptr;
-    if (int e = dev_alloc_bytes(v, &q, count * sizeof(Tp))) return e;
-    *p = (Tp*)q;
-    return 0;
-}
-#define ALLOC(ptr, count) do { int _r = dev_alloc(v, &(ptr), (count)); if (_r) return _r; } while (0)
-int dev_alloc_op(PrxVit* v, void** p, size_t count) {   // `count` operand elements
-    return dev_alloc_bytes(v, p, count * op_esz(v->f32));
-}
-#define ALLOC_OP(ptr, count) do { int _r = dev_alloc_op(v, &(ptr), (count)); if (_r) return _r; } while (0)
-
-int copy_f32(PrxVit* v, float** dst, const float* src, size_t n, hipStream_t s) {
-    ALLOC(*dst, n);
-    PRX_CHECK_HIP(hipMemcpyAsync(*dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return 0;
-}
 int pack_both(PrxVit* v, void** W, void** WT, const float* src, int out, int in, hipStream_t s) {
-    ALLOC_OP(*W, (size_t)out * in);
-    ALLOC_OP(*WT, (size_t)out * in);
+    DEV_ALLOC(v->mem, alloc_op, *W, (size_t)out * in, v->f32);
+    DEV_ALLOC(v->mem, alloc_op, *WT, (size_t)out * in, v->f32);
     int r = prx_pack_op(src, *W, (size_t)out * in, v->prec, s);
     if (r) return r;
     return prx_pack_transpose_op(src, *WT, out, in, v->prec, s);
@@ -241,8 +206,13 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
                 "vit_create: LayerNorm eps and the channel std must be positive");
     const int G = res / patch;
     const int T = G * G + 1;
-    PrxVit* v = new PrxVit();
-    std::unique_ptr<PrxVit, void (*)(PrxVit*)> guard(v, prx_vit_destroy_impl);      // a failed create frees what it allocated
+    std::unique_ptr<PrxVit> guard(new PrxVit());      // a failed create frees what it allocated (DevArena)
+    PrxVit* v = guard.get();
+    DevArena& m = v->mem;
+    const int f32 = prec_is_f32(precision);
+    // the runner keeps one forward's activations for max_n cutouts, so a smaller max_batch is the way out of a failed allocation
+    v->mem.describe("vit_create", ": the runner keeps one forward's activations for max_batch = %d cutouts of %d tokens (width %d, %d layers)",
+                    max_n, T, width, layers);
     v->T = T; v->max_n = max_n;
     v->res = res; v->patch = patch; v->width = width; v->layers = layers; v->heads = heads; v->out_dim = out_dim;
     v->prec = precision; v->f32 = prec_is_f32(precision); v->h16 = prec_is_h16(precision);
@@ -250,8 +220,8 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
     const int AW = v->aw;
     float *pad_w = nullptr, *pad_b = nullptr;       // fp32 staging of the padded qkv / out-projection weights, reused by every block (stream order)
     if (hd != 64) {
-        if (int r_ = dev_alloc(v, &pad_w, (size_t)3 * AW * width)) return r_;
-        if (int r_ = dev_alloc(v, &pad_b, (size_t)3 * AW)) return r_;
+        DEV_ALLOC(m, alloc, pad_w, (size_t)3 * AW * width);
+        DEV_ALLOC(m, alloc, pad_b, (size_t)3 * AW);
     }
     { const char* e = getenv("PRX_LEAN"); v->lean = (v->h16 && !(e && atoi(e) == 0)) ? 1 : 0; }
     { const char* e = getenv("PRX_VIT_CLS_TAIL"); v->cls_tail = (e && atoi(e) == 0) ? 0 : 1; }
@@ -261,31 +231,31 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
     {   // conv1.weight [W, 3*P*P] -> zero-padded to KP columns, both orientations
         const int K0 = 3 * patch * patch;
         float* padded;
-        ALLOC(padded, (size_t)W * KP);
+        DEV_ALLOC(m, alloc, padded, (size_t)W * KP);
         PRX_CHECK_HIP(hipMemsetAsync(padded, 0, sizeof(float) * (size_t)W * KP, s));
         PRX_CHECK_HIP(hipMemcpy2DAsync(padded, sizeof(float) * KP, w[0], sizeof(float) * K0, sizeof(float) * K0, W,
                                        hipMemcpyDeviceToDevice, s));
         if ((r = pack_both(v, &v->Wp, &v->WpT, padded, W, KP, s))) return r;
     }
     const float* const* wh = w + 1;
-    if (fam.patch_bias) { if ((r = copy_f32(v, &v->bp, *wh++, W, s))) return r; }
-    if ((r = copy_f32(v, &v->cls, *wh++, W, s))) return r;
-    if ((r = copy_f32(v, &v->pos, *wh++, (size_t)T * W, s))) return r;
+    if (fam.patch_bias) { if ((r = v->mem.copy_f32(&v->bp, *wh++, W, s))) return r; }
+    if ((r = v->mem.copy_f32(&v->cls, *wh++, W, s))) return r;
+    if ((r = v->mem.copy_f32(&v->pos, *wh++, (size_t)T * W, s))) return r;
     v->lnpre_g = v->lnpre_b = nullptr;
     if (fam.ln_pre) {
-        if ((r = copy_f32(v, &v->lnpre_g, *wh++, W, s))) return r;
-        if ((r = copy_f32(v, &v->lnpre_b, *wh++, W, s))) return r;
+        if ((r = v->mem.copy_f32(&v->lnpre_g, *wh++, W, s))) return r;
+        if ((r = v->mem.copy_f32(&v->lnpre_b, *wh++, W, s))) return r;
     }
     v->L.resize(layers);
     const size_t R = (size_t)max_n * T;
     for (int l = 0; l < layers; ++l) {
         const float* const* q = w + n_head + 12 * l;
         VitLayer& y = v->L[l];
-        if ((r = copy_f32(v, &y.ln1_g, q[0], W, s))) return r;
-        if ((r = copy_f32(v, &y.ln1_b, q[1], W, s))) return r;
+        if ((r = v->mem.copy_f32(&y.ln1_g, q[0], W, s))) return r;
+        if ((r = v->mem.copy_f32(&y.ln1_b, q[1], W, s))) return r;
         if (hd == 64) {
             if ((r = pack_both(v, &y.Wqkv, &y.WqkvT, q[2], 3 * W, W, s))) return r;
-            if ((r = copy_f32(v, &y.bqkv, q[3], 3 * W, s))) return r;
+            if ((r = v->mem.copy_f32(&y.bqkv, q[3], 3 * W, s))) return r;
             if ((r = pack_both(v, &y.Wo, &y.WoT, q[4], W, W, s))) return r;
         } else {
             const float qs = sqrtf(64.f / (float)hd);
@@ -301,58 +271,56 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
             if ((r = prx_vit_scale_f32(pad_w, (size_t)AW * W, qs, 256, s))) return r;
             if ((r = prx_vit_scale_f32(pad_b, (size_t)AW, qs, 1, s))) return r;
             if ((r = pack_both(v, &y.Wqkv, &y.WqkvT, pad_w, 3 * AW, W, s))) return r;
-            if ((r = copy_f32(v, &y.bqkv, pad_b, 3 * AW, s))) return r;
+            if ((r = v->mem.copy_f32(&y.bqkv, pad_b, 3 * AW, s))) return r;
             // out-projection [W, W]: input columns head x hd -> the first hd of every head's 64 columns of [W, AW]
             PRX_CHECK_HIP(hipMemsetAsync(pad_w, 0, sizeof(float) * (size_t)W * AW, s));
             PRX_CHECK_HIP(hipMemcpy2DAsync(pad_w, sizeof(float) * 64, q[4], sizeof(float) * hd, sizeof(float) * hd, (size_t)W * heads,
                                            hipMemcpyDeviceToDevice, s));
             if ((r = pack_both(v, &y.Wo, &y.WoT, pad_w, W, AW, s))) return r;
         }
-        if ((r = copy_f32(v, &y.bo, q[5], W, s))) return r;
-        if ((r = copy_f32(v, &y.ln2_g, q[6], W, s))) return r;
-        if ((r = copy_f32(v, &y.ln2_b, q[7], W, s))) return r;
+        if ((r = v->mem.copy_f32(&y.bo, q[5], W, s))) return r;
+        if ((r = v->mem.copy_f32(&y.ln2_g, q[6], W, s))) return r;
+        if ((r = v->mem.copy_f32(&y.ln2_b, q[7], W, s))) return r;
         if ((r = pack_both(v, &y.W1, &y.W1T, q[8], 4 * W, W, s))) return r;
-        if ((r = copy_f32(v, &y.b1, q[9], 4 * W, s))) return r;
+        if ((r = v->mem.copy_f32(&y.b1, q[9], 4 * W, s))) return r;
         if ((r = pack_both(v, &y.W2, &y.W2T, q[10], W, 4 * W, s))) return r;
-        if ((r = copy_f32(v, &y.b2, q[11], W, s))) return r;
-        if (v->lean) { ALLOC_OP(y.x_in, R * W); ALLOC_OP(y.x_mid, R * W); }
-        else { float *a_, *b_; ALLOC(a_, R * W); ALLOC(b_, R * W); y.x_in = a_; y.x_mid = b_; }
-        ALLOC(y.mean1, R); ALLOC(y.rstd1, R); ALLOC(y.mean2, R); ALLOC(y.rstd2, R);
-        ALLOC_OP(y.qkv, R * 3 * AW); ALLOC_OP(y.t, R * 4 * W);
+        if ((r = v->mem.copy_f32(&y.b2, q[11], W, s))) return r;
+        if (v->lean) { DEV_ALLOC(m, alloc_op, y.x_in, R * W, f32); DEV_ALLOC(m, alloc_op, y.x_mid, R * W, f32); }
+        else { float *a_, *b_; DEV_ALLOC(m, alloc, a_, R * W); DEV_ALLOC(m, alloc, b_, R * W); y.x_in = a_; y.x_mid = b_; }
+        DEV_ALLOC(m, alloc, y.mean1, R); DEV_ALLOC(m, alloc, y.rstd1, R); DEV_ALLOC(m, alloc, y.mean2, R); DEV_ALLOC(m, alloc, y.rstd2, R);
+        DEV_ALLOC(m, alloc_op, y.qkv, R * 3 * AW, f32); DEV_ALLOC(m, alloc_op, y.t, R * 4 * W, f32);
         y.o_save = nullptr; y.lse = nullptr;
-        if (T > 64 || v->f32) { ALLOC_OP(y.o_save, R * AW); ALLOC(y.lse, (size_t)max_n * heads * T); }
+        if (T > 64 || v->f32) { DEV_ALLOC(m, alloc_op, y.o_save, R * AW, f32); DEV_ALLOC(m, alloc, y.lse, (size_t)max_n * heads * T); }
     }
     const float* const* q = w + n_head + 12 * layers;
-    if ((r = copy_f32(v, &v->lnpost_g, q[0], W, s))) return r;
-    if ((r = copy_f32(v, &v->lnpost_b, q[1], W, s))) return r;
+    if ((r = v->mem.copy_f32(&v->lnpost_g, q[0], W, s))) return r;
+    if ((r = v->mem.copy_f32(&v->lnpost_b, q[1], W, s))) return r;
     // proj is [width, out]: forward Bt = proj^T [out, width]; dgrad Bt = proj [width, out]
     if ((r = pack_both(v, &v->proj, &v->projT, q[2], W, out_dim, s))) return r;
-    ALLOC_OP(v->A0, R * KP); ALLOC_OP(v->h, R * W); ALLOC_OP(v->att_o, R * AW); ALLOC_OP(v->u, R * 4 * W);
-    ALLOC_OP(v->hpost, (size_t)max_n * W); ALLOC_OP(v->de16, (size_t)max_n * out_dim); ALLOC_OP(v->dt, R * 4 * W); ALLOC_OP(v->do_, R * AW); ALLOC_OP(v->dqkv, R * 3 * AW);
-    ALLOC(v->xpre, R * W); ALLOC(v->mean_pre, R); ALLOC(v->rstd_pre, R);
-    if (v->lean) ALLOC_OP(v->x_final, R * W);
-    else { float* a_; ALLOC(a_, R * W); v->x_final = a_; }
-    ALLOC(v->mean_post, max_n); ALLOC(v->rstd_post, max_n); ALLOC(v->e, (size_t)max_n * out_dim);
+    DEV_ALLOC(m, alloc_op, v->A0, R * KP, f32); DEV_ALLOC(m, alloc_op, v->h, R * W, f32);
+    DEV_ALLOC(m, alloc_op, v->att_o, R * AW, f32); DEV_ALLOC(m, alloc_op, v->u, R * 4 * W, f32);
+    DEV_ALLOC(m, alloc_op, v->hpost, (size_t)max_n * W, f32); DEV_ALLOC(m, alloc_op, v->de16, (size_t)max_n * out_dim, f32);
+    DEV_ALLOC(m, alloc_op, v->dt, R * 4 * W, f32); DEV_ALLOC(m, alloc_op, v->do_, R * AW, f32); DEV_ALLOC(m, alloc_op, v->dqkv, R * 3 * AW, f32);
+    DEV_ALLOC(m, alloc, v->xpre, R * W); DEV_ALLOC(m, alloc, v->mean_pre, R); DEV_ALLOC(m, alloc, v->rstd_pre, R);
+    if (v->lean) DEV_ALLOC(m, alloc_op, v->x_final, R * W, f32);
+    else { float* a_; DEV_ALLOC(m, alloc, a_, R * W); v->x_final = a_; }
+    DEV_ALLOC(m, alloc, v->mean_post, max_n); DEV_ALLOC(m, alloc, v->rstd_post, max_n); DEV_ALLOC(m, alloc, v->e, (size_t)max_n * out_dim);
     v->dx = v->dh = nullptr;
-    if (!v->lean) { ALLOC(v->dx, R * W); ALLOC(v->dh, R * W); }
-    ALLOC(v->dA0, R * KP); ALLOC(v->de, (size_t)max_n * out_dim);
+    if (!v->lean) { DEV_ALLOC(m, alloc, v->dx, R * W); DEV_ALLOC(m, alloc, v->dh, R * W); }
+    DEV_ALLOC(m, alloc, v->dA0, R * KP); DEV_ALLOC(m, alloc, v->de, (size_t)max_n * out_dim);
     // bf16 twins of the fp32 gradient streams (the dgrad GEMMs' A operands); the exact mode reads the fp32 streams themselves;
     // in the lean layout they ARE the gradient streams
     if (v->f32) { v->dx_bf = v->dx; v->dh_bf = v->dh; }
-    else { ALLOC_OP(v->dx_bf, R * W); ALLOC_OP(v->dh_bf, R * W); }
-    ALLOC(v->dhpost, (size_t)max_n * W); ALLOC(v->mm_part, 2 * 1024);
-    if (v->h16) ALLOC(v->gs, 2 + 64);
+    else { DEV_ALLOC(m, alloc_op, v->dx_bf, R * W, f32); DEV_ALLOC(m, alloc_op, v->dh_bf, R * W, f32); }
+    DEV_ALLOC(m, alloc, v->dhpost, (size_t)max_n * W); DEV_ALLOC(m, alloc, v->mm_part, 2 * 1024);
+    if (v->h16) DEV_ALLOC(m, alloc, v->gs, 2 + 64);
     v->ws_bytes = (size_t)64 << 20;
-    ALLOC(v->ws, v->ws_bytes / sizeof(float));
+    DEV_ALLOC(m, alloc, v->ws, v->ws_bytes / sizeof(float));
     *out = guard.release();
     return 0;
 }
 
-void prx_vit_destroy_impl(PrxVit* v) {
-    if (!v) return;
-    for (void* p : v->allocs) (void)hipFree(p);
-    delete v;
-}
+void prx_vit_destroy_impl(PrxVit* v) { delete v; }
 
 static int vit_gemm(PrxVit* v, GemmDesc& d, hipStream_t s) {
     if (v->f32) { d.f32 = 1; d.a_is_f32 = 0; }

@@ -14,6 +14,7 @@
 #include "elementwise.h"
 #include "prompt_vq.h"
 #include "vit.h"  // prx_pack_* helpers
+#include "dev_arena.h"
 #include <vector>
 #include <memory>
 #include <stdlib.h>
@@ -105,7 +106,7 @@ struct PrxVqgan {
     int lean;
     float* gs;        // half mode: device {S, 1/S} = the power-of-two scale of the backward in flight (common.h) + 256 partials; else null
     GemmCtx gctx;     // this handle's engine state
-    std::vector<void*> allocs;
+    DevArena mem;     // every device buffer below: freed with the handle
     float *codebook, *cnorm, *zmin, *zmax;
     Conv1 pq; Conv3 conv_in, conv_out; GN norm_out;
     std::vector<ResBlock> res; std::vector<AttnBlock> attn; std::vector<UpBlock> ups; std::vector<Stage> stages;
@@ -125,46 +126,18 @@ struct PrxVqgan {
 };
 
 namespace {
-template <typename Tp>
-int dalloc(PrxVqgan* v, Tp** p, size_t count) {
-    void* q = nullptr;
-    PRX_CHECK_HIP(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(Tp)));
-    v->allocs.push_back(q);
-    *p = (Tp*)q;
-    return 0;
-}
-#define VALLOC(ptr, count) do { int _r = dalloc(v, &(ptr), (count)); if (_r) return _r; } while (0)
-int dalloc_op(PrxVqgan* v, void** p, size_t count) {   // `count` operand elements
-    void* q = nullptr;
-    PRX_CHECK_HIP(hipMalloc(&q, std::max<size_t>(count, 1) * op_esz(v->f32)));
-    v->allocs.push_back(q);
-    *p = q;
-    return 0;
-}
-#define VALLOC_OP(ptr, count) do { int _r = dalloc_op(v, &(ptr), (count)); if (_r) return _r; } while (0)
-int dalloc_stream(PrxVqgan* v, void** p, size_t count) {   // `count` stream elements: fp32, or 16-bit in the lean layout
-    void* q = nullptr;
-    PRX_CHECK_HIP(hipMalloc(&q, std::max<size_t>(count, 1) * (v->lean ? sizeof(bf16_t) : sizeof(float))));
-    v->allocs.push_back(q);
-    *p = q;
-    return 0;
-}
-#define VALLOC_S(ptr, count) do { int _r = dalloc_stream(v, &(ptr), (count)); if (_r) return _r; } while (0)
+// `count` stream elements: fp32, or 16-bit in the lean layout
+int alloc_stream(PrxVqgan* v, void** p, size_t count) { return v->mem.alloc_op(p, count, !v->lean); }
 
 struct WCursor { const float* const* w; int n, pos; };
 #define NEXTW(cur, dst) do { PRX_REQUIRE((cur).pos < (cur).n, "vqgan_create: weight list too short"); (dst) = (cur).w[(cur).pos++]; } while (0)
 
-int copyf(PrxVqgan* v, float** dst, const float* src, size_t n, hipStream_t s) {
-    VALLOC(*dst, n);
-    PRX_CHECK_HIP(hipMemcpyAsync(*dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return 0;
-}
 int make_gn(PrxVqgan* v, GN& g, int C, WCursor& cur, hipStream_t s) {
     const float *w, *b; NEXTW(cur, w); NEXTW(cur, b);
     g.C = C;
     int r;
-    if ((r = copyf(v, &g.g, w, C, s))) return r;
-    if ((r = copyf(v, &g.b, b, C, s))) return r;
+    if ((r = v->mem.copy_f32(&g.g, w, C, s))) return r;
+    if ((r = v->mem.copy_f32(&g.b, b, C, s))) return r;
     g.id = v->n_gn++;
     g.stats = g.bstats = nullptr;   // assigned once every GroupNorm is known
     return 0;
@@ -174,11 +147,11 @@ int make_conv3(PrxVqgan* v, Conv3& c, int Cin, int Cout, WCursor& cur, hipStream
     c.Cin = Cin; c.Cout = Cout; c.CoP = (Cout + 7) / 8 * 8;
     // the forward pack has CoP rows too (zero rows beyond Cout, zero bias): N % 8 == 0 puts conv_out (3 channels) on the MFMA tiles
     // with vector epilogues like every other convolution; its fp32 output is [pixels][CoP]
-    VALLOC_OP(c.Wf, (size_t)c.CoP * 9 * Cin);
+    DEV_ALLOC(v->mem, alloc_op, c.Wf, (size_t)c.CoP * 9 * Cin, v->f32);
     if (c.CoP != Cout) PRX_CHECK_HIP(hipMemsetAsync(c.Wf, 0, (size_t)c.CoP * 9 * Cin * op_esz(v->f32), s));
-    VALLOC_OP(c.Wd, (size_t)Cin * 9 * c.CoP);
+    DEV_ALLOC(v->mem, alloc_op, c.Wd, (size_t)Cin * 9 * c.CoP, v->f32);
     { int e_ = prx_vqgan_pack_conv3x3(w, c.Wf, c.Wd, Cout, Cin, c.CoP, v->prec, s); if (e_) return e_; }
-    VALLOC(c.b, c.CoP);
+    DEV_ALLOC(v->mem, alloc, c.b, c.CoP);
     if (c.CoP != Cout) PRX_CHECK_HIP(hipMemsetAsync(c.b, 0, sizeof(float) * c.CoP, s));
     PRX_CHECK_HIP(hipMemcpyAsync(c.b, b, sizeof(float) * Cout, hipMemcpyDeviceToDevice, s));
     return 0;
@@ -186,11 +159,11 @@ int make_conv3(PrxVqgan* v, Conv3& c, int Cin, int Cout, WCursor& cur, hipStream
 int make_conv1(PrxVqgan* v, Conv1& c, int Cin, int Cout, WCursor& cur, hipStream_t s) {
     const float *w, *b; NEXTW(cur, w); NEXTW(cur, b);
     c.Cin = Cin; c.Cout = Cout;
-    VALLOC_OP(c.W, (size_t)Cout * Cin); VALLOC_OP(c.WT, (size_t)Cout * Cin);
+    DEV_ALLOC(v->mem, alloc_op, c.W, (size_t)Cout * Cin, v->f32); DEV_ALLOC(v->mem, alloc_op, c.WT, (size_t)Cout * Cin, v->f32);
     int r;
     if ((r = prx_pack_op(w, c.W, (size_t)Cout * Cin, v->prec, s))) return r;
     if ((r = prx_pack_transpose_op(w, c.WT, Cout, Cin, v->prec, s))) return r;
-    return copyf(v, &c.b, b, Cout, s);
+    return v->mem.copy_f32(&c.b, b, Cout, s);
 }
 int make_res(PrxVqgan* v, int Cin, int Cout, int rh, int rw, WCursor& cur, hipStream_t s) {
     ResBlock rb{};
@@ -203,9 +176,10 @@ int make_res(PrxVqgan* v, int Cin, int Cout, int rh, int rw, WCursor& cur, hipSt
     const size_t P = (size_t)rh * rw;
     if (rb.has_sc) {
         if ((r = make_conv1(v, rb.sc, Cin, Cout, cur, s))) return r;
-        VALLOC_S(rb.scbuf, P * Cout);
+        if ((r = alloc_stream(v, &rb.scbuf, P * Cout))) return r;
     }
-    VALLOC_S(rb.h1, P * Cout); VALLOC_S(rb.out, P * Cout);
+    if ((r = alloc_stream(v, &rb.h1, P * Cout))) return r;
+    if ((r = alloc_stream(v, &rb.out, P * Cout))) return r;
     v->stages.push_back({0, (int)v->res.size()});
     v->res.push_back(rb);
     return 0;
@@ -219,21 +193,23 @@ int make_attn(PrxVqgan* v, int C, int rh, int rw, WCursor& cur, hipStream_t s) {
     const float *wq, *bq, *wk, *bk, *wv, *bv;
     NEXTW(cur, wq); NEXTW(cur, bq); NEXTW(cur, wk); NEXTW(cur, bk); NEXTW(cur, wv); NEXTW(cur, bv);
     float *wcat, *bcat;
-    VALLOC(wcat, (size_t)3 * C * C); VALLOC(bcat, 3 * C);
+    DEV_ALLOC(v->mem, alloc, wcat, (size_t)3 * C * C); DEV_ALLOC(v->mem, alloc, bcat, 3 * C);
     const float* ws_[3] = {wq, wk, wv}; const float* bs_[3] = {bq, bk, bv};
     for (int i = 0; i < 3; ++i) {
         PRX_CHECK_HIP(hipMemcpyAsync(wcat + (size_t)i * C * C, ws_[i], sizeof(float) * C * C, hipMemcpyDeviceToDevice, s));
         PRX_CHECK_HIP(hipMemcpyAsync(bcat + i * C, bs_[i], sizeof(float) * C, hipMemcpyDeviceToDevice, s));
     }
     ab.qkv.Cin = C; ab.qkv.Cout = 3 * C; ab.qkv.b = bcat;
-    VALLOC_OP(ab.qkv.W, (size_t)3 * C * C); VALLOC_OP(ab.qkv.WT, (size_t)3 * C * C);
+    DEV_ALLOC(v->mem, alloc_op, ab.qkv.W, (size_t)3 * C * C, v->f32); DEV_ALLOC(v->mem, alloc_op, ab.qkv.WT, (size_t)3 * C * C, v->f32);
     if ((r = prx_pack_op(wcat, ab.qkv.W, (size_t)3 * C * C, v->prec, s))) return r;
     if ((r = prx_pack_transpose_op(wcat, ab.qkv.WT, 3 * C, C, v->prec, s))) return r;
     if ((r = make_conv1(v, ab.proj, C, C, cur, s))) return r;
     const size_t P = (size_t)rh * rw;
     const size_t P8 = (size_t)pad8((int)P);
-    VALLOC_OP(ab.qkvb, P * 3 * C); VALLOC_OP(ab.Pm, P * P8); VALLOC_OP(ab.PT, P * P8); VALLOC_S(ab.out, P * C);
-    VALLOC_OP(ab.qkvT, (size_t)3 * C * P8);
+    DEV_ALLOC(v->mem, alloc_op, ab.qkvb, P * 3 * C, v->f32);
+    DEV_ALLOC(v->mem, alloc_op, ab.Pm, P * P8, v->f32); DEV_ALLOC(v->mem, alloc_op, ab.PT, P * P8, v->f32);
+    if ((r = alloc_stream(v, &ab.out, P * C))) return r;
+    DEV_ALLOC(v->mem, alloc_op, ab.qkvT, (size_t)3 * C * P8, v->f32);
     PRX_CHECK_HIP(hipMemsetAsync(ab.qkvT, 0, (size_t)3 * C * P8 * op_esz(v->f32), s));
     PRX_CHECK_HIP(hipMemsetAsync(ab.Pm, 0, P * P8 * op_esz(v->f32), s));      // pad columns stay zero: the kernels never write them
     PRX_CHECK_HIP(hipMemsetAsync(ab.PT, 0, P * P8 * op_esz(v->f32), s));
@@ -246,7 +222,7 @@ int make_up(PrxVqgan* v, int C, int rh, int rw, WCursor& cur, hipStream_t s) {
     ub.C = C; ub.rh = rh; ub.rw = rw;
     int r;
     if ((r = make_conv3(v, ub.c, C, C, cur, s))) return r;
-    VALLOC_S(ub.out, (size_t)rh * rw * C);
+    if ((r = alloc_stream(v, &ub.out, (size_t)rh * rw * C))) return r;
     v->stages.push_back({2, (int)v->ups.size()});
     v->ups.push_back(ub);
     return 0;
@@ -259,8 +235,11 @@ int prx_vqgan_create_impl(PrxVqgan** out, int ch, const int* ch_mult, int n_mult
     PRX_REQUIRE(h0 >= 1 && w0 >= 1, "vqgan_create: bad latent size %dx%d", h0, w0);
     PRX_REQUIRE(prec_valid(precision), "vqgan_create: unknown precision %d", precision);
     PRX_REQUIRE(embed_dim == z_channels, "vqgan_create: embed_dim must equal z_channels");
-    PrxVqgan* v = new PrxVqgan();
-    std::unique_ptr<PrxVqgan> guard(v);
+    std::unique_ptr<PrxVqgan> guard(new PrxVqgan());      // a failed create frees what it allocated (DevArena)
+    PrxVqgan* v = guard.get();
+    DevArena& m = v->mem;
+    const int f32 = prec_is_f32(precision);
+    m.describe("vqgan_create", ": the decoder keeps one forward's activations and the backward's gradient streams for a %d x %d latent", h0, w0);
     v->prec = precision; v->f32 = prec_is_f32(precision); v->h16 = prec_is_h16(precision);
     v->gs = nullptr;
     { const char* e = getenv("PRX_LEAN"); v->lean = (v->h16 && !(e && atoi(e) == 0)) ? 1 : 0; }
@@ -268,8 +247,8 @@ int prx_vqgan_create_impl(PrxVqgan** out, int ch, const int* ch_mult, int n_mult
     WCursor cur{w, n_w, 0};
     int r;
     const float* cb; NEXTW(cur, cb);
-    if ((r = copyf(v, &v->codebook, cb, (size_t)n_embed * embed_dim, s))) return r;
-    VALLOC(v->cnorm, n_embed); VALLOC(v->zmin, embed_dim); VALLOC(v->zmax, embed_dim);
+    if ((r = m.copy_f32(&v->codebook, cb, (size_t)n_embed * embed_dim, s))) return r;
+    DEV_ALLOC(m, alloc, v->cnorm, n_embed); DEV_ALLOC(m, alloc, v->zmin, embed_dim); DEV_ALLOC(m, alloc, v->zmax, embed_dim);
     if ((r = prx_sqnorm_rows(v->codebook, v->cnorm, n_embed, embed_dim, s))) return r;
     if ((r = prx_colminmax(v->codebook, v->zmin, v->zmax, n_embed, embed_dim, s))) return r;
     if ((r = make_conv1(v, v->pq, embed_dim, z_channels, cur, s))) return r;
@@ -303,25 +282,28 @@ int prx_vqgan_create_impl(PrxVqgan** out, int ch, const int* ch_mult, int n_mult
     for (auto& rb : v->res) maxPC = std::max(maxPC, (size_t)rb.rh * rb.rw * std::max(rb.Cin, rb.Cout));
     for (auto& ub : v->ups) maxPC = std::max(maxPC, (size_t)ub.rh * ub.rw * ub.C);
     for (auto& ab : v->attn) maxAttnPC = std::max(maxAttnPC, (size_t)pad8(ab.rh * ab.rw) * (size_t)std::max(ab.C, pad8(ab.rh * ab.rw)));
-    VALLOC(v->zq, P0 * embed_dim); VALLOC_OP(v->pqo_bf, P0 * z_channels); VALLOC_OP(v->dpq_bf, P0 * z_channels);
-    VALLOC_S(v->h_in, P0 * (size_t)(ch * ch_mult[n_mult - 1]));
-    VALLOC(v->y, PH * (size_t)v->conv_out.CoP); VALLOC(v->idx, P0); VALLOC(v->dzq, P0 * embed_dim);
+    DEV_ALLOC(m, alloc, v->zq, P0 * embed_dim); DEV_ALLOC(m, alloc_op, v->pqo_bf, P0 * z_channels, f32);
+    DEV_ALLOC(m, alloc_op, v->dpq_bf, P0 * z_channels, f32);
+    if ((r = alloc_stream(v, &v->h_in, P0 * (size_t)(ch * ch_mult[n_mult - 1])))) return r;
+    DEV_ALLOC(m, alloc, v->y, PH * (size_t)v->conv_out.CoP); DEV_ALLOC(m, alloc, v->idx, P0); DEV_ALLOC(m, alloc, v->dzq, P0 * embed_dim);
     const int ntiles = ceil_div(n_embed, 64);
-    VALLOC(v->pmin, P0 * ntiles); VALLOC(v->pidx, P0 * ntiles);
-    VALLOC_OP(v->a, maxPC);
-    VALLOC_OP(v->tA, maxAttnPC); VALLOC_OP(v->tB, maxAttnPC); VALLOC_OP(v->tC, maxAttnPC); VALLOC_OP(v->tD, maxAttnPC);
-    VALLOC_OP(v->dqkv, maxAttnPC * 3); VALLOC_OP(v->dy8, PH * 8);
+    DEV_ALLOC(m, alloc, v->pmin, P0 * ntiles); DEV_ALLOC(m, alloc, v->pidx, P0 * ntiles);
+    DEV_ALLOC(m, alloc_op, v->a, maxPC, f32);
+    DEV_ALLOC(m, alloc_op, v->tA, maxAttnPC, f32); DEV_ALLOC(m, alloc_op, v->tB, maxAttnPC, f32); DEV_ALLOC(m, alloc_op, v->tC, maxAttnPC, f32);
+    DEV_ALLOC(m, alloc_op, v->tD, maxAttnPC, f32);
+    DEV_ALLOC(m, alloc_op, v->dqkv, maxAttnPC * 3, f32); DEV_ALLOC(m, alloc_op, v->dy8, PH * 8, f32);
     v->dycol = v->Wd_col = nullptr;
     if (!v->f32 && v->conv_out.CoP == 8) {
         const int Cin = v->conv_out.Cin;
-        VALLOC_OP(v->dycol, PH * 128); VALLOC_OP(v->Wd_col, (size_t)Cin * 128);
+        DEV_ALLOC(m, alloc_op, v->dycol, PH * 128, f32); DEV_ALLOC(m, alloc_op, v->Wd_col, (size_t)Cin * 128, f32);
         PRX_CHECK_HIP(hipMemsetAsync(v->Wd_col, 0, (size_t)Cin * 128 * sizeof(bf16_t), s));
         PRX_CHECK_HIP(hipMemcpy2DAsync(v->Wd_col, 128 * sizeof(bf16_t), v->conv_out.Wd, 72 * sizeof(bf16_t), 72 * sizeof(bf16_t), Cin, hipMemcpyDeviceToDevice, s));
     }
-    VALLOC(v->S, maxAttnPC);
-    VALLOC_S(v->g0, maxPC); VALLOC_S(v->g1, maxPC); VALLOC_S(v->g2, maxPC);
+    DEV_ALLOC(m, alloc, v->S, maxAttnPC);
+    for (void** g : {&v->g0, &v->g1, &v->g2})
+        if ((r = alloc_stream(v, g, maxPC))) return r;
     if (v->f32 || v->lean) { v->g0b = v->g0; v->g1b = v->g1; v->g2b = v->g2; }     // the gradient streams are the dgrad operands
-    else { VALLOC_OP(v->g0b, maxPC); VALLOC_OP(v->g1b, maxPC); VALLOC_OP(v->g2b, maxPC); }
+    else { DEV_ALLOC(m, alloc_op, v->g0b, maxPC, f32); DEV_ALLOC(m, alloc_op, v->g1b, maxPC, f32); DEV_ALLOC(m, alloc_op, v->g2b, maxPC, f32); }
     // bf16 twins of stage outputs that feed a GEMM directly (1x1 shortcut or upsample conv of the next stage)
     v->h_in_bf = nullptr;
     for (size_t i = 0; i < v->stages.size(); ++i) {
@@ -337,27 +319,23 @@ int prx_vqgan_create_impl(PrxVqgan** out, int ch, const int* ch_mult, int n_mult
             else { UpBlock& b = v->ups[pr.idx]; slot = &b.out_bf; cnt = (size_t)b.rh * b.rw * b.C; self = b.out; }
         }
         if (v->f32 || v->lean) *slot = self;          // exact mode / lean layout: the stage output is the operand
-        else VALLOC_OP(*slot, cnt);
+        else DEV_ALLOC(m, alloc_op, *slot, cnt, f32);
     }
     {   // one contiguous stats slab: forward stats of every GroupNorm, then the backward stats
-        VALLOC(v->all_stats, (size_t)2 * v->n_gn * 64);
+        DEV_ALLOC(m, alloc, v->all_stats, (size_t)2 * v->n_gn * 64);
         auto fix = [&](GN& g) { g.stats = v->all_stats + (size_t)g.id * 64; g.bstats = v->all_stats + (size_t)(v->n_gn + g.id) * 64; };
         for (auto& b : v->res) { fix(b.n1); fix(b.n2); }
         for (auto& b : v->attn) fix(b.n);
         fix(v->norm_out);
     }
     v->ws_bytes = (size_t)64 << 20;
-    VALLOC(v->ws, v->ws_bytes / sizeof(float));
-    if (v->h16) VALLOC(v->gs, 2 + 256);
+    DEV_ALLOC(m, alloc, v->ws, v->ws_bytes / sizeof(float));
+    if (v->h16) DEV_ALLOC(m, alloc, v->gs, 2 + 256);
     *out = guard.release();
     return 0;
 }
 
-void prx_vqgan_destroy_impl(PrxVqgan* v) {
-    if (!v) return;
-    for (void* p : v->allocs) (void)hipFree(p);
-    delete v;
-}
+void prx_vqgan_destroy_impl(PrxVqgan* v) { delete v; }
 
 // the GEMM epilogue can accumulate the next GroupNorm's sums only for power-of-two group sizes >= 4 channels
 // (the exact mode too: its fp32-operand fit kernels carry the sums, and the engine falls back to the norm kernels' own

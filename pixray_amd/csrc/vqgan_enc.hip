@@ -12,6 +12,7 @@
 #include "elementwise.h"
 #include "prompt_vq.h"
 #include "vit.h"  // prx_pack_* helpers
+#include "dev_arena.h"
 #include <vector>
 #include <memory>
 #include <algorithm>
@@ -49,7 +50,7 @@ int prx_vqgan_enc_pack_conv3x3(const float* w, void* Wf, int Cout, int Cin, int 
 
 struct PrxVqganEnc {
     int in_ch, zc, D, NC, H, W, h0, w0;
-    std::vector<void*> allocs;
+    DevArena mem;     // every device buffer below: freed with the handle
     float *codebook, *cnorm;
     EConv3 conv_in, conv_out; EConv1 quant; EGN norm_out;
     std::vector<ERes> res; std::vector<EAttn> attn; std::vector<EConv3> downs; std::vector<EOp> ops;
@@ -61,44 +62,30 @@ struct PrxVqganEnc {
 };
 
 namespace {
-template <typename Tp>
-int ealloc(PrxVqganEnc* e, Tp** p, size_t count) {
-    void* q = nullptr;
-    PRX_CHECK_HIP(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(Tp)));
-    e->allocs.push_back(q);
-    *p = (Tp*)q;
-    return 0;
-}
-#define EALLOC(ptr, count) do { int _r = ealloc(e, &(ptr), (count)); if (_r) return _r; } while (0)
 struct ECursor { const float* const* w; int n, pos; };
 #define ENEXT(cur, dst) do { PRX_REQUIRE((cur).pos < (cur).n, "vqgan_enc_create: weight list too short"); (dst) = (cur).w[(cur).pos++]; } while (0)
 
-int ecopy(PrxVqganEnc* e, float** dst, const float* src, size_t n, hipStream_t s) {
-    EALLOC(*dst, n);
-    PRX_CHECK_HIP(hipMemcpyAsync(*dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return 0;
-}
 int e_gn(PrxVqganEnc* e, EGN& g, int C, ECursor& cur, hipStream_t s) {
     const float *w, *b; ENEXT(cur, w); ENEXT(cur, b);
     g.C = C;
     int r;
-    if ((r = ecopy(e, &g.g, w, C, s))) return r;
-    return ecopy(e, &g.b, b, C, s);
+    if ((r = e->mem.copy_f32(&g.g, w, C, s))) return r;
+    return e->mem.copy_f32(&g.b, b, C, s);
 }
 int e_conv3(PrxVqganEnc* e, EConv3& c, int Cin, int Cout, ECursor& cur, hipStream_t s) {
     const float *w, *b; ENEXT(cur, w); ENEXT(cur, b);
     c.Cin = Cin; c.CiP = (Cin + 7) / 8 * 8; c.Cout = Cout;
-    EALLOC(c.W, (size_t)Cout * 9 * c.CiP);
+    DEV_ALLOC(e->mem, alloc, c.W, (size_t)Cout * 9 * c.CiP);
     { int r_ = prx_vqgan_enc_pack_conv3x3(w, c.W, Cout, Cin, c.CiP, s); if (r_) return r_; }
-    return ecopy(e, &c.b, b, Cout, s);
+    return e->mem.copy_f32(&c.b, b, Cout, s);
 }
 int e_conv1(PrxVqganEnc* e, EConv1& c, int Cin, int Cout, ECursor& cur, hipStream_t s) {
     const float *w, *b; ENEXT(cur, w); ENEXT(cur, b);
     c.Cin = Cin; c.Cout = Cout;
-    EALLOC(c.W, (size_t)Cout * Cin);
+    DEV_ALLOC(e->mem, alloc, c.W, (size_t)Cout * Cin);
     int r;
     if ((r = prx_pack_bf16(w, c.W, (size_t)Cout * Cin, s))) return r;
-    return ecopy(e, &c.b, b, Cout, s);
+    return e->mem.copy_f32(&c.b, b, Cout, s);
 }
 int e_res(PrxVqganEnc* e, int Cin, int Cout, int H, int W, ECursor& cur, hipStream_t s) {
     ERes rb{};
@@ -121,14 +108,14 @@ int e_attn(PrxVqganEnc* e, int C, int H, int W, ECursor& cur, hipStream_t s) {
     const float *wq, *bq, *wk, *bk, *wv, *bv;
     ENEXT(cur, wq); ENEXT(cur, bq); ENEXT(cur, wk); ENEXT(cur, bk); ENEXT(cur, wv); ENEXT(cur, bv);
     float *wcat, *bcat;
-    EALLOC(wcat, (size_t)3 * C * C); EALLOC(bcat, 3 * C);
+    DEV_ALLOC(e->mem, alloc, wcat, (size_t)3 * C * C); DEV_ALLOC(e->mem, alloc, bcat, 3 * C);
     const float* ws_[3] = {wq, wk, wv}; const float* bs_[3] = {bq, bk, bv};
     for (int i = 0; i < 3; ++i) {
         PRX_CHECK_HIP(hipMemcpyAsync(wcat + (size_t)i * C * C, ws_[i], sizeof(float) * C * C, hipMemcpyDeviceToDevice, s));
         PRX_CHECK_HIP(hipMemcpyAsync(bcat + i * C, bs_[i], sizeof(float) * C, hipMemcpyDeviceToDevice, s));
     }
     ab.qkv.Cin = C; ab.qkv.Cout = 3 * C; ab.qkv.b = bcat;
-    EALLOC(ab.qkv.W, (size_t)3 * C * C);
+    DEV_ALLOC(e->mem, alloc, ab.qkv.W, (size_t)3 * C * C);
     if ((r = prx_pack_bf16(wcat, ab.qkv.W, (size_t)3 * C * C, s))) return r;
     if ((r = e_conv1(e, ab.proj, C, C, cur, s))) return r;
     e->ops.push_back({1, (int)e->attn.size(), H, W});
@@ -157,14 +144,16 @@ int prx_vqgan_enc_create_impl(PrxVqganEnc** out, int ch, const int* ch_mult, int
     const int f = 1 << (n_mult - 1);
     PRX_REQUIRE(H > 0 && W > 0 && H % f == 0 && W % f == 0, "vqgan_enc_create: image %dx%d must be a multiple of %d", H, W, f);
     PRX_REQUIRE(in_ch >= 1 && in_ch <= 8, "vqgan_enc_create: in_channels %d not supported", in_ch);
-    PrxVqganEnc* e = new PrxVqganEnc();
-    std::unique_ptr<PrxVqganEnc> guard(e);
+    std::unique_ptr<PrxVqganEnc> guard(new PrxVqganEnc());      // a failed create frees what it allocated (DevArena)
+    PrxVqganEnc* e = guard.get();
+    DevArena& m = e->mem;
+    m.describe("vqgan_enc_create", ": the encoder keeps the activations of one %d x %d image", H, W);
     e->in_ch = in_ch; e->zc = z_channels; e->D = embed_dim; e->NC = n_embed; e->H = H; e->W = W; e->h0 = H / f; e->w0 = W / f;
     ECursor cur{w, n_w, 0};
     int r;
     const float* cb; ENEXT(cur, cb);
-    if ((r = ecopy(e, &e->codebook, cb, (size_t)n_embed * embed_dim, s))) return r;
-    EALLOC(e->cnorm, n_embed);
+    if ((r = m.copy_f32(&e->codebook, cb, (size_t)n_embed * embed_dim, s))) return r;
+    DEV_ALLOC(m, alloc, e->cnorm, n_embed);
     if ((r = prx_sqnorm_rows(e->codebook, e->cnorm, n_embed, embed_dim, s))) return r;
     if ((r = e_conv3(e, e->conv_in, in_ch, ch, cur, s))) return r;
     int block_in = ch, h = H, wd = W, nominal = resolution;
@@ -198,27 +187,24 @@ int prx_vqgan_enc_create_impl(PrxVqganEnc** out, int ch, const int* ch_mult, int
     const size_t P0 = (size_t)e->h0 * e->w0;
     size_t maxAttnC = 1;
     for (auto& ab : e->attn) maxAttnC = std::max(maxAttnC, (size_t)ab.C);
-    EALLOC(e->img8, (size_t)H * W * 8);
-    EALLOC(e->a, maxPC); EALLOC(e->xb0, maxPC); EALLOC(e->xb1, maxPC);
-    EALLOC(e->x0, maxPC); EALLOC(e->x1, maxPC); EALLOC(e->h1, maxPC); EALLOC(e->sc, maxPC);
+    DEV_ALLOC(m, alloc, e->img8, (size_t)H * W * 8);
+    DEV_ALLOC(m, alloc, e->a, maxPC); DEV_ALLOC(m, alloc, e->xb0, maxPC); DEV_ALLOC(m, alloc, e->xb1, maxPC);
+    DEV_ALLOC(m, alloc, e->x0, maxPC); DEV_ALLOC(m, alloc, e->x1, maxPC); DEV_ALLOC(m, alloc, e->h1, maxPC); DEV_ALLOC(m, alloc, e->sc, maxPC);
     const size_t maxP8 = (maxP + 7) & ~(size_t)7;
-    EALLOC(e->qkvb, maxP * 3 * maxAttnC); EALLOC(e->tA, maxP8 * maxAttnC); EALLOC(e->tB, maxP * maxAttnC);
-    EALLOC(e->Pm, maxP * maxP8); EALLOC(e->PT, maxP * maxP8); EALLOC(e->S, maxP * maxP);
-    EALLOC(e->co_bf, P0 * z_channels); EALLOC(e->hq, P0 * embed_dim); EALLOC(e->zq, P0 * embed_dim); EALLOC(e->idx, P0);
+    DEV_ALLOC(m, alloc, e->qkvb, maxP * 3 * maxAttnC); DEV_ALLOC(m, alloc, e->tA, maxP8 * maxAttnC); DEV_ALLOC(m, alloc, e->tB, maxP * maxAttnC);
+    DEV_ALLOC(m, alloc, e->Pm, maxP * maxP8); DEV_ALLOC(m, alloc, e->PT, maxP * maxP8); DEV_ALLOC(m, alloc, e->S, maxP * maxP);
+    DEV_ALLOC(m, alloc, e->co_bf, P0 * z_channels); DEV_ALLOC(m, alloc, e->hq, P0 * embed_dim); DEV_ALLOC(m, alloc, e->zq, P0 * embed_dim);
+    DEV_ALLOC(m, alloc, e->idx, P0);
     const int ntiles = ceil_div(n_embed, 64);
-    EALLOC(e->pmin, P0 * ntiles); EALLOC(e->pidx, P0 * ntiles);
-    EALLOC(e->stats, 64);
+    DEV_ALLOC(m, alloc, e->pmin, P0 * ntiles); DEV_ALLOC(m, alloc, e->pidx, P0 * ntiles);
+    DEV_ALLOC(m, alloc, e->stats, 64);
     e->ws_bytes = (size_t)64 << 20;
-    EALLOC(e->ws, e->ws_bytes / sizeof(float));
+    DEV_ALLOC(m, alloc, e->ws, e->ws_bytes / sizeof(float));
     *out = guard.release();
     return 0;
 }
 
-void prx_vqgan_enc_destroy_impl(PrxVqganEnc* e) {
-    if (!e) return;
-    for (void* p : e->allocs) (void)hipFree(p);
-    delete e;
-}
+void prx_vqgan_enc_destroy_impl(PrxVqganEnc* e) { delete e; }
 
 // img: NCHW [1, in_ch, H, W] fp32 in [-1, 1] (what pixray feeds: vqgan.py:174, pixray.py:718-727) ->
 // z: NCHW [1, D, h0, w0] = the selected code vectors; z_pre (optional): NCHW pre-quantisation latent; indices (optional)

@@ -56,6 +56,28 @@ def _weight_array(tensors: Sequence[torch.Tensor]):
     return arr
 
 
+def _keep(obj, arr):
+    obj._arr = arr   # keep the ctypes array alive for the duration of the call
+    return ctypes.addressof(arr)
+
+
+class _Handle:
+    """Base of the runner handles.  `h` is the C handle (a ctypes.c_void_p, or the bare pointer `prx_fft_drawer_create` returns);
+    `_destroy` names the `prx_*_destroy` that frees it with all its device memory (csrc/dev_arena.h); `_arr` is the ctypes array of
+    weight pointers, `_keep`ed for the create call."""
+    _destroy = None
+    _arr = None
+    h = None
+
+    def __del__(self):
+        h, self.h = self.h, None
+        if getattr(h, "value", h):
+            try:
+                _destroy_handle(self._destroy, h)
+            except Exception:
+                pass
+
+
 # --------------------------------------------------------------------------------------- cutouts
 class _MakeCutoutsFn(torch.autograd.Function):
     @staticmethod
@@ -119,10 +141,11 @@ def _weights_in_abi_order(params, shapes, device, what):
     return ws
 
 
-class ClipVitHandle:
+class ClipVitHandle(_Handle):
     """Owns a `prx_clip_vit` (packed weights + activation workspace for `max_batch` cutouts, allocated at create time; an allocation
     that fails raises PrxError with the bytes asked for and held, and the partly built handle is freed).
     `precision`: "fp16" (default) / "bf16" (fast paths) or "f32" (exact-f32 MFMA parity mode, include/prx.h PRX_PREC_*)."""
+    _destroy = "prx_clip_vit_destroy"
     abi = "prx_clip_vit"
 
     def __init__(self, cfg, params, max_batch: int, device, precision=None):
@@ -142,15 +165,6 @@ class ClipVitHandle:
     @property
     def gemm_ctx(self):
         return _lib.load().prx_clip_vit_gemm_ctx(self.h)
-
-    def __del__(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            try:
-                _destroy_handle("prx_clip_vit_destroy", h)
-            except Exception:
-                pass
-            self.h = None
 
 
 class _VitTowerCfg(ctypes.Structure):
@@ -183,17 +197,12 @@ class SlipVitHandle(ClipVitHandle):
         self.generation = 0
 
 
-def _keep(obj, arr):
-    obj._arr = arr   # keep the ctypes array alive for the duration of the call
-    return ctypes.addressof(arr)
-
-
 class _ClipResNetCfg(ctypes.Structure):
     _fields_ = [("input_resolution", ctypes.c_int), ("width", ctypes.c_int), ("layers", ctypes.c_int * 4), ("heads", ctypes.c_int),
                 ("output_dim", ctypes.c_int), ("max_batch", ctypes.c_int), ("precision", ctypes.c_int)]
 
 
-class ClipResNetHandle:
+class ClipResNetHandle(_Handle):
     """Owns a `prx_clip_resnet` (CLIP ModifiedResNet tower: RN50, RN101, RN50x4, RN50x16, RN50x64); same protocol as ClipVitHandle.
     `params` is the OpenAI `visual.*` state dict (BatchNorm un-folded); the fold happens here.
 
@@ -202,6 +211,7 @@ class ClipResNetHandle:
     (1077 MiB) with bf16 and 1 636 394 240 (1561 MiB) in the exact-f32 mode, beside 1.7 GB (half) of packed weights: 35.7 GiB at
     max_batch = 64 in the default mode.  RN50x16 at 384 x 384 takes 262 / 470 / 683 MiB per cutout.  An allocation that fails raises
     PrxError with the bytes asked for and the bytes held so far; the partly built handle is freed and the process goes on."""
+    _destroy = "prx_clip_resnet_destroy"
     abi = "prx_clip_resnet"
 
     def __init__(self, cfg, params, max_batch: int, device, precision=None):
@@ -227,15 +237,6 @@ class ClipResNetHandle:
     @property
     def gemm_ctx(self):
         return _lib.load().prx_clip_resnet_gemm_ctx(self.h)
-
-    def __del__(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            try:
-                _destroy_handle("prx_clip_resnet_destroy", h)
-            except Exception:
-                pass
-            self.h = None
 
 
 class _ClipCfg(ctypes.Structure):
@@ -331,8 +332,9 @@ class _ClipTextCfg(ctypes.Structure):
                                             "max_batch")]
 
 
-class ClipTextHandle:
+class ClipTextHandle(_Handle):
     """Owns a `prx_clip_text` (CLIP text transformer, forward only: CLIP_Base.encode_text, slip.py:68-70)."""
+    _destroy = "prx_clip_text_destroy"
 
     def __init__(self, cfg, params, max_batch: int, device):
         from .weights import clip_text_param_shapes
@@ -345,15 +347,6 @@ class ClipTextHandle:
         self.cfg = cfg
         self.max_batch = max_batch
         self.device = device
-
-    def __del__(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            try:
-                _destroy_handle("prx_clip_text_destroy", h)
-            except Exception:
-                pass
-            self.h = None
 
 
 @torch.no_grad()
@@ -385,8 +378,9 @@ def _single_attn_resolution(cfg) -> int:
     return hits[0] if hits else -1
 
 
-class VqganHandle:
+class VqganHandle(_Handle):
     """Owns a `prx_vqgan` (codebook, weight packs, activations of one forward).  `precision`: "fp16" (default) | "bf16" | "f32"."""
+    _destroy = "prx_vqgan_destroy"
 
     def __init__(self, cfg, params, latent_hw, device, precision=None):
         from .weights import vqgan_param_shapes
@@ -426,15 +420,6 @@ class VqganHandle:
         zmax = torch.empty(self.cfg.embed_dim, device=self.device)
         call("prx_vqgan_z_bounds", self.h, zmin, zmax, _stream())
         return zmin, zmax
-
-    def __del__(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            try:
-                _destroy_handle("prx_vqgan_destroy", h)
-            except Exception:
-                pass
-            self.h = None
 
 
 class _VqganSynthFn(torch.autograd.Function):
@@ -480,9 +465,10 @@ def vqgan_synth(z, handle: VqganHandle, quantize: bool = True):
     return _VqganSynthFn.apply(z, handle, quantize)
 
 
-class VqganEncHandle:
+class VqganEncHandle(_Handle):
     """Owns a `prx_vqgan_enc` (taming Encoder + quant_conv + codebook) for one image size; forward only
     (VqganDrawer.init_from_tensor / reapply_from_tensor / get_z_from_tensor, vqgan.py:174-185)."""
+    _destroy = "prx_vqgan_enc_destroy"
 
     def __init__(self, cfg, params, image_hw, device, in_channels: int = 3):
         from .weights import vqgan_encoder_param_shapes
@@ -511,15 +497,6 @@ class VqganEncHandle:
         self.image_hw = (H, W)
         self.in_channels = in_channels
         self.device = device
-
-    def __del__(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            try:
-                _destroy_handle("prx_vqgan_enc_destroy", h)
-            except Exception:
-                pass
-            self.h = None
 
 
 @torch.no_grad()
@@ -640,9 +617,10 @@ VGG16_CONV_INDICES = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)       # to
 VGG16_CAPTURE_LAYERS = (1, 3, 6, 8, 11, 13, 15, 22, 29)                     # Losses/StyleLoss.py:31
 
 
-class Vgg16Handle:
+class Vgg16Handle(_Handle):
     """Owns a `prx_vgg16` (torchvision VGG16 `features` up to relu5_3, frozen) for inputs up to `max_hw`.
     `params`: {"features.N.weight", "features.N.bias"} (torchvision state-dict names)."""
+    _destroy = "prx_vgg16_destroy"
 
     def __init__(self, params, max_hw, device, precision=None):
         self.precision = precision_code(precision)
@@ -664,15 +642,6 @@ class Vgg16Handle:
         h, w, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         call("prx_vgg16_feature_shape", int(H), int(W), int(k), ctypes.addressof(h), ctypes.addressof(w), ctypes.addressof(c))
         return h.value, w.value, c.value
-
-    def __del__(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            try:
-                _destroy_handle("prx_vgg16_destroy", h)
-            except Exception:
-                pass
-            self.h = None
 
 
 class _Vgg16Fn(torch.autograd.Function):
@@ -845,9 +814,10 @@ def vgg16_features(x, handle: Vgg16Handle):
 
 
 # --------------------------------------------------------------------------------------- fft drawer (configs[3])
-class FftDrawerHandle:
+class FftDrawerHandle(_Handle):
     """`prx_fft_drawer` (csrc/fft_drawer.hip): spectrum [1,3,H,Wf,2] -> image [1,3,H,W] as exact-f32 GEMMs against twiddle
     matrices, and its backward.  One handle per canvas size."""
+    _destroy = "prx_fft_drawer_destroy"
 
     def __init__(self, width: int, height: int, decay: float = 1.5, colors: float = 1.5):
         lib = _lib.load()
@@ -856,14 +826,6 @@ class FftDrawerHandle:
             raise PrxError("prx_fft_drawer_create failed: " + _lib.last_error())
         self.width, self.height = int(width), int(height)
         self.freq_columns = lib.prx_fft_drawer_freq_columns(self.h)
-
-    def __del__(self):
-        h, self.h = getattr(self, "h", None), None
-        if h:
-            try:
-                _destroy_handle("prx_fft_drawer_destroy", h)
-            except Exception:
-                pass
 
 
 class _FftSynthFn(torch.autograd.Function):
@@ -892,9 +854,10 @@ def fft_synth(params: torch.Tensor, handle: FftDrawerHandle, contrast: float = 0
 
 
 # --------------------------------------------------------------------------------------- RRDBNet x4 (super_resolution drawer)
-class RrdbNetHandle:
+class RrdbNetHandle(_Handle):
     """Owns a `prx_rrdbnet` (csrc/rrdbnet.hip): weight packs and every activation / gradient buffer of one latent size,
     allocated here and never afterwards.  `precision`: "fp16" (default) | "f32"; "bf16" is refused by name."""
+    _destroy = "prx_rrdbnet_destroy"
 
     def __init__(self, cfg, params, latent_hw, device, precision=None):
         from .weights import rrdbnet_param_shapes
@@ -910,15 +873,6 @@ class RrdbNetHandle:
         self.latent_hw = (hh, ww)
         self.device = device
         self.generation = 0              # see _ClipEncodeFn: one forward's activations per handle
-
-    def __del__(self):
-        h = getattr(self, "h", None)
-        if h is not None and h.value:
-            try:
-                _destroy_handle("prx_rrdbnet_destroy", h)
-            except Exception:
-                pass
-            self.h = None
 
 
 class _RrdbNetSynthFn(torch.autograd.Function):

@@ -148,6 +148,85 @@ def test_runners_on_random_geometries(emu):
     assert _emu_fuzz.resnet_encoder_cases(emu.lib, 2, 6) == []
 
 
+def _runner_cases():
+    """(name, create, one forward) of every runner handle at its smallest synthetic configuration"""
+    from oracle import fft_ref
+    from pixray_amd import ops, weights
+    cpu = torch.device("cpu")
+    vit, rn, vq, tx = (weights.CLIP_CONFIGS["tiny-B/32"], weights.CLIP_RESNET_CONFIGS["tiny-RN"], weights.VQGAN_CONFIGS["tiny_f4"],
+                       weights.CLIP_TEXT_CONFIGS["tiny-B/32"])
+    rr = weights.RRDBNET_CONFIGS["tiny-RRDB"]
+    p_vit, p_rn, p_vq = weights.synthetic_clip_vit_params(vit, 0), weights.synthetic_clip_resnet_params(rn, 0), weights.synthetic_vqgan_params(vq, 0)
+    p_tx, p_enc = weights.synthetic_clip_text_params(tx, 0), weights.synthetic_vqgan_encoder_params(vq, 0)
+    p_vgg, p_rr = weights.synthetic_vgg16_params(0), weights.synthetic_rrdbnet_params(rr, 0)
+    return [
+        ("vit", lambda: ops.ClipVitHandle(vit, p_vit, 1, cpu), lambda h: ops.clip_encode_image(torch.rand(1, 3, 224, 224), h)),
+        ("resnet", lambda: ops.ClipResNetHandle(rn, p_rn, 1, cpu), lambda h: ops.clip_encode_image(torch.rand(1, 3, 96, 96), h)),
+        ("vqgan", lambda: ops.VqganHandle(vq, p_vq, (4, 4), cpu), lambda h: ops.vqgan_synth(torch.randn(1, vq.z_channels, 4, 4), h)),
+        ("clip_text", lambda: ops.ClipTextHandle(tx, p_tx, 1, cpu),
+         lambda h: ops.clip_encode_text_tokens(torch.randint(0, tx.vocab_size, (1, tx.context_length)), h)),
+        ("vqgan_enc", lambda: ops.VqganEncHandle(vq, p_enc, (16, 16), cpu), lambda h: ops.vqgan_encode(torch.rand(1, 3, 16, 16) * 2 - 1, h)[0]),
+        ("vgg", lambda: ops.Vgg16Handle(p_vgg, (32, 32), cpu), lambda h: torch.cat([f.flatten() for f in ops.vgg16_features(torch.randn(1, 3, 32, 32), h)])),
+        ("rrdbnet", lambda: ops.RrdbNetHandle(rr, p_rr, (4, 4), cpu), lambda h: ops.rrdbnet_synth(torch.rand(1, 3, 4, 4), h)),
+        ("fft_drawer", lambda: ops.FftDrawerHandle(8, 6), lambda h: ops.fft_synth(fft_ref.rand_init((8, 6), 3).detach(), h)),
+    ]
+
+
+# (allocations, bytes) of one successful create, measured with the same hooks on the PARENT commit's sources (every runner with its own
+# allocation helpers): the move onto DevArena changed neither the number nor the sizes of the hipMalloc calls
+_PARENT_ALLOCS = {"vit": (83, 81787872), "resnet": (121, 74024360), "vqgan": (190, 111966312), "clip_text": (41, 21634668),
+                  "vqgan_enc": (92, 82447936), "vgg": (44, 126643720), "rrdbnet": (83, 3803148), "fft_drawer": (15, 33588332)}
+
+
+def test_a_failed_create_frees_its_device_memory_and_a_dropped_handle_all_of_it(emu):
+    """every runner handle keeps its device memory in a DevArena (csrc/dev_arena.h).  Per runner, on the emulator's allocation hooks:
+    create + drop returns the live allocations to the baseline; with the k-th allocation refused (k = 0, N / 2, N - 1) the create
+    raises PrxError naming the bytes asked for and the bytes held -- the figure the emulator saw live at that moment --, nothing stays
+    allocated, and the next create works and runs a finite forward.  N and the byte total equal _PARENT_ALLOCS, which were measured
+    on the parent commit; there the `nothing stays allocated` check failed for vqgan, clip_text and vqgan_enc (the struct was
+    deleted, its buffers were not)."""
+    import ctypes
+    import gc
+    import re
+    from pixray_amd._lib import PrxError
+    lib = emu.lib
+    lib.hipemu_live_allocs.argtypes, lib.hipemu_live_allocs.restype = [ctypes.c_void_p, ctypes.c_void_p], None
+    lib.hipemu_fail_alloc.argtypes, lib.hipemu_fail_alloc.restype = [ctypes.c_longlong], ctypes.c_longlong
+
+    def live():
+        gc.collect()
+        n, b = ctypes.c_longlong(), ctypes.c_longlong()
+        lib.hipemu_live_allocs(ctypes.addressof(n), ctypes.addressof(b))
+        return n.value, b.value
+
+    measured = {}
+    for name, create, forward in _runner_cases():
+        base = live()
+        h = create()
+        now = live()
+        N, total = now[0] - base[0], now[1] - base[1]
+        measured[name] = (N, total)
+        del h
+        assert live() == base, name
+        for k in sorted({0, N // 2, N - 1}):
+            lib.hipemu_fail_alloc(k)
+            try:
+                with pytest.raises(PrxError, match=r"device allocation of \d+ bytes failed .* with \d+ bytes already held") as ei:
+                    create()
+            finally:
+                at_failure = lib.hipemu_fail_alloc(-1)
+            held = int(re.search(r"with (\d+) bytes already held", str(ei.value)).group(1))
+            assert held == at_failure - base[1], (name, k, held, at_failure - base[1])
+            del ei
+            assert live() == base, (name, k, live(), base)
+            h = create()
+            assert bool(torch.isfinite(forward(h)).all()), (name, k)
+            del h
+            base = live()          # a first forward may have made the engine's process-wide zero page (gemm.hip): not the handle's
+    print("allocations, bytes per create:", measured)
+    assert measured == _PARENT_ALLOCS
+
+
 def test_handles_refuse_weights_whose_shapes_do_not_fit_the_configuration(emu):
     """the C ABI takes bare pointers: a tensor smaller than the configuration implies would be read out of bounds on the device
     (AddressSanitizer on the emulated create shows exactly that), so the Python handles check names and shapes first"""

@@ -467,6 +467,29 @@ def test_vqgan_synth_vs_oracle(name, hw):
     assert cosine(gd, gref) > 0.9999
 
 
+def test_a_latent_that_cannot_be_allocated_is_an_error_with_the_figure():
+    """the decoder allocates one forward's activations for its latent size when it is created.  tiny_f4 at a 44300 x 44300 latent:
+    1 962 490 000 positions (below 2^31, and create forms the product in size_t: `(size_t)rh * rw`), so the first stream request --
+    the first ResBlock's h1, positions x 256 channels of 2-byte (lean half) elements -- is 1 004 794 880 000 bytes, over three times
+    the card's memory: the runtime refuses it with only the codebook and three weight packs held.  PrxError with the bytes asked
+    for and the bytes held, the partly built handle freed; the 4 x 4 handle made next runs forward and backward as usual."""
+    import re
+    from pixray_amd._lib import PrxError
+    cfg = weights.VQGAN_CONFIGS["tiny_f4"]
+    params = weights.synthetic_vqgan_params(cfg, 0)
+    with pytest.raises(PrxError, match=r"device allocation of \d+ bytes failed .* with \d+ bytes already held") as ei:
+        ops.VqganHandle(cfg, params, (44300, 44300), DEV)
+    asked = int(re.search(r"device allocation of (\d+) bytes", str(ei.value)).group(1))
+    assert asked >= 10 ** 12 and asked % (44300 * 44300 * 256) == 0, asked          # 2 bytes per element (4 with PRX_LEAN=0)
+    if DEV == "cuda":
+        torch.cuda.synchronize()
+    h = ops.VqganHandle(cfg, params, (4, 4), DEV)
+    z = torch.randn(1, cfg.z_channels, 4, 4, device=DEV).requires_grad_(True)
+    img = ops.vqgan_synth(z, h)
+    (dz,) = torch.autograd.grad(img.sum(), z)
+    assert bool(torch.isfinite(img).all()) and bool(torch.isfinite(dz).all())
+
+
 # ------------------------------------------------------------------------------------------ VQGAN encoder (SURVEY §8f-1)
 @pytest.mark.parametrize("name,HW", [("tiny_f4", (64, 64)), ("tiny_f4", (32, 96)), ("tiny_f4", (40, 56)),   # 140 tokens: not a multiple of 8
                                      ("imagenet_f16_16384", (256, 256))])

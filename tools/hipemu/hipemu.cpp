@@ -194,6 +194,8 @@ constexpr size_t GUARD = 4096;
 constexpr unsigned char GUARD_BYTE = 0xA5;
 std::map<char*, size_t>& live_allocs() { static std::map<char*, size_t> m; return m; }
 unsigned long long launch_count = 0;
+long long fail_alloc_in = -1;   // hipemu_fail_alloc: the allocation that many requests from now returns null (one-shot); -1 = disarmed
+long long live_at_failure = 0;  // requested bytes live when that allocation was refused
 bool zone_clean(const char* z) {
     for (size_t i = 0; i < GUARD; ++i) if ((unsigned char)z[i] != GUARD_BYTE) return false;
     return true;
@@ -216,6 +218,11 @@ void check_guards(const char* when) {
 }
 }  // namespace
 void* dev_alloc(size_t n) {
+    if (fail_alloc_in >= 0 && fail_alloc_in-- == 0) {
+        live_at_failure = 0;
+        for (auto& kv : live_allocs()) live_at_failure += (long long)kv.second;
+        return nullptr;
+    }
     const size_t body = (n + 255) / 256 * 256;
     char* raw = (char*)aligned_alloc(4096, (body + 2 * GUARD + 4095) / 4096 * 4096);
     if (!raw) return nullptr;
@@ -322,3 +329,16 @@ extern "C" void hipemu_set_dma_eager(int on) { hipemu::dma_eager = on ? 1 : 0; }
 // execution order of work-items and workgroups reversed: results of a kernel that claims a fixed summation order must not change
 extern "C" void hipemu_set_reverse_order(int on) { hipemu::set_reverse_order(on != 0); }
 extern "C" void hipemu_set_strict_barrier(int on) { hipemu::set_strict_barrier(on != 0); }
+// allocation hooks for the tests of the runners' create / destroy paths: the number and the total bytes (as requested) of live device
+// allocations, and "the k-th hipMalloc from now on fails" (k = 0 is the next one; one-shot: the failure disarms it, and so does k = -1)
+// -- a request of terabytes is not certain to fail on a host that overcommits.  Returns the live bytes at the last failure it caused.
+extern "C" void hipemu_live_allocs(long long* count, long long* bytes) {
+    long long b = 0;
+    for (auto& kv : hipemu::live_allocs()) b += (long long)kv.second;
+    *count = (long long)hipemu::live_allocs().size();
+    *bytes = b;
+}
+extern "C" long long hipemu_fail_alloc(long long k) {
+    hipemu::fail_alloc_in = k < 0 ? -1 : k;
+    return hipemu::live_at_failure;
+}
