@@ -37,11 +37,12 @@ def emu():
         import test_kernels_cutouts_gpu as tc
         import test_kernels_strotss_gpu as ts
         import test_kernels_select_gpu as tsel
+        import test_kernels_plugins_gpu as tplug
         import test_path_gpu as tp
-        for m in (tk, th, tr, tc, ts, tsel, tp):
+        for m in (tk, th, tr, tc, ts, tsel, tplug, tp):
             m.DEV = "cpu"
-        yield types_ns(lib=lib, tk=tk, th=th, tr=tr, tc=tc, ts=ts, tsel=tsel, tp=tp)
-        for m in (tk, th, tr, tc, ts, tsel, tp):
+        yield types_ns(lib=lib, tk=tk, th=th, tr=tr, tc=tc, ts=ts, tsel=tsel, tplug=tplug, tp=tp)
+        for m in (tk, th, tr, tc, ts, tsel, tplug, tp):
             m.DEV = "cuda"
 
 
@@ -339,6 +340,16 @@ def test_prompt_vq_palette_and_smoothness_kernels_at_their_switch_points(emu):
     equidistant entries; the smoothness stencils at the smallest size, across cutouts, on a flat patch and around the kink; the refusals"""
     figs = emu.tsel.emu_subset()
     assert any(k.startswith("prompt-tie/") for k in figs) and any(k.startswith("smooth-flat-") for k in figs)
+
+
+def test_builtin_loss_blur_and_wallpaper_plugin_kernels_at_their_edges(emu):
+    """tests/test_kernels_plugins_gpu.py on the emulated kernels, every case: saturation at N = 2, on an offset, a constant and a grey
+    image; symmetry at w = 1 and odd w; the edge bands meeting, oversized and under a mask with planted zeros; the gaussian weights at
+    h != w; the aesthetic head at d = 1 .. 80 and 4100 rows; the blur and its adjoint with asymmetric taps; the wallpaper modes with odd
+    edge match, negative and oversized shifts; the launch-shape sweeps up to one element past the workgroup cap; the refusals"""
+    figs = emu.tplug.emu_subset()
+    for family in ("sat/", "sym/", "edge/", "edget/", "gauss/", "aes/", "blur/", "wall/", "sweep/"):
+        assert any(k.startswith(family) for k in figs), family
 
 
 # ------------------------------------------------------------------------------------------------ the path's own ops
