@@ -187,6 +187,18 @@ int prx_k_mha_bwd_op(const void* qkv, const void* dout, void* dqkv, int N, int T
 int prx_k_mha_fwd_gen_op(const void* qkv, void* out, float* lse, int N, int T, int C, int heads, int h16, prx_stream_t s);
 int prx_k_mha_bwd_gen_op(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int N, int T, int C,
                          int heads, int h16, prx_stream_t s);
+/* prx_k_mha_{fwd,bwd}_gen_op with the operand columns per head as an argument.  head_cols 64: the two calls above, bit for bit.
+ * head_cols 96: heads of dim 80 zero-padded to 96 columns (OpenCLIP ViT-H/14; csrc/attention_hd96.hip): C == heads * 96, head h at
+ * columns 96h .. 96h+95 of q, k, v, out and their gradients, the caller's columns 80 .. 95 of every head zero, softmax scale
+ * 1 / sqrt(80), 1 <= T <= 640; columns 80 .. 95 of `out` and `dqkv` are written as exact zeros. */
+int prx_k_mha_fwd_hd_op(const void* qkv, void* out, float* lse, int N, int T, int C, int heads, int h16, int head_cols, prx_stream_t s);
+int prx_k_mha_bwd_hd_op(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int N, int T, int C,
+                        int heads, int h16, int head_cols, prx_stream_t s);
+/* the head padding prx_vit_tower_create applies when it packs a block's weights (fp32 device tensors, width == heads * hd):
+ * qkv_w [3 width, width] -> qkv_w_pad [3 heads hp, width] (every head's hd rows of q, k and v become the first hd of hp rows),
+ * out_w [width, width] -> out_w_pad [width, heads hp] (the matching input columns); pad rows / columns are zero. */
+int prx_k_vit_pad_heads(const float* qkv_w, float* qkv_w_pad, const float* out_w, float* out_w_pad, int width, int heads, int hd, int hp,
+                        prx_stream_t s);
 /* forward only, causal mask (CLIP text transformer) */
 int prx_k_mha_fwd_causal_op(const void* qkv, void* out, int N, int T, int C, int heads, int h16, prx_stream_t s);
 int prx_k_softmax_rows_op(const float* S, int lds_, float scale, void* P, int ldp, void* PT, int ldpt, int rows, int cols,
@@ -531,9 +543,15 @@ int prx_clip_vit_create(prx_clip_vit** out, const prx_clip_vit_config* cfg, cons
  * head_dim: 0 / 64, or 32 / 16 (= width / heads; SLIP's ViT-S/16 has 12 heads of 32 on width 384).  Narrower heads are zero-padded
  *   to 64 when the weights are packed (q, k, v rows of qkv.weight / qkv.bias, input columns of proj.weight; sqrt(64 / head_dim)
  *   folded into the q rows): the values and gradients of the narrow heads, at 64 / head_dim times the qkv, attention and
- *   out-projection work.  width must be a multiple of 128. */
+ *   out-projection work.  width must be a multiple of 128.
+ *   80 (OpenCLIP ViT-H/14: 16 heads on width 1280) is zero-padded to 96 the same way and runs on the 96-wide attention kernels, which
+ *   take the softmax scale 1 / sqrt(80) as an argument (nothing is folded into q) and at most 640 tokens.
+ * family PRX_VIT_FAMILY_OPENCLIP: the OpenCLIP (LAION) ViT towers [UPSTREAM open_clip model_configs ViT-B-32, ViT-B-16, ViT-L-14, ViT-H-14]:
+ *   weights[] and every switch as for PRX_VIT_FAMILY_CLIP (no patch-embed bias, ln_pre, ln_eps 1e-5 and CLIP's constants as given),
+ *   but the MLP activation is the exact GELU. */
 #define PRX_VIT_FAMILY_CLIP 0
 #define PRX_VIT_FAMILY_SLIP 1
+#define PRX_VIT_FAMILY_OPENCLIP 2
 typedef struct prx_vit_tower_config {
     int input_resolution;  /* 224 */
     int patch_size;        /* 16 */
@@ -544,7 +562,7 @@ typedef struct prx_vit_tower_config {
     int max_batch;         /* capacity in cutouts */
     int precision;         /* PRX_PREC_F16 | PRX_PREC_BF16 | PRX_PREC_F32 (the reference runs this family in fp32 on a GPU) */
     int family;            /* PRX_VIT_FAMILY_* */
-    int head_dim;          /* 0 = 64; 32 | 16: padded to 64 */
+    int head_dim;          /* 0 = 64; 32 | 16: padded to 64; 80: padded to 96 */
     float ln_eps;          /* 1e-6 (timm) | 1e-5 (CLIP) */
     float mean[3];         /* Normalize constants of the fused preprocessing: ImageNet's (0.485, 0.456, 0.406) */
     float std[3];          /* (0.229, 0.224, 0.225) */
@@ -614,6 +632,16 @@ typedef struct prx_clip_text_config {
 } prx_clip_text_config;
 int prx_clip_text_create(prx_clip_text** out, const prx_clip_text_config* cfg, const float* const* weights, int n_weights,
                          prx_stream_t s);
+/* The same runner for a family of text towers: PRX_TEXT_FAMILY_CLIP is prx_clip_text_create; PRX_TEXT_FAMILY_OPENCLIP has the exact
+ * GELU in place of QuickGELU (the OpenCLIP / LAION text transformers; ViT-H-14: width 1024, 16 heads, 24 layers).  weights[] as above. */
+#define PRX_TEXT_FAMILY_CLIP 0
+#define PRX_TEXT_FAMILY_OPENCLIP 1
+typedef struct prx_text_tower_config {
+    int vocab_size, context_length, width, layers, heads, output_dim, max_batch;      /* as prx_clip_text_config */
+    int family;           /* PRX_TEXT_FAMILY_* */
+} prx_text_tower_config;
+int prx_text_tower_create(prx_clip_text** out, const prx_text_tower_config* cfg, const float* const* weights, int n_weights,
+                          prx_stream_t s);
 void prx_clip_text_destroy(prx_clip_text* h);
 int prx_clip_text_encode(prx_clip_text* h, const int* tokens, int n, float* embeds, prx_stream_t s);
 

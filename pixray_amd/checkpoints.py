@@ -5,6 +5,8 @@ are exercised in tests with randomly initialised upstream-format state dicts; th
   `visual.positional_embedding`, `visual.ln_pre.*`, `visual.transformer.resblocks.{i}.*`, `visual.ln_post.*`,
   `visual.proj` -> strip the `visual.` prefix (weights may be fp16 on CUDA: cast to fp32).  The ModifiedResNet models (RN50 ...
   RN50x64) carry `visual.conv{1,2,3}`, `visual.bn{1,2,3}.*`, `visual.layer{1..4}.{b}.*` and `visual.attnpool.*` instead.
+* OpenCLIP (`open_clip.create_model(name, pretrained=...).state_dict()`, the LAION towers): its native ViT models keep OpenAI's key
+  names on both sides; the geometry comes from the named configuration (`clip_visual_from_openclip` / `clip_text_from_openclip`).
 * HF `CLIPVisionModelWithProjection` -> the same names (q/k/v projections are concatenated into `in_proj_*`).
 * taming-transformers VQGAN Lightning checkpoint (`vqgan.py:124-140`): `state_dict` with `decoder.*`,
   `post_quant_conv.*`, `quantize.embedding.weight` for the decoder runner, plus `encoder.*` / `quant_conv.*` for the
@@ -44,6 +46,31 @@ def clip_visual_from_openai(state_dict: Dict[str, torch.Tensor], cfg):
     if isinstance(cfg, ClipResNetConfig):
         return _check(params, clip_resnet_param_shapes(cfg))
     return _check(params, clip_vit_param_shapes(cfg))
+
+
+def _openclip_configs(name_or_cfg, text: bool):
+    from .weights import CLIP_TEXT_CONFIGS, OPENCLIP_CONFIGS
+    if not isinstance(name_or_cfg, str):
+        return name_or_cfg
+    if name_or_cfg not in OPENCLIP_CONFIGS:
+        raise KeyError(f"unknown OpenCLIP model {name_or_cfg!r} (supported: {sorted(OPENCLIP_CONFIGS)})")
+    return CLIP_TEXT_CONFIGS[name_or_cfg] if text else OPENCLIP_CONFIGS[name_or_cfg]
+
+
+def clip_visual_from_openclip(state_dict: Dict[str, torch.Tensor], name_or_cfg):
+    """visual side of an OpenCLIP state dict of a native ViT model (`visual.conv1.weight`, `visual.class_embedding`, ...: OpenAI's key
+    names) for the named configuration (`ViT-B-32`, `ViT-B-16`, `ViT-L-14`, `ViT-H-14`) or an OpenClipVitConfig.  The geometry is the
+    configuration's, never read off the tensors: `clip_config_from_state_dict` takes heads = width // 64 as `clip.model.build_model`
+    does, which is wrong for ViT-H-14 (16 heads of 80 on width 1280).  A missing or mis-shaped tensor is named."""
+    cfg = _openclip_configs(name_or_cfg, text=False)
+    params = {k[len("visual."):]: v for k, v in state_dict.items() if k.startswith("visual.")}
+    return _check(params, clip_vit_param_shapes(cfg))
+
+
+def clip_text_from_openclip(state_dict: Dict[str, torch.Tensor], name_or_cfg):
+    """text side of the same state dict: the un-prefixed entries under OpenAI's names, for the named configuration's geometry
+    (`attn_mask` and `logit_scale` ride along in the file and are not read)"""
+    return _check(dict(state_dict), clip_text_param_shapes(_openclip_configs(name_or_cfg, text=True)))
 
 
 def clip_visual_from_hf(state_dict: Dict[str, torch.Tensor], cfg: ClipVitConfig):

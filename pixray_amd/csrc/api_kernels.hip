@@ -128,6 +128,24 @@ int prx_k_mha_bwd_gen_op(const void* qkv, const void* out, const void* dout, con
                          int heads, int h16, prx_stream_t s) {
     return prx_mha_bwd_gen(CB_(qkv), CB_(out), CB_(dout), lse, B_(dqkv), N, T, C, heads, S_(s), h16);
 }
+// columns per head 64: the calls above; 96: head dim 80 zero-padded, softmax scale 1 / sqrt(80) (attention_hd96.hip)
+int prx_k_mha_fwd_hd_op(const void* qkv, void* out, float* lse, int N, int T, int C, int heads, int h16, int head_cols, prx_stream_t s) {
+    PRX_REQUIRE(head_cols == 64 || head_cols == 96, "mha_fwd_hd: %d columns per head (64 | 96)", head_cols);
+    if (head_cols == 64) return prx_mha_fwd_gen(CB_(qkv), B_(out), lse, N, T, C, heads, S_(s), h16);
+    return prx_mha_fwd_hd96(CB_(qkv), B_(out), lse, N, T, C, heads, 1.f / sqrtf(80.f), S_(s), h16);
+}
+int prx_k_mha_bwd_hd_op(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int N, int T, int C,
+                        int heads, int h16, int head_cols, prx_stream_t s) {
+    PRX_REQUIRE(head_cols == 64 || head_cols == 96, "mha_bwd_hd: %d columns per head (64 | 96)", head_cols);
+    if (head_cols == 64) return prx_mha_bwd_gen(CB_(qkv), CB_(out), CB_(dout), lse, B_(dqkv), N, T, C, heads, S_(s), h16);
+    return prx_mha_bwd_hd96(CB_(qkv), CB_(out), CB_(dout), lse, B_(dqkv), N, T, C, heads, 1.f / sqrtf(80.f), S_(s), h16);
+}
+int prx_k_vit_pad_heads(const float* qkv_w, float* qkv_w_pad, const float* out_w, float* out_w_pad, int width, int heads, int hd, int hp,
+                        prx_stream_t s) {
+    PRX_REQUIRE(qkv_w && qkv_w_pad && out_w && out_w_pad && width == heads * hd, "vit_pad_heads: null argument or width != heads * head dim");
+    int r = prx_vit_pad_head_rows(qkv_w, qkv_w_pad, heads, hd, hp, width, S_(s));
+    return r ? r : prx_vit_pad_head_cols(out_w, out_w_pad, width, heads, hd, hp, S_(s));
+}
 int prx_k_mha_fwd_causal_op(const void* qkv, void* out, int N, int T, int C, int heads, int h16, prx_stream_t s) {
     return prx_mha_fwd_causal(CB_(qkv), B_(out), N, T, C, heads, S_(s), h16);
 }

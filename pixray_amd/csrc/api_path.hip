@@ -119,11 +119,13 @@ int prx_clip_vit_create(prx_clip_vit** out, const prx_clip_vit_config* c, const 
 int prx_vit_tower_create(prx_clip_vit** out, const prx_vit_tower_config* c, const float* const* weights, int n_weights,
                          prx_stream_t s) {
     PRX_REQUIRE(out && c && weights, "prx_vit_tower_create: null argument");
-    PRX_REQUIRE(c->family == PRX_VIT_FAMILY_CLIP || c->family == PRX_VIT_FAMILY_SLIP, "prx_vit_tower_create: unknown family %d", c->family);
-    PRX_REQUIRE(c->head_dim == 0 || c->head_dim == 64 || c->head_dim == 32 || c->head_dim == 16,
-                "prx_vit_tower_create: head dim %d (want 64, or 32 / 16: padded to 64)", c->head_dim);
+    PRX_REQUIRE(c->family == PRX_VIT_FAMILY_CLIP || c->family == PRX_VIT_FAMILY_SLIP || c->family == PRX_VIT_FAMILY_OPENCLIP,
+                "prx_vit_tower_create: unknown family %d", c->family);
+    PRX_REQUIRE(c->head_dim == 0 || c->head_dim == 64 || c->head_dim == 32 || c->head_dim == 16 || c->head_dim == 80,
+                "prx_vit_tower_create: head dim %d (want 64, or 32 / 16: padded to 64, or 80: padded to 96)", c->head_dim);
     VitFamily f = prx_vit_family_clip();
     if (c->family == PRX_VIT_FAMILY_SLIP) { f.patch_bias = 1; f.ln_pre = 0; f.act = PRX_ACT_GELU; f.dact = PRX_ACT_MUL_DGELU; }
+    if (c->family == PRX_VIT_FAMILY_OPENCLIP) { f.act = PRX_ACT_GELU; f.dact = PRX_ACT_MUL_DGELU; }      // CLIP's layout, the exact GELU
     f.eps = c->ln_eps; f.head_dim = c->head_dim;
     for (int i = 0; i < 3; ++i) { f.norm.mean[i] = c->mean[i]; f.norm.std[i] = c->std[i]; }
     return prx_vit_create_impl((PrxVit**)out, c->input_resolution, c->patch_size, c->width, c->layers, c->heads,
@@ -202,6 +204,13 @@ int prx_clip_text_create(prx_clip_text** out, const prx_clip_text_config* c, con
     PRX_REQUIRE(out && c && weights, "prx_clip_text_create: null argument");
     return prx_clip_text_create_impl((PrxClipText**)out, c->vocab_size, c->context_length, c->width, c->layers, c->heads,
                                      c->output_dim, c->max_batch, weights, n_weights, S_(s));
+}
+int prx_text_tower_create(prx_clip_text** out, const prx_text_tower_config* c, const float* const* weights, int n_weights,
+                          prx_stream_t s) {
+    PRX_REQUIRE(out && c && weights, "prx_text_tower_create: null argument");
+    PRX_REQUIRE(c->family == PRX_TEXT_FAMILY_CLIP || c->family == PRX_TEXT_FAMILY_OPENCLIP, "prx_text_tower_create: unknown family %d", c->family);
+    return prx_clip_text_create_impl((PrxClipText**)out, c->vocab_size, c->context_length, c->width, c->layers, c->heads,
+                                     c->output_dim, c->max_batch, weights, n_weights, S_(s), c->family == PRX_TEXT_FAMILY_OPENCLIP);
 }
 void prx_clip_text_destroy(prx_clip_text* h) { prx_clip_text_destroy_impl((PrxClipText*)h); }
 int prx_clip_text_encode(prx_clip_text* h, const int* tokens, int n, float* embeds, prx_stream_t s) {

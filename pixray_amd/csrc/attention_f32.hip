@@ -9,14 +9,17 @@
 
 namespace {
 
-constexpr int HD = 64;        // head dim
+// Every kernel is templated on the head dim HD and on the head's column stride HS >= HD in qkv / out / dqkv: <64, 64> are the towers
+// with 64-wide heads, <80, 96> the towers whose 80-wide heads are zero-padded to 96 operand columns (attention_hd96.hip, vit.hip) --
+// there the HS - HD pad columns are not read, and are written as zeros.
 constexpr int BT = 64;        // tokens per LDS block
 
-// stage `rows` x 64 floats of a [T, ld] matrix (rows r0.., columns c0..c0+63) into lds[BT][HD]; rows >= T are zeroed
+// stage `rows` x HD floats of a [T, ld] matrix (rows r0.., columns c0..c0+HD-1) into lds[BT][HD]; rows >= T are zeroed
+template <int HD>
 __device__ __forceinline__ void stage_block(const float* __restrict__ src, long long ld, int r0, int T, float* lds, int lane) {
 #pragma unroll 4
     for (int idx = lane; idx < BT * (HD / 4); idx += 64) {
-        const int row = idx >> 4, c4 = idx & 15;
+        const int row = idx / (HD / 4), c4 = idx % (HD / 4);
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (r0 + row < T) v = *reinterpret_cast<const float4*>(src + (long long)(r0 + row) * ld + c4 * 4);
         *reinterpret_cast<float4*>(lds + row * HD + c4 * 4) = v;
@@ -24,6 +27,7 @@ __device__ __forceinline__ void stage_block(const float* __restrict__ src, long 
 }
 
 // grid (ceil(T/64), heads, N), one wave; lane = one query
+template <int HD, int HS>
 __global__ __launch_bounds__(64) void mha_fwd_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                          float* __restrict__ lse, int T, int C, int heads, float scale) {
     __shared__ __attribute__((aligned(16))) float Ks[BT * HD];
@@ -34,7 +38,7 @@ __global__ __launch_bounds__(64) void mha_fwd_f32_kernel(const float* __restrict
     const int t = blockIdx.x * 64 + lane;
     const bool live = t < T;
     const long long ld = 3LL * C;
-    const float* base = qkv + (long long)n * T * ld + h * HD;
+    const float* base = qkv + (long long)n * T * ld + h * HS;
     float q[HD], o[HD];
 #pragma unroll
     for (int d = 0; d < HD; d += 4) {
@@ -46,8 +50,8 @@ __global__ __launch_bounds__(64) void mha_fwd_f32_kernel(const float* __restrict
     float m = -INFINITY, l = 0.f;
     for (int k0 = 0; k0 < T; k0 += BT) {
         __syncthreads();
-        stage_block(base + C, ld, k0, T, Ks, lane);
-        stage_block(base + 2 * C, ld, k0, T, Vs, lane);
+        stage_block<HD>(base + C, ld, k0, T, Ks, lane);
+        stage_block<HD>(base + 2 * C, ld, k0, T, Vs, lane);
         __syncthreads();
         const int nk = min(BT, T - k0);
         float bm = -INFINITY;
@@ -80,14 +84,17 @@ __global__ __launch_bounds__(64) void mha_fwd_f32_kernel(const float* __restrict
     }
     if (!live) return;
     const float inv = 1.f / l;
-    float* op = out + ((long long)n * T + t) * C + h * HD;
+    float* op = out + ((long long)n * T + t) * C + h * HS;
 #pragma unroll
     for (int d = 0; d < HD; d += 4)
         *reinterpret_cast<float4*>(op + d) = make_float4(o[d] * inv, o[d + 1] * inv, o[d + 2] * inv, o[d + 3] * inv);
+#pragma unroll
+    for (int d = HD; d < HS; d += 4) *reinterpret_cast<float4*>(op + d) = make_float4(0.f, 0.f, 0.f, 0.f);
     if (lse) lse[((long long)n * heads + h) * T + t] = m + logf(l);
 }
 
 // dQ: lane = one query; recomputes P from the saved log-sum-exp.  D = rowsum(dO o O).
+template <int HD, int HS>
 __global__ __launch_bounds__(64) void mha_bwd_dq_f32_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
                                                             const float* __restrict__ dout, const float* __restrict__ lse,
                                                             float* __restrict__ dqkv, int T, int C, int heads, float scale) {
@@ -98,7 +105,7 @@ __global__ __launch_bounds__(64) void mha_bwd_dq_f32_kernel(const float* __restr
     const int t = blockIdx.x * 64 + lane;
     const bool live = t < T;
     const long long ld = 3LL * C;
-    const float* base = qkv + (long long)n * T * ld + h * HD;
+    const float* base = qkv + (long long)n * T * ld + h * HS;
     float q[HD], dO[HD], dq[HD];
     float D = 0.f;
 #pragma unroll
@@ -106,8 +113,8 @@ __global__ __launch_bounds__(64) void mha_bwd_dq_f32_kernel(const float* __restr
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f), g = v, ov = v;
         if (live) {
             v = *reinterpret_cast<const float4*>(base + (long long)t * ld + d);
-            g = *reinterpret_cast<const float4*>(dout + ((long long)n * T + t) * C + h * HD + d);
-            ov = *reinterpret_cast<const float4*>(o + ((long long)n * T + t) * C + h * HD + d);
+            g = *reinterpret_cast<const float4*>(dout + ((long long)n * T + t) * C + h * HS + d);
+            ov = *reinterpret_cast<const float4*>(o + ((long long)n * T + t) * C + h * HS + d);
         }
         q[d] = v.x * scale; q[d + 1] = v.y * scale; q[d + 2] = v.z * scale; q[d + 3] = v.w * scale;
         dO[d] = g.x; dO[d + 1] = g.y; dO[d + 2] = g.z; dO[d + 3] = g.w;
@@ -117,8 +124,8 @@ __global__ __launch_bounds__(64) void mha_bwd_dq_f32_kernel(const float* __restr
     const float L = live ? lse[((long long)n * heads + h) * T + t] : 0.f;
     for (int k0 = 0; k0 < T; k0 += BT) {
         __syncthreads();
-        stage_block(base + C, ld, k0, T, Ks, lane);
-        stage_block(base + 2 * C, ld, k0, T, Vs, lane);
+        stage_block<HD>(base + C, ld, k0, T, Ks, lane);
+        stage_block<HD>(base + 2 * C, ld, k0, T, Vs, lane);
         __syncthreads();
         const int nk = min(BT, T - k0);
         for (int j = 0; j < nk; ++j) {
@@ -141,13 +148,16 @@ __global__ __launch_bounds__(64) void mha_bwd_dq_f32_kernel(const float* __restr
         }
     }
     if (!live) return;
-    float* dst = dqkv + ((long long)n * T + t) * ld + h * HD;
+    float* dst = dqkv + ((long long)n * T + t) * ld + h * HS;
 #pragma unroll
     for (int d = 0; d < HD; d += 4)
         *reinterpret_cast<float4*>(dst + d) = make_float4(dq[d] * scale, dq[d + 1] * scale, dq[d + 2] * scale, dq[d + 3] * scale);
+#pragma unroll
+    for (int d = HD; d < HS; d += 4) *reinterpret_cast<float4*>(dst + d) = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 // dK, dV: lane = one key; the queries (scaled), their dO, log-sum-exp and D are broadcast from LDS in 64-token blocks
+template <int HD, int HS>
 __global__ __launch_bounds__(64) void mha_bwd_dkv_f32_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
                                                              const float* __restrict__ dout, const float* __restrict__ lse,
                                                              float* __restrict__ dqkv, int T, int C, int heads, float scale) {
@@ -159,9 +169,9 @@ __global__ __launch_bounds__(64) void mha_bwd_dkv_f32_kernel(const float* __rest
     const int t = blockIdx.x * 64 + lane;
     const bool live = t < T;
     const long long ld = 3LL * C;
-    const float* base = qkv + (long long)n * T * ld + h * HD;
-    const float* obase = o + (long long)n * T * C + h * HD;
-    const float* gbase = dout + (long long)n * T * C + h * HD;
+    const float* base = qkv + (long long)n * T * ld + h * HS;
+    const float* obase = o + (long long)n * T * C + h * HS;
+    const float* gbase = dout + (long long)n * T * C + h * HS;
     float k[HD], v[HD], dk[HD], dv[HD];
 #pragma unroll
     for (int d = 0; d < HD; d += 4) {
@@ -177,8 +187,8 @@ __global__ __launch_bounds__(64) void mha_bwd_dkv_f32_kernel(const float* __rest
     }
     for (int q0 = 0; q0 < T; q0 += BT) {
         __syncthreads();
-        stage_block(base, ld, q0, T, Qs, lane);
-        stage_block(gbase, C, q0, T, Gs, lane);
+        stage_block<HD>(base, ld, q0, T, Qs, lane);
+        stage_block<HD>(gbase, C, q0, T, Gs, lane);
         {
             const int qi = q0 + lane;
             float D = 0.f, L = 0.f;
@@ -219,11 +229,16 @@ __global__ __launch_bounds__(64) void mha_bwd_dkv_f32_kernel(const float* __rest
         }
     }
     if (!live) return;
-    float* dst = dqkv + ((long long)n * T + t) * ld + h * HD;
+    float* dst = dqkv + ((long long)n * T + t) * ld + h * HS;
 #pragma unroll
     for (int d = 0; d < HD; d += 4) {
         *reinterpret_cast<float4*>(dst + C + d) = make_float4(dk[d], dk[d + 1], dk[d + 2], dk[d + 3]);
         *reinterpret_cast<float4*>(dst + 2 * C + d) = make_float4(dv[d], dv[d + 1], dv[d + 2], dv[d + 3]);
+    }
+#pragma unroll
+    for (int d = HD; d < HS; d += 4) {
+        *reinterpret_cast<float4*>(dst + C + d) = make_float4(0.f, 0.f, 0.f, 0.f);
+        *reinterpret_cast<float4*>(dst + 2 * C + d) = make_float4(0.f, 0.f, 0.f, 0.f);
     }
 }
 
@@ -231,7 +246,7 @@ __global__ __launch_bounds__(64) void mha_bwd_dkv_f32_kernel(const float* __rest
 
 int prx_mha_fwd_f32(const float* qkv, float* out, float* lse, int N, int T, int C, int heads, hipStream_t s) {
     PRX_REQUIRE(C == heads * 64 && T >= 1, "mha(f32): needs head dim 64 (T=%d C=%d heads=%d)", T, C, heads);
-    hipLaunchKernelGGL(mha_fwd_f32_kernel, dim3(ceil_div(T, 64), heads, N), dim3(64), 0, s, qkv, out, lse, T, C, heads, 0.125f);
+    hipLaunchKernelGGL((mha_fwd_f32_kernel<64, 64>), dim3(ceil_div(T, 64), heads, N), dim3(64), 0, s, qkv, out, lse, T, C, heads, 0.125f);
     PRX_LAUNCH_CHECK();
     return 0;
 }
@@ -240,9 +255,29 @@ int prx_mha_bwd_f32(const float* qkv, const float* out, const float* dout, const
                     int heads, hipStream_t s) {
     PRX_REQUIRE(C == heads * 64 && T >= 1, "mha(f32) bwd: needs head dim 64 (T=%d C=%d heads=%d)", T, C, heads);
     const dim3 grid(ceil_div(T, 64), heads, N);
-    hipLaunchKernelGGL(mha_bwd_dq_f32_kernel, grid, dim3(64), 0, s, qkv, out, dout, lse, dqkv, T, C, heads, 0.125f);
+    hipLaunchKernelGGL((mha_bwd_dq_f32_kernel<64, 64>), grid, dim3(64), 0, s, qkv, out, dout, lse, dqkv, T, C, heads, 0.125f);
     PRX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(mha_bwd_dkv_f32_kernel, grid, dim3(64), 0, s, qkv, out, dout, lse, dqkv, T, C, heads, 0.125f);
+    hipLaunchKernelGGL((mha_bwd_dkv_f32_kernel<64, 64>), grid, dim3(64), 0, s, qkv, out, dout, lse, dqkv, T, C, heads, 0.125f);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+
+// head dim 80 in 96 columns per head, softmax scale 1 / sqrt(80)
+int prx_mha_fwd_f32_hd96(const float* qkv, float* out, float* lse, int N, int T, int C, int heads, hipStream_t s) {
+    PRX_REQUIRE(C == heads * 96 && T >= 1, "mha(f32, hd96): needs 96 columns per head (T=%d C=%d heads=%d)", T, C, heads);
+    hipLaunchKernelGGL((mha_fwd_f32_kernel<80, 96>), dim3(ceil_div(T, 64), heads, N), dim3(64), 0, s, qkv, out, lse, T, C, heads,
+                       0.11180339887498948f);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+
+int prx_mha_bwd_f32_hd96(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int N, int T, int C,
+                         int heads, hipStream_t s) {
+    PRX_REQUIRE(C == heads * 96 && T >= 1, "mha(f32, hd96) bwd: needs 96 columns per head (T=%d C=%d heads=%d)", T, C, heads);
+    const dim3 grid(ceil_div(T, 64), heads, N);
+    hipLaunchKernelGGL((mha_bwd_dq_f32_kernel<80, 96>), grid, dim3(64), 0, s, qkv, out, dout, lse, dqkv, T, C, heads, 0.11180339887498948f);
+    PRX_LAUNCH_CHECK();
+    hipLaunchKernelGGL((mha_bwd_dkv_f32_kernel<80, 96>), grid, dim3(64), 0, s, qkv, out, dout, lse, dqkv, T, C, heads, 0.11180339887498948f);
     PRX_LAUNCH_CHECK();
     return 0;
 }

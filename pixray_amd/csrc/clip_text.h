@@ -3,8 +3,9 @@
 #include "common.h"
 
 struct PrxClipText;
+// gelu: the MLP activation is the exact (erf) GELU of the OpenCLIP towers instead of OpenAI's QuickGELU
 int prx_clip_text_create_impl(PrxClipText** out, int vocab, int ctx, int width, int layers, int heads, int out_dim, int max_n,
-                              const float* const* w, int n_w, hipStream_t s);
+                              const float* const* w, int n_w, hipStream_t s, int gelu = 0);
 void prx_clip_text_destroy_impl(PrxClipText* t);
 int prx_clip_text_encode_impl(PrxClipText* t, const int* tokens, int n, float* embeds, hipStream_t s);
 // launchers of the runner's own kernels (the runner calls these; exported as prx_k_* for the kernel-level tests)

@@ -1,6 +1,7 @@
 // CLIP text tower on MI355X (call sites slip.py:68-70, pixray.py:859-877):
 //   x = token_embedding[tokens] + positional_embedding                       [n, ctx, width]
-//   12 x ResidualAttentionBlock with the causal mask (LN -> MHA -> +res -> LN -> FC -> QuickGELU -> FC -> +res)
+//   12 x ResidualAttentionBlock with the causal mask (LN -> MHA -> +res -> LN -> FC -> QuickGELU -> FC -> +res);
+//        the OpenCLIP (LAION) towers have the exact GELU there [UPSTREAM open_clip model_configs: no "quick_gelu"]: PrxClipText::act
 //   x = ln_final(x)[i, argmax_j tokens[i, j]] @ text_projection               (the EOT token has the largest id)
 // Forward only: prompt embeddings are computed once before the loop and enter it as constants (pixray.py:873-877).
 // Same kernels and layout as the image tower (tokens [n*ctx, width] row-major, fp32 residual stream, bf16 GEMM operands).
@@ -64,6 +65,7 @@ int prx_gather_rows(const float* x, const int* eot, float* out, int n, int ctx, 
 
 struct PrxClipText {
     int vocab, ctx, width, layers, heads, out_dim, max_n;
+    int act;          // PRX_ACT_QUICKGELU | PRX_ACT_GELU: the epilogue code of the c_fc product
     DevArena mem;     // every device buffer below: freed with the handle
     float *tok, *pos, *lnf_g, *lnf_b;
     bf16_t* projT;
@@ -85,7 +87,7 @@ int tg(PrxClipText* t, GemmDesc& d, hipStream_t s) { return prx_gemm_launch(d, t
 // weights: token_embedding.weight [vocab, W], positional_embedding [ctx, W], per layer the 12 tensors of a
 // ResidualAttentionBlock in state-dict order, ln_final.{weight,bias}, text_projection [W, out_dim]
 int prx_clip_text_create_impl(PrxClipText** out, int vocab, int ctx, int width, int layers, int heads, int out_dim, int max_n,
-                              const float* const* w, int n_w, hipStream_t s) {
+                              const float* const* w, int n_w, hipStream_t s, int gelu) {
     PRX_REQUIRE(n_w == 2 + 12 * layers + 3, "clip_text_create: expected %d weight tensors, got %d", 2 + 12 * layers + 3, n_w);
     PRX_REQUIRE(width == heads * 64 && width % 256 == 0 && ctx >= 1 && vocab >= 1 && max_n >= 1, "clip_text_create: unsupported geometry");
     std::unique_ptr<PrxClipText> guard(new PrxClipText());      // a failed create frees what it allocated (DevArena)
@@ -94,6 +96,7 @@ int prx_clip_text_create_impl(PrxClipText** out, int vocab, int ctx, int width, 
     m.describe("clip_text_create", ": the text tower keeps one forward's activations for max_batch = %d sequences of %d tokens (width %d, %d layers)",
                     max_n, ctx, width, layers);
     t->vocab = vocab; t->ctx = ctx; t->width = width; t->layers = layers; t->heads = heads; t->out_dim = out_dim; t->max_n = max_n;
+    t->act = gelu ? PRX_ACT_GELU : PRX_ACT_QUICKGELU;
     const int W = width;
     int r;
     if ((r = m.copy_f32(&t->tok, w[0], (size_t)vocab * W, s))) return r;
@@ -153,7 +156,7 @@ int prx_clip_text_encode_impl(PrxClipText* t, const int* tokens, int n, float* e
             if ((r = tg(t, d, s))) return r; }
         if ((r = prx_layernorm_fwd(t->x_mid, W, y.ln2_g, y.ln2_b, t->h, nullptr, t->mean, t->rstd, R, W, 1e-5f, s))) return r;
         {   GemmDesc d; d.A = t->h; d.lda = W; d.B = y.W1; d.ldb = W; d.M = R; d.N = 4 * W; d.K = W;
-            d.bias_n = y.b1; d.act = PRX_ACT_QUICKGELU; d.out_bf16 = t->u; d.ldc_bf16 = 4 * W;
+            d.bias_n = y.b1; d.act = t->act; d.out_bf16 = t->u; d.ldc_bf16 = 4 * W;
             if ((r = tg(t, d, s))) return r; }
         {   GemmDesc d; d.A = t->u; d.lda = 4 * W; d.B = y.W2; d.ldb = 4 * W; d.M = R; d.N = W; d.K = 4 * W;
             d.bias_n = y.b2; d.resid = t->x_mid; d.ldr = W; d.out_f32 = t->x; d.ldc_f32 = W;

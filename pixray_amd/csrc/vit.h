@@ -11,7 +11,8 @@ struct VitFamily {
     float eps;          // every LayerNorm's eps
     int act, dact;      // PRX_ACT_* of the c_fc product and of its dgrad
     PatchNorm norm;     // channel mean / std of the fused preprocessing
-    int head_dim;       // 0 / 64, or 32 / 16: narrower heads are zero-padded to 64 at weight-packing time (vit.hip PrxVit::hd)
+    int head_dim;       // 0 / 64, or 32 / 16: narrower heads are zero-padded to 64 at weight-packing time (vit.hip PrxVit::hd);
+                        // 80: zero-padded to 96, the attention on the 96-wide family (attention_hd96.hip)
 };
 VitFamily prx_vit_family_clip();
 struct GemmCtx;
@@ -37,3 +38,7 @@ int prx_vit_add_cls_pos(float* x, const float* cls, const float* pos, int N, int
 int prx_vit_embed_tokens(const float* x, const float* cls, const float* pos, void* out, int out16, int N, int T, int W, hipStream_t s);
 int prx_vit_gelu_f32(const float* t, float* io, size_t n, int bwd, hipStream_t s);
 int prx_vit_scale_f32(float* x, size_t n, float scale, int blocks, hipStream_t s);
+// the head padding of the weight packs (fp32 device tensors): qkv rows [3 * heads * hd, row] -> [3 * heads * hp, row], out-projection
+// input columns [W, heads * hd] -> [W, heads * hp]; the pad rows / columns are zero
+int prx_vit_pad_head_rows(const float* src, float* dst, int heads, int hd, int hp, int row, hipStream_t s);
+int prx_vit_pad_head_cols(const float* src, float* dst, int W, int heads, int hd, int hp, hipStream_t s);

@@ -126,6 +126,24 @@ int prx_vit_scale_f32(float* x, size_t n, float scale, int blocks, hipStream_t s
     return 0;
 }
 
+// Padded heads (PrxVit::hd below): every head's hd rows of the qkv projection (sections q | k | v; `row` floats per row: the weight's
+// width, or 1 for the bias) become the first hd of hp rows, the rest zero ...
+int prx_vit_pad_head_rows(const float* src, float* dst, int heads, int hd, int hp, int row, hipStream_t s) {
+    PRX_REQUIRE(heads >= 1 && hd >= 1 && hp >= hd && row >= 1, "pad_head_rows: %d heads of %d -> %d, %d floats per row", heads, hd, hp, row);
+    PRX_CHECK_HIP(hipMemsetAsync(dst, 0, sizeof(float) * (size_t)3 * heads * hp * row, s));
+    for (int sect = 0; sect < 3; ++sect)
+        PRX_CHECK_HIP(hipMemcpy2DAsync(dst + (size_t)sect * heads * hp * row, sizeof(float) * hp * row, src + (size_t)sect * heads * hd * row,
+                                       sizeof(float) * hd * row, sizeof(float) * hd * row, heads, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+// ... and the matching input columns of the out-projection: [W, heads * hd] -> [W, heads * hp]
+int prx_vit_pad_head_cols(const float* src, float* dst, int W, int heads, int hd, int hp, hipStream_t s) {
+    PRX_REQUIRE(W >= 1 && heads >= 1 && hd >= 1 && hp >= hd, "pad_head_cols: %d heads of %d -> %d", heads, hd, hp);
+    PRX_CHECK_HIP(hipMemsetAsync(dst, 0, sizeof(float) * (size_t)W * heads * hp, s));
+    PRX_CHECK_HIP(hipMemcpy2DAsync(dst, sizeof(float) * hp, src, sizeof(float) * hd, sizeof(float) * hd, (size_t)W * heads, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
 struct VitLayer {
     float *ln1_g, *ln1_b, *bqkv, *bo, *ln2_g, *ln2_b, *b1, *b2;
     void *Wqkv, *WqkvT, *Wo, *WoT, *W1, *W1T, *W2, *W2T;   // operand precision (bf16 | fp32)
@@ -145,7 +163,9 @@ struct PrxVit {
     // kernels' softmax scale is fixed at 1 / sqrt(64).  The padded lanes carry exact zeros forward (zero weights, zero bias) and
     // backward (dQ_pad = dS K_pad, dK_pad = dS^T Q_pad, dV_pad = P^T dO_pad with dO_pad = dx Wo_pad^T = 0), so values and gradients
     // are those of the narrow heads; the price is 64 / head dim times the qkv, attention and out-projection work.
-    int hd, aw;        // head dim of the weights; attention width = heads * 64 (== width when hd == 64)
+    // Heads of 80 (OpenCLIP ViT-H/14: 16 heads on width 1280) are padded the same way to hp = 96 columns and run on the 96-wide
+    // attention family (attention_hd96.hip), which takes the softmax scale 1 / sqrt(80) as an argument: nothing is folded into q.
+    int hd, hp, aw;    // head dim of the weights; operand columns per head (64 | 96); attention width = heads * hp (== width when hd == 64)
     int prec;         // PRX_PREC_*: element type of every operand buffer below (void*)
     int f32, h16;     // derived: operands are fp32 / the 16-bit operand format is IEEE half
     float* gs;        // half mode: device {S, 1/S} = the power-of-two scale of the backward in flight (common.h) + 64 partials; else null
@@ -199,13 +219,15 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
     PRX_REQUIRE(prec_valid(precision), "vit_create: unknown precision %d", precision);
     PRX_REQUIRE(n_w == n_head + 12 * layers + 3, "vit_create: expected %d weight tensors, got %d", n_head + 12 * layers + 3, n_w);
     const int hd = fam.head_dim > 0 ? fam.head_dim : 64;
-    PRX_REQUIRE(res % patch == 0 && width == heads * hd && width % 128 == 0 && (hd == 64 || hd == 32 || hd == 16),
+    PRX_REQUIRE(res % patch == 0 && width == heads * hd && width % 128 == 0 && (hd == 64 || hd == 32 || hd == 16 || hd == 80),
                 "vit_create: unsupported geometry (width %d, %d heads of %d)", width, heads, hd);
     PRX_REQUIRE(fam.ln_pre || layers >= 1, "vit_create: a tower without ln_pre needs at least one block");
     PRX_REQUIRE(fam.eps > 0.f && fam.norm.std[0] > 0.f && fam.norm.std[1] > 0.f && fam.norm.std[2] > 0.f,
                 "vit_create: LayerNorm eps and the channel std must be positive");
     const int G = res / patch;
     const int T = G * G + 1;
+    const int hp = hd == 80 ? 96 : 64;
+    PRX_REQUIRE(hp == 64 || T <= 640 || prec_is_f32(precision), "vit_create: heads of %d run on the 96-wide attention kernels, which take at most 640 tokens (got %d)", hd, T);
     std::unique_ptr<PrxVit> guard(new PrxVit());      // a failed create frees what it allocated (DevArena)
     PrxVit* v = guard.get();
     DevArena& m = v->mem;
@@ -216,7 +238,7 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
     v->T = T; v->max_n = max_n;
     v->res = res; v->patch = patch; v->width = width; v->layers = layers; v->heads = heads; v->out_dim = out_dim;
     v->prec = precision; v->f32 = prec_is_f32(precision); v->h16 = prec_is_h16(precision);
-    v->gs = nullptr; v->fam = fam; v->bp = nullptr; v->hd = hd; v->aw = heads * 64;
+    v->gs = nullptr; v->fam = fam; v->bp = nullptr; v->hd = hd; v->hp = hp; v->aw = heads * hp;
     const int AW = v->aw;
     float *pad_w = nullptr, *pad_b = nullptr;       // fp32 staging of the padded qkv / out-projection weights, reused by every block (stream order)
     if (hd != 64) {
@@ -258,24 +280,16 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
             if ((r = v->mem.copy_f32(&y.bqkv, q[3], 3 * W, s))) return r;
             if ((r = pack_both(v, &y.Wo, &y.WoT, q[4], W, W, s))) return r;
         } else {
-            const float qs = sqrtf(64.f / (float)hd);
-            // qkv rows: section (q | k | v) x head x hd rows of W floats -> the first hd of every head's 64 rows
-            PRX_CHECK_HIP(hipMemsetAsync(pad_w, 0, sizeof(float) * (size_t)3 * AW * W, s));
-            PRX_CHECK_HIP(hipMemsetAsync(pad_b, 0, sizeof(float) * (size_t)3 * AW, s));
-            for (int sect = 0; sect < 3; ++sect) {
-                PRX_CHECK_HIP(hipMemcpy2DAsync(pad_w + (size_t)sect * AW * W, sizeof(float) * 64 * W, q[2] + (size_t)sect * W * W, sizeof(float) * hd * W,
-                                               sizeof(float) * hd * W, heads, hipMemcpyDeviceToDevice, s));
-                PRX_CHECK_HIP(hipMemcpy2DAsync(pad_b + (size_t)sect * AW, sizeof(float) * 64, q[3] + (size_t)sect * W, sizeof(float) * hd,
-                                               sizeof(float) * hd, heads, hipMemcpyDeviceToDevice, s));
+            if ((r = prx_vit_pad_head_rows(q[2], pad_w, heads, hd, hp, W, s))) return r;
+            if ((r = prx_vit_pad_head_rows(q[3], pad_b, heads, hd, hp, 1, s))) return r;
+            if (hp == 64) {      // the 64-wide kernels' softmax scale is fixed at 1 / sqrt(64)
+                const float qs = sqrtf(64.f / (float)hd);
+                if ((r = prx_vit_scale_f32(pad_w, (size_t)AW * W, qs, 256, s))) return r;
+                if ((r = prx_vit_scale_f32(pad_b, (size_t)AW, qs, 1, s))) return r;
             }
-            if ((r = prx_vit_scale_f32(pad_w, (size_t)AW * W, qs, 256, s))) return r;
-            if ((r = prx_vit_scale_f32(pad_b, (size_t)AW, qs, 1, s))) return r;
             if ((r = pack_both(v, &y.Wqkv, &y.WqkvT, pad_w, 3 * AW, W, s))) return r;
             if ((r = v->mem.copy_f32(&y.bqkv, pad_b, 3 * AW, s))) return r;
-            // out-projection [W, W]: input columns head x hd -> the first hd of every head's 64 columns of [W, AW]
-            PRX_CHECK_HIP(hipMemsetAsync(pad_w, 0, sizeof(float) * (size_t)W * AW, s));
-            PRX_CHECK_HIP(hipMemcpy2DAsync(pad_w, sizeof(float) * 64, q[4], sizeof(float) * hd, sizeof(float) * hd, (size_t)W * heads,
-                                           hipMemcpyDeviceToDevice, s));
+            if ((r = prx_vit_pad_head_cols(q[4], pad_w, W, heads, hd, hp, s))) return r;
             if ((r = pack_both(v, &y.Wo, &y.WoT, pad_w, W, AW, s))) return r;
         }
         if ((r = v->mem.copy_f32(&y.bo, q[5], W, s))) return r;
@@ -290,7 +304,7 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
         DEV_ALLOC(m, alloc, y.mean1, R); DEV_ALLOC(m, alloc, y.rstd1, R); DEV_ALLOC(m, alloc, y.mean2, R); DEV_ALLOC(m, alloc, y.rstd2, R);
         DEV_ALLOC(m, alloc_op, y.qkv, R * 3 * AW, f32); DEV_ALLOC(m, alloc_op, y.t, R * 4 * W, f32);
         y.o_save = nullptr; y.lse = nullptr;
-        if (T > 64 || v->f32) { DEV_ALLOC(m, alloc_op, y.o_save, R * AW, f32); DEV_ALLOC(m, alloc, y.lse, (size_t)max_n * heads * T); }
+        if (T > 64 || v->f32 || hp == 96) { DEV_ALLOC(m, alloc_op, y.o_save, R * AW, f32); DEV_ALLOC(m, alloc, y.lse, (size_t)max_n * heads * T); }
     }
     const float* const* q = w + n_head + 12 * layers;
     if ((r = v->mem.copy_f32(&v->lnpost_g, q[0], W, s))) return r;
@@ -384,7 +398,12 @@ int prx_vit_forward_impl(PrxVit* v, const float* cutouts, int n, const float* mm
             d.bias_n = y.bqkv; d.out_bf16 = y.qkv; d.ldc_bf16 = 3 * AW;
             if ((r = vit_gemm(v, d, s))) return r; }
         const void* att = v->att_o;
-        if (v->f32) { if ((r = prx_mha_fwd_f32((const float*)y.qkv, (float*)y.o_save, y.lse, n, T, AW, v->heads, s))) return r; att = y.o_save; }
+        if (v->hp == 96) {
+            if (v->f32) { if ((r = prx_mha_fwd_f32_hd96((const float*)y.qkv, (float*)y.o_save, y.lse, n, T, AW, v->heads, s))) return r; }
+            else if ((r = prx_mha_fwd_hd96((const bf16_t*)y.qkv, (bf16_t*)y.o_save, y.lse, n, T, AW, v->heads, 1.f / sqrtf((float)v->hd), s, v->h16))) return r;
+            att = y.o_save;
+        }
+        else if (v->f32) { if ((r = prx_mha_fwd_f32((const float*)y.qkv, (float*)y.o_save, y.lse, n, T, AW, v->heads, s))) return r; att = y.o_save; }
         else if (T <= 64) { if ((r = prx_mha_fwd((const bf16_t*)y.qkv, (bf16_t*)v->att_o, n, T, AW, v->heads, s, v->h16))) return r; }
         else { if ((r = prx_mha_fwd_gen((const bf16_t*)y.qkv, (bf16_t*)y.o_save, y.lse, n, T, AW, v->heads, s, v->h16))) return r; att = y.o_save; }
         // the class-token tail: rows = the n class tokens, reached through a row stride of T * W in the token-major buffers;
@@ -479,7 +498,12 @@ int prx_vit_backward_a_impl(PrxVit* v, const float* cutouts, const float* mm, co
         {   GemmDesc d; d.A = v->dx_bf; d.lda = ldt; d.B = y.WoT; d.ldb = W; d.M = rows; d.N = AW; d.K = W;
             d.out_bf16 = v->do_; d.ldc_bf16 = tail ? T * AW : AW;
             if ((r = vit_gemm(v, d, s))) return r; }
-        if (v->f32) { if ((r = prx_mha_bwd_f32((const float*)y.qkv, (const float*)y.o_save, (const float*)v->do_, y.lse, (float*)v->dqkv, n, T, AW, v->heads, s))) return r; }
+        if (v->hp == 96) {
+            if (v->f32) { if ((r = prx_mha_bwd_f32_hd96((const float*)y.qkv, (const float*)y.o_save, (const float*)v->do_, y.lse, (float*)v->dqkv, n, T, AW, v->heads, s))) return r; }
+            else if ((r = prx_mha_bwd_hd96((const bf16_t*)y.qkv, (const bf16_t*)y.o_save, (const bf16_t*)v->do_, y.lse, (bf16_t*)v->dqkv, n, T, AW, v->heads,
+                                           1.f / sqrtf((float)v->hd), s, v->h16))) return r;
+        }
+        else if (v->f32) { if ((r = prx_mha_bwd_f32((const float*)y.qkv, (const float*)y.o_save, (const float*)v->do_, y.lse, (float*)v->dqkv, n, T, AW, v->heads, s))) return r; }
         else if (T <= 64) { if ((r = prx_mha_bwd((const bf16_t*)y.qkv, (const bf16_t*)v->do_, (bf16_t*)v->dqkv, n, T, AW, v->heads, s, v->h16))) return r; }
         else { if ((r = prx_mha_bwd_gen((const bf16_t*)y.qkv, (const bf16_t*)y.o_save, (const bf16_t*)v->do_, y.lse, (bf16_t*)v->dqkv, n, T, AW, v->heads, s, v->h16))) return r; }
         {   GemmDesc d; d.A = v->dqkv; d.lda = 3 * AW; d.B = y.WqkvT; d.ldb = 3 * AW; d.M = R; d.N = W; d.K = 3 * AW;

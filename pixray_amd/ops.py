@@ -174,7 +174,7 @@ class _VitTowerCfg(ctypes.Structure):
                [("ln_eps", ctypes.c_float), ("mean", ctypes.c_float * 3), ("std", ctypes.c_float * 3)]
 
 
-VIT_FAMILY_CLIP, VIT_FAMILY_SLIP = 0, 1
+VIT_FAMILY_CLIP, VIT_FAMILY_SLIP, VIT_FAMILY_OPENCLIP = 0, 1, 2
 
 
 class SlipVitHandle(ClipVitHandle):
@@ -187,6 +187,28 @@ class SlipVitHandle(ClipVitHandle):
         self.precision = precision_code(precision)
         c = _VitTowerCfg(cfg.input_resolution, cfg.patch_size, cfg.width, cfg.layers, cfg.heads, cfg.output_dim, max_batch, self.precision,
                          VIT_FAMILY_SLIP, cfg.head_dim, cfg.ln_eps, (ctypes.c_float * 3)(*IMAGENET_MEAN), (ctypes.c_float * 3)(*IMAGENET_STD))
+        h = ctypes.c_void_p()
+        call("prx_vit_tower_create", ctypes.addressof(h), ctypes.addressof(c), _keep(self, _weight_array(ws)), len(ws), _stream())
+        torch.cuda.synchronize(device)   # weight tensors may now be released
+        self.h = h
+        self.cfg = cfg
+        self.max_batch = max_batch
+        self.device = device
+        self.generation = 0
+
+
+class OpenClipVitHandle(ClipVitHandle):
+    """A `prx_clip_vit` made by `prx_vit_tower_create` for the OpenCLIP (LAION) family: CLIP's tensors and switches with the exact
+    GELU; heads of 80 (ViT-H-14) are zero-padded to 96 columns by the runner and run on the 96-wide attention kernels."""
+
+    def __init__(self, cfg, params, max_batch: int, device, precision=None):
+        from .perceptor import ClipVitPerceptor
+        from .weights import clip_vit_param_shapes
+        ws = _weights_in_abi_order(params, clip_vit_param_shapes(cfg), device, f"OpenCLIP ViT {getattr(cfg, 'name', '')}")
+        self.precision = precision_code(precision)
+        c = _VitTowerCfg(cfg.input_resolution, cfg.patch_size, cfg.width, cfg.layers, cfg.heads, cfg.output_dim, max_batch, self.precision,
+                         VIT_FAMILY_OPENCLIP, cfg.head_dim, 1e-5, (ctypes.c_float * 3)(*ClipVitPerceptor.CLIP_MEAN),
+                         (ctypes.c_float * 3)(*ClipVitPerceptor.CLIP_STD))
         h = ctypes.c_void_p()
         call("prx_vit_tower_create", ctypes.addressof(h), ctypes.addressof(c), _keep(self, _weight_array(ws)), len(ws), _stream())
         torch.cuda.synchronize(device)   # weight tensors may now be released
@@ -332,8 +354,17 @@ class _ClipTextCfg(ctypes.Structure):
                                             "max_batch")]
 
 
+class _TextTowerCfg(ctypes.Structure):
+    """mirror of `prx_text_tower_config` (include/prx.h)"""
+    _fields_ = _ClipTextCfg._fields_ + [("family", ctypes.c_int)]
+
+
+TEXT_FAMILY_CLIP, TEXT_FAMILY_OPENCLIP = 0, 1
+
+
 class ClipTextHandle(_Handle):
-    """Owns a `prx_clip_text` (CLIP text transformer, forward only: CLIP_Base.encode_text, slip.py:68-70)."""
+    """Owns a `prx_clip_text` (CLIP text transformer, forward only: CLIP_Base.encode_text, slip.py:68-70).  A configuration with
+    `gelu` set (weights.OpenClipTextConfig) is built by `prx_text_tower_create` with the exact GELU in place of QuickGELU."""
     _destroy = "prx_clip_text_destroy"
 
     def __init__(self, cfg, params, max_batch: int, device):
@@ -341,7 +372,11 @@ class ClipTextHandle(_Handle):
         ws = _weights_in_abi_order(params, clip_text_param_shapes(cfg), device, f"CLIP text tower {getattr(cfg, 'name', '')}")
         c = _ClipTextCfg(cfg.vocab_size, cfg.context_length, cfg.width, cfg.layers, cfg.heads, cfg.output_dim, max_batch)
         h = ctypes.c_void_p()
-        call("prx_clip_text_create", ctypes.addressof(h), ctypes.addressof(c), _keep(self, _weight_array(ws)), len(ws), _stream())
+        if getattr(cfg, "gelu", False):
+            c = _TextTowerCfg(cfg.vocab_size, cfg.context_length, cfg.width, cfg.layers, cfg.heads, cfg.output_dim, max_batch, TEXT_FAMILY_OPENCLIP)
+            call("prx_text_tower_create", ctypes.addressof(h), ctypes.addressof(c), _keep(self, _weight_array(ws)), len(ws), _stream())
+        else:
+            call("prx_clip_text_create", ctypes.addressof(h), ctypes.addressof(c), _keep(self, _weight_array(ws)), len(ws), _stream())
         torch.cuda.synchronize(device)
         self.h = h
         self.cfg = cfg

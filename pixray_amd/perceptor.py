@@ -7,7 +7,7 @@ import torch
 
 from . import ops
 from .weights import (IMAGENET_MEAN, IMAGENET_STD, SLIP_CONFIGS, SLIP_REFUSED, SlipVitConfig, synthetic_slip_vit_params,
-                      CLIP_CONFIGS, CLIP_RESNET_CONFIGS, CLIP_TEXT_CONFIGS, ClipResNetConfig, synthetic_clip_resnet_params, ClipTextConfig, ClipVitConfig, clip_text_param_shapes,
+                      OPENCLIP_CONFIGS, OPENCLIP_SEED, OpenClipVitConfig, CLIP_CONFIGS, CLIP_RESNET_CONFIGS, CLIP_TEXT_CONFIGS, ClipResNetConfig, synthetic_clip_resnet_params, ClipTextConfig, ClipVitConfig, clip_text_param_shapes,
                       synthetic_clip_text_params, synthetic_clip_vit_params)
 
 
@@ -26,6 +26,8 @@ class ClipVitPerceptor:
         self.group = group          # torch.distributed group when the cutout batch is sharded
         if isinstance(cfg, SlipVitConfig):          # SLIP family: the ViT runner through its tower-family constructor
             self.handle = ops.SlipVitHandle(cfg, params, max_batch, self.device, precision=precision)
+        elif isinstance(cfg, OpenClipVitConfig):    # OpenCLIP (LAION) family: CLIP's tower with the exact GELU, heads of 64 or 80
+            self.handle = ops.OpenClipVitHandle(cfg, params, max_batch, self.device, precision=precision)
         elif isinstance(cfg, ClipResNetConfig):     # ModifiedResNet family (RN50x4, ...): same protocol, different runner
             self.handle = ops.ClipResNetHandle(cfg, params, max_batch, self.device, precision=precision)
         else:
@@ -146,15 +148,16 @@ def slip_checkpoint_path(name, root="models"):
 
 def clip_perceptor_config(clip_model_name):
     """-> (vision configuration, text configuration or None) of a perceptor name: every `clip.available_models()` name (RN50, RN101,
-    RN50x4, RN50x16, RN50x64, ViT-B/32, ViT-B/16, ViT-L/14, ViT-L/14@336px), the SLIP family and the reduced test towers.  Needs no device:
+    RN50x4, RN50x16, RN50x64, ViT-B/32, ViT-B/16, ViT-L/14, ViT-L/14@336px), the OpenCLIP names (ViT-B-32, ViT-B-16, ViT-L-14, ViT-H-14),
+    the SLIP family and the reduced test towers.  Needs no device:
     the front end reads the cutout size of a name from here before any tower exists."""
     if clip_model_name in SLIP_REFUSED:
         raise ValueError(SLIP_REFUSED[clip_model_name])
-    for table in (CLIP_RESNET_CONFIGS, SLIP_CONFIGS, CLIP_CONFIGS):
+    for table in (CLIP_RESNET_CONFIGS, SLIP_CONFIGS, CLIP_CONFIGS, OPENCLIP_CONFIGS):
         if clip_model_name in table:
             return table[clip_model_name], CLIP_TEXT_CONFIGS.get(clip_model_name)
     raise KeyError(f"unknown / unsupported perceptor {clip_model_name!r} "
-                   f"(supported: {sorted(CLIP_CONFIGS) + sorted(CLIP_RESNET_CONFIGS) + sorted(SLIP_CONFIGS)})")
+                   f"(supported: {sorted(CLIP_CONFIGS) + sorted(OPENCLIP_CONFIGS) + sorted(CLIP_RESNET_CONFIGS) + sorted(SLIP_CONFIGS)})")
 
 
 def get_clip_perceptor(clip_model_name, device, params=None, max_batch=64, seed=0, group=None, text_params=None,
@@ -180,6 +183,6 @@ def get_clip_perceptor(clip_model_name, device, params=None, max_batch=64, seed=
         return SlipPerceptor(cfg, params, device, max_batch=max_batch, group=group, text_cfg=text_cfg,
                              text_params=text_params, tokenizer=tokenizer, seed=seed, precision=precision)
     if params is None:
-        params = synthetic_clip_vit_params(cfg, seed)
+        params = synthetic_clip_vit_params(cfg, seed + (OPENCLIP_SEED if clip_model_name in OPENCLIP_CONFIGS else 0))
     return ClipVitPerceptor(cfg, params, device, max_batch=max_batch, group=group, text_cfg=text_cfg,
                             text_params=text_params, tokenizer=tokenizer, seed=seed, precision=precision)

@@ -271,6 +271,32 @@ def synthetic_clip_vit_params(cfg: ClipVitConfig, seed: int = 0) -> "OrderedDict
     return out
 
 
+# --------------------------------------------------------------------------- OpenCLIP (LAION) ViT towers
+# [UPSTREAM mlfoundations/open_clip src/open_clip/model_configs/{ViT-B-32,ViT-B-16,ViT-L-14,ViT-H-14}.json; the package is not
+# installed, so the geometry is restated from the published configs, parity unpinned].  OpenCLIP spells its names with hyphens, which
+# keeps them apart from OpenAI's towers of the same geometry.  Against those: the exact (erf) GELU instead of QuickGELU (the LAION
+# checkpoints are trained without "quick_gelu"), on both the image and the text side; same tensors, same state-dict names, CLIP's
+# preprocessing constants.  ViT-H-14 has 16 heads of 80 on width 1280: the runner pads them to 96 columns (csrc/attention_hd96.hip).
+# ViT-g-14 (width 1408) and ViT-bigG-14 (width 1664) are not provided: LayerNorm needs a width that is a multiple of 256.
+@dataclass
+class OpenClipVitConfig(ClipVitConfig):
+    @property
+    def head_dim(self) -> int:
+        return self.width // self.heads
+
+
+OPENCLIP_CONFIGS = {
+    "ViT-B-32": OpenClipVitConfig("ViT-B-32", 224, 32, 768, 12, 12, 512),
+    "ViT-B-16": OpenClipVitConfig("ViT-B-16", 224, 16, 768, 12, 12, 512),
+    "ViT-L-14": OpenClipVitConfig("ViT-L-14", 224, 14, 1024, 24, 16, 768),
+    "ViT-H-14": OpenClipVitConfig("ViT-H-14", 224, 14, 1280, 32, 16, 1024),            # 257 tokens, MLP 5120, heads of 80
+    # reduced towers with heads of 80 (same operators, 2 layers; 640 is the smallest width that is a multiple of 80 and of 128)
+    "tiny-H-32": OpenClipVitConfig("tiny-H-32", 224, 32, 640, 2, 8, 128),              # 50 tokens
+    "tiny-H-14": OpenClipVitConfig("tiny-H-14", 224, 14, 640, 2, 8, 128),              # 257 tokens
+}
+OPENCLIP_SEED = 7919            # the synthetic weights of `ViT-B-32` are not those of `ViT-B/32`
+
+
 # --------------------------------------------------------------------------- SLIP image towers (timm VisionTransformer)
 # [UPSTREAM facebookresearch/SLIP models.py + timm vision_transformer.py; the SLIP/ submodule of the reference checkout is empty, so
 # this is restated from the published sources, parity unpinned]: `timm.create_model(vit_*_patch16_224, num_classes=0)` followed by
@@ -380,6 +406,12 @@ class ClipTextConfig:
     output_dim: int = 512
 
 
+@dataclass
+class OpenClipTextConfig(ClipTextConfig):
+    """CLIP's text transformer with the exact GELU (the OpenCLIP towers); heads are 64 wide in every published config"""
+    gelu: bool = True
+
+
 # text-side hyper-parameters of the OpenAI checkpoints (clip/model.py `build_model`: heads = width // 64)
 CLIP_TEXT_CONFIGS = {
     "ViT-B/32": ClipTextConfig(),
@@ -393,6 +425,14 @@ CLIP_TEXT_CONFIGS = {
     "RN50x16": ClipTextConfig("RN50x16", width=768, heads=12, output_dim=768),
     "RN50x64": ClipTextConfig("RN50x64", width=1024, heads=16, output_dim=1024),
 }
+CLIP_TEXT_CONFIGS.update({
+    "ViT-B-32": OpenClipTextConfig("ViT-B-32"),
+    "ViT-B-16": OpenClipTextConfig("ViT-B-16"),
+    "ViT-L-14": OpenClipTextConfig("ViT-L-14", width=768, heads=12, output_dim=768),
+    "ViT-H-14": OpenClipTextConfig("ViT-H-14", width=1024, layers=24, heads=16, output_dim=1024),
+    "tiny-H-32": OpenClipTextConfig("tiny-H-32", vocab_size=1000, context_length=77, width=256, layers=2, heads=4, output_dim=128),
+    "tiny-H-14": OpenClipTextConfig("tiny-H-14", vocab_size=1000, context_length=77, width=256, layers=2, heads=4, output_dim=128),
+})
 # every SLIP model size carries CLIP's text transformer at width 512 / 8 heads / 12 layers [UPSTREAM SLIP models.py]
 CLIP_TEXT_CONFIGS.update({n: ClipTextConfig(n) for n in ("SLIP_VITS16", "SLIP_VITB16", "SLIP_VITL16", "SLIP_CC3M", "SLIP_CC12M",
                                                          "CLIP_VITS16", "CLIP_VITB16", "CLIP_VITL16")})

@@ -4,6 +4,8 @@
     python tools/mha_bench.py --ab 577   # ViT-L/14@336px (N = 32, T = 577, 16 heads): the workgroup family against the tile kernels
                                          # on one build in one process, the two routes alternating over --rounds rounds (prx_mha_route,
                                          # include/prx.h); prints every round, the medians, each route's spread and the verdict
+    python tools/mha_bench.py --hd96 257 --cutouts 16   # the 96-wide family (heads of 80 zero-padded, OpenCLIP ViT-H-14: 16 heads) alone:
+                                         # every round, the median and the spread; a single measured value, not a comparison
 The A/B verdict follows the rule for comparing two timings: a route is "faster" in a direction only if the gap between the medians
 exceeds the larger of the two spreads (max - min over the rounds) measured in this very run."""
 import argparse
@@ -92,6 +94,30 @@ def ab(T, N, heads, rounds, iters):
                                             if all(v == "workgroups faster" for v in verdicts) else "the workgroup family is NOT faster throughout: " + "; ".join(verdicts)))
 
 
+def hd96(T, N, heads, rounds, iters):
+    """prx_k_mha_{fwd,bwd}_hd_op at 96 columns per head (head dim 80, columns 80 .. 95 of every head zero), both operand formats"""
+    C = 96 * heads
+    for dtype in (torch.float16, torch.bfloat16):
+        g = torch.Generator(device=DEV).manual_seed(0)
+        qkv = torch.randn(N * T, 3, heads, 96, device=DEV, generator=g)
+        do = torch.randn(N * T, heads, 96, device=DEV, generator=g)
+        qkv[..., 80:] = 0
+        do[..., 80:] = 0
+        qkv, do = qkv.to(dtype), do.to(dtype)
+        out = torch.empty(N * T, C, dtype=dtype, device=DEV)
+        lse = torch.empty(N * heads * T, device=DEV)
+        dqkv = torch.empty(N * T, 3 * C, dtype=dtype, device=DEV)
+        h16 = 1 if dtype == torch.float16 else 0
+        fwd = lambda: call("prx_k_mha_fwd_hd_op", qkv, out, lse, N, T, C, heads, h16, 96, stream())
+        bwd = lambda: call("prx_k_mha_bwd_hd_op", qkv, out, do, lse, dqkv, N, T, C, heads, h16, 96, stream())
+        flop_f = 4.0 * N * heads * T * T * 80            # algorithmic: the 80 live columns
+        for d, fn, fl in (("fwd", fwd, flop_f), ("bwd", bwd, 2.5 * flop_f)):
+            ts = [time_us(fn, iters) for _ in range(rounds)]
+            med = statistics.median(ts)
+            print(f"  hd96 N={N} T={T} heads={heads} {str(dtype):15s} {d}: " + " ".join(f"{t:8.1f}" for t in ts) +
+                  f"   median {med:8.1f} us  spread {max(ts) - min(ts):6.1f} us  ({fl / med / 1e6:6.1f} TFLOP/s on the live columns)")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--ab", type=int, default=0, metavar="T", help="A/B the two routes at T tokens (64 < T <= 640)")
@@ -99,8 +125,11 @@ if __name__ == "__main__":
     ap.add_argument("--heads", type=int, default=16)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=500)
+    ap.add_argument("--hd96", type=int, default=0, metavar="T", help="time the 96-wide family at T tokens (T <= 640)")
     a = ap.parse_args()
-    if a.ab:
+    if a.hd96:
+        hd96(a.hd96, a.cutouts, a.heads, a.rounds, a.iters)
+    elif a.ab:
         ab(a.ab, a.cutouts, a.heads, a.rounds, a.iters)
     else:
         table()
