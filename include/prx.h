@@ -241,6 +241,24 @@ int prx_k_tokens_fwd(const float* x, const float* pos, void* t, int N, int P, in
 int prx_k_tokens_bwd(const float* dt, float* dx, int N, int P, int C, int prec, prx_stream_t s);
 int prx_k_tok0_gather(const void* t, void* out, int N, int T, int C, int prec, prx_stream_t s);
 int prx_k_tok0_scatter(const void* g0, void* dt, int N, int T, int C, int prec, prx_stream_t s);
+/* OpenCLIP ConvNeXt (convnext.hip).  Maps are NHWC [N][H][W][C], C a multiple of 8, N*H*W*C below 2^31.
+ * pack_dw: the depthwise weight [C][49] as [2][49][C] in the operand format, the taps as given and flipped (the data gradient's).
+ * dwconv: out = 7x7 depthwise convolution of x with padding 3, taps pack[flip] [+ bias[c]] [+ add (fp32 [N][H][W][C])]; out_op
+ *   (operand format) and / or out_f32.  space_to_depth: [N][H][W][C] -> [N][H/2][W/2][4C], output channel (dy * 2 + dx) * C + c;
+ *   depth_to_space takes the [N][H/2][W/2][4C] map back (N, H, W, C are those of the large map in both).  avgpool_fwd: the mean over
+ *   HW of [N][HW][C] as fp32 [N][C]; avgpool_bwd: g[n][c] / HW on every pixel.  layernorm: over the channels of `rows` pixels; x is
+ *   fp32 when x_f32, else in the operand format; group > 0: x (and dx) have one unused leading row per `group` rows (the stem). */
+int prx_k_cnx_pack_dw(const float* w, void* pack, int C, int prec, prx_stream_t s);
+int prx_k_cnx_dwconv(const void* x, const void* pack, const float* bias, const float* add, void* out_op, float* out_f32, int N, int H,
+                     int W, int C, int flip, int prec, prx_stream_t s);
+int prx_k_cnx_space_to_depth(const void* in, void* out, int N, int H, int W, int C, int prec, prx_stream_t s);
+int prx_k_cnx_depth_to_space(const void* in, void* out, int N, int H, int W, int C, int prec, prx_stream_t s);
+int prx_k_cnx_avgpool_fwd(const void* x, float* out, int N, int HW, int C, int prec, prx_stream_t s);
+int prx_k_cnx_avgpool_bwd(const float* g, float* dx_f32, void* dx_op, int N, int HW, int C, int prec, prx_stream_t s);
+int prx_k_cnx_layernorm_fwd(const void* x, int x_f32, const float* gamma, const float* beta, void* out_op, float* out_f32, float* mean,
+                            float* rstd, int rows, int C, float eps, int group, int prec, prx_stream_t s);
+int prx_k_cnx_layernorm_bwd(const float* g, const void* x, int x_f32, const float* gamma, const float* mean, const float* rstd,
+                            void* dx_op, float* dx_f32, int rows, int C, int group, int prec, prx_stream_t s);
 /* batch min / max, patchify and the min/max renormalisation backward (cutouts.hip); m0..s2: the channel means / stds */
 int prx_k_minmax(const float* x, size_t n, float* part, int nparts, float* mm, prx_stream_t s);
 int prx_k_patchify_fwd(const float* cut, const float* mm, void* A, int prec, int N, int S, int P, int T, float m0, float m1, float m2,
@@ -612,6 +630,46 @@ int prx_clip_resnet_backward_reduce(prx_clip_resnet* h, const float* cutouts, co
 int prx_clip_resnet_backward_finish(prx_clip_resnet* h, const float* cutouts, const float* mm, const double* acc,
                                     float* g_cutouts, prx_stream_t s);
 
+/* --- encode_image for an OpenCLIP ConvNeXt visual tower (convnext_base, convnext_base_w, convnext_base_w_320, convnext_large_d,
+ *     convnext_large_d_320, convnext_xxlarge) [UPSTREAM timm convnext.py ConvNeXt + open_clip timm_model.py head; neither package is
+ *     installed: restated from the published sources, parity unpinned].  Same call sequence and min/max contract as the ResNet entry
+ *     points above; CLIP's preprocessing constants.  csrc/convnext.hip.
+ * weights[]: fp32 device tensors as pixray_amd/weights.py::fold_clip_convnext_params lays them out from the `visual.*` state dict:
+ *   stem {weight [d0, 3*4*4], bias, LayerNorm weight, bias};
+ *   per stage i: for i > 0 the downsample {LayerNorm weight [d(i-1)], bias, conv weight [d(i), 4*d(i-1)] with the input column
+ *   (dy * 2 + dx) * d(i-1) + c, bias}; then per block: conv_dw {weight [C, 49], bias}, norm {weight, bias}, mlp.fc1 {weight [4C, C],
+ *   bias}, mlp.fc2 {weight [C, 4C], bias} with the block's layer scale gamma[C] folded into both (rows of the weight, the bias);
+ *   head.norm {weight [d3], bias}; then proj.weight [embed, d3] (proj_mlp == 0) or mlp.fc1 {weight [2*embed, d3], bias},
+ *   mlp.fc2.weight [embed, 2*embed] (proj_mlp == 1).  4 + 12 + 8 * sum(depths) + 2 + (1 | 3) tensors.
+ * Device memory per cutout of max_batch, beside the packed weights (saved GELU pre-activations [pixels][4C] and stencil outputs
+ * [pixels][C] of every block, the fp32 residual stream with its operand twin as two buffers per stage, the backward's gradient
+ * streams): convnext_base_w at 256^2: 95 181 104 bytes (90.8 MiB) with half or bf16 operands -- 46.5 MiB of it the pre-activations
+ * --, 163 087 760 (155.5 MiB) in the exact mode; convnext_base at 224^2: 69.5 / 119.1 MiB; convnext_base_w_320: 141.8 / 243.0 MiB;
+ * convnext_large_d at 256^2: 135.5 / 232.4 MiB; convnext_large_d_320: 211.6 / 363.1 MiB; convnext_xxlarge at 256^2: 288.3 / 500.6 MiB
+ * (pixray_amd/weights.py::clip_convnext_activation_bytes restates the allocation list). */
+typedef struct prx_clip_convnext prx_clip_convnext;
+typedef struct prx_clip_convnext_config {
+    int input_resolution;  /* 224 | 256 | 320; a multiple of 32 (the maps are R/4, R/8, R/16, R/32 on a side) */
+    int depths[4];         /* {3,3,27,3} | {3,4,30,3}; each >= 1 */
+    int dims[4];           /* {128,256,512,1024} | {192,384,768,1536} | {384,768,1536,3072}; multiples of 8 */
+    int output_dim;        /* 512 | 640 | 768 | 1024; a multiple of 8 */
+    int proj_mlp;          /* 0: linear projection; 1: fc1 (2 * output_dim), GELU, fc2 (the convnext_large_d towers) */
+    float ln_eps;          /* 1e-6; convnext_xxlarge: 1e-5 */
+    int max_batch;         /* capacity in cutouts: create allocates one forward's activations for this many (figures above); an allocation
+                              that fails is an error of the call (rc < 0, prx_last_error names the bytes asked for and the bytes held),
+                              nothing stays allocated */
+    int precision;         /* PRX_PREC_F16 | PRX_PREC_BF16 | PRX_PREC_F32 */
+} prx_clip_convnext_config;
+int prx_clip_convnext_create(prx_clip_convnext** out, const prx_clip_convnext_config* cfg, const float* const* weights, int n_weights,
+                             prx_stream_t s);
+void prx_clip_convnext_destroy(prx_clip_convnext* h);
+int prx_clip_convnext_minmax(prx_clip_convnext* h, const float* cutouts, int n, float* mm, prx_stream_t s);
+int prx_clip_convnext_encode(prx_clip_convnext* h, const float* cutouts, int n, const float* mm, float* embeds, prx_stream_t s);
+int prx_clip_convnext_backward_reduce(prx_clip_convnext* h, const float* cutouts, const float* mm, const float* d_embeds,
+                                      double* acc, prx_stream_t s);
+int prx_clip_convnext_backward_finish(prx_clip_convnext* h, const float* cutouts, const float* mm, const double* acc,
+                                      float* g_cutouts, prx_stream_t s);
+
 /* --- CLIP_Base.encode_text (slip.py:68-70) = openai/CLIP `CLIP.encode_text` [UPSTREAM clip/model.py] on token ids:
  *     token_embedding[tokens] + positional_embedding -> causal transformer -> ln_final -> row at argmax(tokens) (the EOT
  *     token) @ text_projection.  Forward only; the result is NOT normalised (as the reference's, slip.py:70).
@@ -749,6 +807,7 @@ int prx_profile_gemm_collect(prx_gemm_ctx* c, double* total_ms, double* total_fl
 prx_gemm_ctx* prx_vqgan_gemm_ctx(prx_vqgan* h);
 prx_gemm_ctx* prx_clip_vit_gemm_ctx(prx_clip_vit* h);
 prx_gemm_ctx* prx_clip_resnet_gemm_ctx(prx_clip_resnet* h);
+prx_gemm_ctx* prx_clip_convnext_gemm_ctx(prx_clip_convnext* h);
 prx_gemm_ctx* prx_vgg16_gemm_ctx(prx_vgg16* h);
 
 /* ---- the exchange step of the cutout-sharded iteration ------------------------------------------------

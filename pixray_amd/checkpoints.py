@@ -7,6 +7,8 @@ are exercised in tests with randomly initialised upstream-format state dicts; th
   RN50x64) carry `visual.conv{1,2,3}`, `visual.bn{1,2,3}.*`, `visual.layer{1..4}.{b}.*` and `visual.attnpool.*` instead.
 * OpenCLIP (`open_clip.create_model(name, pretrained=...).state_dict()`, the LAION towers): its native ViT models keep OpenAI's key
   names on both sides; the geometry comes from the named configuration (`clip_visual_from_openclip` / `clip_text_from_openclip`).
+  Its ConvNeXt models wrap a timm trunk: `visual.trunk.stem.*`, `visual.trunk.stages.{i}.{downsample,blocks.{b}}.*`,
+  `visual.trunk.head.norm.*`, `visual.head.{proj | mlp.fc1, mlp.fc2}.*` (`clip_convnext_from_openclip`).
 * HF `CLIPVisionModelWithProjection` -> the same names (q/k/v projections are concatenated into `in_proj_*`).
 * taming-transformers VQGAN Lightning checkpoint (`vqgan.py:124-140`): `state_dict` with `decoder.*`,
   `post_quant_conv.*`, `quantize.embedding.weight` for the decoder runner, plus `encoder.*` / `quant_conv.*` for the
@@ -71,6 +73,25 @@ def clip_text_from_openclip(state_dict: Dict[str, torch.Tensor], name_or_cfg):
     """text side of the same state dict: the un-prefixed entries under OpenAI's names, for the named configuration's geometry
     (`attn_mask` and `logit_scale` ride along in the file and are not read)"""
     return _check(dict(state_dict), clip_text_param_shapes(_openclip_configs(name_or_cfg, text=True)))
+
+
+def clip_convnext_from_openclip(state_dict: Dict[str, torch.Tensor], name_or_cfg, text_cfg=None):
+    """-> (params, text_params) of an OpenCLIP ConvNeXt model's state dict (`open_clip.create_model("convnext_base_w", ...)`): the
+    visual side's `visual.trunk.*` and `visual.head.*` entries with the prefix stripped, in the order of `clip_convnext_param_shapes`
+    (the layer scale `gamma` un-folded: ops.ClipConvNextHandle folds), and the un-prefixed text entries under OpenAI's names.  The
+    geometry is the named configuration's (or a ClipConvNextConfig with its OpenClipTextConfig); a missing or mis-shaped tensor is
+    named."""
+    from .weights import CLIP_CONVNEXT_CONFIGS, CLIP_TEXT_CONFIGS, clip_convnext_param_shapes
+    if isinstance(name_or_cfg, str):
+        if name_or_cfg not in CLIP_CONVNEXT_CONFIGS:
+            raise KeyError(f"unknown OpenCLIP ConvNeXt model {name_or_cfg!r} (supported: {sorted(CLIP_CONVNEXT_CONFIGS)})")
+        cfg, text_cfg = CLIP_CONVNEXT_CONFIGS[name_or_cfg], CLIP_TEXT_CONFIGS[name_or_cfg]
+    else:
+        cfg = name_or_cfg
+        if text_cfg is None:
+            text_cfg = CLIP_TEXT_CONFIGS[cfg.name]
+    visual = {k[len("visual."):]: v for k, v in state_dict.items() if k.startswith("visual.")}
+    return _check(visual, clip_convnext_param_shapes(cfg)), _check(dict(state_dict), clip_text_param_shapes(text_cfg))
 
 
 def clip_visual_from_hf(state_dict: Dict[str, torch.Tensor], cfg: ClipVitConfig):

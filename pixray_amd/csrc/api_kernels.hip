@@ -9,6 +9,7 @@
 #include "elementwise.h"
 #include "attention.h"
 #include "resnet.h"
+#include "convnext.h"
 #include "cutouts.h"
 #include "vgg.h"
 #include "vit.h"
@@ -91,6 +92,33 @@ int prx_k_mha_fwd_f32(const float* qkv, float* out, float* lse, int N, int T, in
 int prx_k_mha_bwd_f32(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int N, int T, int C,
                       int heads, prx_stream_t s) {
     return prx_mha_bwd_f32(qkv, out, dout, lse, dqkv, N, T, C, heads, S_(s));
+}
+
+// ---- OpenCLIP ConvNeXt runner kernels (convnext.hip; tests/test_convnext_gpu.py) ------------------------------------------------
+int prx_k_cnx_pack_dw(const float* w, void* pack, int C, int prec, prx_stream_t s) { return prx_cnx_pack_dw(w, pack, C, prec, S_(s)); }
+int prx_k_cnx_dwconv(const void* x, const void* pack, const float* bias, const float* add, void* out_op, float* out_f32, int N, int H,
+                     int W, int C, int flip, int prec, prx_stream_t s) {
+    return prx_cnx_dwconv(x, pack, bias, add, out_op, out_f32, N, H, W, C, flip, prec, S_(s));
+}
+int prx_k_cnx_space_to_depth(const void* in, void* out, int N, int H, int W, int C, int prec, prx_stream_t s) {
+    return prx_cnx_space_to_depth(in, out, N, H, W, C, prec, S_(s));
+}
+int prx_k_cnx_depth_to_space(const void* in, void* out, int N, int H, int W, int C, int prec, prx_stream_t s) {
+    return prx_cnx_depth_to_space(in, out, N, H, W, C, prec, S_(s));
+}
+int prx_k_cnx_avgpool_fwd(const void* x, float* out, int N, int HW, int C, int prec, prx_stream_t s) {
+    return prx_cnx_avgpool_fwd(x, out, N, HW, C, prec, S_(s));
+}
+int prx_k_cnx_avgpool_bwd(const float* g, float* dx_f32, void* dx_op, int N, int HW, int C, int prec, prx_stream_t s) {
+    return prx_cnx_avgpool_bwd(g, dx_f32, dx_op, N, HW, C, prec, S_(s));
+}
+int prx_k_cnx_layernorm_fwd(const void* x, int x_f32, const float* gamma, const float* beta, void* out_op, float* out_f32, float* mean,
+                            float* rstd, int rows, int C, float eps, int group, int prec, prx_stream_t s) {
+    return prx_cnx_layernorm_fwd(x, x_f32, gamma, beta, out_op, out_f32, mean, rstd, rows, C, eps, group, prec, S_(s));
+}
+int prx_k_cnx_layernorm_bwd(const float* g, const void* x, int x_f32, const float* gamma, const float* mean, const float* rstd,
+                            void* dx_op, float* dx_f32, int rows, int C, int group, int prec, prx_stream_t s) {
+    return prx_cnx_layernorm_bwd(g, x, x_f32, gamma, mean, rstd, dx_op, dx_f32, rows, C, group, prec, S_(s));
 }
 
 // ---- every argument forwarded: the half-mode / lean-layout variants (tests/test_kernels_half_gpu.py) ----------------------------

@@ -6,6 +6,7 @@
 #include "vgg.h"
 #include "clip_text.h"
 #include "resnet.h"
+#include "convnext.h"
 #include "cutouts.h"
 #include "prompt_vq.h"
 #include "elementwise.h"
@@ -238,6 +239,33 @@ int prx_clip_resnet_backward_reduce(prx_clip_resnet* h, const float* cutouts, co
                                     double* acc, prx_stream_t s) {
     PRX_REQUIRE(h && cutouts && mm && d_embeds && acc, "prx_clip_resnet_backward_reduce: null argument");
     return prx_resnet_backward_a_impl((PrxResNet*)h, cutouts, mm, d_embeds, acc, S_(s));
+}
+// ---- OpenCLIP ConvNeXt tower ------------------------------------------------------------------
+int prx_clip_convnext_create(prx_clip_convnext** out, const prx_clip_convnext_config* c, const float* const* weights, int n_weights,
+                             prx_stream_t s) {
+    PRX_REQUIRE(out && c && weights, "prx_clip_convnext_create: null argument");
+    return prx_convnext_create_impl((PrxConvNext**)out, c->input_resolution, c->depths, c->dims, c->output_dim, c->proj_mlp, c->ln_eps,
+                                    c->max_batch, c->precision, weights, n_weights, S_(s));
+}
+void prx_clip_convnext_destroy(prx_clip_convnext* h) { prx_convnext_destroy_impl((PrxConvNext*)h); }
+prx_gemm_ctx* prx_clip_convnext_gemm_ctx(prx_clip_convnext* h) { return (prx_gemm_ctx*)prx_convnext_gemm_ctx_impl((PrxConvNext*)h); }
+int prx_clip_convnext_minmax(prx_clip_convnext* h, const float* cutouts, int n, float* mm, prx_stream_t s) {
+    PRX_REQUIRE(h && cutouts && mm, "prx_clip_convnext_minmax: null argument");
+    return prx_convnext_minmax_impl((PrxConvNext*)h, cutouts, n, mm, S_(s));
+}
+int prx_clip_convnext_encode(prx_clip_convnext* h, const float* cutouts, int n, const float* mm, float* embeds, prx_stream_t s) {
+    PRX_REQUIRE(h && cutouts && mm && embeds, "prx_clip_convnext_encode: null argument");
+    return prx_convnext_forward_impl((PrxConvNext*)h, cutouts, n, mm, embeds, S_(s));
+}
+int prx_clip_convnext_backward_reduce(prx_clip_convnext* h, const float* cutouts, const float* mm, const float* d_embeds,
+                                      double* acc, prx_stream_t s) {
+    PRX_REQUIRE(h && cutouts && mm && d_embeds && acc, "prx_clip_convnext_backward_reduce: null argument");
+    return prx_convnext_backward_a_impl((PrxConvNext*)h, cutouts, mm, d_embeds, acc, S_(s));
+}
+int prx_clip_convnext_backward_finish(prx_clip_convnext* h, const float* cutouts, const float* mm, const double* acc,
+                                      float* g_cutouts, prx_stream_t s) {
+    PRX_REQUIRE(h && cutouts && mm && acc && g_cutouts, "prx_clip_convnext_backward_finish: null argument");
+    return prx_convnext_backward_b_impl((PrxConvNext*)h, cutouts, mm, acc, g_cutouts, S_(s));
 }
 int prx_clip_resnet_backward_finish(prx_clip_resnet* h, const float* cutouts, const float* mm, const double* acc,
                                     float* g_cutouts, prx_stream_t s) {

@@ -261,6 +261,48 @@ class ClipResNetHandle(_Handle):
         return _lib.load().prx_clip_resnet_gemm_ctx(self.h)
 
 
+class _ClipConvNextCfg(ctypes.Structure):
+    """mirror of `prx_clip_convnext_config` (include/prx.h)"""
+    _fields_ = [("input_resolution", ctypes.c_int), ("depths", ctypes.c_int * 4), ("dims", ctypes.c_int * 4), ("output_dim", ctypes.c_int),
+                ("proj_mlp", ctypes.c_int), ("ln_eps", ctypes.c_float), ("max_batch", ctypes.c_int), ("precision", ctypes.c_int)]
+
+
+class ClipConvNextHandle(_Handle):
+    """Owns a `prx_clip_convnext` (OpenCLIP ConvNeXt tower: convnext_base ... convnext_xxlarge); same protocol as ClipVitHandle.
+    `params` is the open_clip `visual.*` state dict (`trunk.*`, `head.*`, the layer scale `gamma` un-folded); the fold into fc2 and
+    the matrix layouts of the convolutions happen here (weights.fold_clip_convnext_params).
+
+    The runner allocates one forward's activations and the backward's gradient streams for `max_batch` cutouts when it is created
+    (weights.clip_convnext_activation_bytes: convnext_base_w at 256 x 256 takes 90.8 MiB per cutout with 16-bit operands, 155.5 MiB in the exact mode).  An
+    allocation that fails raises PrxError with the bytes asked for and the bytes held so far; the partly built handle is freed."""
+    _destroy = "prx_clip_convnext_destroy"
+    abi = "prx_clip_convnext"
+
+    def __init__(self, cfg, params, max_batch: int, device, precision=None):
+        from .weights import clip_convnext_param_shapes, fold_clip_convnext_params
+        _weights_in_abi_order(params, clip_convnext_param_shapes(cfg), "cpu", f"OpenCLIP ConvNeXt {getattr(cfg, 'name', '')}")   # names / shapes only
+        folded = fold_clip_convnext_params(cfg, params)
+        ws = [t.to(device=device, dtype=torch.float32).contiguous() for t in folded.values()]
+        self.precision = precision_code(precision)
+        c = _ClipConvNextCfg()
+        c.input_resolution, c.output_dim, c.proj_mlp, c.ln_eps = cfg.input_resolution, cfg.output_dim, int(cfg.proj == "mlp"), cfg.ln_eps
+        c.max_batch, c.precision = max_batch, self.precision
+        for i in range(4):
+            c.depths[i], c.dims[i] = cfg.depths[i], cfg.dims[i]
+        h = ctypes.c_void_p()
+        call("prx_clip_convnext_create", ctypes.addressof(h), ctypes.addressof(c), _keep(self, _weight_array(ws)), len(ws), _stream())
+        torch.cuda.synchronize(device)   # weight tensors may now be released
+        self.h = h
+        self.cfg = cfg
+        self.max_batch = max_batch
+        self.device = device
+        self.generation = 0
+
+    @property
+    def gemm_ctx(self):
+        return _lib.load().prx_clip_convnext_gemm_ctx(self.h)
+
+
 class _ClipCfg(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ("input_resolution", "patch_size", "width", "layers", "heads",
                                             "output_dim", "max_batch", "precision")]

@@ -7,6 +7,7 @@ import torch
 
 from . import ops
 from .weights import (IMAGENET_MEAN, IMAGENET_STD, SLIP_CONFIGS, SLIP_REFUSED, SlipVitConfig, synthetic_slip_vit_params,
+                      CLIP_CONVNEXT_CONFIGS, ClipConvNextConfig, synthetic_clip_convnext_params,
                       OPENCLIP_CONFIGS, OPENCLIP_SEED, OpenClipVitConfig, CLIP_CONFIGS, CLIP_RESNET_CONFIGS, CLIP_TEXT_CONFIGS, ClipResNetConfig, synthetic_clip_resnet_params, ClipTextConfig, ClipVitConfig, clip_text_param_shapes,
                       synthetic_clip_text_params, synthetic_clip_vit_params)
 
@@ -30,6 +31,8 @@ class ClipVitPerceptor:
             self.handle = ops.OpenClipVitHandle(cfg, params, max_batch, self.device, precision=precision)
         elif isinstance(cfg, ClipResNetConfig):     # ModifiedResNet family (RN50x4, ...): same protocol, different runner
             self.handle = ops.ClipResNetHandle(cfg, params, max_batch, self.device, precision=precision)
+        elif isinstance(cfg, ClipConvNextConfig):   # OpenCLIP ConvNeXt family (convnext_base_w, ...): the depthwise-conv runner
+            self.handle = ops.ClipConvNextHandle(cfg, params, max_batch, self.device, precision=precision)
         else:
             self.handle = ops.ClipVitHandle(cfg, params, max_batch, self.device, precision=precision)
 
@@ -148,16 +151,17 @@ def slip_checkpoint_path(name, root="models"):
 
 def clip_perceptor_config(clip_model_name):
     """-> (vision configuration, text configuration or None) of a perceptor name: every `clip.available_models()` name (RN50, RN101,
-    RN50x4, RN50x16, RN50x64, ViT-B/32, ViT-B/16, ViT-L/14, ViT-L/14@336px), the OpenCLIP names (ViT-B-32, ViT-B-16, ViT-L-14, ViT-H-14),
-    the SLIP family and the reduced test towers.  Needs no device:
+    RN50x4, RN50x16, RN50x64, ViT-B/32, ViT-B/16, ViT-L/14, ViT-L/14@336px), the OpenCLIP names (ViT-B-32, ViT-B-16, ViT-L-14, ViT-H-14;
+    convnext_base, convnext_base_w, convnext_base_w_320, convnext_large_d, convnext_large_d_320, convnext_xxlarge), the SLIP family and
+    the reduced test towers.  Needs no device:
     the front end reads the cutout size of a name from here before any tower exists."""
     if clip_model_name in SLIP_REFUSED:
         raise ValueError(SLIP_REFUSED[clip_model_name])
-    for table in (CLIP_RESNET_CONFIGS, SLIP_CONFIGS, CLIP_CONFIGS, OPENCLIP_CONFIGS):
+    for table in (CLIP_RESNET_CONFIGS, SLIP_CONFIGS, CLIP_CONFIGS, OPENCLIP_CONFIGS, CLIP_CONVNEXT_CONFIGS):
         if clip_model_name in table:
             return table[clip_model_name], CLIP_TEXT_CONFIGS.get(clip_model_name)
     raise KeyError(f"unknown / unsupported perceptor {clip_model_name!r} "
-                   f"(supported: {sorted(CLIP_CONFIGS) + sorted(OPENCLIP_CONFIGS) + sorted(CLIP_RESNET_CONFIGS) + sorted(SLIP_CONFIGS)})")
+                   f"(supported: {sorted(CLIP_CONFIGS) + sorted(OPENCLIP_CONFIGS) + sorted(CLIP_CONVNEXT_CONFIGS) + sorted(CLIP_RESNET_CONFIGS) + sorted(SLIP_CONFIGS)})")
 
 
 def get_clip_perceptor(clip_model_name, device, params=None, max_batch=64, seed=0, group=None, text_params=None,
@@ -169,6 +173,12 @@ def get_clip_perceptor(clip_model_name, device, params=None, max_batch=64, seed=
     if clip_model_name in CLIP_RESNET_CONFIGS:
         if params is None:
             params = synthetic_clip_resnet_params(cfg, seed)
+        return ClipVitPerceptor(cfg, params, device, max_batch=max_batch, group=group, text_cfg=text_cfg,
+                                text_params=text_params, tokenizer=tokenizer, seed=seed, precision=precision)
+    if clip_model_name in CLIP_CONVNEXT_CONFIGS:
+        if params is None:              # no checkpoint exists offline: seeded random weights of the real architecture
+            print(f"perceptor {clip_model_name}: no checkpoint given, using seeded synthetic weights")
+            params = synthetic_clip_convnext_params(cfg, seed)
         return ClipVitPerceptor(cfg, params, device, max_batch=max_batch, group=group, text_cfg=text_cfg,
                                 text_params=text_params, tokenizer=tokenizer, seed=seed, precision=precision)
     if clip_model_name in SLIP_CONFIGS:           # slip.py:183-184: every name that is not an OpenAI CLIP model is a SLIP_Base

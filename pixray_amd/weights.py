@@ -613,6 +613,171 @@ def fold_clip_resnet_params(cfg: ClipResNetConfig, p) -> "OrderedDict[str, torch
     return out
 
 
+# --------------------------------------------------------------------------- OpenCLIP ConvNeXt towers (LAION)
+# [UPSTREAM mlfoundations/open_clip src/open_clip/model_configs/convnext_*.json and timm convnext.py (convnext_base, convnext_large,
+# convnext_xxlarge); neither package is installed, so the geometry is restated from the published configs and sources, parity
+# unpinned].  The trunk under `visual.trunk.`: stem.0 = Conv2d(3, d0, 4, stride 4) with a bias, stem.1 = LayerNorm over the channels;
+# per stage i > 0 `stages.i.downsample.0` = LayerNorm, `.1` = Conv2d(d(i-1), d(i), 2, stride 2) with a bias; per block conv_dw
+# (depthwise 7x7, padding 3, bias), norm (LayerNorm), mlp.fc1 (C -> 4C), the exact GELU, mlp.fc2 (4C -> C), a multiply by gamma[C] and
+# the addition of the block input; then the mean over H x W, head.norm (LayerNorm) and, under `visual.head.`, the projection:
+# `linear`: proj.weight [embed, d3] without a bias; `mlp`: mlp.fc1 {weight [2 embed, d3], bias}, GELU, mlp.fc2.weight [embed, 2 embed]
+# without a bias.  Every LayerNorm has eps 1e-6 except convnext_xxlarge's 1e-5; CLIP's preprocessing constants; the text side is
+# CLIP's transformer with the exact GELU (OpenClipTextConfig).
+@dataclass
+class ClipConvNextConfig:
+    name: str = "convnext_base_w"
+    input_resolution: int = 256
+    depths: Tuple[int, ...] = (3, 3, 27, 3)
+    dims: Tuple[int, ...] = (128, 256, 512, 1024)
+    output_dim: int = 640
+    proj: str = "linear"            # "linear" | "mlp"
+    ln_eps: float = 1e-6
+
+
+CLIP_CONVNEXT_CONFIGS = {
+    "convnext_base": ClipConvNextConfig("convnext_base", 224, (3, 3, 27, 3), (128, 256, 512, 1024), 512, "linear"),
+    "convnext_base_w": ClipConvNextConfig("convnext_base_w", 256, (3, 3, 27, 3), (128, 256, 512, 1024), 640, "linear"),
+    "convnext_base_w_320": ClipConvNextConfig("convnext_base_w_320", 320, (3, 3, 27, 3), (128, 256, 512, 1024), 640, "linear"),
+    "convnext_large_d": ClipConvNextConfig("convnext_large_d", 256, (3, 3, 27, 3), (192, 384, 768, 1536), 768, "mlp"),
+    "convnext_large_d_320": ClipConvNextConfig("convnext_large_d_320", 320, (3, 3, 27, 3), (192, 384, 768, 1536), 768, "mlp"),
+    "convnext_xxlarge": ClipConvNextConfig("convnext_xxlarge", 256, (3, 4, 30, 3), (384, 768, 1536, 3072), 1024, "linear", 1e-5),
+    # reduced towers with the same operators: maps 16 / 8 / 4 / 2 and 24 / 12 / 6 / 3 -- the last ones smaller than the 7x7 filter
+    "tiny-cnx": ClipConvNextConfig("tiny-cnx", 64, (1, 1, 2, 1), (64, 128, 256, 512), 128, "linear"),
+    "tiny-cnx-d": ClipConvNextConfig("tiny-cnx-d", 96, (1, 1, 1, 1), (96, 192, 384, 768), 128, "mlp"),
+}
+CLIP_TEXT_CONFIGS.update({
+    "convnext_base": OpenClipTextConfig("convnext_base"),
+    "convnext_base_w": OpenClipTextConfig("convnext_base_w", width=640, heads=10, output_dim=640),
+    "convnext_base_w_320": OpenClipTextConfig("convnext_base_w_320", width=640, heads=10, output_dim=640),
+    "convnext_large_d": OpenClipTextConfig("convnext_large_d", width=768, layers=16, heads=12, output_dim=768),
+    "convnext_large_d_320": OpenClipTextConfig("convnext_large_d_320", width=768, layers=16, heads=12, output_dim=768),
+    "convnext_xxlarge": OpenClipTextConfig("convnext_xxlarge", width=1024, layers=24, heads=16, output_dim=1024),
+    "tiny-cnx": OpenClipTextConfig("tiny-cnx", vocab_size=1000, context_length=77, width=256, layers=2, heads=4, output_dim=128),
+    "tiny-cnx-d": OpenClipTextConfig("tiny-cnx-d", vocab_size=1000, context_length=77, width=256, layers=2, heads=4, output_dim=128),
+})
+CONVNEXT_SEED = 611953
+# Synthetic-weight scales (no checkpoint exists offline).  The layer scale gamma is drawn with a spread of order 1 around
+# CONVNEXT_GAMMA_MEAN -- not timm's 1e-6 initialisation, under which every block would be the identity and the tests blind.  With
+# unit-variance LayerNorm outputs and fc1 at std 1/sqrt(C) the pre-activations are N(0, 1) and E[gelu^2] = 0.425; fc2 at std
+# CONVNEXT_FC2_STD/sqrt(4C) and the layer scale then add 0.425 * CONVNEXT_FC2_STD^2 * (mean^2 + spread^2) = 0.053 of variance per
+# block to a stream of variance about 1: x 6.5 in variance (x 2.5 in magnitude) over the 36 blocks of the deepest tower -- far inside
+# IEEE half's range, and every block still moves the stream by a fifth of its size.
+CONVNEXT_GAMMA_MEAN, CONVNEXT_GAMMA_SPREAD, CONVNEXT_FC2_STD = 0.5, 0.5, 0.5
+
+
+def clip_convnext_param_shapes(cfg: ClipConvNextConfig) -> "OrderedDict[str, Tuple[int, ...]]":
+    """open_clip `visual.*` state-dict names of a ConvNeXt tower (prefix stripped), in definition order"""
+    sh: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    d = cfg.dims
+
+    def pair(name, c):
+        sh[name + ".weight"] = (c,); sh[name + ".bias"] = (c,)
+
+    sh["trunk.stem.0.weight"] = (d[0], 3, 4, 4); sh["trunk.stem.0.bias"] = (d[0],)
+    pair("trunk.stem.1", d[0])
+    for i in range(4):
+        if i > 0:
+            pair(f"trunk.stages.{i}.downsample.0", d[i - 1])
+            sh[f"trunk.stages.{i}.downsample.1.weight"] = (d[i], d[i - 1], 2, 2); sh[f"trunk.stages.{i}.downsample.1.bias"] = (d[i],)
+        for b in range(cfg.depths[i]):
+            p = f"trunk.stages.{i}.blocks.{b}."
+            sh[p + "gamma"] = (d[i],)
+            sh[p + "conv_dw.weight"] = (d[i], 1, 7, 7); sh[p + "conv_dw.bias"] = (d[i],)
+            pair(p + "norm", d[i])
+            sh[p + "mlp.fc1.weight"] = (4 * d[i], d[i]); sh[p + "mlp.fc1.bias"] = (4 * d[i],)
+            sh[p + "mlp.fc2.weight"] = (d[i], 4 * d[i]); sh[p + "mlp.fc2.bias"] = (d[i],)
+    pair("trunk.head.norm", d[3])
+    if cfg.proj == "linear":
+        sh["head.proj.weight"] = (cfg.output_dim, d[3])
+    elif cfg.proj == "mlp":
+        sh["head.mlp.fc1.weight"] = (2 * cfg.output_dim, d[3]); sh["head.mlp.fc1.bias"] = (2 * cfg.output_dim,)
+        sh["head.mlp.fc2.weight"] = (cfg.output_dim, 2 * cfg.output_dim)
+    else:
+        raise ValueError(f"ConvNeXt projection {cfg.proj!r}: want 'linear' or 'mlp'")
+    return sh
+
+
+def synthetic_clip_convnext_params(cfg: ClipConvNextConfig, seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
+    """Seeded random weights of the real architecture at the scales stated above (CONVNEXT_*)"""
+    g = torch.Generator().manual_seed(seed + CONVNEXT_SEED)
+    out: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    for name, shape in clip_convnext_param_shapes(cfg).items():
+        if name.endswith("gamma"):
+            t = CONVNEXT_GAMMA_MEAN + CONVNEXT_GAMMA_SPREAD * torch.randn(shape, generator=g)
+        elif len(shape) == 4:                                    # stem, downsample, depthwise: fan-in scaled
+            t = torch.randn(shape, generator=g) / math.sqrt(shape[1] * shape[2] * shape[3])
+        elif name.endswith("fc2.weight") and ".blocks." in name:
+            t = torch.randn(shape, generator=g) * (CONVNEXT_FC2_STD / math.sqrt(shape[1]))
+        elif len(shape) == 2:                                    # fc1, head projections
+            t = torch.randn(shape, generator=g) / math.sqrt(shape[1])
+        elif name.endswith(".weight"):                           # LayerNorm gamma
+            t = 1.0 + 0.05 * torch.randn(shape, generator=g)
+        else:                                                    # biases / LayerNorm beta
+            t = 0.02 * torch.randn(shape, generator=g)
+        out[name] = t
+    return out
+
+
+def fold_clip_convnext_params(cfg: ClipConvNextConfig, p) -> "OrderedDict[str, torch.Tensor]":
+    """The tensors prx_clip_convnext_create expects, in its order (include/prx.h).  The layer scale is folded into fc2 --
+    W2' = diag(gamma) W2, b2' = gamma * b2: the weights are frozen, so the fold is exact for values and data gradients and the engine
+    needs no per-column scale.  The convolutions become matrices: the stem [d0, 3*4*4] in patchify's column order (c, py, px), the
+    downsamples [d(i), 4 d(i-1)] in space-to-depth's ((dy, dx), c), the depthwise filters [C, 49]."""
+    out: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    d = cfg.dims
+
+    def keep(key, name):
+        out[key] = p[name].float()
+
+    out["stem.weight"] = p["trunk.stem.0.weight"].float().reshape(d[0], 48)
+    keep("stem.bias", "trunk.stem.0.bias"); keep("stem.ln.weight", "trunk.stem.1.weight"); keep("stem.ln.bias", "trunk.stem.1.bias")
+    for i in range(4):
+        s = f"trunk.stages.{i}."
+        if i > 0:
+            keep(f"stages.{i}.ds.ln.weight", s + "downsample.0.weight"); keep(f"stages.{i}.ds.ln.bias", s + "downsample.0.bias")
+            out[f"stages.{i}.ds.weight"] = p[s + "downsample.1.weight"].float().permute(0, 2, 3, 1).reshape(d[i], 4 * d[i - 1]).contiguous()
+            keep(f"stages.{i}.ds.bias", s + "downsample.1.bias")
+        for b in range(cfg.depths[i]):
+            q, k = f"{s}blocks.{b}.", f"stages.{i}.blocks.{b}."
+            out[k + "dw.weight"] = p[q + "conv_dw.weight"].float().reshape(d[i], 49)
+            keep(k + "dw.bias", q + "conv_dw.bias"); keep(k + "ln.weight", q + "norm.weight"); keep(k + "ln.bias", q + "norm.bias")
+            keep(k + "fc1.weight", q + "mlp.fc1.weight"); keep(k + "fc1.bias", q + "mlp.fc1.bias")
+            gamma = p[q + "gamma"].double()
+            out[k + "fc2.weight"] = (gamma.view(-1, 1) * p[q + "mlp.fc2.weight"].double()).float()
+            out[k + "fc2.bias"] = (gamma * p[q + "mlp.fc2.bias"].double()).float()
+    keep("head.ln.weight", "trunk.head.norm.weight"); keep("head.ln.bias", "trunk.head.norm.bias")
+    if cfg.proj == "linear":
+        keep("head.proj.weight", "head.proj.weight")
+    else:
+        keep("head.fc1.weight", "head.mlp.fc1.weight"); keep("head.fc1.bias", "head.mlp.fc1.bias"); keep("head.fc2.weight", "head.mlp.fc2.weight")
+    return out
+
+
+def clip_convnext_activation_bytes(cfg: ClipConvNextConfig, precision: str = "fp16") -> int:
+    """Device bytes per cutout of `max_batch` that prx_clip_convnext_create allocates beside the packed weights (csrc/convnext.hip):
+    per block the GELU pre-activation [pixels][4C] and the stencil output [pixels][C] in the operand format with two fp32 statistics
+    per pixel; per stage two fp32 stream buffers (and two operand twins in the 16-bit modes) and the downsample's statistics; the
+    stem's patch matrix, product and their gradients; the backward's workspace sized by the largest map."""
+    f32 = precision == "f32"
+    op = 4 if f32 else 2
+    g0 = cfg.input_resolution // 4
+    total, emax = 0, 0
+    for i in range(4):
+        m = (g0 >> i) ** 2
+        e = m * cfg.dims[i]
+        emax = max(emax, e)
+        total += 2 * e * 4 + (0 if f32 else 2 * e * op)
+        if i > 0:
+            total += 2 * 4 * m * 4
+        total += cfg.depths[i] * (5 * e * op + 2 * m * 4)
+    t = g0 * g0 + 1
+    total += t * 48 * op + t * cfg.dims[0] * 4 + t * 48 * 4 + t * cfg.dims[0] * op + 2 * t * 4
+    total += emax * op * (1 + 4 + 4 + 1) + 3 * emax * 4 + (0 if f32 else emax * op)
+    d3, e_ = cfg.dims[3], cfg.output_dim
+    total += 3 * d3 * 4 + 2 * 4 + d3 * op + 3 * 2 * e_ * op + e_ * op + 2 * e_ * 4
+    return total
+
+
 # ------------------------------------------------------------------------------------------ VGG16 (StyleLoss plugin)
 VGG16_CFG = (64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512)   # torchvision cfg "D" to relu5_3
 

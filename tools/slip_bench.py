@@ -37,7 +37,8 @@ def time_tower(name, n, iters, warmup, precision):
     launch stream, so host launch overhead that the device does not hide is part of the figure"""
     perc = get_clip_perceptor(name, "cuda", max_batch=n, precision=precision)
     g = torch.Generator().manual_seed(1)
-    cut = torch.rand(n, 3, 224, 224, generator=g).cuda().requires_grad_(True)
+    R = perc.input_resolution             # 224 for the ViT towers; --towers also takes the ConvNeXt names (256, 320: tools/convnext_bench.py)
+    cut = torch.rand(n, 3, R, R, generator=g).cuda().requires_grad_(True)
     gout = torch.randn(n, perc.output_dim, generator=g).cuda()
     times = []
     for it in range(warmup + iters):
