@@ -407,6 +407,26 @@ void prx_fft_drawer_destroy(prx_fft_drawer* h);
 int prx_fft_drawer_freq_columns(const prx_fft_drawer* h);
 int prx_fft_drawer_synth(prx_fft_drawer* h, const float* params, float contrast, float* image, prx_stream_t stream);
 int prx_fft_drawer_backward(prx_fft_drawer* h, const float* g_image, float* g_params, prx_stream_t stream);
+/* Test surface.  Read-only copy of one of the handle's tables into a device buffer of exactly its size, fp32:
+ *   0 scale [H][Wh]   1 A1 [W][K1p]   2 A1T [K1p][WP]   3 T2 [H][HP2]   4 T2T [HP2][HP]   5 colour matrix [c][d]
+ * with Wh = W/2 + 1 and the padded strides HP = up4(H), HP2 = up4(2 H), WP = up4(W), K1p = up4(2 Wh) (up4: next multiple of 4). */
+int prx_fft_drawer_table(const prx_fft_drawer* h, int which, float* dst, size_t dst_elems, prx_stream_t stream);
+/* The drawer's kernels one at a time, through the launchers synth / backward call (csrc/fft_drawer.h), for a W x H canvas:
+ *   pack:     params [3][H][Wf][2], scale [H][Wh] -> bt1 [3 HP2][K1p] (both copies of the spectrum, (re, im) and i * it, times scale)
+ *   unpack:   dP [3 HP2][K1p], scale -> g_params [3][H][Wf][2] (the adjoint of pack)
+ *   moments:  acc[0..2] = sum x, sum x^2, sum x y (y may be null: 0) over n elements, in double and in a fixed order;
+ *             part: scratch of 3 * min(ceil(n / 256), 1024) doubles
+ *   tail_fwd: x [3][H][W], acc = moments(x) -> rgb [3][H][W] = sigmoid(cm^T (contrast / std) x), std unbiased over all of x
+ *   tail_bwd_gy: g = d/d(rgb) -> gy = d/d(contrast / std * x) [3][H][W]
+ *   tail_bwd_dx: bacc = moments(gy, x) -> dxT [3][W][HP] = d/dx, transposed, rows zero padded to HP */
+int prx_k_fft_pack(const float* params, const float* scale, float* bt1, int W, int H, prx_stream_t s);
+int prx_k_fft_unpack(const float* dP, const float* scale, float* g_params, int W, int H, prx_stream_t s);
+int prx_k_fft_moments(const float* x, const float* y, size_t n, double* part, double* acc, prx_stream_t s);
+int prx_k_fft_tail_fwd(const float* x, const double* acc, float contrast, const float* cm, float* rgb, int W, int H, prx_stream_t s);
+int prx_k_fft_tail_bwd_gy(const float* x, const float* g, const double* acc, float contrast, const float* cm, float* gy, int W, int H,
+                          prx_stream_t s);
+int prx_k_fft_tail_bwd_dx(const float* x, const float* gy, const double* acc, const double* bacc, float contrast, float* dxT, int W, int H,
+                          prx_stream_t s);
 
 /* --- SuperResolutionDrawer.synth (super_resolution.py:34-102): clamp_with_grad(RRDBNet(z), 0, 1), the RealESRGAN x4 network
  * [UPSTREAM basicsr/archs/rrdbnet_arch.py] with the drawer's arguments (scale 4, no tiling, no padding, fp32), and its data

@@ -17,6 +17,7 @@
 #include "prompt_vq.h"
 #include "vqgan.h"
 #include "vqgan_enc.h"
+#include "fft_drawer.h"
 #include "../../include/prx.h"
 
 #define S_(x) ((hipStream_t)(x))
@@ -364,6 +365,28 @@ int prx_k_vqgan_enc_pack_conv3x3(const float* w, void* Wf, int Cout, int Cin, in
 }
 int prx_k_colminmax(const float* w, float* mn, float* mx, int rows, int D, prx_stream_t s) {
     return prx_colminmax(w, mn, mx, rows, D, S_(s));
+}
+
+// ---- the fft drawer's kernels (fft_drawer.hip), through the launchers prx_fft_drawer_synth / _backward call
+int prx_k_fft_pack(const float* params, const float* scale, float* bt1, int W, int H, prx_stream_t s) {
+    return prx_fft_pack(params, scale, bt1, W, H, S_(s));
+}
+int prx_k_fft_unpack(const float* dP, const float* scale, float* g_params, int W, int H, prx_stream_t s) {
+    return prx_fft_unpack(dP, scale, g_params, W, H, S_(s));
+}
+int prx_k_fft_moments(const float* x, const float* y, size_t n, double* part, double* acc, prx_stream_t s) {
+    return prx_fft_moments(x, y, n, part, acc, S_(s));
+}
+int prx_k_fft_tail_fwd(const float* x, const double* acc, float contrast, const float* cm, float* rgb, int W, int H, prx_stream_t s) {
+    return prx_fft_tail_fwd(x, acc, contrast, cm, rgb, W, H, S_(s));
+}
+int prx_k_fft_tail_bwd_gy(const float* x, const float* g, const double* acc, float contrast, const float* cm, float* gy, int W, int H,
+                          prx_stream_t s) {
+    return prx_fft_tail_bwd_gy(x, g, acc, contrast, cm, gy, W, H, S_(s));
+}
+int prx_k_fft_tail_bwd_dx(const float* x, const float* gy, const double* acc, const double* bacc, float contrast, float* dxT, int W, int H,
+                          prx_stream_t s) {
+    return prx_fft_tail_bwd_dx(x, gy, acc, bacc, contrast, dxT, W, H, S_(s));
 }
 
 }  // extern "C"

@@ -23,6 +23,7 @@
 // copies of the spectrum and the scale back into d(spectrum).
 // Every row stride is padded to 4 floats (the engine's 16-byte operand chunks); padding columns of the operands are zero.
 #include "gemm.h"
+#include "fft_drawer.h"
 #include "../../include/prx.h"
 #include <algorithm>
 #include <cmath>
@@ -31,9 +32,6 @@
 #include "dev_arena.h"
 
 namespace {
-inline int up4(int v) { return (v + 3) & ~3; }
-inline int fgrid(size_t total) { return (int)std::min<size_t>((total + 255) / 256, 8192); }
-
 // params [3][H][Wf][2] (Wf >= Wh columns; the surplus one of an odd width is ignored) -> Bt1 [3 * HP2][K1p], zero padded
 __global__ __launch_bounds__(256) void fft_pack_kernel(const float* __restrict__ prm, const float* __restrict__ scale, float* __restrict__ bt1,
                                                        int H, int Wf, int Wh, int HP2, int K1p) {
@@ -56,7 +54,7 @@ __global__ __launch_bounds__(256) void fft_pack_kernel(const float* __restrict__
 // Moments in float64 with a FIXED summation order (the image's std scales every pixel and every gradient entry: the drawer is
 // bit-reproducible run to run, like the rest of the path): every block writes its three partial sums, one block adds them up
 // part[b][0] = sum x, part[b][1] = sum x^2, part[b][2] = sum x * y (when y is given) over block b's grid-stride share
-constexpr int FFT_MOM_BLOCKS = 1024;
+// (at most FFT_MOM_BLOCKS blocks: fft_drawer.h)
 __global__ __launch_bounds__(256) void fft_moments_kernel(const float* __restrict__ x, const float* __restrict__ y, size_t n, double* __restrict__ part) {
     __shared__ double red[3][4];
     double s0 = 0.0, s1 = 0.0, s2 = 0.0;
@@ -117,7 +115,7 @@ __global__ __launch_bounds__(256) void fft_tail_fwd_kernel(const float* __restri
     }
 }
 
-// pass 1 of the tail backward: gy_c = sum_d g_d s_d (1 - s_d) M[c][d] (s recomputed from x), stored
+// pass 1 of the tail backward: gy_c = sum_d g_d s_d (1 - s_d) M[c][d] (s recomputed from x; 1 - s_d kept to relative accuracy), stored
 __global__ __launch_bounds__(256) void fft_tail_bwd_gy_kernel(const float* __restrict__ x, const float* __restrict__ g, const double* __restrict__ acc,
                                                               float contrast, const float* __restrict__ cm, float* __restrict__ gy, size_t P) {
     const FftStd st = fft_std(acc, 3 * P);
@@ -131,8 +129,11 @@ __global__ __launch_bounds__(256) void fft_tail_bwd_gy_kernel(const float* __res
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
             const float z = y0 * m[d] + y1 * m[3 + d] + y2 * m[6 + d];
-            const float s = 1.f / (1.f + __expf(-z));
-            gz[d] = g[d * P + i] * s * (1.f - s);
+            const float e = __expf(-z);
+            const float s = 1.f / (1.f + e);
+            // 1 - s = e s: above z = 0 the subtraction would leave 1 - s with the absolute rounding of s (nothing of it by z = 17, where
+            // a DC-heavy spectrum puts every pixel); below, e may be inf and 1 - s is exact
+            gz[d] = g[d * P + i] * s * (z > 0.f ? e * s : 1.f - s);
         }
 #pragma unroll
         for (int c = 0; c < 3; ++c) gy[c * P + i] = gz[0] * m[3 * c] + gz[1] * m[3 * c + 1] + gz[2] * m[3 * c + 2];
@@ -183,6 +184,69 @@ __global__ __launch_bounds__(256) void fft_unpack_kernel(const float* __restrict
 }
 }  // namespace
 
+// ---- host launchers (fft_drawer.h): the drawer below and the prx_k_fft_* entries of api_kernels.hip both go through these
+#define FFT_CANVAS(what) PRX_REQUIRE(W >= 2 && H >= 2, "fft " what ": canvas %d x %d too small", W, H)
+
+int prx_fft_pack(const float* params, const float* scale, float* bt1, int W, int H, hipStream_t s) {
+    PRX_REQUIRE(params && scale && bt1, "fft pack: null argument");
+    FFT_CANVAS("pack");
+    const FftGeom g = fft_geom(W, H);
+    hipLaunchKernelGGL(fft_pack_kernel, dim3(fft_grid((size_t)3 * g.HP2 * g.K1p)), dim3(256), 0, s, params, scale, bt1, H, g.Wf, g.Wh, g.HP2,
+                       g.K1p);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+
+int prx_fft_unpack(const float* dP, const float* scale, float* g_params, int W, int H, hipStream_t s) {
+    PRX_REQUIRE(dP && scale && g_params, "fft unpack: null argument");
+    FFT_CANVAS("unpack");
+    const FftGeom g = fft_geom(W, H);
+    hipLaunchKernelGGL(fft_unpack_kernel, dim3(fft_grid((size_t)3 * H * g.Wf)), dim3(256), 0, s, dP, scale, g_params, H, g.Wf, g.Wh, g.HP2,
+                       g.K1p);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+
+int prx_fft_moments(const float* x, const float* y, size_t n, double* part, double* acc, hipStream_t s) {
+    PRX_REQUIRE(x && part && acc, "fft moments: null argument");
+    PRX_REQUIRE(n >= 1, "fft moments: no elements");
+    const int mb = fft_moment_blocks(n);
+    hipLaunchKernelGGL(fft_moments_kernel, dim3(mb), dim3(256), 0, s, x, y, n, part);
+    PRX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(fft_moments_final_kernel, dim3(1), dim3(256), 0, s, part, mb, acc);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+
+int prx_fft_tail_fwd(const float* x, const double* acc, float contrast, const float* cm, float* rgb, int W, int H, hipStream_t s) {
+    PRX_REQUIRE(x && acc && cm && rgb, "fft tail forward: null argument");
+    FFT_CANVAS("tail forward");
+    const size_t P = (size_t)H * W;
+    hipLaunchKernelGGL(fft_tail_fwd_kernel, dim3(fft_grid(P)), dim3(256), 0, s, x, acc, contrast, cm, rgb, P);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+
+int prx_fft_tail_bwd_gy(const float* x, const float* g, const double* acc, float contrast, const float* cm, float* gy, int W, int H,
+                        hipStream_t s) {
+    PRX_REQUIRE(x && g && acc && cm && gy, "fft tail backward (gy): null argument");
+    FFT_CANVAS("tail backward (gy)");
+    const size_t P = (size_t)H * W;
+    hipLaunchKernelGGL(fft_tail_bwd_gy_kernel, dim3(fft_grid(P)), dim3(256), 0, s, x, g, acc, contrast, cm, gy, P);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+
+int prx_fft_tail_bwd_dx(const float* x, const float* gy, const double* acc, const double* bacc, float contrast, float* dxT, int W, int H,
+                        hipStream_t s) {
+    PRX_REQUIRE(x && gy && acc && bacc && dxT, "fft tail backward (dx): null argument");
+    FFT_CANVAS("tail backward (dx)");
+    const int HP = fft_geom(W, H).HP;
+    hipLaunchKernelGGL(fft_tail_bwd_dx_kernel, dim3(fft_grid((size_t)3 * W * HP)), dim3(256), 0, s, x, gy, acc, bacc, contrast, dxT, H, W, HP);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+
 struct prx_fft_drawer {
     int W, H, Wf, Wh, HP, HP2, WP, K1p;
     float* scale = nullptr;      // [H][Wh]
@@ -223,10 +287,11 @@ int gemm_f32(prx_fft_drawer* h, const float* A, int lda, const float* B, int ldb
 // the twiddle matrices, the colour matrix and every buffer of one canvas size
 int fft_build(prx_fft_drawer* h, int W, int H, float decay, float colors) {
     h->mem.describe("fft drawer", ": the drawer keeps its twiddle matrices and one synth's buffers for a %d x %d canvas", W, H);
+    const FftGeom geo = fft_geom(W, H);
     h->W = W; h->H = H;
-    h->Wh = W / 2 + 1;
-    h->Wf = W / 2 + (W % 2 ? 2 : 1);        // the lucid frequency helper keeps one surplus column for an odd width
-    h->HP = up4(H); h->HP2 = up4(2 * H); h->WP = up4(W); h->K1p = up4(2 * h->Wh);
+    h->Wh = geo.Wh;
+    h->Wf = geo.Wf;                         // the lucid frequency helper keeps one surplus column for an odd width
+    h->HP = geo.HP; h->HP2 = geo.HP2; h->WP = geo.WP; h->K1p = geo.K1p;
     const int Wh = h->Wh, HP = h->HP, HP2 = h->HP2, WP = h->WP, K1p = h->K1p;
     const double two_pi = 6.283185307179586476925286766559;
     // scale[u][v] = sqrt(W H) / max(|f|, 1 / max(W, H)) ^ decay
@@ -299,22 +364,16 @@ int prx_fft_drawer_synth(prx_fft_drawer* h, const float* params, float contrast,
     const int W = h->W, H = h->H, HP2 = h->HP2, K1p = h->K1p;
     const size_t P = (size_t)H * W;
     h->contrast = contrast;
-    hipLaunchKernelGGL(fft_pack_kernel, dim3(fgrid((size_t)3 * HP2 * K1p)), dim3(256), 0, s, params, h->scale, h->bt1, H, h->Wf, h->Wh, HP2, K1p);
-    PRX_LAUNCH_CHECK();
-    int rc = gemm_f32(h, h->A1, K1p, h->bt1, K1p, W, 3 * HP2, K1p, h->c1, 3 * HP2, s);
+    int rc = prx_fft_pack(params, h->scale, h->bt1, W, H, s);
+    if (rc) return rc;
+    rc = gemm_f32(h, h->A1, K1p, h->bt1, K1p, W, 3 * HP2, K1p, h->c1, 3 * HP2, s);
     if (rc) return rc;
     for (int c = 0; c < 3; ++c) {
         rc = gemm_f32(h, h->T2, HP2, h->c1 + (size_t)c * HP2, 3 * HP2, H, W, HP2, h->x + (size_t)c * P, W, s);
         if (rc) return rc;
     }
-    const int mb = std::min(fgrid(3 * P), FFT_MOM_BLOCKS);
-    hipLaunchKernelGGL(fft_moments_kernel, dim3(mb), dim3(256), 0, s, h->x, (const float*)nullptr, 3 * P, h->acc + 6);
-    PRX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(fft_moments_final_kernel, dim3(1), dim3(256), 0, s, h->acc + 6, mb, h->acc);
-    PRX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(fft_tail_fwd_kernel, dim3(fgrid(P)), dim3(256), 0, s, h->x, h->acc, contrast, h->cm, image, P);
-    PRX_LAUNCH_CHECK();
-    return 0;
+    if ((rc = prx_fft_moments(h->x, nullptr, 3 * P, h->acc + 6, h->acc, s))) return rc;
+    return prx_fft_tail_fwd(h->x, h->acc, contrast, h->cm, image, W, H, s);
 }
 
 int prx_fft_drawer_backward(prx_fft_drawer* h, const float* g_image, float* g_params, prx_stream_t stream) {
@@ -322,24 +381,27 @@ int prx_fft_drawer_backward(prx_fft_drawer* h, const float* g_image, float* g_pa
     hipStream_t s = (hipStream_t)stream;
     const int W = h->W, H = h->H, HP = h->HP, HP2 = h->HP2, WP = h->WP, K1p = h->K1p;
     const size_t P = (size_t)H * W;
-    hipLaunchKernelGGL(fft_tail_bwd_gy_kernel, dim3(fgrid(P)), dim3(256), 0, s, h->x, g_image, h->acc, h->contrast, h->cm, h->gy, P);
-    PRX_LAUNCH_CHECK();
-    const int mb = std::min(fgrid(3 * P), FFT_MOM_BLOCKS);
-    hipLaunchKernelGGL(fft_moments_kernel, dim3(mb), dim3(256), 0, s, h->gy, h->x, 3 * P, h->acc + 6);
-    PRX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(fft_moments_final_kernel, dim3(1), dim3(256), 0, s, h->acc + 6, mb, h->acc + 3);
-    PRX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(fft_tail_bwd_dx_kernel, dim3(fgrid((size_t)3 * W * HP)), dim3(256), 0, s, h->x, h->gy, h->acc, h->acc + 3, h->contrast,
-                       h->dxT, H, W, HP);
-    PRX_LAUNCH_CHECK();
+    int rc = prx_fft_tail_bwd_gy(h->x, g_image, h->acc, h->contrast, h->cm, h->gy, W, H, s);
+    if (rc) return rc;
+    if ((rc = prx_fft_moments(h->gy, h->x, 3 * P, h->acc + 6, h->acc + 3, s))) return rc;
+    if ((rc = prx_fft_tail_bwd_dx(h->x, h->gy, h->acc, h->acc + 3, h->contrast, h->dxT, W, H, s))) return rc;
     for (int c = 0; c < 3; ++c) {        // dC1T[(c,k)][w] = sum_h T2T[k][h] dxT_c[w][h]
-        int rc = gemm_f32(h, h->T2T, HP, h->dxT + (size_t)c * W * HP, HP, 2 * H, W, HP, h->dc1t + (size_t)c * HP2 * WP, WP, s);
+        rc = gemm_f32(h, h->T2T, HP, h->dxT + (size_t)c * W * HP, HP, 2 * H, W, HP, h->dc1t + (size_t)c * HP2 * WP, WP, s);
         if (rc) return rc;
     }
-    int rc = gemm_f32(h, h->dc1t, WP, h->A1T, WP, 3 * HP2, K1p, WP, h->dP, K1p, s);      // dBt1[n][kk] = sum_w dC1T[n][w] A1T[kk][w]
+    rc = gemm_f32(h, h->dc1t, WP, h->A1T, WP, 3 * HP2, K1p, WP, h->dP, K1p, s);          // dBt1[n][kk] = sum_w dC1T[n][w] A1T[kk][w]
     if (rc) return rc;
-    hipLaunchKernelGGL(fft_unpack_kernel, dim3(fgrid((size_t)3 * H * h->Wf)), dim3(256), 0, s, h->dP, h->scale, g_params, H, h->Wf, h->Wh, HP2, K1p);
-    PRX_LAUNCH_CHECK();
+    return prx_fft_unpack(h->dP, h->scale, g_params, W, H, s);
+}
+
+int prx_fft_drawer_table(const prx_fft_drawer* h, int which, float* dst, size_t dst_elems, prx_stream_t stream) {
+    PRX_REQUIRE(h && dst, "fft drawer table: null argument");
+    const float* src[6] = {h->scale, h->A1, h->A1T, h->T2, h->T2T, h->cm};
+    const size_t n[6] = {(size_t)h->H * h->Wh, (size_t)h->W * h->K1p, (size_t)h->K1p * h->WP, (size_t)h->H * h->HP2,
+                         (size_t)h->HP2 * h->HP, 9};
+    PRX_REQUIRE(which >= 0 && which < 6, "fft drawer table: no table %d (0 .. 5)", which);
+    PRX_REQUIRE(dst_elems == n[which], "fft drawer table %d: %zu elements, not %zu", which, n[which], dst_elems);
+    PRX_CHECK_HIP(hipMemcpyAsync(dst, src[which], n[which] * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 

@@ -92,6 +92,8 @@ class FftDrawer(DrawingInterface):
             logit = torch.log(x) - torch.log1p(-x)
             dec = torch.einsum("ndhw,dc->nchw", logit, torch.linalg.inv(color_matrix(1.5)))
             spec = torch.view_as_real(torch.fft.rfftn(dec, s=(h, w), dim=(-2, -1), norm="ortho"))
+            # rfftn has w // 2 + 1 columns; the drawer's layout keeps one surplus column for an odd width (never read: zero)
+            spec = torch.nn.functional.pad(spec, (0, 0, 0, freqs.shape[1] - spec.shape[-2]))
             spectrum = spec / self._scale.cpu()
         self.params = [spectrum.to(self.device).requires_grad_(True)]
 

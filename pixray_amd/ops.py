@@ -903,6 +903,7 @@ class FftDrawerHandle(_Handle):
             raise PrxError("prx_fft_drawer_create failed: " + _lib.last_error())
         self.width, self.height = int(width), int(height)
         self.freq_columns = lib.prx_fft_drawer_freq_columns(self.h)
+        self.ticket = 0            # counts the synths: the handle keeps the state of the latest one only
 
 
 class _FftSynthFn(torch.autograd.Function):
@@ -914,11 +915,15 @@ class _FftSynthFn(torch.autograd.Function):
             raise PrxError(f"fft drawer: spectrum {tuple(p.shape)} does not fit a {handle.width} x {handle.height} canvas")
         img = torch.empty(1, 3, handle.height, handle.width, device=p.device)
         call("prx_fft_drawer_synth", handle.h, p, float(contrast), img, _stream())
-        ctx.handle, ctx.shape = handle, p.shape
+        handle.ticket += 1
+        ctx.handle, ctx.shape, ctx.ticket = handle, p.shape, handle.ticket
         return img
 
     @staticmethod
     def backward(ctx, g):
+        if ctx.ticket != ctx.handle.ticket:
+            raise PrxError(f"fft drawer: stale backward -- this is the backward of synth {ctx.ticket} of its handle, which now holds "
+                           f"the state of synth {ctx.handle.ticket}; a handle differentiates its latest synth only")
         g = g.contiguous().float()
         gp = torch.empty(ctx.shape, device=g.device)
         call("prx_fft_drawer_backward", ctx.handle.h, g, gp, _stream())
@@ -926,7 +931,9 @@ class _FftSynthFn(torch.autograd.Function):
 
 
 def fft_synth(params: torch.Tensor, handle: FftDrawerHandle, contrast: float = 0.9) -> torch.Tensor:
-    """differentiable w.r.t. `params`; a backward differentiates the handle's LAST synth (one synth per backward, as the loop does)"""
+    """differentiable w.r.t. `params`; a backward differentiates the handle's LAST synth (one synth per backward, as the loop does):
+    each synth takes a ticket on its handle, and the backward of an earlier synth raises PrxError instead of returning the gradient of
+    another image.  Repeated backwards of the latest synth are fine."""
     return _FftSynthFn.apply(params, handle, contrast)
 
 

@@ -38,11 +38,12 @@ def emu():
         import test_kernels_strotss_gpu as ts
         import test_kernels_select_gpu as tsel
         import test_kernels_plugins_gpu as tplug
+        import test_kernels_fft_gpu as tfft
         import test_path_gpu as tp
-        for m in (tk, th, tr, tc, ts, tsel, tplug, tp):
+        for m in (tk, th, tr, tc, ts, tsel, tplug, tfft, tp):
             m.DEV = "cpu"
-        yield types_ns(lib=lib, tk=tk, th=th, tr=tr, tc=tc, ts=ts, tsel=tsel, tplug=tplug, tp=tp)
-        for m in (tk, th, tr, tc, ts, tsel, tplug, tp):
+        yield types_ns(lib=lib, tk=tk, th=th, tr=tr, tc=tc, ts=ts, tsel=tsel, tplug=tplug, tfft=tfft, tp=tp)
+        for m in (tk, th, tr, tc, ts, tsel, tplug, tfft, tp):
             m.DEV = "cuda"
 
 
@@ -349,6 +350,17 @@ def test_builtin_loss_blur_and_wallpaper_plugin_kernels_at_their_edges(emu):
     edge match, negative and oversized shifts; the launch-shape sweeps up to one element past the workgroup cap; the refusals"""
     figs = emu.tplug.emu_subset()
     for family in ("sat/", "sym/", "edge/", "edget/", "gauss/", "aes/", "blur/", "wall/", "sweep/"):
+        assert any(k.startswith(family) for k in figs), family
+
+
+def test_fft_drawer_kernels_tables_engine_geometry_and_whole_map_at_their_edges(emu):
+    """tests/test_kernels_fft_gpu.py on the emulated kernels, every check but the four cases one trip past the grid cap: the tables at
+    three decays and colour settings, pack and unpack with NaN planted where nothing may be read, the moments up to 2 * 262144 + 1
+    elements, the tail kernels at three contrasts, a mean of 0 / 10 / 100 standard deviations and a saturated sigmoid, the four GEMM
+    calls at the drawer's strides, the whole map at four settings, DC-heavy spectra, the odd-width init, the stale backward, the refusals"""
+    figs = emu.tfft.emu_subset()
+    for family in ("tab/", "pack/", "unpack/", "unpack-adjoint/", "mom/", "tail-fwd/", "tail-gy/", "tail-dx/", "engine/", "map-img/",
+                   "map-grad/"):
         assert any(k.startswith(family) for k in figs), family
 
 

@@ -246,6 +246,27 @@ def test_fft_drawer_plugin_runs_with_its_own_optimiser_cpu():
         bad = FftDrawer(_Settings(size=(32, 32), fft_use="dwt")); bad.load_model(None, "cpu"); bad.init_from_tensor(None)
 
 
+@pytest.mark.parametrize("size", [(45, 32), (7, 5)])
+def test_fft_drawer_starts_from_an_image_on_an_odd_width_canvas(size):
+    """rfftn gives W // 2 + 1 columns, the drawer's spectrum has W // 2 + 2 for an odd W: the image-derived spectrum gets the drawer's
+    own column count (one zero surplus column), through init_from_tensor and reapply_from_tensor; the even case's assertion"""
+    from pixray_amd.fft_drawer import FftDrawer
+    w, h = size
+    st = _Settings(size=size, fft_use="fft", fft_decay=1.5, fft_lrate=0.3)
+    dr = FftDrawer(st)
+    dr.load_model(st, "cpu")
+    t = torch.rand(1, 3, h, w, generator=torch.Generator().manual_seed(w))
+    for start in (dr.init_from_tensor, dr.reapply_from_tensor):
+        start(t * 2 - 1)
+        assert dr.params[0].shape == (1, 3, h, w // 2 + 2, 2) and dr.params[0].requires_grad
+        assert float(dr.params[0][..., -1, :].abs().max()) == 0.0
+        with torch.no_grad():
+            spec = torch.view_as_complex((dr._scale * dr.params[0]).contiguous())
+            rec = torch.sigmoid(torch.einsum("nchw,cd->ndhw", torch.fft.irfftn(spec, s=(h, w), dim=(-2, -1), norm="ortho"), dr._colors))
+        assert (rec - t.clamp(1e-3, 1 - 1e-3)).abs().max() < 1e-4
+    assert dr.synth(0).shape == (1, 3, h, w)
+
+
 # two loss plugins as a third party writes them for pixray: their own modules, importing the interface from pixray's module
 # layout (`Losses.LossInterface`), one scoring the cutouts (a list with one term per cutout table), one the image
 _CUTOUT_PLUGIN = """
