@@ -188,7 +188,7 @@ int prx_k_mha_fwd_gen_op(const void* qkv, void* out, float* lse, int N, int T, i
 int prx_k_mha_bwd_gen_op(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int N, int T, int C,
                          int heads, int h16, prx_stream_t s);
 /* prx_k_mha_{fwd,bwd}_gen_op with the operand columns per head as an argument.  head_cols 64: the two calls above, bit for bit.
- * head_cols 96: heads of dim 80 zero-padded to 96 columns (OpenCLIP ViT-H/14; csrc/attention_hd96.hip): C == heads * 96, head h at
+ * head_cols 96: heads of dim 80 zero-padded to 96 columns (OpenCLIP ViT-H/14; the 96-wide instances of csrc/attention_kernels.h): C == heads * 96, head h at
  * columns 96h .. 96h+95 of q, k, v, out and their gradients, the caller's columns 80 .. 95 of every head zero, softmax scale
  * 1 / sqrt(80), 1 <= T <= 640; columns 80 .. 95 of `out` and `dqkv` are written as exact zeros. */
 int prx_k_mha_fwd_hd_op(const void* qkv, void* out, float* lse, int N, int T, int C, int heads, int h16, int head_cols, prx_stream_t s);

@@ -157,7 +157,7 @@ int prx_k_mha_bwd_gen_op(const void* qkv, const void* out, const void* dout, con
                          int heads, int h16, prx_stream_t s) {
     return prx_mha_bwd_gen(CB_(qkv), CB_(out), CB_(dout), lse, B_(dqkv), N, T, C, heads, S_(s), h16);
 }
-// columns per head 64: the calls above; 96: head dim 80 zero-padded, softmax scale 1 / sqrt(80) (attention_hd96.hip)
+// columns per head 64: the calls above; 96: head dim 80 zero-padded, softmax scale 1 / sqrt(80) (the 96-wide instances of attention_kernels.h)
 int prx_k_mha_fwd_hd_op(const void* qkv, void* out, float* lse, int N, int T, int C, int heads, int h16, int head_cols, prx_stream_t s) {
     PRX_REQUIRE(head_cols == 64 || head_cols == 96, "mha_fwd_hd: %d columns per head (64 | 96)", head_cols);
     if (head_cols == 64) return prx_mha_fwd_gen(CB_(qkv), B_(out), lse, N, T, C, heads, S_(s), h16);

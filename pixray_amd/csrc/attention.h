@@ -15,7 +15,7 @@ int prx_mha_fwd_causal(const bf16_t* qkv, bf16_t* out, int N, int T, int C, int 
 int prx_mha_fwd_f32(const float* qkv, float* out, float* lse, int N, int T, int C, int heads, hipStream_t s);
 int prx_mha_bwd_f32(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int N, int T, int C,
                     int heads, hipStream_t s);
-// heads of 96 operand columns = head dim 80 zero-padded (attention_hd96.hip; OpenCLIP ViT-H/14): qkv [N*T, 3C] with head h at columns
+// heads of 96 operand columns = head dim 80 zero-padded (the 96-wide instances of attention_kernels.h; OpenCLIP ViT-H/14): qkv [N*T, 3C] with head h at columns
 // h*96.., C == heads * 96, 1 <= T <= 640, `scale` the softmax scale (1 / sqrt(80)); pad columns of out / dqkv come out as exact zeros
 int prx_mha_fwd_hd96(const bf16_t* qkv, bf16_t* out, float* lse, int N, int T, int C, int heads, float scale, hipStream_t s, int h16 = 0);
 int prx_mha_bwd_hd96(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, int N, int T, int C,

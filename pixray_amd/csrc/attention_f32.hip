@@ -10,7 +10,7 @@
 namespace {
 
 // Every kernel is templated on the head dim HD and on the head's column stride HS >= HD in qkv / out / dqkv: <64, 64> are the towers
-// with 64-wide heads, <80, 96> the towers whose 80-wide heads are zero-padded to 96 operand columns (attention_hd96.hip, vit.hip) --
+// with 64-wide heads, <80, 96> the towers whose 80-wide heads are zero-padded to 96 operand columns (attention_kernels.h, vit.hip) --
 // there the HS - HD pad columns are not read, and are written as zeros.
 constexpr int BT = 64;        // tokens per LDS block
 

@@ -12,7 +12,7 @@ struct VitFamily {
     int act, dact;      // PRX_ACT_* of the c_fc product and of its dgrad
     PatchNorm norm;     // channel mean / std of the fused preprocessing
     int head_dim;       // 0 / 64, or 32 / 16: narrower heads are zero-padded to 64 at weight-packing time (vit.hip PrxVit::hd);
-                        // 80: zero-padded to 96, the attention on the 96-wide family (attention_hd96.hip)
+                        // 80: zero-padded to 96, the attention on the 96-wide instances of attention_kernels.h
 };
 VitFamily prx_vit_family_clip();
 struct GemmCtx;

@@ -164,7 +164,7 @@ struct PrxVit {
     // backward (dQ_pad = dS K_pad, dK_pad = dS^T Q_pad, dV_pad = P^T dO_pad with dO_pad = dx Wo_pad^T = 0), so values and gradients
     // are those of the narrow heads; the price is 64 / head dim times the qkv, attention and out-projection work.
     // Heads of 80 (OpenCLIP ViT-H/14: 16 heads on width 1280) are padded the same way to hp = 96 columns and run on the 96-wide
-    // attention family (attention_hd96.hip), which takes the softmax scale 1 / sqrt(80) as an argument: nothing is folded into q.
+    // attention family (the 96-wide instances of attention_kernels.h), which takes the softmax scale 1 / sqrt(80) as an argument: nothing is folded into q.
     int hd, hp, aw;    // head dim of the weights; operand columns per head (64 | 96); attention width = heads * hp (== width when hd == 64)
     int prec;         // PRX_PREC_*: element type of every operand buffer below (void*)
     int f32, h16;     // derived: operands are fp32 / the 16-bit operand format is IEEE half

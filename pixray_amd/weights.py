@@ -276,7 +276,7 @@ def synthetic_clip_vit_params(cfg: ClipVitConfig, seed: int = 0) -> "OrderedDict
 # installed, so the geometry is restated from the published configs, parity unpinned].  OpenCLIP spells its names with hyphens, which
 # keeps them apart from OpenAI's towers of the same geometry.  Against those: the exact (erf) GELU instead of QuickGELU (the LAION
 # checkpoints are trained without "quick_gelu"), on both the image and the text side; same tensors, same state-dict names, CLIP's
-# preprocessing constants.  ViT-H-14 has 16 heads of 80 on width 1280: the runner pads them to 96 columns (csrc/attention_hd96.hip).
+# preprocessing constants.  ViT-H-14 has 16 heads of 80 on width 1280: the runner pads them to 96 columns (csrc/attention.hip, the 96-wide instances).
 # ViT-g-14 (width 1408) and ViT-bigG-14 (width 1664) are not provided: LayerNorm needs a width that is a multiple of 256.
 @dataclass
 class OpenClipVitConfig(ClipVitConfig):

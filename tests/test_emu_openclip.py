@@ -1,5 +1,5 @@
 """A subset of tests/test_openclip_gpu.py on the CPU emulation of the kernels (tools/hipemu): the 96-wide attention forward and
-backward at T = 33, a reduced tower with heads of 80, and the GELU text tower.  Test infrastructure; says nothing about speed."""
+backward at T = 33 and 129, a reduced tower with heads of 80, and the GELU text tower.  Test infrastructure; says nothing about speed."""
 import os
 import shutil
 import sys
@@ -27,7 +27,8 @@ def emu():
 
 @pytest.mark.parametrize("h16", [1, 0])
 def test_mha_96_columns_on_the_emulated_kernels(emu, h16):
-    emu.attention96_checks(33, h16)
+    for T in (33, 129):          # 129: one key in the second LDS chunk, one live lane in the fifth wave
+        emu.attention96_checks(T, h16)
 
 
 @pytest.mark.parametrize("precision", ["f32", "fp16"])

@@ -540,7 +540,7 @@ def attention_case(N, T, C, heads, h16, qs=1.0, general=False, grid=False, seed=
 @pytest.mark.parametrize("h16", [0, 1], ids=["bf16", "half"])
 @pytest.mark.parametrize("N,T", [(64, 50), (3, 64), (2, 17), (2, 1)])
 def test_mha_both_formats(N, T, h16):
-    """att_bf16 / att_f16 :: mha_fwd_kernel, mha_bwd_kernel (T <= 64); measured figures and gates: ATT_GATES"""
+    """mha_fwd_kernel, mha_bwd_kernel <FmtBf16 | FmtF16> (T <= 64); measured figures and gates: ATT_GATES"""
     print(attention_case(N, T, 768, 12, h16)[0])
 
 
@@ -548,7 +548,7 @@ def test_mha_both_formats(N, T, h16):
 @pytest.mark.parametrize("N,T,qs", [(2, 65, 1.0), (3, 197, 1.0), (2, 257, 1.0), (4, 50, 1.0), (2, 82, 1.0), (1, 130, 1.0), (1, 300, 1.0),
                                     (1, 512, 1.0), (1, 577, 1.0), (2, 257, 6.0), (1, 197, 6.0)])
 def test_mha_general_both_formats(N, T, qs, h16):
-    """att_bf16 / att_f16 :: mha_fwd_blk_kernel, mha_bwd_dq/dkv_blk_kernel (T <= 512), mha_fwd_gen_kernel<false>, mha_bwd_dq/dkv_gen_kernel
+    """<FmtBf16 | FmtF16> of mha_fwd_blk_kernel<F, 64>, mha_bwd_dq/dkv_blk_kernel<F, 64> (T <= 512), mha_fwd_gen_kernel<F, false>, mha_bwd_dq/dkv_gen_kernel<F>
     (T = 577); `qs` scales the queries so that the running maximum of the online softmax moves between key blocks"""
     print(attention_case(N, T, 256, 4, h16, qs=qs, general=True, seed=1)[0])
 

@@ -89,6 +89,9 @@ def _max_err(got, ref):
 
 
 ATT_T = (1, 31, 33, 50, 257, 577)
+# lengths for the 96-wide family only, outside the yardstick: 129 puts one key in the second 128-token LDS chunk and one live lane in
+# the fifth wave; 640 is 20 full token blocks on 4 x 5 waves, no partial block anywhere, the last length before the refusal
+ATT_T_EDGE = (129, 640)
 ATT_KEYS = ("out", "lse", "dqkv")
 
 
@@ -130,7 +133,7 @@ def attention96_checks(T, h16):
 
 
 @pytest.mark.parametrize("h16", [1, 0])
-@pytest.mark.parametrize("T", ATT_T)
+@pytest.mark.parametrize("T", ATT_T + ATT_T_EDGE)
 def test_mha_96_columns_vs_float64(T, h16):
     """prx_k_mha_{fwd,bwd}_hd_op at 96 columns per head with the last 16 of each head zeroed, N = 2, 2 heads: out, lse and d(qkv)
     against float64 attention of the rounded operands at head dim 80, scale 1 / sqrt(80); pad columns of out and dqkv exactly 0;
@@ -141,6 +144,9 @@ def test_mha_96_columns_vs_float64(T, h16):
     Measured on an MI355X, max |kernel - float64| / max |float64|, worst of the six lengths, 96-wide (64-wide yardstick):
       fp16: out 3.80e-04 (4.76e-04), lse 1.43e-07 (1.38e-07), d(qkv) 5.71e-04 (4.20e-04)
       bf16: out 3.29e-03 (3.24e-03), lse 1.51e-07 (1.50e-07), d(qkv) 4.32e-03 (4.10e-03)
+    and at the two edge lengths (ATT_T_EDGE; same gate, not part of the yardstick):
+      T = 129  fp16: out 3.87e-04, lse 1.24e-07, d(qkv) 4.06e-04   bf16: out 2.26e-03, lse 1.46e-07, d(qkv) 3.35e-03
+      T = 640  fp16: out 2.86e-04, lse 1.28e-07, d(qkv) 3.61e-04   bf16: out 1.74e-03, lse 1.28e-07, d(qkv) 2.87e-03
     (per length: DESIGN.md section 6d)"""
     attention96_checks(T, h16)
 

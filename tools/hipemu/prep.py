@@ -1,4 +1,4 @@
-"""Source preparation for the host build of pixray_amd/csrc (tools/hipemu/Makefile): copies every .hip / .h / .inc into
+"""Source preparation for the host build of pixray_amd/csrc (tools/hipemu/Makefile): copies every .hip / .h into
 _build/src with the handful of textual changes the host compiler needs.  The product sources are never modified.
 
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(EXPR) : "memory")   ->  hipemu::waitcnt_vm(EXPR)       counted wait for this wave's DMA
@@ -6,7 +6,7 @@ _build/src with the handful of textual changes the host compiler needs.  The pro
   asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")          ->  hipemu::waitcnt_vm(n)          (macro argument, gemm8p.h)
   any other asm volatile( ... )                                 ->  HIPEMU_ASM( ... )              (lgkmcnt waits, register pins: no-ops)
   /*hipemu:wave_sync*/                                          ->  hipemu::wave_sync();           lockstep exchange inside one wave
-  __attribute__((amdgpu_waves_per_eu(a, b)))                    ->  (dropped)
+  __attribute__((amdgpu_waves_per_eu(a, b)))                    ->  (dropped; a, b: numbers, names or template expressions without parentheses)
   "../../include/prx.h"                                         ->  the path from _build/src
 """
 import os
@@ -21,11 +21,11 @@ rules = [
     (re.compile(r'asm volatile\("s_waitcnt vmcnt\(" #(\w+) "\)" ::: "memory"\)'), r'hipemu::waitcnt_vm(\1)'),
     (re.compile(r'asm volatile\('), 'HIPEMU_ASM('),
     (re.compile(r'/\*hipemu:wave_sync\*/'), 'hipemu::wave_sync();'),
-    (re.compile(r'__attribute__\(\(amdgpu_waves_per_eu\([0-9, ]*\)\)\)'), ''),
+    (re.compile(r'__attribute__\(\(amdgpu_waves_per_eu\([^()]*\)\)\)'), ''),
     (re.compile(r'"\.\./\.\./include/prx\.h"'), '"../../../../include/prx.h"'),
 ]
 for name in sorted(os.listdir(src)):
-    if not name.endswith((".hip", ".h", ".inc")):
+    if not name.endswith((".hip", ".h")):
         continue
     text = open(os.path.join(src, name)).read()
     for rx, rep in rules:

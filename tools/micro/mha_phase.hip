@@ -6,6 +6,25 @@
 #include <cstdarg>
 #include <vector>
 void prx_set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); fputc(10, stderr); }
+using F = FmtBf16;
+
+// softmax over j in the C layout (one wave holds all 64 keys of a row: 32-lane butterflies); s holds raw q.k sums; returns p in s
+__device__ __forceinline__ void softmax_c_layout(f32x16 (&s)[2][2], float scale, int T, int lane) {
+    const int j0 = lane & 31;
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float v0 = (j0 < T) ? s[mi][0][r] * scale : -INFINITY;
+            float v1 = (j0 + 32 < T) ? s[mi][1][r] * scale : -INFINITY;
+            float mx = half_max(fmaxf(v0, v1));
+            float e0 = __expf(v0 - mx), e1 = __expf(v1 - mx);
+            float sum = half_sum(e0 + e1);
+            float inv = 1.f / sum;
+            s[mi][0][r] = e0 * inv;
+            s[mi][1][r] = e1 * inv;
+        }
+}
 
 __global__ __launch_bounds__(64) void fwd_timed(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, int T, int C, float scale,
                                                 long long* __restrict__ stamps) {
@@ -17,26 +36,26 @@ __global__ __launch_bounds__(64) void fwd_timed(const bf16_t* __restrict__ qkv, 
     const bf16_t* base = qkv + (long long)n * T * ld + h * 64;
     long long t[8]; int k = 0;
     t[k++] = __builtin_amdgcn_s_memtime();
-    load_tile(base, ld, T, Qs, nullptr, lane);
-    load_tile(base + C, ld, T, Ks, nullptr, lane);
+    load_rows<F>(base, ld, 0, T, Qs, nullptr, lane);
+    load_rows<F>(base + C, ld, 0, T, Ks, nullptr, lane);
     t[k++] = __builtin_amdgcn_s_memtime();
-    load_tile(base + 2 * C, ld, T, nullptr, Vt, lane);
+    load_rows<F>(base + 2 * C, ld, 0, T, nullptr, Vt, lane);
     __syncthreads();
     t[k++] = __builtin_amdgcn_s_memtime();
     f32x16 s[2][2];
     zero_acc(s);
-    mma_64x64x64(Qs, Ks, s, lane);
+    mma_64x64x64<F>(Qs, Ks, s, lane);
     t[k++] = __builtin_amdgcn_s_memtime();
     softmax_c_layout(s, scale, T, lane);
     t[k++] = __builtin_amdgcn_s_memtime();
-    store_c_tile(s, Ps, nullptr, lane);
+    store_c_tile<F>(s, Ps, nullptr, lane);
     __syncthreads();
     t[k++] = __builtin_amdgcn_s_memtime();
     f32x16 o[2][2];
     zero_acc(o);
-    mma_64x64x64(Ps, Vt, o, lane);
+    mma_64x64x64<F>(Ps, Vt, o, lane);
     t[k++] = __builtin_amdgcn_s_memtime();
-    store_c_global(o, out + (long long)n * T * C + h * 64, C, T, lane);
+    store_c_global<F>(o, out + (long long)n * T * C + h * 64, C, T, lane);
     t[k++] = __builtin_amdgcn_s_memtime();
     if (lane == 0 && h == 3 && n == 5) for (int i = 0; i < 8; ++i) stamps[i] = t[i];
 }
