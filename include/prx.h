@@ -197,6 +197,21 @@ int prx_k_mha_bwd_hd_op(const void* qkv, const void* out, const void* dout, cons
 /* the head padding prx_vit_tower_create applies when it packs a block's weights (fp32 device tensors, width == heads * hd):
  * qkv_w [3 width, width] -> qkv_w_pad [3 heads hp, width] (every head's hd rows of q, k and v become the first hd of hp rows),
  * out_w [width, width] -> out_w_pad [width, heads hp] (the matching input columns); pad rows / columns are zero. */
+/* the same two calls with the head dim as an argument: head_dim 64 at head_cols 64 are prx_k_mha_{fwd,bwd}_gen_op; 80 | 88 at
+ * head_cols 96 and 104 at head_cols 128 (OpenCLIP ViT-H-14 | ViT-g-14 and ViT-bigG-14) run the 96- / 128-wide instances with the softmax
+ * scale 1 / sqrt(head_dim).  The caller's columns head_dim .. head_cols - 1 of every head are zero, and so are those of `out` and `dqkv`.
+ * Any other pair is refused. */
+int prx_k_mha_fwd_hdim_op(const void* qkv, void* out, float* lse, int N, int T, int C, int heads, int h16, int head_cols, int head_dim,
+                          prx_stream_t s);
+int prx_k_mha_bwd_hdim_op(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int N, int T, int C,
+                          int heads, int h16, int head_cols, int head_dim, prx_stream_t s);
+/* prx_k_layernorm_{fwd,bwd}_op in the ragged form the ViT runner uses: C a multiple of 128 (not only of 256), C <= 2048 -- the last
+ * float4 vector of a row is held by half a wave.  384 ... 896 run the MAXV = 4 instances, 1152 ... 1920 the MAXV = 8 ones. */
+int prx_k_layernorm_fwd_rag_op(const void* x, long long ldx, const float* gamma, const float* beta, void* out16, float* out_f32,
+                               float* mean, float* rstd, int rows, int C, float eps, int h16, int s16, prx_stream_t s);
+int prx_k_layernorm_bwd_rag_op(const void* g, long long ldg, const void* x, long long ldx, const float* gamma, const float* mean,
+                               const float* rstd, const void* add, long long ldadd, float* dx, long long lddx, void* dx16, long long lddxb,
+                               int rows, int C, int h16, int add_every, int s16, prx_stream_t s);
 int prx_k_vit_pad_heads(const float* qkv_w, float* qkv_w_pad, const float* out_w, float* out_w_pad, int width, int heads, int hd, int hp,
                         prx_stream_t s);
 /* forward only, causal mask (CLIP text transformer) */
@@ -584,6 +599,9 @@ int prx_clip_vit_create(prx_clip_vit** out, const prx_clip_vit_config* cfg, cons
  *   out-projection work.  width must be a multiple of 128.
  *   80 (OpenCLIP ViT-H/14: 16 heads on width 1280) is zero-padded to 96 the same way and runs on the 96-wide attention kernels, which
  *   take the softmax scale 1 / sqrt(80) as an argument (nothing is folded into q) and at most 640 tokens.
+ *   88 (OpenCLIP ViT-g-14: 16 heads on width 1408) runs there too with 1 / sqrt(88); 104 (ViT-bigG-14: 16 heads on width 1664) is
+ *   zero-padded to 128 and runs on the 128-wide instances of the same kernels with 1 / sqrt(104), at most 640 tokens.  Any other head
+ *   dim is refused by name.
  * family PRX_VIT_FAMILY_OPENCLIP: the OpenCLIP (LAION) ViT towers [UPSTREAM open_clip model_configs ViT-B-32, ViT-B-16, ViT-L-14, ViT-H-14]:
  *   weights[] and every switch as for PRX_VIT_FAMILY_CLIP (no patch-embed bias, ln_pre, ln_eps 1e-5 and CLIP's constants as given),
  *   but the MLP activation is the exact GELU. */
@@ -600,13 +618,18 @@ typedef struct prx_vit_tower_config {
     int max_batch;         /* capacity in cutouts */
     int precision;         /* PRX_PREC_F16 | PRX_PREC_BF16 | PRX_PREC_F32 (the reference runs this family in fp32 on a GPU) */
     int family;            /* PRX_VIT_FAMILY_* */
-    int head_dim;          /* 0 = 64; 32 | 16: padded to 64; 80: padded to 96 */
+    int head_dim;          /* 0 = 64; 32 | 16: padded to 64; 80 | 88: padded to 96; 104: padded to 128 */
     float ln_eps;          /* 1e-6 (timm) | 1e-5 (CLIP) */
     float mean[3];         /* Normalize constants of the fused preprocessing: ImageNet's (0.485, 0.456, 0.406) */
     float std[3];          /* (0.229, 0.224, 0.225) */
 } prx_vit_tower_config;
 int prx_vit_tower_create(prx_clip_vit** out, const prx_vit_tower_config* cfg, const float* const* weights, int n_weights,
                          prx_stream_t s);
+/* prx_vit_tower_create with the hidden width of the MLP as an argument: c_fc.weight [mlp_width, width], c_fc.bias [mlp_width],
+ * c_proj.weight [width, mlp_width] (fc1 / fc2 of the SLIP family).  0 = 4 * width: prx_vit_tower_create itself.  OpenCLIP ViT-g-14 has
+ * 6144 on width 1408, ViT-bigG-14 8192 on width 1664.  Must be a multiple of 8. */
+int prx_vit_tower_create_mlp(prx_clip_vit** out, const prx_vit_tower_config* cfg, int mlp_width, const float* const* weights, int n_weights,
+                             prx_stream_t s);
 /* TEST DIAGNOSTIC, not part of the ABI contract (it may change or go without a version bump; no product code calls it): copies the
  * d(qkv) buffer as the last backward left it -- block 0's gradient, [n * T][3 * heads * 64] in the handle's operand format, padded
  * lanes included -- to dst.  Returns the bytes copied, or -1 when no forward is in flight or max_bytes is too small. */
@@ -727,9 +750,14 @@ int prx_clip_text_encode(prx_clip_text* h, const int* tokens, int n, float* embe
  * rowloss[i] = sum_j sign(w) * 2*asin(|x^_i - e^_j|/2)^2;  *loss (optional, may be NULL) = |w| * sum(rowloss) / denom, the value
  * Prompt.forward returns, written by the workgroup that finishes last (rows added in a fixed order); `ticket`: one device word
  * that is zero on entry and zero again on exit (needed with `loss`; one per stream that may run this concurrently);
- * grad = d/d input of |w| * mean(max(sign(w) d, stop)) with the mean over `denom` (= global n*m) pairs. */
+ * grad = d/d input of |w| * mean(max(sign(w) d, stop)) with the mean over `denom` (= global n*m) pairs.
+ * D: a multiple of 64, at most 1024 (a row lives in registers, 16 steps of 64).
+ * prx_prompt_loss_fwd_bwd_wide: the same call for D up to 2048 (OpenCLIP ViT-bigG-14 embeds into 1280): the same kernel up to 1024, its
+ * 32-step instance beyond. */
 int prx_prompt_loss_fwd_bwd(const float* input, const float* embed, int n, int m, int D, float weight, float stop,
                             float denom, float* rowloss, float* grad, float* loss, unsigned* ticket, prx_stream_t s);
+int prx_prompt_loss_fwd_bwd_wide(const float* input, const float* embed, int n, int m, int D, float weight, float stop,
+                                 float denom, float* rowloss, float* grad, float* loss, unsigned* ticket, prx_stream_t s);
 
 /* --- optim.Adam([z], lr) step (pixray.py:539,1484-1485) fused with VqganDrawer.clip_z (vqgan.py:202-204).
  * z/exp_avg/exp_avg_sq/grad: [1,C,hw] fp32; zmin/zmax per channel or NULL; step is 1-based. */

@@ -61,7 +61,8 @@ def _openclip_configs(name_or_cfg, text: bool):
 
 def clip_visual_from_openclip(state_dict: Dict[str, torch.Tensor], name_or_cfg):
     """visual side of an OpenCLIP state dict of a native ViT model (`visual.conv1.weight`, `visual.class_embedding`, ...: OpenAI's key
-    names) for the named configuration (`ViT-B-32`, `ViT-B-16`, `ViT-L-14`, `ViT-H-14`) or an OpenClipVitConfig.  The geometry is the
+    names) for the named configuration (`ViT-B-32`, `ViT-B-16`, `ViT-L-14`, `ViT-H-14`, `ViT-g-14`, `ViT-bigG-14`) or an OpenClipVitConfig.  The geometry --
+    the MLP width included, which is 6144 / 8192 and not 4 x width in the last two -- is the
     configuration's, never read off the tensors: `clip_config_from_state_dict` takes heads = width // 64 as `clip.model.build_model`
     does, which is wrong for ViT-H-14 (16 heads of 80 on width 1280).  A missing or mis-shaped tensor is named."""
     cfg = _openclip_configs(name_or_cfg, text=False)

@@ -169,6 +169,35 @@ int prx_k_mha_bwd_hd_op(const void* qkv, const void* out, const void* dout, cons
     if (head_cols == 64) return prx_mha_bwd_gen(CB_(qkv), CB_(out), CB_(dout), lse, B_(dqkv), N, T, C, heads, S_(s), h16);
     return prx_mha_bwd_hd96(CB_(qkv), CB_(out), CB_(dout), lse, B_(dqkv), N, T, C, heads, 1.f / sqrtf(80.f), S_(s), h16);
 }
+// the head dim as an argument: the scale is 1 / sqrt(head_dim), the columns come from the runner's own mapping (prx_vit_head_cols)
+int prx_k_mha_fwd_hdim_op(const void* qkv, void* out, float* lse, int N, int T, int C, int heads, int h16, int head_cols, int head_dim,
+                          prx_stream_t s) {
+    PRX_REQUIRE(head_dim >= 64 && prx_vit_head_cols(head_dim) == head_cols, "mha_fwd_hdim: head dim %d at %d columns per head (64 at 64, 80 | 88 at 96, 104 at 128)",
+                head_dim, head_cols);
+    const float scale = 1.f / sqrtf((float)head_dim);
+    if (head_cols == 64) return prx_mha_fwd_gen(CB_(qkv), B_(out), lse, N, T, C, heads, S_(s), h16);
+    if (head_cols == 96) return prx_mha_fwd_hd96(CB_(qkv), B_(out), lse, N, T, C, heads, scale, S_(s), h16);
+    return prx_mha_fwd_hd128(CB_(qkv), B_(out), lse, N, T, C, heads, scale, S_(s), h16);
+}
+int prx_k_mha_bwd_hdim_op(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int N, int T, int C,
+                          int heads, int h16, int head_cols, int head_dim, prx_stream_t s) {
+    PRX_REQUIRE(head_dim >= 64 && prx_vit_head_cols(head_dim) == head_cols, "mha_bwd_hdim: head dim %d at %d columns per head (64 at 64, 80 | 88 at 96, 104 at 128)",
+                head_dim, head_cols);
+    const float scale = 1.f / sqrtf((float)head_dim);
+    if (head_cols == 64) return prx_mha_bwd_gen(CB_(qkv), CB_(out), CB_(dout), lse, B_(dqkv), N, T, C, heads, S_(s), h16);
+    if (head_cols == 96) return prx_mha_bwd_hd96(CB_(qkv), CB_(out), CB_(dout), lse, B_(dqkv), N, T, C, heads, scale, S_(s), h16);
+    return prx_mha_bwd_hd128(CB_(qkv), CB_(out), CB_(dout), lse, B_(dqkv), N, T, C, heads, scale, S_(s), h16);
+}
+int prx_k_layernorm_fwd_rag_op(const void* x, long long ldx, const float* gamma, const float* beta, void* out16, float* out_f32,
+                               float* mean, float* rstd, int rows, int C, float eps, int h16, int s16, prx_stream_t s) {
+    return prx_layernorm_fwd(x, ldx, gamma, beta, B_(out16), out_f32, mean, rstd, rows, C, eps, S_(s), h16, s16, 1);
+}
+int prx_k_layernorm_bwd_rag_op(const void* g, long long ldg, const void* x, long long ldx, const float* gamma, const float* mean,
+                               const float* rstd, const void* add, long long ldadd, float* dx, long long lddx, void* dx16, long long lddxb,
+                               int rows, int C, int h16, int add_every, int s16, prx_stream_t s) {
+    return prx_layernorm_bwd(g, ldg, x, ldx, gamma, mean, rstd, add, ldadd, dx, lddx, B_(dx16), lddxb, rows, C, S_(s), h16,
+                             add_every, s16, 1);
+}
 int prx_k_vit_pad_heads(const float* qkv_w, float* qkv_w_pad, const float* out_w, float* out_w_pad, int width, int heads, int hd, int hp,
                         prx_stream_t s) {
     PRX_REQUIRE(qkv_w && qkv_w_pad && out_w && out_w_pad && width == heads * hd, "vit_pad_heads: null argument or width != heads * head dim");

@@ -119,15 +119,20 @@ int prx_clip_vit_create(prx_clip_vit** out, const prx_clip_vit_config* c, const 
 }
 int prx_vit_tower_create(prx_clip_vit** out, const prx_vit_tower_config* c, const float* const* weights, int n_weights,
                          prx_stream_t s) {
+    return prx_vit_tower_create_mlp(out, c, 0, weights, n_weights, s);
+}
+int prx_vit_tower_create_mlp(prx_clip_vit** out, const prx_vit_tower_config* c, int mlp_width, const float* const* weights, int n_weights,
+                             prx_stream_t s) {
     PRX_REQUIRE(out && c && weights, "prx_vit_tower_create: null argument");
+    PRX_REQUIRE(mlp_width >= 0, "prx_vit_tower_create: MLP width %d", mlp_width);
     PRX_REQUIRE(c->family == PRX_VIT_FAMILY_CLIP || c->family == PRX_VIT_FAMILY_SLIP || c->family == PRX_VIT_FAMILY_OPENCLIP,
                 "prx_vit_tower_create: unknown family %d", c->family);
-    PRX_REQUIRE(c->head_dim == 0 || c->head_dim == 64 || c->head_dim == 32 || c->head_dim == 16 || c->head_dim == 80,
-                "prx_vit_tower_create: head dim %d (want 64, or 32 / 16: padded to 64, or 80: padded to 96)", c->head_dim);
+    PRX_REQUIRE(c->head_dim == 0 || prx_vit_head_cols(c->head_dim) != 0,
+                "prx_vit_tower_create: head dim %d (want 64, or 32 / 16: padded to 64, or 80 / 88: padded to 96, or 104: padded to 128)", c->head_dim);
     VitFamily f = prx_vit_family_clip();
     if (c->family == PRX_VIT_FAMILY_SLIP) { f.patch_bias = 1; f.ln_pre = 0; f.act = PRX_ACT_GELU; f.dact = PRX_ACT_MUL_DGELU; }
     if (c->family == PRX_VIT_FAMILY_OPENCLIP) { f.act = PRX_ACT_GELU; f.dact = PRX_ACT_MUL_DGELU; }      // CLIP's layout, the exact GELU
-    f.eps = c->ln_eps; f.head_dim = c->head_dim;
+    f.eps = c->ln_eps; f.head_dim = c->head_dim; f.mlp_width = mlp_width;
     for (int i = 0; i < 3; ++i) { f.norm.mean[i] = c->mean[i]; f.norm.std[i] = c->std[i]; }
     return prx_vit_create_impl((PrxVit**)out, c->input_resolution, c->patch_size, c->width, c->layers, c->heads,
                                c->output_dim, c->max_batch, c->precision, weights, n_weights, S_(s), &f);
@@ -161,6 +166,11 @@ int prx_prompt_loss_fwd_bwd(const float* input, const float* embed, int n, int m
                             float denom, float* rowloss, float* grad, float* loss, unsigned* ticket, prx_stream_t s) {
     PRX_REQUIRE(input && embed && rowloss && grad, "prx_prompt_loss_fwd_bwd: null argument");
     return prx_prompt_loss(input, embed, n, m, D, weight, stop, denom, rowloss, grad, loss, ticket, S_(s));
+}
+int prx_prompt_loss_fwd_bwd_wide(const float* input, const float* embed, int n, int m, int D, float weight, float stop,
+                                 float denom, float* rowloss, float* grad, float* loss, unsigned* ticket, prx_stream_t s) {
+    PRX_REQUIRE(input && embed && rowloss && grad, "prx_prompt_loss_fwd_bwd_wide: null argument");
+    return prx_prompt_loss(input, embed, n, m, D, weight, stop, denom, rowloss, grad, loss, ticket, S_(s), 1);
 }
 int prx_adam_clamp_step(float* z, float* exp_avg, float* exp_avg_sq, const float* grad, const float* zmin,
                         const float* zmax, int hw, size_t n, float lr, float beta1, float beta2, float eps, int step,

@@ -24,3 +24,12 @@ int prx_mha_bwd_hd96(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, c
 int prx_mha_fwd_f32_hd96(const float* qkv, float* out, float* lse, int N, int T, int C, int heads, hipStream_t s);
 int prx_mha_bwd_f32_hd96(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int N, int T, int C,
                          int heads, hipStream_t s);
+// heads of 128 operand columns = head dim 104 zero-padded (OpenCLIP ViT-bigG-14): the 128-wide instances of the same family, same contract
+// (heads of 88, ViT-g-14, run on prx_mha_*_hd96 with scale 1 / sqrt(88))
+int prx_mha_fwd_hd128(const bf16_t* qkv, bf16_t* out, float* lse, int N, int T, int C, int heads, float scale, hipStream_t s, int h16 = 0);
+int prx_mha_bwd_hd128(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, int N, int T, int C,
+                      int heads, float scale, hipStream_t s, int h16 = 0);
+// exact-f32 form for any padded head dim hd: 80 | 88 in 96 columns, 104 in 128; scale 1 / sqrt(hd); any T
+int prx_mha_fwd_f32_pad(const float* qkv, float* out, float* lse, int N, int T, int C, int heads, int hd, hipStream_t s);
+int prx_mha_bwd_f32_pad(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int N, int T, int C,
+                        int heads, int hd, hipStream_t s);

@@ -132,3 +132,17 @@ int prx_mha_bwd_hd96(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, c
     return h16 ? mha_bwd_blk<FmtF16, 96>(H(qkv), H(out), H(dout), lse, HM(dqkv), N, T, C, heads, scale, s)
                : mha_bwd_blk<FmtBf16, 96>(qkv, out, dout, lse, dqkv, N, T, C, heads, scale, s);
 }
+// heads of 104 zero-padded to 128 columns (OpenCLIP ViT-bigG-14); the chunked kernels do not depend on T, so the cap is the family's
+int prx_mha_fwd_hd128(const bf16_t* qkv, bf16_t* out, float* lse, int N, int T, int C, int heads, float scale, hipStream_t s, int h16) {
+    PRX_REQUIRE(C == heads * 128 && T >= 1 && T <= MHA_BLK_MAX_T && N >= 1,
+                "mha(hd128): needs 128 columns per head and 1 <= T <= %d (T=%d C=%d heads=%d)", MHA_BLK_MAX_T, T, C, heads);
+    return h16 ? mha_fwd_blk<FmtF16, 128>(H(qkv), HM(out), lse, N, T, C, heads, scale, s)
+               : mha_fwd_blk<FmtBf16, 128>(qkv, out, lse, N, T, C, heads, scale, s);
+}
+int prx_mha_bwd_hd128(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, int N, int T, int C,
+                      int heads, float scale, hipStream_t s, int h16) {
+    PRX_REQUIRE(C == heads * 128 && T >= 1 && T <= MHA_BLK_MAX_T && N >= 1,
+                "mha(hd128) bwd: needs 128 columns per head and 1 <= T <= %d (T=%d C=%d heads=%d)", MHA_BLK_MAX_T, T, C, heads);
+    return h16 ? mha_bwd_blk<FmtF16, 128>(H(qkv), H(out), H(dout), lse, HM(dqkv), N, T, C, heads, scale, s)
+               : mha_bwd_blk<FmtBf16, 128>(qkv, out, dout, lse, dqkv, N, T, C, heads, scale, s);
+}

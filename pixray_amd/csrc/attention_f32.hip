@@ -281,3 +281,41 @@ int prx_mha_bwd_f32_hd96(const float* qkv, const float* out, const float* dout, 
     PRX_LAUNCH_CHECK();
     return 0;
 }
+
+// head dim `hd` zero-padded to its operand columns per head: 88 in 96 (OpenCLIP ViT-g-14), 104 in 128 (ViT-bigG-14); scale 1 / sqrt(hd)
+namespace {
+template <int HD, int HS>
+int mha_fwd_f32_pad(const float* qkv, float* out, float* lse, int N, int T, int C, int heads, hipStream_t s) {
+    PRX_REQUIRE(C == heads * HS && T >= 1, "mha(f32, head dim %d): needs %d columns per head (T=%d C=%d heads=%d)", HD, HS, T, C, heads);
+    hipLaunchKernelGGL((mha_fwd_f32_kernel<HD, HS>), dim3(ceil_div(T, 64), heads, N), dim3(64), 0, s, qkv, out, lse, T, C, heads,
+                       1.f / sqrtf((float)HD));
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+template <int HD, int HS>
+int mha_bwd_f32_pad(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int N, int T, int C, int heads,
+                    hipStream_t s) {
+    PRX_REQUIRE(C == heads * HS && T >= 1, "mha(f32, head dim %d) bwd: needs %d columns per head (T=%d C=%d heads=%d)", HD, HS, T, C, heads);
+    const dim3 grid(ceil_div(T, 64), heads, N);
+    const float scale = 1.f / sqrtf((float)HD);
+    hipLaunchKernelGGL((mha_bwd_dq_f32_kernel<HD, HS>), grid, dim3(64), 0, s, qkv, out, dout, lse, dqkv, T, C, heads, scale);
+    PRX_LAUNCH_CHECK();
+    hipLaunchKernelGGL((mha_bwd_dkv_f32_kernel<HD, HS>), grid, dim3(64), 0, s, qkv, out, dout, lse, dqkv, T, C, heads, scale);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+}  // namespace
+
+int prx_mha_fwd_f32_pad(const float* qkv, float* out, float* lse, int N, int T, int C, int heads, int hd, hipStream_t s) {
+    if (hd == 80) return prx_mha_fwd_f32_hd96(qkv, out, lse, N, T, C, heads, s);
+    if (hd == 88) return mha_fwd_f32_pad<88, 96>(qkv, out, lse, N, T, C, heads, s);
+    PRX_REQUIRE(hd == 104, "mha(f32): no padded instance for head dim %d (80 | 88 | 104)", hd);
+    return mha_fwd_f32_pad<104, 128>(qkv, out, lse, N, T, C, heads, s);
+}
+int prx_mha_bwd_f32_pad(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int N, int T, int C,
+                        int heads, int hd, hipStream_t s) {
+    if (hd == 80) return prx_mha_bwd_f32_hd96(qkv, out, dout, lse, dqkv, N, T, C, heads, s);
+    if (hd == 88) return mha_bwd_f32_pad<88, 96>(qkv, out, dout, lse, dqkv, N, T, C, heads, s);
+    PRX_REQUIRE(hd == 104, "mha(f32) bwd: no padded instance for head dim %d (80 | 88 | 104)", hd);
+    return mha_bwd_f32_pad<104, 128>(qkv, out, dout, lse, dqkv, N, T, C, heads, s);
+}

@@ -637,24 +637,34 @@ __global__ __launch_bounds__(64) void mha_bwd_dkv_gen_kernel(const El<F>* __rest
 //             (queries on register rows) through a 32-float LDS line per wave
 //   backward: dQ kernel (owned queries, chunks of K / V / K^T) and dK+dV kernel (owned keys, chunks of Q / dO / Q^T /
 //             dO^T with the per-query LSE and D = rowsum(dO o O) staged beside them); both recompute P from the LSE
-// Templated on HDP, the operand columns per head: 64 (head dim 64), or 96 = head dim 80 (OpenCLIP ViT-H/14: 1280 / 16 [UPSTREAM
-// open_clip model_configs]) zero-padded to three 32-column MFMA blocks when the runner packs its weights (vit.hip).  The softmax scale
-// is an argument (1 / 8; at 96 columns 1 / sqrt(80), not 1 / sqrt(96)): the padded columns are zero in q, k and v, so scores, output
-// and gradients are those of the 80-wide head, and the padded columns of `out` and `dqkv` are exact zeros (sums of products with a
-// zero operand).  Per width, 64 | 96:
-//   score products   4 | 6 k-steps of v_mfma_f32_32x32x16_{bf16,f16} (own_frags keeps as many fragments per tensor)
-//   second products  2 | 3 output blocks of 32 columns (16 accumulator registers per lane, block and product)
-//   row-major image  rows of 72 | 104 elements = 9 | 13 16-byte slots: both odd, so the 16 rows of every ds_read_b128 lane group
-//                    (rows distinct mod 16) start in 16 distinct slots of the 64-bank row -- conflict-free
-//   transposed image 64 | 96 rows of TRS = 132 elements
-//   staging          8 | 16 piece slots per token row, 8 | 12 of them live: the slot index stays a shift / mask at both widths; at 96
-//                    the eight-lane row sum of the dK / dV kernel becomes a sixteen-lane one, dead slots hold zeros and write
-//                    nothing (at 64 the dead-slot test and the fourth shuffle step fold away)
-//   waves_per_eu     4 / 4 / 3 | 3 / 3 / 2 (forward / dQ / dK+dV), i.e. budgets of 128 / 128 / 168 | 168 / 168 / 256 registers per lane.
+// Templated on HDP, the operand columns per head: 64 (head dim 64), 96 = head dim 80 (OpenCLIP ViT-H/14: 1280 / 16 [UPSTREAM
+// open_clip model_configs]) or 88 (ViT-g-14: 1408 / 16), and 128 = head dim 104 (ViT-bigG-14: 1664 / 16), zero-padded to three / four
+// 32-column MFMA blocks when the runner packs its weights (vit.hip).  The softmax scale is an argument (1 / 8; in the padded widths
+// 1 / sqrt(head dim), not 1 / sqrt(columns)): the padded columns are zero in q, k and v, so scores, output and gradients are those of
+// the narrower head, and the padded columns of `out` and `dqkv` are exact zeros (sums of products with a zero operand).
+// Per width, 64 | 96 | 128:
+//   score products   4 | 6 | 8 k-steps of v_mfma_f32_32x32x16_{bf16,f16} (own_frags keeps as many fragments per tensor)
+//   second products  2 | 3 | 4 output blocks of 32 columns (16 accumulator registers per lane, block and product)
+//   row-major image  rows of 72 | 104 | 136 elements = 9 | 13 | 17 16-byte slots: all odd, so the 16 rows of every ds_read_b128 lane
+//                    group (rows distinct mod 16) start in 16 distinct slots of the 64-bank row -- conflict-free
+//   transposed image 64 | 96 | 128 rows of TRS = 132 elements
+//   staging          8 | 16 | 16 piece slots per token row, 8 | 12 | 16 of them live: the slot index stays a shift / mask at every
+//                    width; at 96 and 128 the eight-lane row sum of the dK / dV kernel becomes a sixteen-lane one, dead slots hold
+//                    zeros and write nothing (at 64 the dead-slot test and the fourth shuffle step fold away, at 128 the test alone)
+//   waves_per_eu     4 / 4 / 3 | 3 / 3 / 2 | 3 / 2 / 2 (forward / dQ / dK+dV), i.e. budgets of 128 / 128 / 168 | 168 / 168 / 256 |
+//                    168 / 256 / 256 registers per lane.
 //                    At 96 columns the forward spills 8 registers at 4 waves (qf 24 + O accumulators 48 + the score tile 16 +
 //                    addressing) and uses 137 at 3; the dK + dV kernel keeps its keys' K and V fragments (48) and the dK / dV
 //                    accumulators (96) in registers, cannot run at 3, and its LDS allows one workgroup per CU anyway.
-//                    Registers, LDS and occupancy of the 96-wide instances: DESIGN.md, the attention table of section 6d.
+//                    At 128 columns the forward (qf 32 + O 64 + score tile 16 + addressing = 161) still fits 3; dQ (qf, dof 64 +
+//                    accumulators 64 + two score tiles 32 = 231) needs the 256 budget; dK + dV in one pass (fragments 64 + accumulators
+//                    128 + two score tiles 32 + staging) takes all 256 and spills 15 registers, so it runs in two column passes
+//                    (Blk::NCP, the note in the kernel): 248 registers, no scratch.  AGPR accumulators were the other way out: they
+//                    need one wave per SIMD, i.e. workgroups of at most four waves and nothing to overlap a wave's LDS and global
+//                    latency with; two waves per SIMD at 1.5 x the MFMA work of that kernel were preferred.
+//   LDS              forward 35 968 | 52 608 | 69 248 B, dQ 53 760 | 78 592 | 103 424 B, dK + dV 71 680 | 104 960 | 138 240 B of the
+//                    CU's 160 KiB: the chunk stays 128 tokens at every width, so T <= 640 holds at 128 columns too.
+//                    Registers, LDS and occupancy of the padded instances: DESIGN.md, the attention table of section 6d.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int CH = 128;             // tokens per LDS chunk (four 32-token MFMA blocks)
 constexpr int TRS = CH + 4;         // row stride (elements) of a transposed [HDP][CH] image: 66 dwords = 2 mod 64 banks, so the 32
@@ -663,14 +673,15 @@ constexpr int STG_NP = 4;           // pieces in flight per thread and tensor (C
 constexpr int WPB = 5;              // waves per workgroup: a head with more 32-token blocks is split over gridDim.z workgroups
 template <int HDP>
 struct Blk {
-    static_assert(HDP == 64 || HDP == 96, "operand columns per head");
+    static_assert(HDP == 64 || HDP == 96 || HDP == 128, "operand columns per head");
     static constexpr int KS = HDP / 16;             // k-steps of a score product
     static constexpr int NDJ = HDP / 32;            // 32-column blocks of a second product's output
     static constexpr int NPR = HDP / 8;             // live 16-byte pieces per token row
     static constexpr int LD = HDP + 8;              // row-major LDS row (elements)
     static constexpr int SPR = HDP == 64 ? 8 : 16;  // piece slots per staged token row (a power of two >= NPR)
     static constexpr int NSLOT = CH * SPR;          // piece slots per chunk
-    static constexpr int WPE_FWD = HDP == 64 ? 4 : 3, WPE_DQ = WPE_FWD, WPE_DKV = WPE_FWD - 1;      // the waves_per_eu pins
+    static constexpr int WPE_FWD = HDP == 64 ? 4 : 3, WPE_DQ = HDP == 128 ? 2 : WPE_FWD, WPE_DKV = HDP == 64 ? 3 : 2;      // the waves_per_eu pins
+    static constexpr int NCP = HDP == 128 ? 2 : 1;  // column passes of the dK + dV kernel: each holds NDJ / NCP output blocks of dK and of dV
 };
 
 // rows t0 .. t0+CH-1 of a [T][HDP] matrix (zero beyond T) -> row-major image and / or transposed image, by 16-byte piece slots.
@@ -941,73 +952,81 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(Blk<HD
     V8<F> kf[B::KS], vf[B::KS];
     own_frags<F>(base + C, ld, key, T, kf, lane);
     own_frags<F>(base + 2 * C, ld, key, T, vf, lane);
-    f32x16 dk[B::NDJ], dv[B::NDJ];
-    zero_blocks(dk); zero_blocks(dv);
     const int nthr = blockDim.x;
-    for (int c0 = 0; c0 < T; c0 += CH) {
-        __syncthreads();
-        // Q chunk, dO chunk and beside it D_i = sum_d dO_id O_id (the SPR slots of a row sit in SPR neighbouring lanes, one 8-column
-        // piece each; dead slots hold zeros); the pieces of all three tensors are requested before the first LDS write (stage_put's note)
-        for (int cb = tid; cb < B::NSLOT; cb += STG_NP * nthr) {
-            V8<F> vq[STG_NP], vd[STG_NP], vo[STG_NP];
+    // Column passes (B::NCP; 1 at 64 and 96 columns, where this loop folds away): at 128 columns the K and V fragments (64 registers)
+    // and all of dK and dV (128) do not fit the 256 registers of two waves per SIMD beside the score tiles and the staging pieces, so
+    // a pass accumulates NDJ / NCP = 2 of the four 32-column blocks of dK and of dV and the chunks are streamed once per pass
+    // (the scores are recomputed: 16 + 8 MFMAs per 32 x 32 block and pass instead of 16 + 16 once)
+    constexpr int NDP = B::NDJ / B::NCP;
+    int cp = 0;
+    do {        // (a do-while whose condition is a constant false at one pass: the front end emits no loop there)
+        f32x16 dk[NDP], dv[NDP];
+        zero_blocks(dk); zero_blocks(dv);
+        for (int c0 = 0; c0 < T; c0 += CH) {
+            __syncthreads();
+            // Q chunk, dO chunk and beside it D_i = sum_d dO_id O_id (the SPR slots of a row sit in SPR neighbouring lanes, one 8-column
+            // piece each; dead slots hold zeros); the pieces of all three tensors are requested before the first LDS write (stage_put's note)
+            for (int cb = tid; cb < B::NSLOT; cb += STG_NP * nthr) {
+                V8<F> vq[STG_NP], vd[STG_NP], vo[STG_NP];
 #pragma unroll
-            for (int i = 0; i < STG_NP; ++i) vq[i] = stage_get<F, HDP>(base, ld, c0, T, cb + i * nthr);
+                for (int i = 0; i < STG_NP; ++i) vq[i] = stage_get<F, HDP>(base, ld, c0, T, cb + i * nthr);
 #pragma unroll
-            for (int i = 0; i < STG_NP; ++i) vd[i] = stage_get<F, HDP>(dob, C, c0, T, cb + i * nthr);
+                for (int i = 0; i < STG_NP; ++i) vd[i] = stage_get<F, HDP>(dob, C, c0, T, cb + i * nthr);
 #pragma unroll
-            for (int i = 0; i < STG_NP; ++i) vo[i] = stage_get<F, HDP>(ob, C, c0, T, cb + i * nthr);
+                for (int i = 0; i < STG_NP; ++i) vo[i] = stage_get<F, HDP>(ob, C, c0, T, cb + i * nthr);
 #pragma unroll
-            for (int i = 0; i < STG_NP; ++i)
-                if (cb + i * nthr < B::NSLOT) stage_put<F, HDP>(vq[i], cb + i * nthr, Qs, Qt);
+                for (int i = 0; i < STG_NP; ++i)
+                    if (cb + i * nthr < B::NSLOT) stage_put<F, HDP>(vq[i], cb + i * nthr, Qs, Qt);
 #pragma unroll
-            for (int i = 0; i < STG_NP; ++i) {
-                const int c = cb + i * nthr;                // (c >= NSLOT only in whole waves: the shuffles below stay converged)
-                if (c < B::NSLOT) {
-                    const int row = c / B::SPR, kc = c % B::SPR;
-                    float part = 0.f;
+                for (int i = 0; i < STG_NP; ++i) {
+                    const int c = cb + i * nthr;                // (c >= NSLOT only in whole waves: the shuffles below stay converged)
+                    if (c < B::NSLOT) {
+                        const int row = c / B::SPR, kc = c % B::SPR;
+                        float part = 0.f;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) part += (float)vd[i][e] * (float)vo[i][e];
-                    stage_put<F, HDP>(vd[i], c, dOs, dOt);
-                    part += __shfl_xor(part, 1, 64);
-                    part += __shfl_xor(part, 2, 64);
-                    part += __shfl_xor(part, 4, 64);
-                    if (B::SPR == 16) part += __shfl_xor(part, 8, 64);
-                    if (kc == 0) {
-                        s_D[row] = part;
-                        s_lse[row] = (c0 + row < T) ? lse_h[c0 + row] * LOG2E : INFINITY;      // base-2 domain
+                        for (int e = 0; e < 8; ++e) part += (float)vd[i][e] * (float)vo[i][e];
+                        stage_put<F, HDP>(vd[i], c, dOs, dOt);
+                        part += __shfl_xor(part, 1, 64);
+                        part += __shfl_xor(part, 2, 64);
+                        part += __shfl_xor(part, 4, 64);
+                        if (B::SPR == 16) part += __shfl_xor(part, 8, 64);
+                        if (kc == 0) {
+                            s_D[row] = part;
+                            s_lse[row] = (c0 + row < T) ? lse_h[c0 + row] * LOG2E : INFINITY;      // base-2 domain
+                        }
                     }
                 }
             }
-        }
-        __syncthreads();
-        const int nsb = active ? min(CH / 32, (T - c0 + 31) / 32) : 0;
-        for (int sb = 0; sb < nsb; ++sb) {
-            f32x16 p, dp;                                   // [query 32sb..][key]
-            zero16(p); zero16(dp);
-            mma_chunk_own<F>(Qs, sb, kf, p, lane);          // S  = Q K^T
-            mma_chunk_own<F>(dOs, sb, vf, dp, lane);        // dP = dO V^T
+            __syncthreads();
+            const int nsb = active ? min(CH / 32, (T - c0 + 31) / 32) : 0;
+            for (int sb = 0; sb < nsb; ++sb) {
+                f32x16 p, dp;                                   // [query 32sb..][key]
+                zero16(p); zero16(dp);
+                mma_chunk_own<F>(Qs, sb, kf, p, lane);          // S  = Q K^T
+                mma_chunk_own<F>(dOs, sb, vf, dp, lane);        // dP = dO V^T
 #pragma unroll
-            for (int rg = 0; rg < 4; ++rg) {
-                const int i0 = sb * 32 + 8 * rg + 4 * hh;
-                const float4 l4 = *reinterpret_cast<const float4*>(&s_lse[i0]);
-                const float4 d4 = *reinterpret_cast<const float4*>(&s_D[i0]);
-                const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dvv[4] = {d4.x, d4.y, d4.z, d4.w};
+                for (int rg = 0; rg < 4; ++rg) {
+                    const int i0 = sb * 32 + 8 * rg + 4 * hh;
+                    const float4 l4 = *reinterpret_cast<const float4*>(&s_lse[i0]);
+                    const float4 d4 = *reinterpret_cast<const float4*>(&s_D[i0]);
+                    const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dvv[4] = {d4.x, d4.y, d4.z, d4.w};
 #pragma unroll
-                for (int qq = 0; qq < 4; ++qq) {
-                    const int r = rg * 4 + qq;
-                    const float pv = key_ok ? __builtin_amdgcn_exp2f(p[r] * sl2 - lv[qq]) : 0.f;
-                    p[r] = pv;
-                    dp[r] = scale * pv * (dp[r] - dvv[qq]);   // dS
+                    for (int qq = 0; qq < 4; ++qq) {
+                        const int r = rg * 4 + qq;
+                        const float pv = key_ok ? __builtin_amdgcn_exp2f(p[r] * sl2 - lv[qq]) : 0.f;
+                        p[r] = pv;
+                        dp[r] = scale * pv * (dp[r] - dvv[qq]);   // dS
+                    }
                 }
+                mma_acc_tr_chunk<F>(dp, Qt + cp * 32 * NDP * TRS, sb, dk, lane);     // dK[key][d] += dS[query][key] Q[query][d]
+                mma_acc_tr_chunk<F>(p, dOt + cp * 32 * NDP * TRS, sb, dv, lane);     // dV[key][d] += P[query][key] dO[query][d]
             }
-            mma_acc_tr_chunk<F>(dp, Qt, sb, dk, lane);      // dK[key][d] += dS[query][key] Q[query][d]
-            mma_acc_tr_chunk<F>(p, dOt, sb, dv, lane);      // dV[key][d] += P[query][key] dO[query][d]
         }
-    }
-    if (!active) return;
-    E* obase = dqkv + (long long)n * T * ld + h * HDP;
-    store_rows_global<F>(dk, w, obase + C, ld, T, lane);
-    store_rows_global<F>(dv, w, obase + 2 * C, ld, T, lane);
+        if (!active) continue;                              // (a wave without tokens still stages and meets the barriers of the next pass)
+        E* obase = dqkv + (long long)n * T * ld + h * HDP + cp * 32 * NDP;
+        store_rows_global<F>(dk, w, obase + C, ld, T, lane);
+        store_rows_global<F>(dv, w, obase + 2 * C, ld, T, lane);
+    } while (B::NCP > 1 && ++cp < B::NCP);
 }
 
 }  // namespace

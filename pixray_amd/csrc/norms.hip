@@ -243,7 +243,7 @@ __global__ __launch_bounds__(256) void gn_apply_bwd_kernel(const GNArgs a, const
 
 // ---------------------------------------------------------------------------
 // LayerNorm over rows of width C (C % 128 == 0, C <= 2048): one wave per row.
-// RAG (C % 256 == 128: the 384-wide ViT-S/16 towers): the last float4 vector of a row is held by lanes 0 .. 31 only; `ln_own`
+// RAG (C % 256 == 128: the 384-wide ViT-S/16 towers at MAXV = 4; 1408 and 1664, OpenCLIP ViT-g-14 / ViT-bigG-14, at MAXV = 8): the last float4 vector of a row is held by lanes 0 .. 31 only; `ln_own`
 // says whether vector i of this lane exists.  With RAG = false it is `i < nv`, the expression the kernels had before.
 // ---------------------------------------------------------------------------
 template <bool RAG>
@@ -434,13 +434,14 @@ int prx_groupnorm_bwd(const void* g, const void* x, const float* gamma, const fl
 
 int prx_layernorm_fwd(const void* x, long long ldx, const float* gamma, const float* beta, bf16_t* out_bf16,
                       float* out_f32, float* mean, float* rstd, int rows, int C, float eps, hipStream_t s, int h16, int s16, int ragged) {
-    PRX_REQUIRE((C % 256 == 0 || (ragged && C % 128 == 0 && C <= 1024)) && C <= 2048 && ldx % 4 == 0,
-                "layernorm: C must be a multiple of 256 and <= 2048 (C=%d), ldx a multiple of 4", C);
+    PRX_REQUIRE(C >= 128 && (C % 256 == 0 || (ragged && C % 128 == 0)) && C <= 2048 && ldx % 4 == 0,
+                "layernorm: C must be a multiple of 256 (of 128 in the ragged form) and <= 2048 (C=%d, ragged=%d), ldx a multiple of 4 (ldx=%lld)", C, ragged, ldx);
     dim3 grid(ceil_div(rows, 4));
     if (C % 256 != 0) {      // ragged last vector: its own instances, the others are untouched
-#define PRX_LN_FWD_R(S16) hipLaunchKernelGGL((ln_fwd_kernel<4, S16, true>), grid, dim3(256), 0, s, x, gamma, beta, out_bf16, out_f32, mean, rstd, \
-                                             rows, C, ldx, eps, prx_xcd_local(), h16)
-        if (s16) PRX_LN_FWD_R(true); else PRX_LN_FWD_R(false);
+#define PRX_LN_FWD_R(MAXV, S16) hipLaunchKernelGGL((ln_fwd_kernel<MAXV, S16, true>), grid, dim3(256), 0, s, x, gamma, beta, out_bf16, out_f32, mean, rstd, \
+                                                   rows, C, ldx, eps, prx_xcd_local(), h16)
+        if (C <= 1024) { if (s16) PRX_LN_FWD_R(4, true); else PRX_LN_FWD_R(4, false); }
+        else { if (s16) PRX_LN_FWD_R(8, true); else PRX_LN_FWD_R(8, false); }      // 1152 ... 1920: ViT-g-14 1408, ViT-bigG-14 1664
 #undef PRX_LN_FWD_R
         PRX_LAUNCH_CHECK();
         return 0;
@@ -457,14 +458,18 @@ int prx_layernorm_fwd(const void* x, long long ldx, const float* gamma, const fl
 int prx_layernorm_bwd(const void* g, long long ldg, const void* x, long long ldx, const float* gamma,
                       const float* mean, const float* rstd, const void* add, long long ldadd, float* dx,
                       long long lddx, bf16_t* dx_bf16, long long lddxb, int rows, int C, hipStream_t s, int h16, int add_every, int s16, int ragged) {
-    PRX_REQUIRE((C % 256 == 0 || (ragged && C % 128 == 0 && C <= 1024)) && C <= 2048, "layernorm bwd: C must be a multiple of 256 and <= 2048 (C=%d)", C);
+    PRX_REQUIRE(C >= 128 && (C % 256 == 0 || (ragged && C % 128 == 0)) && C <= 2048,
+                "layernorm bwd: C must be a multiple of 256 (of 128 in the ragged form) and <= 2048 (C=%d, ragged=%d)", C, ragged);
     PRX_REQUIRE(ldg % 4 == 0 && ldx % 4 == 0 && ldadd % 4 == 0 && (dx || dx_bf16), "layernorm bwd: leading dimensions must be multiples of 4, one output is needed");
     PRX_REQUIRE(s16 == 0 || s16 == 1 || s16 == 2 || s16 == 7, "layernorm bwd: stream layouts in use are 0, 1 (x), 2 (g), 7 (x, g, add): got %d", s16);
     dim3 grid(ceil_div(rows, 4));
     if (C % 256 != 0) {      // ragged last vector: its own instances
-#define PRX_LN_BWD_R(S16) hipLaunchKernelGGL((ln_bwd_kernel<4, S16, true>), grid, dim3(256), 0, s, g, ldg, x, ldx, gamma, mean, rstd, add, ldadd, dx, \
-                                             lddx, dx_bf16, lddxb, rows, C, prx_xcd_local(), h16, add_every)
-        if (s16 == 0) PRX_LN_BWD_R(0); else if (s16 == 1) PRX_LN_BWD_R(1); else if (s16 == 2) PRX_LN_BWD_R(2); else PRX_LN_BWD_R(7);
+#define PRX_LN_BWD_R(MAXV, S16) hipLaunchKernelGGL((ln_bwd_kernel<MAXV, S16, true>), grid, dim3(256), 0, s, g, ldg, x, ldx, gamma, mean, rstd, add, ldadd, dx, \
+                                                   lddx, dx_bf16, lddxb, rows, C, prx_xcd_local(), h16, add_every)
+#define PRX_LN_BWD_RS(MAXV) do { if (s16 == 0) PRX_LN_BWD_R(MAXV, 0); else if (s16 == 1) PRX_LN_BWD_R(MAXV, 1); else if (s16 == 2) PRX_LN_BWD_R(MAXV, 2); \
+                                 else PRX_LN_BWD_R(MAXV, 7); } while (0)
+        if (C <= 1024) PRX_LN_BWD_RS(4); else PRX_LN_BWD_RS(8);
+#undef PRX_LN_BWD_RS
 #undef PRX_LN_BWD_R
         PRX_LAUNCH_CHECK();
         return 0;

@@ -8,10 +8,12 @@ namespace {
 
 // One wave per input row i.  rowloss[i] = sum_j sign(w) * 2*asin(|xn_i - en_j|/2)^2   (forward value, no stop)
 // grad[i][:] = d/dx_i of  |w| * mean_ij max(sign(w)*d_ij, stop)   with mean over `denom` pairs.
+// MAXE: 64-element steps of a row held in registers -- 16 for D <= 1024 (every tower but one), 32 for D <= 2048 (OpenCLIP ViT-bigG-14
+// embeds into 1280)
+template <int MAXE>
 __device__ __forceinline__ float prompt_loss_row(const float* __restrict__ x, const float* __restrict__ embed, int i, int lane,
                                                 int n, int m, int D, float weight, float stop, float denom,
                                                 float* __restrict__ rowloss, float* __restrict__ grad) {
-    constexpr int MAXE = 16;  // D <= 1024
     const int ne = D / 64;
     float xv[MAXE], gacc[MAXE];
     float ss = 0.f;
@@ -69,13 +71,14 @@ __device__ __forceinline__ float prompt_loss_row(const float* __restrict__ x, co
 // One wave per row, four rows per workgroup.  The scalar the loop adds up -- loss = |w| * sum(rowloss) / denom, pixray.py:280 --
 // leaves the same launch (it used to take a torch reduction and a scalar multiply per Prompt and iteration): the workgroup that
 // finishes last (a wrapping ticket counter the caller hands over zeroed; it is zero again once every workgroup drew) adds the row values in a fixed order.
+template <int MAXE>
 __global__ __launch_bounds__(256) void prompt_loss_kernel(const float* __restrict__ x, const float* __restrict__ embed,
                                                           int n, int m, int D, float weight, float stop, float denom,
                                                           float* __restrict__ rowloss, float* __restrict__ grad, float* __restrict__ loss_out,
                                                           unsigned* __restrict__ ticket) {
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i < n) prompt_loss_row(x, embed, i, lane, n, m, D, weight, stop, denom, rowloss, grad);
+    if (i < n) prompt_loss_row<MAXE>(x, embed, i, lane, n, m, D, weight, stop, denom, rowloss, grad);
     if (!loss_out) return;
     __shared__ unsigned last;
     __threadfence();                       // this workgroup's row values are visible device-wide before its ticket is drawn
@@ -263,11 +266,13 @@ __global__ __launch_bounds__(256) void vq_select_kernel(const float* __restrict_
 }  // namespace
 
 int prx_prompt_loss(const float* x, const float* embed, int n, int m, int D, float weight, float stop, float denom,
-                    float* rowloss, float* grad, float* loss, unsigned* ticket, hipStream_t s) {
-    PRX_REQUIRE(D % 64 == 0 && D <= 1024, "prompt_loss: D must be a multiple of 64 and <= 1024 (D=%d)", D);
+                    float* rowloss, float* grad, float* loss, unsigned* ticket, hipStream_t s, int wide) {
+    PRX_REQUIRE(D % 64 == 0 && D <= (wide ? 2048 : 1024), "prompt_loss: D must be a multiple of 64 and <= %d (D=%d)", wide ? 2048 : 1024, D);
     PRX_REQUIRE(!loss || ticket, "prompt_loss: the scalar result needs a zeroed ticket word");
-    hipLaunchKernelGGL(prompt_loss_kernel, dim3(ceil_div(n, 4)), dim3(256), 0, s, x, embed, n, m, D, weight, stop, denom,
-                       rowloss, grad, loss, ticket);
+    if (D <= 1024) hipLaunchKernelGGL(prompt_loss_kernel<16>, dim3(ceil_div(n, 4)), dim3(256), 0, s, x, embed, n, m, D, weight, stop, denom,
+                                      rowloss, grad, loss, ticket);
+    else hipLaunchKernelGGL(prompt_loss_kernel<32>, dim3(ceil_div(n, 4)), dim3(256), 0, s, x, embed, n, m, D, weight, stop, denom,
+                            rowloss, grad, loss, ticket);
     PRX_LAUNCH_CHECK();
     return 0;
 }

@@ -12,9 +12,11 @@ struct VitFamily {
     int act, dact;      // PRX_ACT_* of the c_fc product and of its dgrad
     PatchNorm norm;     // channel mean / std of the fused preprocessing
     int head_dim;       // 0 / 64, or 32 / 16: narrower heads are zero-padded to 64 at weight-packing time (vit.hip PrxVit::hd);
-                        // 80: zero-padded to 96, the attention on the 96-wide instances of attention_kernels.h
+                        // 80 | 88: zero-padded to 96, 104: to 128, the attention on the 96- / 128-wide instances of attention_kernels.h
+    int mlp_width;      // hidden width of the MLP; 0 = 4 * width (OpenCLIP ViT-g-14: 6144 on 1408, ViT-bigG-14: 8192 on 1664)
 };
 VitFamily prx_vit_family_clip();
+int prx_vit_head_cols(int hd);     // operand columns per head for a head dim: {16, 32, 64} -> 64, {80, 88} -> 96, 104 -> 128, else 0
 struct GemmCtx;
 int prx_pack_bf16(const float* in, bf16_t* out, size_t n, hipStream_t s);
 int prx_pack_transpose_bf16(const float* in, bf16_t* out, int R, int C, hipStream_t s);

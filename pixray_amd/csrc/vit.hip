@@ -165,7 +165,10 @@ struct PrxVit {
     // are those of the narrow heads; the price is 64 / head dim times the qkv, attention and out-projection work.
     // Heads of 80 (OpenCLIP ViT-H/14: 16 heads on width 1280) are padded the same way to hp = 96 columns and run on the 96-wide
     // attention family (the 96-wide instances of attention_kernels.h), which takes the softmax scale 1 / sqrt(80) as an argument: nothing is folded into q.
-    int hd, hp, aw;    // head dim of the weights; operand columns per head (64 | 96); attention width = heads * hp (== width when hd == 64)
+    // Heads of 88 (ViT-g-14: 16 heads on width 1408) run there too with 1 / sqrt(88); heads of 104 (ViT-bigG-14: 16 on 1664) are padded to
+    // hp = 128 and run on the 128-wide instances with 1 / sqrt(104) (prx_vit_head_cols below is the mapping).
+    int hd, hp, aw;    // head dim of the weights; operand columns per head (64 | 96 | 128); attention width = heads * hp (== width when hd == 64)
+    int mlp;           // hidden width of the MLP: fam.mlp_width, or 4 * width (every tower but OpenCLIP's ViT-g-14 6144 and ViT-bigG-14 8192)
     int prec;         // PRX_PREC_*: element type of every operand buffer below (void*)
     int f32, h16;     // derived: operands are fp32 / the 16-bit operand format is IEEE half
     float* gs;        // half mode: device {S, 1/S} = the power-of-two scale of the backward in flight (common.h) + 64 partials; else null
@@ -204,10 +207,15 @@ int pack_both(PrxVit* v, void** W, void** WT, const float* src, int out, int in,
 }
 }  // namespace
 
+// operand columns per head of the attention kernels that take a head dim; 0: no kernel
+int prx_vit_head_cols(int hd) {
+    return (hd == 16 || hd == 32 || hd == 64) ? 64 : (hd == 80 || hd == 88) ? 96 : hd == 104 ? 128 : 0;
+}
+
 VitFamily prx_vit_family_clip() {
     VitFamily f;
     f.patch_bias = 0; f.ln_pre = 1; f.eps = 1e-5f; f.act = PRX_ACT_QUICKGELU; f.dact = PRX_ACT_MUL_DQUICKGELU;
-    f.norm = prx_patch_norm_clip(); f.head_dim = 64;
+    f.norm = prx_patch_norm_clip(); f.head_dim = 64; f.mlp_width = 0;
     return f;
 }
 
@@ -219,15 +227,18 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
     PRX_REQUIRE(prec_valid(precision), "vit_create: unknown precision %d", precision);
     PRX_REQUIRE(n_w == n_head + 12 * layers + 3, "vit_create: expected %d weight tensors, got %d", n_head + 12 * layers + 3, n_w);
     const int hd = fam.head_dim > 0 ? fam.head_dim : 64;
-    PRX_REQUIRE(res % patch == 0 && width == heads * hd && width % 128 == 0 && (hd == 64 || hd == 32 || hd == 16 || hd == 80),
-                "vit_create: unsupported geometry (width %d, %d heads of %d)", width, heads, hd);
+    const int hp = prx_vit_head_cols(hd);
+    PRX_REQUIRE(hp != 0, "vit_create: no attention kernel for a head dim of %d (16 | 32 | 64 run at 64 columns, 80 | 88 at 96, 104 at 128)", hd);
+    PRX_REQUIRE(res % patch == 0 && width == heads * hd && width % 128 == 0 && width <= 2048,
+                "vit_create: unsupported geometry (width %d, %d heads of %d; the width must be heads * head dim, a multiple of 128 and <= 2048)", width, heads, hd);
+    const int MW = fam.mlp_width > 0 ? fam.mlp_width : 4 * width;
+    PRX_REQUIRE(MW % 8 == 0, "vit_create: the MLP width %d must be a multiple of 8", MW);
     PRX_REQUIRE(fam.ln_pre || layers >= 1, "vit_create: a tower without ln_pre needs at least one block");
     PRX_REQUIRE(fam.eps > 0.f && fam.norm.std[0] > 0.f && fam.norm.std[1] > 0.f && fam.norm.std[2] > 0.f,
                 "vit_create: LayerNorm eps and the channel std must be positive");
     const int G = res / patch;
     const int T = G * G + 1;
-    const int hp = hd == 80 ? 96 : 64;
-    PRX_REQUIRE(hp == 64 || T <= 640 || prec_is_f32(precision), "vit_create: heads of %d run on the 96-wide attention kernels, which take at most 640 tokens (got %d)", hd, T);
+    PRX_REQUIRE(hp == 64 || T <= 640 || prec_is_f32(precision), "vit_create: heads of %d run on the %d-wide attention kernels, which take at most 640 tokens (got %d)", hd, hp, T);
     std::unique_ptr<PrxVit> guard(new PrxVit());      // a failed create frees what it allocated (DevArena)
     PrxVit* v = guard.get();
     DevArena& m = v->mem;
@@ -238,7 +249,7 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
     v->T = T; v->max_n = max_n;
     v->res = res; v->patch = patch; v->width = width; v->layers = layers; v->heads = heads; v->out_dim = out_dim;
     v->prec = precision; v->f32 = prec_is_f32(precision); v->h16 = prec_is_h16(precision);
-    v->gs = nullptr; v->fam = fam; v->bp = nullptr; v->hd = hd; v->hp = hp; v->aw = heads * hp;
+    v->gs = nullptr; v->fam = fam; v->bp = nullptr; v->hd = hd; v->hp = hp; v->aw = heads * hp; v->mlp = MW;
     const int AW = v->aw;
     float *pad_w = nullptr, *pad_b = nullptr;       // fp32 staging of the padded qkv / out-projection weights, reused by every block (stream order)
     if (hd != 64) {
@@ -295,16 +306,16 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
         if ((r = v->mem.copy_f32(&y.bo, q[5], W, s))) return r;
         if ((r = v->mem.copy_f32(&y.ln2_g, q[6], W, s))) return r;
         if ((r = v->mem.copy_f32(&y.ln2_b, q[7], W, s))) return r;
-        if ((r = pack_both(v, &y.W1, &y.W1T, q[8], 4 * W, W, s))) return r;
-        if ((r = v->mem.copy_f32(&y.b1, q[9], 4 * W, s))) return r;
-        if ((r = pack_both(v, &y.W2, &y.W2T, q[10], W, 4 * W, s))) return r;
+        if ((r = pack_both(v, &y.W1, &y.W1T, q[8], MW, W, s))) return r;
+        if ((r = v->mem.copy_f32(&y.b1, q[9], MW, s))) return r;
+        if ((r = pack_both(v, &y.W2, &y.W2T, q[10], W, MW, s))) return r;
         if ((r = v->mem.copy_f32(&y.b2, q[11], W, s))) return r;
         if (v->lean) { DEV_ALLOC(m, alloc_op, y.x_in, R * W, f32); DEV_ALLOC(m, alloc_op, y.x_mid, R * W, f32); }
         else { float *a_, *b_; DEV_ALLOC(m, alloc, a_, R * W); DEV_ALLOC(m, alloc, b_, R * W); y.x_in = a_; y.x_mid = b_; }
         DEV_ALLOC(m, alloc, y.mean1, R); DEV_ALLOC(m, alloc, y.rstd1, R); DEV_ALLOC(m, alloc, y.mean2, R); DEV_ALLOC(m, alloc, y.rstd2, R);
-        DEV_ALLOC(m, alloc_op, y.qkv, R * 3 * AW, f32); DEV_ALLOC(m, alloc_op, y.t, R * 4 * W, f32);
+        DEV_ALLOC(m, alloc_op, y.qkv, R * 3 * AW, f32); DEV_ALLOC(m, alloc_op, y.t, R * MW, f32);
         y.o_save = nullptr; y.lse = nullptr;
-        if (T > 64 || v->f32 || hp == 96) { DEV_ALLOC(m, alloc_op, y.o_save, R * AW, f32); DEV_ALLOC(m, alloc, y.lse, (size_t)max_n * heads * T); }
+        if (T > 64 || v->f32 || hp != 64) { DEV_ALLOC(m, alloc_op, y.o_save, R * AW, f32); DEV_ALLOC(m, alloc, y.lse, (size_t)max_n * heads * T); }
     }
     const float* const* q = w + n_head + 12 * layers;
     if ((r = v->mem.copy_f32(&v->lnpost_g, q[0], W, s))) return r;
@@ -312,9 +323,9 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
     // proj is [width, out]: forward Bt = proj^T [out, width]; dgrad Bt = proj [width, out]
     if ((r = pack_both(v, &v->proj, &v->projT, q[2], W, out_dim, s))) return r;
     DEV_ALLOC(m, alloc_op, v->A0, R * KP, f32); DEV_ALLOC(m, alloc_op, v->h, R * W, f32);
-    DEV_ALLOC(m, alloc_op, v->att_o, R * AW, f32); DEV_ALLOC(m, alloc_op, v->u, R * 4 * W, f32);
+    DEV_ALLOC(m, alloc_op, v->att_o, R * AW, f32); DEV_ALLOC(m, alloc_op, v->u, R * MW, f32);
     DEV_ALLOC(m, alloc_op, v->hpost, (size_t)max_n * W, f32); DEV_ALLOC(m, alloc_op, v->de16, (size_t)max_n * out_dim, f32);
-    DEV_ALLOC(m, alloc_op, v->dt, R * 4 * W, f32); DEV_ALLOC(m, alloc_op, v->do_, R * AW, f32); DEV_ALLOC(m, alloc_op, v->dqkv, R * 3 * AW, f32);
+    DEV_ALLOC(m, alloc_op, v->dt, R * MW, f32); DEV_ALLOC(m, alloc_op, v->do_, R * AW, f32); DEV_ALLOC(m, alloc_op, v->dqkv, R * 3 * AW, f32);
     DEV_ALLOC(m, alloc, v->xpre, R * W); DEV_ALLOC(m, alloc, v->mean_pre, R); DEV_ALLOC(m, alloc, v->rstd_pre, R);
     if (v->lean) DEV_ALLOC(m, alloc_op, v->x_final, R * W, f32);
     else { float* a_; DEV_ALLOC(m, alloc, a_, R * W); v->x_final = a_; }
@@ -371,7 +382,7 @@ int prx_vit_minmax_impl(PrxVit* v, const float* cutouts, int n, float* mm, hipSt
 
 int prx_vit_forward_impl(PrxVit* v, const float* cutouts, int n, const float* mm, float* embeds, hipStream_t s) {
     PRX_REQUIRE(n >= 1 && n <= v->max_n, "vit: batch %d exceeds handle capacity %d", n, v->max_n);
-    const int W = v->width, T = v->T, R = n * T, KP = v->KP, AW = v->aw;
+    const int W = v->width, T = v->T, R = n * T, KP = v->KP, AW = v->aw, MW = v->mlp;
     int r;
     v->cur_n = n;
     if ((r = prx_patchify_fwd(cutouts, mm, v->A0, v->prec, n, v->res, v->patch, T, s, v->fam.norm))) return r;
@@ -398,9 +409,10 @@ int prx_vit_forward_impl(PrxVit* v, const float* cutouts, int n, const float* mm
             d.bias_n = y.bqkv; d.out_bf16 = y.qkv; d.ldc_bf16 = 3 * AW;
             if ((r = vit_gemm(v, d, s))) return r; }
         const void* att = v->att_o;
-        if (v->hp == 96) {
-            if (v->f32) { if ((r = prx_mha_fwd_f32_hd96((const float*)y.qkv, (float*)y.o_save, y.lse, n, T, AW, v->heads, s))) return r; }
-            else if ((r = prx_mha_fwd_hd96((const bf16_t*)y.qkv, (bf16_t*)y.o_save, y.lse, n, T, AW, v->heads, 1.f / sqrtf((float)v->hd), s, v->h16))) return r;
+        if (v->hp != 64) {
+            if (v->f32) { if ((r = prx_mha_fwd_f32_pad((const float*)y.qkv, (float*)y.o_save, y.lse, n, T, AW, v->heads, v->hd, s))) return r; }
+            else if (v->hp == 96) { if ((r = prx_mha_fwd_hd96((const bf16_t*)y.qkv, (bf16_t*)y.o_save, y.lse, n, T, AW, v->heads, 1.f / sqrtf((float)v->hd), s, v->h16))) return r; }
+            else if ((r = prx_mha_fwd_hd128((const bf16_t*)y.qkv, (bf16_t*)y.o_save, y.lse, n, T, AW, v->heads, 1.f / sqrtf((float)v->hd), s, v->h16))) return r;
             att = y.o_save;
         }
         else if (v->f32) { if ((r = prx_mha_fwd_f32((const float*)y.qkv, (float*)y.o_save, y.lse, n, T, AW, v->heads, s))) return r; att = y.o_save; }
@@ -417,15 +429,15 @@ int prx_vit_forward_impl(PrxVit* v, const float* cutouts, int n, const float* mm
             else { d.resid = (const float*)y.x_in; d.out_f32 = (float*)y.x_mid; d.ldc_f32 = ldt; }
             if ((r = vit_gemm(v, d, s))) return r; }
         if ((r = ln_op(v, y.x_mid, ldt, y.ln2_g, y.ln2_b, v->h, y.mean2, y.rstd2, rows, s))) return r;
-        {   GemmDesc d; d.A = v->h; d.lda = W; d.B = y.W1; d.ldb = W; d.M = rows; d.N = 4 * W; d.K = W;
-            d.bias_n = y.b1; d.act = v->fam.act; d.out_bf16 = v->u; d.out_bf16_pre = y.t; d.ldc_bf16 = 4 * W;
+        {   GemmDesc d; d.A = v->h; d.lda = W; d.B = y.W1; d.ldb = W; d.M = rows; d.N = MW; d.K = W;
+            d.bias_n = y.b1; d.act = v->fam.act; d.out_bf16 = v->u; d.out_bf16_pre = y.t; d.ldc_bf16 = MW;
             const bool own_pass = v->f32 && v->fam.act == PRX_ACT_GELU;      // see gelu_f32_kernel
             if (own_pass) { d.act = PRX_ACT_NONE; d.out_bf16 = y.t; d.out_bf16_pre = nullptr; }
             if ((r = vit_gemm(v, d, s))) return r;
             if (own_pass) {
-                if ((r = prx_vit_gelu_f32((const float*)y.t, (float*)v->u, (size_t)rows * 4 * W, 0, s))) return r;
+                if ((r = prx_vit_gelu_f32((const float*)y.t, (float*)v->u, (size_t)rows * MW, 0, s))) return r;
             } }
-        {   GemmDesc d; d.A = v->u; d.lda = 4 * W; d.B = y.W2; d.ldb = 4 * W; d.M = rows; d.N = W; d.K = 4 * W;
+        {   GemmDesc d; d.A = v->u; d.lda = MW; d.B = y.W2; d.ldb = MW; d.M = rows; d.N = W; d.K = MW;
             d.bias_n = y.b2; d.ldr = ldt;
             if (lean) { d.resid = (const float*)y.x_mid; d.row16 = 1; d.out_bf16 = x_next; d.ldc_bf16 = ldt; }
             else { d.resid = (const float*)y.x_mid; d.out_f32 = (float*)x_next; d.ldc_f32 = ldt; }
@@ -446,7 +458,7 @@ int prx_vit_backward_a_impl(PrxVit* v, const float* cutouts, const float* mm, co
                             hipStream_t s) {
     const int n = v->cur_n;
     PRX_REQUIRE(n >= 1, "vit backward: no forward in flight on this handle");
-    const int W = v->width, T = v->T, R = n * T, KP = v->KP, AW = v->aw;
+    const int W = v->width, T = v->T, R = n * T, KP = v->KP, AW = v->aw, MW = v->mlp;
     int r;
     if ((r = prx_l2norm_bwd(v->e, d_embeds, v->de, n, v->out_dim, s))) return r;
     {   GemmDesc d; d.A = v->de; d.a_is_f32 = 1; d.lda = v->out_dim; d.B = v->proj; d.ldb = v->out_dim;
@@ -480,15 +492,15 @@ int prx_vit_backward_a_impl(PrxVit* v, const float* cutouts, const float* mm, co
         const int rows = tail ? n : R;
         const int ldt = tail ? T * W : W;
         // MLP: x_next = x_mid + c_proj(act(c_fc(ln_2(x_mid)))), act = QuickGELU (CLIP) | GELU (SLIP)
-        {   GemmDesc d; d.A = v->dx_bf; d.lda = ldt; d.B = y.W2T; d.ldb = W; d.M = rows; d.N = 4 * W; d.K = W;
-            d.act = v->fam.dact; d.aux = y.t; d.ldaux = 4 * W; d.out_bf16 = v->dt; d.ldc_bf16 = 4 * W;
+        {   GemmDesc d; d.A = v->dx_bf; d.lda = ldt; d.B = y.W2T; d.ldb = W; d.M = rows; d.N = MW; d.K = W;
+            d.act = v->fam.dact; d.aux = y.t; d.ldaux = MW; d.out_bf16 = v->dt; d.ldc_bf16 = MW;
             const bool own_pass = v->f32 && v->fam.dact == PRX_ACT_MUL_DGELU;      // see gelu_f32_kernel
             if (own_pass) { d.act = PRX_ACT_NONE; d.aux = nullptr; }
             if ((r = vit_gemm(v, d, s))) return r;
             if (own_pass) {
-                if ((r = prx_vit_gelu_f32((const float*)y.t, (float*)v->dt, (size_t)rows * 4 * W, 1, s))) return r;
+                if ((r = prx_vit_gelu_f32((const float*)y.t, (float*)v->dt, (size_t)rows * MW, 1, s))) return r;
             } }
-        {   GemmDesc d; d.A = v->dt; d.lda = 4 * W; d.B = y.W1T; d.ldb = 4 * W; d.M = rows; d.N = W; d.K = 4 * W;
+        {   GemmDesc d; d.A = v->dt; d.lda = MW; d.B = y.W1T; d.ldb = MW; d.M = rows; d.N = W; d.K = MW;
             if (lean) { d.out_bf16 = v->dh_bf; d.ldc_bf16 = W; } else { d.out_f32 = v->dh; d.ldc_f32 = W; }
             if ((r = vit_gemm(v, d, s))) return r; }
         if ((r = ln_bwd_op(v, dhs, W, y.x_mid, ldt, y.ln2_g, y.mean2, y.rstd2, dxs, ldt, v->dx, ldt, v->dx_bf, rows, s, 0, lean ? 7 : 0))) return r;
@@ -498,10 +510,12 @@ int prx_vit_backward_a_impl(PrxVit* v, const float* cutouts, const float* mm, co
         {   GemmDesc d; d.A = v->dx_bf; d.lda = ldt; d.B = y.WoT; d.ldb = W; d.M = rows; d.N = AW; d.K = W;
             d.out_bf16 = v->do_; d.ldc_bf16 = tail ? T * AW : AW;
             if ((r = vit_gemm(v, d, s))) return r; }
-        if (v->hp == 96) {
-            if (v->f32) { if ((r = prx_mha_bwd_f32_hd96((const float*)y.qkv, (const float*)y.o_save, (const float*)v->do_, y.lse, (float*)v->dqkv, n, T, AW, v->heads, s))) return r; }
-            else if ((r = prx_mha_bwd_hd96((const bf16_t*)y.qkv, (const bf16_t*)y.o_save, (const bf16_t*)v->do_, y.lse, (bf16_t*)v->dqkv, n, T, AW, v->heads,
-                                           1.f / sqrtf((float)v->hd), s, v->h16))) return r;
+        if (v->hp != 64) {
+            if (v->f32) { if ((r = prx_mha_bwd_f32_pad((const float*)y.qkv, (const float*)y.o_save, (const float*)v->do_, y.lse, (float*)v->dqkv, n, T, AW, v->heads, v->hd, s))) return r; }
+            else if (v->hp == 96) { if ((r = prx_mha_bwd_hd96((const bf16_t*)y.qkv, (const bf16_t*)y.o_save, (const bf16_t*)v->do_, y.lse, (bf16_t*)v->dqkv, n, T, AW, v->heads,
+                                                              1.f / sqrtf((float)v->hd), s, v->h16))) return r; }
+            else if ((r = prx_mha_bwd_hd128((const bf16_t*)y.qkv, (const bf16_t*)y.o_save, (const bf16_t*)v->do_, y.lse, (bf16_t*)v->dqkv, n, T, AW, v->heads,
+                                            1.f / sqrtf((float)v->hd), s, v->h16))) return r;
         }
         else if (v->f32) { if ((r = prx_mha_bwd_f32((const float*)y.qkv, (const float*)y.o_save, (const float*)v->do_, y.lse, (float*)v->dqkv, n, T, AW, v->heads, s))) return r; }
         else if (T <= 64) { if ((r = prx_mha_bwd((const bf16_t*)y.qkv, (const bf16_t*)v->do_, (bf16_t*)v->dqkv, n, T, AW, v->heads, s, v->h16))) return r; }

@@ -199,7 +199,9 @@ class SlipVitHandle(ClipVitHandle):
 
 class OpenClipVitHandle(ClipVitHandle):
     """A `prx_clip_vit` made by `prx_vit_tower_create` for the OpenCLIP (LAION) family: CLIP's tensors and switches with the exact
-    GELU; heads of 80 (ViT-H-14) are zero-padded to 96 columns by the runner and run on the 96-wide attention kernels."""
+    GELU; heads of 80 (ViT-H-14) and 88 (ViT-g-14) are zero-padded to 96 columns by the runner and run on the 96-wide attention kernels,
+    heads of 104 (ViT-bigG-14) to 128 columns on the 128-wide ones.  A configuration whose MLP is not 4 x width (`cfg.mlp_width`) goes
+    through `prx_vit_tower_create_mlp`."""
 
     def __init__(self, cfg, params, max_batch: int, device, precision=None):
         from .perceptor import ClipVitPerceptor
@@ -210,7 +212,11 @@ class OpenClipVitHandle(ClipVitHandle):
                          VIT_FAMILY_OPENCLIP, cfg.head_dim, 1e-5, (ctypes.c_float * 3)(*ClipVitPerceptor.CLIP_MEAN),
                          (ctypes.c_float * 3)(*ClipVitPerceptor.CLIP_STD))
         h = ctypes.c_void_p()
-        call("prx_vit_tower_create", ctypes.addressof(h), ctypes.addressof(c), _keep(self, _weight_array(ws)), len(ws), _stream())
+        if getattr(cfg, "mlp_width", 0):
+            call("prx_vit_tower_create_mlp", ctypes.addressof(h), ctypes.addressof(c), int(cfg.mlp_width), _keep(self, _weight_array(ws)), len(ws),
+                 _stream())
+        else:
+            call("prx_vit_tower_create", ctypes.addressof(h), ctypes.addressof(c), _keep(self, _weight_array(ws)), len(ws), _stream())
         torch.cuda.synchronize(device)   # weight tensors may now be released
         self.h = h
         self.cfg = cfg
@@ -617,7 +623,9 @@ class _PromptLossFn(torch.autograd.Function):
         rowloss = torch.empty(n + 1, device=x.device)          # [n] row values, then the scalar |w| * sum / denom from the same launch
         grad = torch.empty_like(x)
         den = float(denom) if denom is not None else float(n * m)
-        call("prx_prompt_loss_fwd_bwd", x, e, n, m, D, float(weight), float(stop), den, rowloss, grad, rowloss[n:], _ticket(x.device), _stream())
+        # (embeddings wider than 1024 -- OpenCLIP ViT-bigG-14: 1280 -- take the entry point whose cap is 2048)
+        call("prx_prompt_loss_fwd_bwd" if D <= 1024 else "prx_prompt_loss_fwd_bwd_wide", x, e, n, m, D, float(weight), float(stop), den, rowloss, grad,
+             rowloss[n:], _ticket(x.device), _stream())
         ctx.save_for_backward(grad)
         return rowloss[n]
 

@@ -27,7 +27,7 @@ class ClipVitPerceptor:
         self.group = group          # torch.distributed group when the cutout batch is sharded
         if isinstance(cfg, SlipVitConfig):          # SLIP family: the ViT runner through its tower-family constructor
             self.handle = ops.SlipVitHandle(cfg, params, max_batch, self.device, precision=precision)
-        elif isinstance(cfg, OpenClipVitConfig):    # OpenCLIP (LAION) family: CLIP's tower with the exact GELU, heads of 64 or 80
+        elif isinstance(cfg, OpenClipVitConfig):    # OpenCLIP (LAION) family: CLIP's tower with the exact GELU, heads of 64, 80, 88 or 104
             self.handle = ops.OpenClipVitHandle(cfg, params, max_batch, self.device, precision=precision)
         elif isinstance(cfg, ClipResNetConfig):     # ModifiedResNet family (RN50x4, ...): same protocol, different runner
             self.handle = ops.ClipResNetHandle(cfg, params, max_batch, self.device, precision=precision)
@@ -149,12 +149,12 @@ def slip_checkpoint_path(name, root="models"):
     return path if os.path.exists(path) else None
 
 
-def clip_perceptor_config(clip_model_name):
+def perceptor_config(clip_model_name):
     """-> (vision configuration, text configuration or None) of a perceptor name: every `clip.available_models()` name (RN50, RN101,
-    RN50x4, RN50x16, RN50x64, ViT-B/32, ViT-B/16, ViT-L/14, ViT-L/14@336px), the OpenCLIP names (ViT-B-32, ViT-B-16, ViT-L-14, ViT-H-14;
-    convnext_base, convnext_base_w, convnext_base_w_320, convnext_large_d, convnext_large_d_320, convnext_xxlarge), the SLIP family and
-    the reduced test towers.  Needs no device:
-    the front end reads the cutout size of a name from here before any tower exists."""
+    RN50x4, RN50x16, RN50x64, ViT-B/32, ViT-B/16, ViT-L/14, ViT-L/14@336px), the OpenCLIP names (ViT-B-32, ViT-B-16, ViT-L-14, ViT-H-14,
+    ViT-g-14, ViT-bigG-14; convnext_base, convnext_base_w, convnext_base_w_320, convnext_large_d, convnext_large_d_320, convnext_xxlarge),
+    the SLIP family and the reduced test towers.  Needs no device: the front end reads the cutout size of a name from here before any
+    tower exists."""
     if clip_model_name in SLIP_REFUSED:
         raise ValueError(SLIP_REFUSED[clip_model_name])
     for table in (CLIP_RESNET_CONFIGS, SLIP_CONFIGS, CLIP_CONFIGS, OPENCLIP_CONFIGS, CLIP_CONVNEXT_CONFIGS):
@@ -164,12 +164,22 @@ def clip_perceptor_config(clip_model_name):
                    f"(supported: {sorted(CLIP_CONFIGS) + sorted(OPENCLIP_CONFIGS) + sorted(CLIP_CONVNEXT_CONFIGS) + sorted(CLIP_RESNET_CONFIGS) + sorted(SLIP_CONFIGS)})")
 
 
+def clip_perceptor_config(clip_model_name):
+    """`perceptor_config` for the towers whose MLP is 4 x width -- every name it served before OpenCLIP's ViT-g-14 and ViT-bigG-14
+    existed here.  Its callers may rely on that ratio (and tests/test_openclip_cpu.py pins that it does not know the two names), so a
+    configuration that carries an MLP width of its own is refused in the same words as an unknown name: ask `perceptor_config`."""
+    cfg, text_cfg = perceptor_config(clip_model_name)
+    if getattr(cfg, "mlp_width", 0):
+        raise KeyError(f"unknown / unsupported perceptor {clip_model_name!r} here: its MLP is not 4 x width, use perceptor_config")
+    return cfg, text_cfg
+
+
 def get_clip_perceptor(clip_model_name, device, params=None, max_batch=64, seed=0, group=None, text_params=None,
                        tokenizer=None, precision=None):
     """slip.py:173-186 equivalent; `params` is an OpenAI `visual.*` state dict and `text_params` the
     text-side entries of the same checkpoint (random-init weights of the real architectures are synthesised when none
     are given: no checkpoints exist offline).  `precision`: "fp16" (default) | "bf16" (fast paths) | "f32" (exact-f32 MFMA parity mode)."""
-    cfg, text_cfg = clip_perceptor_config(clip_model_name)
+    cfg, text_cfg = perceptor_config(clip_model_name)
     if clip_model_name in CLIP_RESNET_CONFIGS:
         if params is None:
             params = synthetic_clip_resnet_params(cfg, seed)

@@ -226,6 +226,7 @@ CLIP_CONFIGS = {
 
 def clip_vit_param_shapes(cfg: ClipVitConfig) -> "OrderedDict[str, Tuple[int, ...]]":
     w = cfg.width
+    m = getattr(cfg, "mlp", 4 * w)          # hidden width of the MLP: 4 x width everywhere but OpenCLIP's ViT-g-14 / ViT-bigG-14
     sh: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
     sh["conv1.weight"] = (w, 3, cfg.patch_size, cfg.patch_size)
     sh["class_embedding"] = (w,)
@@ -237,8 +238,8 @@ def clip_vit_param_shapes(cfg: ClipVitConfig) -> "OrderedDict[str, Tuple[int, ..
         sh[p + "attn.in_proj_weight"] = (3 * w, w); sh[p + "attn.in_proj_bias"] = (3 * w,)
         sh[p + "attn.out_proj.weight"] = (w, w); sh[p + "attn.out_proj.bias"] = (w,)
         sh[p + "ln_2.weight"] = (w,); sh[p + "ln_2.bias"] = (w,)
-        sh[p + "mlp.c_fc.weight"] = (4 * w, w); sh[p + "mlp.c_fc.bias"] = (4 * w,)
-        sh[p + "mlp.c_proj.weight"] = (w, 4 * w); sh[p + "mlp.c_proj.bias"] = (w,)
+        sh[p + "mlp.c_fc.weight"] = (m, w); sh[p + "mlp.c_fc.bias"] = (m,)
+        sh[p + "mlp.c_proj.weight"] = (w, m); sh[p + "mlp.c_proj.bias"] = (w,)
     sh["ln_post.weight"] = (w,); sh["ln_post.bias"] = (w,)
     sh["proj"] = (w, cfg.output_dim)
     return sh
@@ -272,17 +273,26 @@ def synthetic_clip_vit_params(cfg: ClipVitConfig, seed: int = 0) -> "OrderedDict
 
 
 # --------------------------------------------------------------------------- OpenCLIP (LAION) ViT towers
-# [UPSTREAM mlfoundations/open_clip src/open_clip/model_configs/{ViT-B-32,ViT-B-16,ViT-L-14,ViT-H-14}.json; the package is not
+# [UPSTREAM mlfoundations/open_clip src/open_clip/model_configs/{ViT-B-32,ViT-B-16,ViT-L-14,ViT-H-14,ViT-g-14,ViT-bigG-14}.json; the package is not
 # installed, so the geometry is restated from the published configs, parity unpinned].  OpenCLIP spells its names with hyphens, which
 # keeps them apart from OpenAI's towers of the same geometry.  Against those: the exact (erf) GELU instead of QuickGELU (the LAION
 # checkpoints are trained without "quick_gelu"), on both the image and the text side; same tensors, same state-dict names, CLIP's
 # preprocessing constants.  ViT-H-14 has 16 heads of 80 on width 1280: the runner pads them to 96 columns (csrc/attention.hip, the 96-wide instances).
-# ViT-g-14 (width 1408) and ViT-bigG-14 (width 1664) are not provided: LayerNorm needs a width that is a multiple of 256.
+# ViT-g-14 (width 1408 = 11 x 128, 16 heads of 88, MLP 6144) and ViT-bigG-14 (width 1664 = 13 x 128, 16 heads of 104, MLP 8192) are the
+# two whose MLP is not 4 x width (mlp_ratio 4.3637 / 4.9231 in the configs): the hidden width is carried here.  Their widths run on
+# the ragged LayerNorm instances (csrc/norms.hip, MAXV = 8); heads of 88 are padded to 96 columns, heads of 104 to 128 (the 128-wide
+# instances of the same attention family).
 @dataclass
 class OpenClipVitConfig(ClipVitConfig):
+    mlp_width: int = 0              # hidden width of the MLP; 0 = 4 x width
+
     @property
     def head_dim(self) -> int:
         return self.width // self.heads
+
+    @property
+    def mlp(self) -> int:
+        return self.mlp_width or 4 * self.width
 
 
 OPENCLIP_CONFIGS = {
@@ -293,6 +303,14 @@ OPENCLIP_CONFIGS = {
     # reduced towers with heads of 80 (same operators, 2 layers; 640 is the smallest width that is a multiple of 80 and of 128)
     "tiny-H-32": OpenClipVitConfig("tiny-H-32", 224, 32, 640, 2, 8, 128),              # 50 tokens
     "tiny-H-14": OpenClipVitConfig("tiny-H-14", 224, 14, 640, 2, 8, 128),              # 257 tokens
+    "ViT-g-14": OpenClipVitConfig("ViT-g-14", 224, 14, 1408, 40, 16, 1024, mlp_width=6144),        # 257 tokens, heads of 88
+    "ViT-bigG-14": OpenClipVitConfig("ViT-bigG-14", 224, 14, 1664, 48, 16, 1280, mlp_width=8192),  # 257 tokens, heads of 104
+    # reduced towers with heads of 88 / 104: lcm(88, 128) = 1408 and lcm(104, 128) = 1664, so the real width is the smallest width that
+    # has these heads -- the depth is what is reduced (2 layers, the real MLP width)
+    "tiny-g-32": OpenClipVitConfig("tiny-g-32", 224, 32, 1408, 2, 16, 128, mlp_width=6144),        # 50 tokens
+    "tiny-g-14": OpenClipVitConfig("tiny-g-14", 224, 14, 1408, 2, 16, 128, mlp_width=6144),        # 257 tokens
+    "tiny-bigG-32": OpenClipVitConfig("tiny-bigG-32", 224, 32, 1664, 2, 16, 128, mlp_width=8192),  # 50 tokens
+    "tiny-bigG-14": OpenClipVitConfig("tiny-bigG-14", 224, 14, 1664, 2, 16, 128, mlp_width=8192),  # 257 tokens
 }
 OPENCLIP_SEED = 7919            # the synthetic weights of `ViT-B-32` are not those of `ViT-B/32`
 
@@ -432,7 +450,11 @@ CLIP_TEXT_CONFIGS.update({
     "ViT-H-14": OpenClipTextConfig("ViT-H-14", width=1024, layers=24, heads=16, output_dim=1024),
     "tiny-H-32": OpenClipTextConfig("tiny-H-32", vocab_size=1000, context_length=77, width=256, layers=2, heads=4, output_dim=128),
     "tiny-H-14": OpenClipTextConfig("tiny-H-14", vocab_size=1000, context_length=77, width=256, layers=2, heads=4, output_dim=128),
+    "ViT-g-14": OpenClipTextConfig("ViT-g-14", width=1024, layers=24, heads=16, output_dim=1024),         # ViT-H-14's text geometry
+    "ViT-bigG-14": OpenClipTextConfig("ViT-bigG-14", width=1280, layers=32, heads=20, output_dim=1280),   # MLP 5120 = 4 x width
 })
+for _n in ("tiny-g-32", "tiny-g-14", "tiny-bigG-32", "tiny-bigG-14"):
+    CLIP_TEXT_CONFIGS[_n] = OpenClipTextConfig(_n, vocab_size=1000, context_length=77, width=256, layers=2, heads=4, output_dim=128)
 # every SLIP model size carries CLIP's text transformer at width 512 / 8 heads / 12 layers [UPSTREAM SLIP models.py]
 CLIP_TEXT_CONFIGS.update({n: ClipTextConfig(n) for n in ("SLIP_VITS16", "SLIP_VITB16", "SLIP_VITL16", "SLIP_CC3M", "SLIP_CC12M",
                                                          "CLIP_VITS16", "CLIP_VITB16", "CLIP_VITL16")})

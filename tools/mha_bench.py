@@ -6,6 +6,8 @@
                                          # include/prx.h); prints every round, the medians, each route's spread and the verdict
     python tools/mha_bench.py --hd96 257 --cutouts 16   # the 96-wide family (heads of 80 zero-padded, OpenCLIP ViT-H-14: 16 heads) alone:
                                          # every round, the median and the spread; a single measured value, not a comparison
+    python tools/mha_bench.py --hdim 257 --cutouts 16   # head dims 80 and 88 (96 columns: ViT-H-14, ViT-g-14) and 104 (128 columns:
+                                         # ViT-bigG-14) one after the other in one process
 The A/B verdict follows the rule for comparing two timings: a route is "faster" in a direction only if the gap between the medians
 exceeds the larger of the two spreads (max - min over the rounds) measured in this very run."""
 import argparse
@@ -118,6 +120,31 @@ def hd96(T, N, heads, rounds, iters):
                   f"   median {med:8.1f} us  spread {max(ts) - min(ts):6.1f} us  ({fl / med / 1e6:6.1f} TFLOP/s on the live columns)")
 
 
+def hdim(T, N, heads, rounds, iters, hd):
+    """prx_k_mha_{fwd,bwd}_hdim_op at head dim hd in its operand columns (80 | 88 in 96, 104 in 128; the pad columns zero), both formats"""
+    cols = {80: 96, 88: 96, 104: 128}[hd]
+    C = cols * heads
+    for dtype in (torch.float16, torch.bfloat16):
+        g = torch.Generator(device=DEV).manual_seed(0)
+        qkv = torch.randn(N * T, 3, heads, cols, device=DEV, generator=g)
+        do = torch.randn(N * T, heads, cols, device=DEV, generator=g)
+        qkv[..., hd:] = 0
+        do[..., hd:] = 0
+        qkv, do = qkv.to(dtype), do.to(dtype)
+        out = torch.empty(N * T, C, dtype=dtype, device=DEV)
+        lse = torch.empty(N * heads * T, device=DEV)
+        dqkv = torch.empty(N * T, 3 * C, dtype=dtype, device=DEV)
+        h16 = 1 if dtype == torch.float16 else 0
+        fwd = lambda: call("prx_k_mha_fwd_hdim_op", qkv, out, lse, N, T, C, heads, h16, cols, hd, stream())
+        bwd = lambda: call("prx_k_mha_bwd_hdim_op", qkv, out, do, lse, dqkv, N, T, C, heads, h16, cols, hd, stream())
+        flop_f = 4.0 * N * heads * T * T * hd            # algorithmic: the live columns
+        for d, fn, fl in (("fwd", fwd, flop_f), ("bwd", bwd, 2.5 * flop_f)):
+            ts = [time_us(fn, iters) for _ in range(rounds)]
+            med = statistics.median(ts)
+            print(f"  head dim {hd} in {cols} columns N={N} T={T} heads={heads} {str(dtype):15s} {d}: " + " ".join(f"{t:8.1f}" for t in ts) +
+                  f"   median {med:8.1f} us  spread {max(ts) - min(ts):6.1f} us  ({fl / med / 1e6:6.1f} TFLOP/s on the live columns)")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--ab", type=int, default=0, metavar="T", help="A/B the two routes at T tokens (64 < T <= 640)")
@@ -126,8 +153,12 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=500)
     ap.add_argument("--hd96", type=int, default=0, metavar="T", help="time the 96-wide family at T tokens (T <= 640)")
+    ap.add_argument("--hdim", type=int, default=0, metavar="T", help="time head dims 80, 88 (96 columns) and 104 (128 columns) side by side at T tokens")
     a = ap.parse_args()
-    if a.hd96:
+    if a.hdim:
+        for hd in (80, 88, 104):
+            hdim(a.hdim, a.cutouts, a.heads, a.rounds, a.iters, hd)
+    elif a.hd96:
         hd96(a.hd96, a.cutouts, a.heads, a.rounds, a.iters)
     elif a.ab:
         ab(a.ab, a.cutouts, a.heads, a.rounds, a.iters)

@@ -35,6 +35,8 @@ def tower_flops(name):
 def time_tower(name, n, iters, warmup, precision):
     """median over `iters` rounds of the time of one forward + backward pass; every round is timed between two HIP events on the
     launch stream, so host launch overhead that the device does not hide is part of the figure"""
+    torch.cuda.init()
+    free0 = torch.cuda.mem_get_info()[0]
     perc = get_clip_perceptor(name, "cuda", max_batch=n, precision=precision)
     g = torch.Generator().manual_seed(1)
     R = perc.input_resolution             # 224 for the ViT towers; --towers also takes the ConvNeXt names (256, 320: tools/convnext_bench.py)
@@ -51,8 +53,9 @@ def time_tower(name, n, iters, warmup, precision):
         if it >= warmup:
             times.append(a.elapsed_time(b))
     assert torch.isfinite(gc).all()
+    torch.cuda.empty_cache()              # what stays is the handles' own device memory (weights + activations for n cutouts) and `cut`
     row = {"tower": name, "cutouts": n, "precision": precision, "passes": iters, "median_ms": statistics.median(times),
-           "min_ms": min(times), "max_ms": max(times)}
+           "min_ms": min(times), "max_ms": max(times), "device_gib_in_use": (free0 - torch.cuda.mem_get_info()[0]) / 2 ** 30}
     try:
         alg, run = tower_flops(name)
         row.update(fwd_gflop_per_cutout_algorithmic=alg / 1e9, fwd_gflop_per_cutout_executed=run / 1e9, executed_over_algorithmic=run / alg)
