@@ -301,6 +301,13 @@ int prx_k_warp_b_fwd(const float* a, int Ha, int Wa, const double* desc, const f
                      prx_stream_t s);
 int prx_k_warp_b_bwd(const float* a, int Ha, int Wa, const double* desc, const float* g, float* grgb, float* uv, float* ga, int n_cut,
                      int S, float* maps_scratch, size_t maps_scratch_bytes, int form, prx_stream_t s);
+/* Form 0 of the two warp backwards runs the tiles of an axis-aligned affine stage under zeros / fill padding through a separable
+ * gather (two 1-D coordinate tables, proved exact per tile) and every other tile through the scatter.  prx_cutout_bwd_separable
+ * switches that path for the following launches of the process (a captured graph keeps the value it was captured with):
+ * 0: off, form 0 is exactly the scatter; 1: on, the sums in the per-pixel gather's order (equal to form 2 bit for bit); 2: on, the
+ * same terms in the scatter's order (equal to setting 0 bit for bit: the iteration keeps its bits); -1: query.  Returns the previous
+ * value.  Default 2; PRX_CUTOUT_BWD_SEP=0 / =1 in the environment start the process at 0 / 1. */
+int prx_cutout_bwd_separable(int on);
 /* VGG16 extractor (vgg.hip) */
 int prx_k_vgg_pack(const float* w, void* Wf, void* Wd, int Cout, int Cin, int CiP, int prec, prx_stream_t s);
 int prx_k_vgg_input(const float* x, void* out, int HW, int prec, prx_stream_t s);

@@ -17,6 +17,7 @@
 // ColorJitter Jacobian is obtained with forward-mode duals.
 #include "cutouts.h"
 #include <algorithm>
+#include <atomic>
 #include <stdlib.h>
 #include <stdio.h>
 
@@ -698,10 +699,37 @@ struct TileRects {
     float ua[MAXR * MAXR], ub[MAXR * MAXR], va[MAXR * MAXR], vb[MAXR * MAXR];
     int x0[MAXR * MAXR], y0[MAXR * MAXR], bw[MAXR * MAXR], cnt[MAXR * MAXR];
 };
+// ---- separable tiles of form 0 (separable_tile below): an axis-aligned affine stage under zeros / fill padding -------------
+constexpr int SEP_CAP = 80;                  // table entries per axis: 18 source pixels at x4 magnification are 72 destination pixels,
+                                             // + 4 for the search margins (eps, +-0.25, floor / ceil) and 4 to spare; x6 (108) falls back
+constexpr int SEP_G_CAP = 1600;              // destination pixels of a box whose gradients are staged in LDS (40 x 40: 18.75 KB); a
+                                             // larger box is read through L2.  The headline's boxes (x1 .. x2: <= 39 x 39) all fit
+// Pre-filter on the matrix's off-diagonal words.  It decides nothing about exactness (the two-ends check of separable_tile does);
+// it only keeps blocks whose check is bound to fail from loading tables first.  The off-diagonal term moves the fp64 grid value by
+// at most |m| (the base grid lies in [-1, 1]); the fp32 grid value it is rounded to has a spacing of 2^-24 relative, so an |m|
+// of 2^-40 moves it by 2^-16 of that spacing -- a check fails on one entry in ~65 000 -- while anything from ~2^-25 upwards
+// (1e-6 is 2^-20) changes most entries.  What the 8 x 8 solve of the resized crop leaves behind is |m| <= 1e-16 = 2^-53.
+constexpr double SEP_OFFDIAG = 0x1p-40;
+__device__ __forceinline__ bool separable_stage(const double* m, int gtype, int mode) {
+    if (gtype != GRID_AFFINE && gtype != GRID_AFFINE_AC) return false;
+    if (mode != MODE_ZEROS && mode != MODE_FILL) return false;
+    return fabs(m[1]) <= SEP_OFFDIAG && fabs(m[3]) <= SEP_OFFDIAG;        // a NaN fails
+}
+struct TileSeparable {
+    float u[SEP_CAP], v[SEP_CAP];            // the forward's raw coordinate of the box's columns / rows
+    int xlo[TILE_W], xhi[TILE_W];            // per source column of the tile: first / last table entry with a non-zero weight
+    int ylo[TILE_W], yhi[TILE_W];            // per source row
+    int differs[4];                          // per wave: a table entry was not the same at both ends
+};
+
 struct TileScatter {                         // form 0: rectangles compacted to the first nrect slots
     int nrect;
     TileRects rect;
-    float acc[4][3][TILE_W * TILE_W];        // one accumulator plane set per wave
+    union {
+        float acc[4][3][TILE_W * TILE_W];    // one accumulator plane set per wave
+        float g[3][SEP_G_CAP];               // separable tile: the gradient planes over the box
+    };
+    TileSeparable sep;
 };
 struct WaveScatter {                         // form 1: rectangle (i, j) in slot 3 j + i, cnt == 0 where there is none
     TileRects rect;
@@ -790,6 +818,159 @@ __device__ __forceinline__ void scatter_tile(const GatherStage& st, const StageM
     __syncthreads();
 #pragma unroll
     for (int c = 0; c < 3; ++c) out[c] = ((ts.acc[0][c][tid] + ts.acc[1][c][tid]) + ts.acc[2][c][tid]) + ts.acc[3][c][tid];
+}
+
+// form 0, separable tile: the same sums for a stage that separable_stage() let through.  Where u depends on x alone and v on y
+// alone, the destination pixels that touch source pixel (sx, sy) are [a run of columns] x [a run of rows], and the weight of
+// (x, y) is tap_weight(v[y], sy) * tap_weight(u[x], sx): no pre-image geometry per pixel, no accumulator in LDS.
+//   * box: the destination box of the tile's raw rectangle, as scatter_tile bounds its search (one preimage_box); more than
+//     SEP_CAP columns or rows -> false;
+//   * tables: u[x] from the box's first destination row, v[y] from its first column, read from the uv map (the forward's own
+//     coordinates), and compared BIT FOR BIT with the last row / last column.  project() is monotone in the other coordinate (the
+//     base grid, the product with the matrix word, the two additions, the conversion and the unnormalisation are each a correctly
+//     rounded monotone operation; no fma contraction in this file), so equal ends mean the coordinate is constant in between: the
+//     tables are then exactly what every pixel of the box holds, whatever noise the off-diagonal words carry.  Any entry that
+//     differs -> false;
+//   * per source column / row the first and the last table entry with a non-zero tap_weight (16 + 16 lanes scan the tables);
+//   * every thread sums its pixel over y ascending, x ascending inside a row, acc += g * (wy * wx), zero weights skipped: the
+//     arithmetic and the order of gather_pixel<false> / gather_candidate under zeros / fill padding, so the result equals form 2's
+//     bit for bit (the fill term has no gradient with respect to the source).
+// Returns false (nothing accumulated, `out` untouched) when the tile has to go through scatter_tile; uniform over the block.  Must
+// be called by all 256 threads.  `live`: the thread's pixel lies inside the source window.
+template <bool STAGED>
+__device__ __forceinline__ void separable_sum(const GatherStage& st, const TileScatter& ts, int x0, int y0, int bw, int tx0, int ty0, float (&acc)[3]) {
+    const int kx = threadIdx.x & 15, ky = threadIdx.x >> 4, sx = tx0 + kx, sy = ty0 + ky;
+    const int xl = ts.sep.xlo[kx], xh = ts.sep.xhi[kx], yl = ts.sep.ylo[ky], yh = ts.sep.yhi[ky];
+    const size_t plane = (size_t)st.Hd * st.Wd;
+    for (int j = yl; j <= yh; ++j) {
+        const float wy = tap_weight(ts.sep.v[j], sy);
+        if (wy == 0.f) continue;
+        const float* gr = st.g + (size_t)(y0 + j) * st.Wd + x0;
+        for (int i = xl; i <= xh; ++i) {
+            const float w = wy * tap_weight(ts.sep.u[i], sx);
+            float g0, g1, g2;
+            if (STAGED) { const int li = j * bw + i; g0 = ts.g[0][li]; g1 = ts.g[1][li]; g2 = ts.g[2][li]; }
+            else { g0 = gr[i]; g1 = gr[plane + i]; g2 = gr[2 * plane + i]; }
+            if (w == 0.f) continue;
+            acc[0] += g0 * w; acc[1] += g1 * w; acc[2] += g2 * w;
+        }
+    }
+}
+// The same terms summed in SCATTER_TILE'S order, so that the result keeps scatter_tile's bits (and with them every bit of the
+// iteration: the 16-bit decoder backward amplifies a last-bit difference of this gradient to its own rounding floor).  The box is
+// scatter_tile's single rectangle (zeros / fill padding have one), so candidate k = j * bw + i of the box was taken there by thread
+// k % 256 as its (k / 256)-th candidate (scatter_rect<256>: k = tid + 256 m, m ascending, four m per trip one after another): wave
+// (k >> 6) & 3 added it to its own accumulator plane.  Within a wave the LDS adds retire in program
+// order -- trip by trip, inside a trip the north-west, north-east, south-west, south-east tap instruction of the candidate (the
+// pixel is the north-west tap where floor == s on both axes, the east / south tap where floor == s - 1), inside one instruction
+// the conflicting lanes ascending -- and the four planes are summed ((p0 + p1) + p2) + p3.  So: per wave, the 64-candidate blocks
+// it owned ascending; per block, tap kind 0..3; per kind, k ascending.  The weights are the same products as scatter_candidate's
+// (1 - (t - floor t) and t - floor t are what tap_weight returns); a zero term, which the scatter adds, changes no sum.
+template <bool STAGED>
+__device__ __forceinline__ void separable_sum_scatter_order(const GatherStage& st, const TileScatter& ts, int x0, int y0, int bw, int tx0, int ty0,
+                                                            float (&acc)[3]) {
+    const int kx = threadIdx.x & 15, ky = threadIdx.x >> 4, sx = tx0 + kx, sy = ty0 + ky;
+    const int xl = ts.sep.xlo[kx], xh = ts.sep.xhi[kx], yl = ts.sep.ylo[ky], yh = ts.sep.yhi[ky];
+    if (xl > xh || yl > yh) return;
+    const size_t plane = (size_t)st.Hd * st.Wd;
+    const int bmin = (yl * bw + xl) >> 6, bmax = (yh * bw + xh) >> 6;
+#pragma unroll
+    for (int wave = 0; wave < 4; ++wave) {
+        float p[3] = {0.f, 0.f, 0.f};
+        for (int b = bmin + ((wave - bmin) & 3); b <= bmax; b += 4) {
+            const int klo = b << 6, khi = klo + 63;
+            for (int kind = 0; kind < 4; ++kind)
+                for (int j = yl; j <= yh; ++j) {
+                    const int ilo = max(xl, klo - j * bw), ihi = min(xh, khi - j * bw);
+                    if (ilo > ihi) continue;
+                    const float v = ts.sep.v[j];
+                    if ((v - (float)sy < 0.f) != ((kind >> 1) != 0)) continue;
+                    const float wy = tap_weight(v, sy);
+                    if (wy == 0.f) continue;
+                    const float* gr = st.g + (size_t)(y0 + j) * st.Wd + x0;
+                    for (int i = ilo; i <= ihi; ++i) {
+                        const float u = ts.sep.u[i];
+                        if ((u - (float)sx < 0.f) != ((kind & 1) != 0)) continue;
+                        const float w = wy * tap_weight(u, sx);
+                        if (w == 0.f) continue;
+                        float g0, g1, g2;
+                        if (STAGED) { const int li = j * bw + i; g0 = ts.g[0][li]; g1 = ts.g[1][li]; g2 = ts.g[2][li]; }
+                        else { g0 = gr[i]; g1 = gr[plane + i]; g2 = gr[2 * plane + i]; }
+                        p[0] += g0 * w; p[1] += g1 * w; p[2] += g2 * w;
+                    }
+                }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] = wave == 0 ? p[c] : acc[c] + p[c];
+    }
+}
+// `order`: 1 = the gather's order (separable_sum: form 2's bits), 2 = the scatter's order (scatter_tile's bits)
+__device__ __forceinline__ bool separable_tile(const GatherStage& st, const StageMap& sm, TileScatter& ts, int tx0, int ty0, bool live, int order,
+                                               float (&out)[3]) {
+    const int tid = threadIdx.x;
+    // uniform: every thread works the box out for itself from block-uniform words
+    int x0 = 0, x1 = -1, y0 = 0, y1 = -1;
+    bool any = false;
+    const int sx0 = max(tx0, 0), sx1 = min(tx0 + TILE_W - 1, st.Ws - 1);
+    const int sy0 = max(ty0, 0), sy1 = min(ty0 + TILE_W - 1, st.Hs - 1);
+    if (sx0 <= sx1 && sy0 <= sy1) {
+        float xa[MAXR], xb[MAXR], ya[MAXR], yb[MAXR];
+        const int nx = tile_intervals(st.mode, sx0, sx1, st.Ws, sm.ulo, sm.uhi, xa, xb);       // zeros / fill: at most one interval
+        const int ny = tile_intervals(st.mode, sy0, sy1, st.Hs, sm.vlo, sm.vhi, ya, yb);
+        if (nx && ny) any = preimage_box(sm, xa[0], xb[0], ya[0], yb[0], st.Wd, st.Hd, x0, x1, y0, y1);
+    }
+    const int bw = any ? x1 - x0 + 1 : 0, bh = any ? y1 - y0 + 1 : 0;       // nothing reaches the tile: empty tables, zero sums
+    if (bw > SEP_CAP || bh > SEP_CAP) return false;
+    const bool staged = bw * bh <= SEP_G_CAP;
+    bool differs = false;
+    if (tid < 128) {
+        if (tid < bw) {
+            const float a = st.uv[(size_t)y0 * st.Wd + x0 + tid].x, b = st.uv[(size_t)y1 * st.Wd + x0 + tid].x;
+            ts.sep.u[tid] = a;
+            differs = __float_as_uint(a) != __float_as_uint(b);
+        }
+    } else if (tid - 128 < bh) {
+        const size_t row = (size_t)(y0 + tid - 128) * st.Wd;
+        const float a = st.uv[row + x0].y, b = st.uv[row + x1].y;
+        ts.sep.v[tid - 128] = a;
+        differs = __float_as_uint(a) != __float_as_uint(b);
+    }
+    const bool wave_differs = __ballot(differs) != 0;
+    if ((tid & 63) == 0) ts.sep.differs[tid >> 6] = wave_differs;
+    if (staged) {                                // 32 columns x 8 rows per trip: no division, rows of the box read contiguously
+        const size_t plane = (size_t)st.Hd * st.Wd;
+        for (int ly = tid >> 5; ly < bh; ly += 8)
+            for (int lx = tid & 31; lx < bw; lx += 32) {
+                const size_t o = (size_t)(y0 + ly) * st.Wd + x0 + lx;
+                const int li = ly * bw + lx;
+                ts.g[0][li] = st.g[o]; ts.g[1][li] = st.g[plane + o]; ts.g[2][li] = st.g[2 * plane + o];
+            }
+    }
+    __syncthreads();
+    if (ts.sep.differs[0] | ts.sep.differs[1] | ts.sep.differs[2] | ts.sep.differs[3]) return false;
+    if (tid < 2 * TILE_W) {
+        const bool rows = tid >= TILE_W;
+        const int k = tid & (TILE_W - 1), s = (rows ? ty0 : tx0) + k, cnt = rows ? bh : bw;
+        const float* tab = rows ? ts.sep.v : ts.sep.u;
+        int lo = cnt, hi = -1;
+        for (int i = 0; i < cnt; ++i)
+            if (tap_weight(tab[i], s) != 0.f) { lo = min(lo, i); hi = i; }
+        (rows ? ts.sep.ylo : ts.sep.xlo)[k] = lo;
+        (rows ? ts.sep.yhi : ts.sep.xhi)[k] = hi;
+    }
+    __syncthreads();
+    float acc[3] = {0.f, 0.f, 0.f};
+    if (live) {
+        if (order == 2) {
+            if (staged) separable_sum_scatter_order<true>(st, ts, x0, y0, bw, tx0, ty0, acc);
+            else separable_sum_scatter_order<false>(st, ts, x0, y0, bw, tx0, ty0, acc);
+        } else {
+            if (staged) separable_sum<true>(st, ts, x0, y0, bw, tx0, ty0, acc);
+            else separable_sum<false>(st, ts, x0, y0, bw, tx0, ty0, acc);
+        }
+    }
+    out[0] = acc[0]; out[1] = acc[1]; out[2] = acc[2];
+    return true;
 }
 
 // form 1: lane l returns the sums of source pixels l, l + 64, l + 128, l + 192 of the tile (row-major 16 x 16)
@@ -1058,6 +1239,28 @@ __global__ __launch_bounds__(256) void warp_b_jac_kernel(const float* __restrict
 //     rectangle boxes on 9 lanes in parallel, and is reproducible by construction: one accumulator, fixed candidate order,
 //     in-order LDS.  It did not move the time either (the figures stand above the host launcher).
 //
+//   FORM 0, separable tiles.  Where the stage of the block's cutout is an AXIS-ALIGNED AFFINE map under zeros / fill padding (at the
+//     headline: stage B of the 38 zoom cutouts, a resized crop; stage A of the 26 wide ones, scale + translation) none of the above is
+//     needed: u depends on x alone and v on y alone, the four tap weights are a column weight times a row weight, and the
+//     destination pixels that touch a source pixel are a run of columns times a run of rows.  Such a block calls separable_tile
+//     instead of scatter_tile (the branch is block-uniform; same ownership, same epilogue): two 1-D coordinate tables read from the uv
+//     map, the runs found by 16 + 16 lanes, then every thread sums its own pixel in registers in a fixed order.  A block takes the
+//     path when ALL of these hold, and runs the scatter otherwise (there is no third behaviour):
+//       * the kernel's `sep` argument is 1 or 2 (prx_cutout_bwd_separable, read by the launcher at launch time);
+//       * the flavour is GRID_AFFINE or GRID_AFFINE_AC and the mode MODE_ZEROS or MODE_FILL (separable_stage);
+//       * the off-diagonal matrix words pass the pre-filter |m| <= 2^-40 (what the resized crop's 8 x 8 solve leaves is <= 1e-16);
+//       * the tile's destination box has at most SEP_CAP = 80 columns and rows (magnifications up to x4);
+//       * EXACTNESS: the table entry of every column is bit-identical in the first and the last row of the box, and that of every
+//         row in the first and the last column.  project() is monotone in the other coordinate (correctly rounded monotone
+//         operations, no fma contraction), so equal ends mean the coordinate is constant across the box and the table is exactly
+//         what the forward used, whatever the off-diagonal noise.
+//     The terms are gather_pixel's (g * (wy * wx), zero weights skipped) and scatter_candidate's alike; `sep` picks the ORDER:
+//       sep == 1: gather_pixel's (y ascending, x ascending): on these cutouts form 0 equals FORM 2 BIT FOR BIT;
+//       sep == 2 (the default): scatter_tile's (separable_sum_scatter_order): form 0 keeps the bits it has with sep == 0, and the
+//         iteration every bit it had before the path existed.  That matters: the 16-bit decoder backward amplifies a last-bit
+//         difference of this gradient to its rounding floor (1e-3), and Adam and the VQ codes part the trajectories from there.
+//     (tests/test_cutout_separable_gpu.py holds both.)
+//
 // Forms 0 and 1 read the cutout's stage map from maps[n] (write_stage_map, in the stage's pre-pass) through a uniform address.
 //
 // The STAGE picks the descriptor words, the planes and the source window; the two stages are the same computation:
@@ -1070,7 +1273,7 @@ template <int FORM, int STAGE>
 __global__ __launch_bounds__(FORM == 1 ? 64 : 256) void warp_bwd_kernel(const double* __restrict__ desc, const float* __restrict__ g,
                                                                         const float* __restrict__ grgb, const float2* __restrict__ uv,
                                                                         const StageMap* __restrict__ maps, float* __restrict__ out,
-                                                                        int Wd, int Hd, int Wo, int Ho) {
+                                                                        int Wd, int Hd, int Wo, int Ho, int sep) {
     constexpr int NT = FORM == 1 ? 64 : 256;       // threads of the block
     constexpr int PPT = TILE_W * TILE_W / NT;      // tile pixels a thread owns: p = threadIdx.x + NT j
     const int n = blockIdx.y;
@@ -1107,7 +1310,13 @@ __global__ __launch_bounds__(FORM == 1 ? 64 : 256) void warp_bwd_kernel(const do
         } else if constexpr (FORM == 0) {
             __shared__ TileScatter ts;
             const StageMap sm = maps[n];          // uniform address: scalar loads
-            scatter_tile(st, sm, ts, tx0, ty0, o[0]);
+            // `sep` (prx_cutout_bwd_separable) and the descriptor words are block-uniform, and so is separable_tile's answer
+            bool done = false;
+            if (sep && separable_stage(d + (STAGE == 1 ? D_M1 : D_M2), (int)d[STAGE == 1 ? D_GRID1 : D_GRID2], mode)) {
+                const int ax = ax0 + (threadIdx.x & 15), ay = ay0 + (threadIdx.x >> 4);
+                done = separable_tile(st, sm, ts, tx0, ty0, ax < Wo && ay < Ho && in_window(ax - ox, ay - oy), sep, o[0]);
+            }
+            if (!done) scatter_tile(st, sm, ts, tx0, ty0, o[0]);
         } else {
             __shared__ WaveScatter ts;
             const StageMap sm = maps[n];
@@ -1410,9 +1619,29 @@ __global__ __launch_bounds__(256) void patchify_bwd_apply_kernel(const float* __
 // 187 / 170 us (workgroup), 209 / 184 us (wave), 150 / 255 us (round-2 gather): neither more tiles in flight nor the removed
 // barriers and serial set-up moved it -- what is left is the ~12 conflicting ds_add_f32 per candidate (4 taps x 3 channels,
 // neighbouring destination pixels share taps), i.e. the LDS atomic rate.
+// Form 0 runs the tiles of an axis-aligned affine stage under zeros / fill padding (at the headline: stage B of the 38 zoom
+// cutouts, stage A of the 26 wide ones) through separable_tile instead: two 1-D tables read from the uv map, proved exact per
+// tile by the two-ends check, then a fixed-order register sum per source pixel -- no pre-image geometry, no LDS adds.  By
+// default the sum runs in the scatter's order, so no bit of the result changes; with the switch at 1 in form 2's order.
+// Perspective, border and reflection cutouts, boxes beyond SEP_CAP and tiles whose check fails stay on the scatter.
+// Measured at the headline (profiles/cutout_separable_ab.txt): stage B / stage A about 189 / 170 us -> 139 / 137 us per
+// iteration in the scatter's order, 91 / 126 us in the gather's.  What is left is the scatter of the other cutouts: launched
+// alone, the 15 perspective cutouts of stage B take 66 us and the 30 perspective cutouts under reflection / border padding
+// of stage A 134 us -- the next target.
 static int cutout_bwd_form(int form) {
     static const int env = [] { const char* e = getenv("PRX_CUTOUT_BWD"); return !e ? 0 : e[0] == 'g' ? 2 : e[0] == 'w' ? 1 : 0; }();
     return form < 0 ? env : form;
+}
+
+// prx_cutout_bwd_separable (include/prx.h): whether form 0 may take the separable path; the launchers read it at launch time and
+// hand it to the kernel as an argument, so a captured graph keeps the value it was captured with.  0 = exactly the scatter, 1 = the
+// separable path in the gather's order, 2 (default) = in the scatter's order.
+static std::atomic<int> g_cutout_bwd_sep{[] {
+    const char* e = getenv("PRX_CUTOUT_BWD_SEP");
+    return !e ? 2 : e[0] == '0' ? 0 : e[0] == '1' ? 1 : 2;
+}()};
+extern "C" int prx_cutout_bwd_separable(int on) {
+    return on < 0 ? g_cutout_bwd_sep.load(std::memory_order_relaxed) : g_cutout_bwd_sep.exchange(on > 2 ? 2 : on);
 }
 
 // the tile pass of one stage in the resolved form (0, 1, 2): the destination plane is Wd x Hd, the output image Wo x Ho;
@@ -1423,11 +1652,12 @@ static int launch_warp_bwd(int form, const double* desc, const float* g, const f
                            int n_cut, int Wd, int Hd, int Wo, int Ho, hipStream_t s) {
     const dim3 grid(((Wo + TILE_W - 1) / TILE_W) * ((Ho + TILE_W - 1) / TILE_W), n_cut);
     if (form == 2)
-        hipLaunchKernelGGL((warp_bwd_kernel<2, STAGE>), grid, dim3(256), 0, s, desc, g, grgb, uv, nullptr, out, Wd, Hd, Wo, Ho);
+        hipLaunchKernelGGL((warp_bwd_kernel<2, STAGE>), grid, dim3(256), 0, s, desc, g, grgb, uv, nullptr, out, Wd, Hd, Wo, Ho, 0);
     else if (form == 0)
-        hipLaunchKernelGGL((warp_bwd_kernel<0, STAGE>), grid, dim3(256), 0, s, desc, g, grgb, uv, maps, out, Wd, Hd, Wo, Ho);
+        hipLaunchKernelGGL((warp_bwd_kernel<0, STAGE>), grid, dim3(256), 0, s, desc, g, grgb, uv, maps, out, Wd, Hd, Wo, Ho,
+                           g_cutout_bwd_sep.load(std::memory_order_relaxed));
     else
-        hipLaunchKernelGGL((warp_bwd_kernel<1, STAGE>), grid, dim3(64), 0, s, desc, g, grgb, uv, maps, out, Wd, Hd, Wo, Ho);
+        hipLaunchKernelGGL((warp_bwd_kernel<1, STAGE>), grid, dim3(64), 0, s, desc, g, grgb, uv, maps, out, Wd, Hd, Wo, Ho, 0);
     PRX_LAUNCH_CHECK();
     return 0;
 }
