@@ -129,6 +129,14 @@ long long prx_gemm_fit_spec_launches(void);
  * elements on (PRX_GEMM_ROWK_MIN, override -14) -- the ModifiedResNet runner's stage-1 / stage-2 convolutions; PRX_GEMM_ROWK=0 keeps
  * them on the tiled kernels). */
 long long prx_gemm_row_launches(void);
+/* n (1..4) products in one launch: g[0..n) agree in every field except A, B, out_f32 and out_bf16 (and share one ctx), and their
+ * outputs do not overlap -- the decoder AttnBlock's dq / dk / dv (call site vqgan.py:195, the backward of taming's AttnBlock): one
+ * shape, three operand pairs, three column slices of one buffer.  Where member 0 plans onto a single direct-to-LDS 4-wave launch
+ * without split-K (row-major A) and the others plan alike, one grid runs them all, bit for bit what n prx_k_gemm calls give; every
+ * other case IS n prx_k_gemm calls in order. */
+int prx_k_gemm_group(const prx_gemm_args* g, int n, void* ws, size_t ws_bytes, prx_stream_t stream);
+/* ... and how many prx_k_gemm_group calls (the decoder runner's included) ran as one grouped launch. */
+long long prx_gemm_group_launches(void);
 
 /* taming `Normalize` = GroupNorm(32, C, eps 1e-6) (+ swish `nonlinearity`) on an NHWC fp32
  * tensor x[NB][P][C]  [UPSTREAM taming/modules/diffusionmodules/model.py; call site vqgan.py:195].
@@ -220,6 +228,14 @@ int prx_k_softmax_rows_op(const float* S, int lds_, float scale, void* P, int ld
                           int prec, prx_stream_t s);
 int prx_k_softmax_rows_bwd_op(const void* P, int ldp, const float* dP, int lddp, float scale, void* dS, int ldds, void* dST,
                               int lddst, int rows, int cols, int prec, prx_stream_t s);
+/* the two softmax launches with the independent transpose tout[c][r] = tin[r][c] (tR x tC, operand precision) in the same launch:
+ * the bytes of prx_k_softmax_rows(_bwd)_op followed by prx_k_transpose_op (taming AttnBlock forward q|k|v -> v^T and backward
+ * d(out) -> d(out)^T; call site vqgan.py:195) */
+int prx_k_softmax_rows_tr_op(const float* S, int lds_, float scale, void* P, int ldp, void* PT, int ldpt, int rows, int cols,
+                             const void* tin, int ldtin, void* tout, int ldtout, int tR, int tC, int prec, prx_stream_t s);
+int prx_k_softmax_rows_bwd_tr_op(const void* P, int ldp, const float* dP, int lddp, float scale, void* dS, int ldds, void* dST,
+                                 int lddst, int rows, int cols, const void* tin, int ldtin, void* tout, int ldtout, int tR, int tC,
+                                 int prec, prx_stream_t s);
 int prx_k_transpose_op(const void* in, int ldin, void* out, int ldout, int R, int C, int f32, prx_stream_t s);
 int prx_k_upsample2x_bwd_op(const void* hi, float* low, void* low16, int NB, int Hl, int Wl, int C, int h16, int s16,
                             prx_stream_t s);

@@ -74,6 +74,17 @@ int prx_k_gemm(const prx_gemm_args* g, void* ws, size_t ws_bytes, prx_stream_t s
     if (r) return r;
     return prx_gemm_launch(d, (float*)ws, ws_bytes, (hipStream_t)stream_, (GemmCtx*)g->ctx);
 }
+int prx_k_gemm_group(const prx_gemm_args* g, int n, void* ws, size_t ws_bytes, prx_stream_t stream_) {
+    PRX_REQUIRE(g != nullptr && n >= 1 && n <= 4, "prx_k_gemm_group: 1 to 4 members (got %d)", n);
+    GemmDesc d[4];
+    for (int i = 0; i < n; ++i) {
+        const int r = desc_of(g + i, d[i]);
+        if (r) return r;
+        PRX_REQUIRE(g[i].ctx == g[0].ctx, "prx_k_gemm_group: the members must share one context");
+    }
+    return prx_gemm_launch_group(d, n, (float*)ws, ws_bytes, (hipStream_t)stream_, (GemmCtx*)g[0].ctx);
+}
+long long prx_gemm_group_launches(void) { return prx_gemm_group_launches_impl(); }
 int prx_k_gemm_gn(const prx_gemm_args* g, double* gn_stats, int gn_gs, const float* gnb_x, const double* gnb_fstats,
                   const float* gnb_gamma, const float* gnb_beta, int gnb_swish, float gnb_eps, void* ws, size_t ws_bytes,
                   prx_stream_t stream_) {

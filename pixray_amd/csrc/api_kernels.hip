@@ -217,6 +217,17 @@ int prx_k_softmax_rows_bwd_op(const void* P, int ldp, const float* dP, int lddp,
     PRX_REQUIRE(prec_valid(prec), "softmax_rows_bwd: unknown precision %d", prec);
     return prx_softmax_rows_bwd(P, ldp, dP, lddp, scale, dS, ldds, dST, lddst, rows, cols, prec, S_(s));
 }
+int prx_k_softmax_rows_tr_op(const float* S, int lds_, float scale, void* P, int ldp, void* PT, int ldpt, int rows, int cols,
+                             const void* tin, int ldtin, void* tout, int ldtout, int tR, int tC, int prec, prx_stream_t s) {
+    PRX_REQUIRE(prec_valid(prec), "softmax_rows_tr: unknown precision %d", prec);
+    return prx_softmax_rows_tr(S, lds_, scale, P, ldp, PT, ldpt, rows, cols, tin, ldtin, tout, ldtout, tR, tC, prec, S_(s));
+}
+int prx_k_softmax_rows_bwd_tr_op(const void* P, int ldp, const float* dP, int lddp, float scale, void* dS, int ldds, void* dST,
+                                 int lddst, int rows, int cols, const void* tin, int ldtin, void* tout, int ldtout, int tR, int tC,
+                                 int prec, prx_stream_t s) {
+    PRX_REQUIRE(prec_valid(prec), "softmax_rows_bwd_tr: unknown precision %d", prec);
+    return prx_softmax_rows_bwd_tr(P, ldp, dP, lddp, scale, dS, ldds, dST, lddst, rows, cols, tin, ldtin, tout, ldtout, tR, tC, prec, S_(s));
+}
 int prx_k_transpose_op(const void* in, int ldin, void* out, int ldout, int R, int C, int f32, prx_stream_t s) {
     return prx_transpose_op(in, ldin, out, ldout, R, C, f32, S_(s));
 }

@@ -7,6 +7,12 @@ int prx_softmax_rows(const float* S, int lds_, float scale, void* P, int ldp, vo
                      int cols, int prec, hipStream_t s);
 int prx_softmax_rows_bwd(const void* P, int ldp, const float* dP, int lddp, float scale, void* dS, int ldds,
                          void* dST, int lddst, int rows, int cols, int prec, hipStream_t s);
+// the same softmax launches with the independent transpose tout[c][r] = tin[r][c] (tR x tC, operand precision of `prec`) riding along
+// in extra workgroups: the bytes of the softmax launch followed by prx_transpose_op, one launch
+int prx_softmax_rows_tr(const float* S, int lds_, float scale, void* P, int ldp, void* PT, int ldpt, int rows, int cols,
+                        const void* tin, int ldtin, void* tout, int ldtout, int tR, int tC, int prec, hipStream_t s);
+int prx_softmax_rows_bwd_tr(const void* P, int ldp, const float* dP, int lddp, float scale, void* dS, int ldds, void* dST, int lddst,
+                            int rows, int cols, const void* tin, int ldtin, void* tout, int ldtout, int tR, int tC, int prec, hipStream_t s);
 // s16: `hi` is a 16-bit stream in the operand format (lean layout); `low` (fp32) may then be null
 int prx_upsample2x_bwd(const void* hi, float* low, bf16_t* low_bf16, int NB, int Hl, int Wl, int C, hipStream_t s, int h16 = 0, int s16 = 0);
 int prx_nchw_to_nhwc(const float* in, float* out_f32, bf16_t* out_bf16, int NB, int C, int HW, int Cpad, hipStream_t s, int h16 = 0);

@@ -9,13 +9,13 @@ namespace {
 
 inline int ew_grid(size_t total, int per = 256) { return (int)std::min<size_t>((total + per - 1) / per, 8192); }
 
-// out[c][r] = in[r][c]   (operand precision: bf16 or fp32), tiled through LDS
+// out[c][r] = in[r][c]   (operand precision: bf16 or fp32), tiled through LDS; (bx, by): the 32 x 32 tile of this workgroup
 template <typename T>
-__global__ __launch_bounds__(256) void transpose_op_kernel(const T* __restrict__ in, int ldin,
-                                                           T* __restrict__ out, int ldout, int R, int C) {
+__device__ __forceinline__ void transpose_op_tile(const T* __restrict__ in, int ldin, T* __restrict__ out, int ldout, int R, int C,
+                                                  int bx, int by) {
     __shared__ T tile[32][33];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-    const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
+    const int r0 = by * 32, c0 = bx * 32;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         int r = r0 + ty + 8 * i, c = c0 + tx;
@@ -28,14 +28,18 @@ __global__ __launch_bounds__(256) void transpose_op_kernel(const T* __restrict__
         if (c < C && r < R) out[(size_t)c * ldout + r] = tile[tx][ty + 8 * i];
     }
 }
-
-// P = softmax(scale * S) per row; one wave per row; writes P (and optionally P^T) at operand precision
 template <typename T>
-__global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restrict__ S, int lds_, float scale,
-                                                           T* __restrict__ P, int ldp, T* __restrict__ PT,
-                                                           int ldpt, int rows, int cols) {
+__global__ __launch_bounds__(256) void transpose_op_kernel(const T* __restrict__ in, int ldin,
+                                                           T* __restrict__ out, int ldout, int R, int C) {
+    transpose_op_tile<T>(in, ldin, out, ldout, R, C, blockIdx.x, blockIdx.y);
+}
+
+// P = softmax(scale * S) per row; one wave per row; writes P (and optionally P^T) at operand precision; `blk`: the 4 rows of this workgroup
+template <typename T>
+__device__ __forceinline__ void softmax_rows_body(const float* __restrict__ S, int lds_, float scale, T* __restrict__ P, int ldp,
+                                                  T* __restrict__ PT, int ldpt, int rows, int cols, int blk) {
     const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int row = blk * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const float* s = S + (size_t)row * lds_;
     float mx = -INFINITY;
@@ -51,15 +55,20 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
         if (PT) PT[(size_t)c * ldpt + row] = p;
     }
 }
+template <typename T>
+__global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restrict__ S, int lds_, float scale,
+                                                           T* __restrict__ P, int ldp, T* __restrict__ PT,
+                                                           int ldpt, int rows, int cols) {
+    softmax_rows_body<T>(S, lds_, scale, P, ldp, PT, ldpt, rows, cols, blockIdx.x);
+}
 
 // dS = scale * P o (dP - rowsum(dP o P));  writes dS and dS^T at operand precision
 template <typename T>
-__global__ __launch_bounds__(256) void softmax_rows_bwd_kernel(const T* __restrict__ P, int ldp,
-                                                               const float* __restrict__ dP, int lddp, float scale,
-                                                               T* __restrict__ dS, int ldds,
-                                                               T* __restrict__ dST, int lddst, int rows, int cols) {
+__device__ __forceinline__ void softmax_rows_bwd_body(const T* __restrict__ P, int ldp, const float* __restrict__ dP, int lddp, float scale,
+                                                      T* __restrict__ dS, int ldds, T* __restrict__ dST, int lddst, int rows, int cols,
+                                                      int blk) {
     const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int row = blk * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     float dot = 0.f;
     for (int c = lane; c < cols; c += 64)
@@ -71,6 +80,36 @@ __global__ __launch_bounds__(256) void softmax_rows_bwd_kernel(const T* __restri
         dS[(size_t)row * ldds + c] = v;
         if (dST) dST[(size_t)c * lddst + row] = v;
     }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void softmax_rows_bwd_kernel(const T* __restrict__ P, int ldp,
+                                                               const float* __restrict__ dP, int lddp, float scale,
+                                                               T* __restrict__ dS, int ldds,
+                                                               T* __restrict__ dST, int lddst, int rows, int cols) {
+    softmax_rows_bwd_body<T>(P, ldp, dP, lddp, scale, dS, ldds, dST, lddst, rows, cols, blockIdx.x);
+}
+
+// The same two with a transpose riding along (the decoder AttnBlock: a pure copy that nothing reads before the launch AFTER the
+// softmax, so it needs no launch of its own).  Workgroups [0, ceil(rows / 4)) are the softmax's, each of the rest one 32 x 32 tile
+// of the independent transpose tout[c][r] = tin[r][c] (tR x tC, tiles_c tiles per row of tiles).  The two bodies are the stand-alone
+// kernels' own; the transposed elements are copied as 16-bit words or floats (TT), as prx_transpose_op does.
+struct TransposeRider { const void* in; int ldin; void* out; int ldout, R, C, tiles_c; };
+template <typename T, typename TT>
+__global__ __launch_bounds__(256) void softmax_rows_tr_kernel(const float* __restrict__ S, int lds_, float scale, T* __restrict__ P, int ldp,
+                                                              T* __restrict__ PT, int ldpt, int rows, int cols, const TransposeRider tr) {
+    const int nsoft = (rows + 3) >> 2;
+    if ((int)blockIdx.x < nsoft) { softmax_rows_body<T>(S, lds_, scale, P, ldp, PT, ldpt, rows, cols, blockIdx.x); return; }
+    const int t = (int)blockIdx.x - nsoft, by = t / tr.tiles_c;
+    transpose_op_tile<TT>((const TT*)tr.in, tr.ldin, (TT*)tr.out, tr.ldout, tr.R, tr.C, t - by * tr.tiles_c, by);
+}
+template <typename T, typename TT>
+__global__ __launch_bounds__(256) void softmax_rows_bwd_tr_kernel(const T* __restrict__ P, int ldp, const float* __restrict__ dP, int lddp,
+                                                                  float scale, T* __restrict__ dS, int ldds, T* __restrict__ dST, int lddst,
+                                                                  int rows, int cols, const TransposeRider tr) {
+    const int nsoft = (rows + 3) >> 2;
+    if ((int)blockIdx.x < nsoft) { softmax_rows_bwd_body<T>(P, ldp, dP, lddp, scale, dS, ldds, dST, lddst, rows, cols, blockIdx.x); return; }
+    const int t = (int)blockIdx.x - nsoft, by = t / tr.tiles_c;
+    transpose_op_tile<TT>((const TT*)tr.in, tr.ldin, (TT*)tr.out, tr.ldout, tr.R, tr.C, t - by * tr.tiles_c, by);
 }
 
 // low[b][y][x][c] = sum over the 2x2 children of hi (NHWC fp32) -- backward of nearest-2x upsample
@@ -316,6 +355,38 @@ int prx_softmax_rows_bwd(const void* P, int ldp, const float* dP, int lddp, floa
     PRX_OP_DISPATCH(prec_is_f32(prec), prec_is_h16(prec), T,
                     hipLaunchKernelGGL(softmax_rows_bwd_kernel<T>, dim3(ceil_div(rows, 4)), dim3(256), 0, s, (const T*)P, ldp, dP, lddp,
                                        scale, (T*)dS, ldds, (T*)dST, lddst, rows, cols));
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+// ... with the transpose tout[c][r] = tin[r][c] (tR x tC, operand precision) in the same launch
+int prx_softmax_rows_tr(const float* S, int lds_, float scale, void* P, int ldp, void* PT, int ldpt, int rows, int cols,
+                        const void* tin, int ldtin, void* tout, int ldtout, int tR, int tC, int prec, hipStream_t s) {
+    PRX_REQUIRE(rows > 0 && tR > 0 && tC > 0 && tin && tout, "softmax_rows_tr: empty softmax or transpose");
+    const TransposeRider tr{tin, ldtin, tout, ldtout, tR, tC, ceil_div(tC, 32)};
+    const dim3 grid(ceil_div(rows, 4) + tr.tiles_c * ceil_div(tR, 32));
+    if (prec_is_f32(prec))
+        hipLaunchKernelGGL((softmax_rows_tr_kernel<float, float>), grid, dim3(256), 0, s, S, lds_, scale, (float*)P, ldp, (float*)PT, ldpt, rows, cols, tr);
+    else if (prec_is_h16(prec))
+        hipLaunchKernelGGL((softmax_rows_tr_kernel<half_t, bf16_t>), grid, dim3(256), 0, s, S, lds_, scale, (half_t*)P, ldp, (half_t*)PT, ldpt, rows, cols, tr);
+    else
+        hipLaunchKernelGGL((softmax_rows_tr_kernel<bf16_t, bf16_t>), grid, dim3(256), 0, s, S, lds_, scale, (bf16_t*)P, ldp, (bf16_t*)PT, ldpt, rows, cols, tr);
+    PRX_LAUNCH_CHECK();
+    return 0;
+}
+int prx_softmax_rows_bwd_tr(const void* P, int ldp, const float* dP, int lddp, float scale, void* dS, int ldds, void* dST, int lddst,
+                            int rows, int cols, const void* tin, int ldtin, void* tout, int ldtout, int tR, int tC, int prec, hipStream_t s) {
+    PRX_REQUIRE(rows > 0 && tR > 0 && tC > 0 && tin && tout, "softmax_rows_bwd_tr: empty softmax or transpose");
+    const TransposeRider tr{tin, ldtin, tout, ldtout, tR, tC, ceil_div(tC, 32)};
+    const dim3 grid(ceil_div(rows, 4) + tr.tiles_c * ceil_div(tR, 32));
+    if (prec_is_f32(prec))
+        hipLaunchKernelGGL((softmax_rows_bwd_tr_kernel<float, float>), grid, dim3(256), 0, s, (const float*)P, ldp, dP, lddp, scale, (float*)dS, ldds,
+                           (float*)dST, lddst, rows, cols, tr);
+    else if (prec_is_h16(prec))
+        hipLaunchKernelGGL((softmax_rows_bwd_tr_kernel<half_t, bf16_t>), grid, dim3(256), 0, s, (const half_t*)P, ldp, dP, lddp, scale, (half_t*)dS, ldds,
+                           (half_t*)dST, lddst, rows, cols, tr);
+    else
+        hipLaunchKernelGGL((softmax_rows_bwd_tr_kernel<bf16_t, bf16_t>), grid, dim3(256), 0, s, (const bf16_t*)P, ldp, dP, lddp, scale, (bf16_t*)dS, ldds,
+                           (bf16_t*)dST, lddst, rows, cols, tr);
     PRX_LAUNCH_CHECK();
     return 0;
 }

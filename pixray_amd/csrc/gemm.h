@@ -135,3 +135,13 @@ int prx_gemm_ctx_profile_collect(GemmCtx* c, double* total_ms, double* total_flo
 // Launch on `stream`.  `ws` is a scratch buffer for split-K partials (may be
 // null -> split-K disabled).  Returns 0 or a negative error code.
 int prx_gemm_launch(const GemmDesc& d, float* ws, size_t ws_bytes, hipStream_t stream, GemmCtx* ctx = nullptr);
+
+// n (1..4) independent products in one launch.  The members d[0..n) must agree in every field except A, B, out_f32 and out_bf16,
+// and their outputs must not overlap (the decoder attention's dq / dk / dv: one shape, three operand pairs, three column slices of
+// one buffer).  Member 0 is planned; when that plan is a single launch of the direct-to-LDS tiled family without split-K -- a
+// row-major product at the ring depth the planner chooses by itself -- and every member plans alike, ONE grid runs them all, its z
+// dimension the member; each element is accumulated exactly as in a launch of its own.  Every other case (another kernel family,
+// split-K, the 8-phase row split, fused GroupNorm sums, members that differ elsewhere) is prx_gemm_launch n times in order: the
+// fallback is part of the contract, not an error.  A profiling context records a grouped launch once, with the members' flop summed.
+int prx_gemm_launch_group(const GemmDesc* d, int n, float* ws, size_t ws_bytes, hipStream_t stream, GemmCtx* ctx = nullptr);
+long long prx_gemm_group_launches_impl();   // grouped launches of this process (the fallback does not count)

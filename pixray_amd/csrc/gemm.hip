@@ -12,6 +12,7 @@
 #include "norms.h"
 #include <vector>
 #include <mutex>
+#include <atomic>
 #include <stdlib.h>
 #include <type_traits>
 
@@ -405,8 +406,10 @@ typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
 // NWM = waves along M (2 -> 4 waves / 256 threads, 4 -> 8 waves / 512 threads for the 256-row tiles); two waves along N.
-template <int BM, int BN, int AMODE, int STAGES, bool C64 = false, int NWM = 2, typename T16 = bf16_t>
-__global__ __launch_bounds__(NWM * 128) void gemm_glds_kernel(const GemmArgs p, const bf16_t* __restrict__ zero_page) {
+// GROUP = 1: a grouped launch (prx_gemm_launch_group) -- blockIdx.z is the member, and the member's A, B and output pointers (grp)
+// replace the descriptor's in a local copy before anything reads them; everything after that is the one body.
+template <int BM, int BN, int AMODE, int STAGES, bool C64 = false, int NWM = 2, typename T16 = bf16_t, int GROUP = 0>
+__global__ __launch_bounds__(NWM * 128) void gemm_glds_kernel(const GemmArgs p, const bf16_t* __restrict__ zero_page, const GemmGroupArg<GROUP> grp) {
     constexpr int NW = NWM * 2;
     constexpr int A_IN = BM / (8 * NW);   // DMA instructions (8 rows x 128 B each) per wave per K tile
     constexpr int B_IN = BN / (8 * NW);
@@ -417,7 +420,17 @@ __global__ __launch_bounds__(NWM * 128) void gemm_glds_kernel(const GemmArgs p, 
 
     __shared__ __attribute__((aligned(16))) bf16_t lds[STAGES * TILE];
 
-    const GemmDesc& d = p.d;
+    GemmDesc dg;
+    if constexpr (GROUP != 0) {
+        // selects on the wave-uniform member index over constant indices: the pointer arrays stay in the kernel arguments
+        const int g = blockIdx.z;
+        dg = p.d;
+        dg.A = g == 0 ? grp.A[0] : g == 1 ? grp.A[1] : g == 2 ? grp.A[2] : grp.A[3];
+        dg.B = g == 0 ? grp.B[0] : g == 1 ? grp.B[1] : g == 2 ? grp.B[2] : grp.B[3];
+        dg.out_f32 = g == 0 ? grp.out_f32[0] : g == 1 ? grp.out_f32[1] : g == 2 ? grp.out_f32[2] : grp.out_f32[3];
+        dg.out_bf16 = g == 0 ? grp.out_bf16[0] : g == 1 ? grp.out_bf16[1] : g == 2 ? grp.out_bf16[2] : grp.out_bf16[3];
+    }
+    const GemmDesc& d = GROUP != 0 ? dg : p.d;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -833,11 +846,11 @@ void launch_f32(const GemmArgs& a, dim3 grid, hipStream_t s) {
 template <int BM, int BN, int STAGES, typename T16>
 void launch_glds_t(const GemmArgs& a, dim3 grid, hipStream_t s, const bf16_t* zero_page, bool c64) {
     if (a.d.a_mode == PRX_A_ROWMAJOR)
-        hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, PRX_A_ROWMAJOR, STAGES, false, 2, T16>), grid, dim3(256), 0, s, a, zero_page);
+        hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, PRX_A_ROWMAJOR, STAGES, false, 2, T16>), grid, dim3(256), 0, s, a, zero_page, GemmGroupArg<0>{});
     else if (c64)
-        hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, PRX_A_CONV3X3, STAGES, true, 2, T16>), grid, dim3(256), 0, s, a, zero_page);
+        hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, PRX_A_CONV3X3, STAGES, true, 2, T16>), grid, dim3(256), 0, s, a, zero_page, GemmGroupArg<0>{});
     else
-        hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, PRX_A_CONV3X3, STAGES, false, 2, T16>), grid, dim3(256), 0, s, a, zero_page);
+        hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, PRX_A_CONV3X3, STAGES, false, 2, T16>), grid, dim3(256), 0, s, a, zero_page, GemmGroupArg<0>{});
 }
 template <int BM, int BN, int STAGES>
 void launch_glds_s(const GemmArgs& a, dim3 grid, hipStream_t s, const bf16_t* zero_page, bool c64) {
@@ -849,6 +862,16 @@ void launch_glds(const GemmArgs& a, dim3 grid, hipStream_t s, const bf16_t* zero
     if (stages >= 4 && (BM + BN) * BK * 2 * 4 <= 160 * 1024) launch_glds_s<BM, BN, 4>(a, grid, s, zero_page, c64);
     else if (stages >= 3) launch_glds_s<BM, BN, 3>(a, grid, s, zero_page, c64);
     else launch_glds_s<BM, BN, 2>(a, grid, s, zero_page, c64);
+}
+
+// grouped launch: the row-major instance of the tile at the ring depth the planner gives it by default (three K tiles for 64 x 64,
+// two for the 128-row tiles); any other plan runs its members as separate launches (prx_gemm_launch_group)
+inline bool glds_group_stages(int bm, int bn, int stages) { return stages == ((bm == 64 && bn == 64) ? 3 : 2); }
+template <int BM, int BN>
+void launch_glds_group(const GemmArgs& a, dim3 grid, hipStream_t s, const bf16_t* zero_page, const GemmGroupArg<1>& grp) {
+    constexpr int ST = (BM == 64 && BN == 64) ? 3 : 2;
+    if (a.d.h16) hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, PRX_A_ROWMAJOR, ST, false, 2, half_t, 1>), grid, dim3(256), 0, s, a, zero_page, grp);
+    else         hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, PRX_A_ROWMAJOR, ST, false, 2, bf16_t, 1>), grid, dim3(256), 0, s, a, zero_page, grp);
 }
 
 // A 256-byte page of zeros per device (source of the DMA for out-of-range / padded operand chunks).  Created once per
@@ -1188,8 +1211,10 @@ int prx_gemm_plan_impl(const GemmDesc& d, const GemmCtx* c, int n_cu, size_t ws_
     return 0;
 }
 
-// one planned launch (and its split-K reduce), timed when the context profiles
-static int launch_planned(const GemmDesc& d, const GemmLaunchPlan& p, float* ws, int n_cu, hipStream_t stream, GemmCtx* ctx) {
+// one planned launch (and its split-K reduce), timed when the context profiles.  grp (n_grp members): the grouped form of a
+// direct-to-LDS launch without split-K -- d is member 0, the grid's z dimension the member, one profile record for all of them
+static int launch_planned(const GemmDesc& d, const GemmLaunchPlan& p, float* ws, int n_cu, hipStream_t stream, GemmCtx* ctx,
+                          const GemmGroupArg<1>* grp = nullptr, int n_grp = 1) {
     const GemmArgs a{d, ceil_div(d.M, p.bm), ceil_div(d.N, p.bn), p.splits, p.kt_per_split, ceil_div(d.K, d.f32 ? BKF : BK), p.vec_epi,
                      p.xcd_swizzle, p.fit_flags, ws};
 
@@ -1203,13 +1228,13 @@ static int launch_planned(const GemmDesc& d, const GemmLaunchPlan& p, float* ws,
         PRX_CHECK_HIP(hipEventCreate(&rec.a));
         PRX_CHECK_HIP(hipEventCreate(&rec.b));
         const bool row = p.family == GEMM_ROW || p.family == GEMM_ROWCONV;
-        rec.flop = 2.0 * d.M * d.N * d.K;
+        rec.flop = 2.0 * d.M * d.N * d.K * n_grp;
         rec.M = d.M; rec.N = d.N; rec.K = d.K; rec.mode = d.a_mode + 2 * d.up + 4 * d.a_is_f32 + 8 * d.f32;
         rec.bm = p.bm + (p.family == GEMM_FIT ? 1000 : (row ? 2000 : 0)); rec.bn = p.bn; rec.splits = p.splits;    // + 1000: the fit kernel of that tile shape
         PRX_CHECK_HIP(hipEventRecord(rec.a, stream));
     }
 
-    const dim3 grid(a.tiles_m * a.tiles_n, p.splits);
+    const dim3 grid(a.tiles_m * a.tiles_n, p.splits, grp ? n_grp : 1);
     const bool t128 = p.bm == 128 && p.bn == 128, t12864 = p.bm == 128 && p.bn == 64;      // (other 4-wave tiles: the 64 x 64 kernel)
     const bf16_t* zp = p.family == GEMM_TILED_GLDS ? zero_page_for_current_device() : nullptr;
     PRX_REQUIRE(zp != nullptr || p.family != GEMM_TILED_GLDS, "gemm: could not allocate the zero page");
@@ -1224,7 +1249,12 @@ static int launch_planned(const GemmDesc& d, const GemmLaunchPlan& p, float* ws,
         else launch_f32<64, 64>(a, grid, stream);
         break;
     case GEMM_TILED_GLDS:
-        if (t128) launch_glds<128, 128>(a, grid, stream, zp, p.stages, p.c64);
+        if (grp) {
+            if (t128) launch_glds_group<128, 128>(a, grid, stream, zp, *grp);
+            else if (t12864) launch_glds_group<128, 64>(a, grid, stream, zp, *grp);
+            else launch_glds_group<64, 64>(a, grid, stream, zp, *grp);
+        }
+        else if (t128) launch_glds<128, 128>(a, grid, stream, zp, p.stages, p.c64);
         else if (t12864) launch_glds<128, 64>(a, grid, stream, zp, p.stages, p.c64);
         else launch_glds<64, 64>(a, grid, stream, zp, p.stages, p.c64);
         break;
@@ -1250,7 +1280,7 @@ static int launch_planned(const GemmDesc& d, const GemmLaunchPlan& p, float* ws,
     return 0;
 }
 
-int prx_gemm_launch(const GemmDesc& d, float* ws, size_t ws_bytes, hipStream_t stream, GemmCtx* ctx) {
+static int launch_n_cu(GemmCtx* ctx) {
     int cur_dev = -1;
     if (ctx && (ctx->n_cu == 0 || (hipGetDevice(&cur_dev) == hipSuccess && cur_dev != ctx->n_cu_dev))) {
         // the planners count tiles against the LAUNCHING device's CUs (cost constants stay MI355X's); re-asked when the context
@@ -1261,7 +1291,11 @@ int prx_gemm_launch(const GemmDesc& d, float* ws, size_t ws_bytes, hipStream_t s
         else
             ctx->n_cu = 256;
     }
-    const int n_cu = ctx && ctx->n_cu > 0 ? ctx->n_cu : 256;
+    return ctx && ctx->n_cu > 0 ? ctx->n_cu : 256;
+}
+
+int prx_gemm_launch(const GemmDesc& d, float* ws, size_t ws_bytes, hipStream_t stream, GemmCtx* ctx) {
+    const int n_cu = launch_n_cu(ctx);
     GemmPlan plan;
     const int r = prx_gemm_plan_impl(d, ctx, n_cu, ws ? ws_bytes : 0, ((uintptr_t)ws & 15) == 0, &plan);
     if (ctx) ctx->dbg_count += plan.dbg_used;
@@ -1275,4 +1309,54 @@ int prx_gemm_launch(const GemmDesc& d, float* ws, size_t ws_bytes, hipStream_t s
     if (!plan.stats_pass) return 0;
     if (d.gnb_x) return prx_groupnorm_bwd_stats(d.out_f32, d.gnb_x, d.gnb_gamma, d.gnb_beta, d.gnb_fstats, d.gn_stats, 1, d.M, d.N, d.gnb_swish, d.gnb_eps, stream);
     return prx_groupnorm_fwd(d.out_f32, nullptr, nullptr, d.gn_stats, nullptr, nullptr, 1, d.M, d.N, 0, 1e-6f, stream, /*zero_stats=*/0, /*stats_ready=*/0);
+}
+
+// ---- grouped launch (gemm.h) ------------------------------------------------------------------------------------------
+namespace { std::atomic<long long> g_group_launches{0}; }
+long long prx_gemm_group_launches_impl() { return g_group_launches.load(std::memory_order_relaxed); }
+
+// every field but A, B, out_f32, out_bf16
+static bool same_but_operands(const GemmDesc& a, const GemmDesc& b) {
+    return a.f32 == b.f32 && a.h16 == b.h16 && a.a_is_f32 == b.a_is_f32 && a.a_mode == b.a_mode && a.lda == b.lda && a.ldb == b.ldb &&
+           a.M == b.M && a.N == b.N && a.K == b.K && a.H == b.H && a.W == b.W && a.Cin == b.Cin && a.up == b.up &&
+           a.alpha == b.alpha && a.alpha_dev == b.alpha_dev && a.bias_n == b.bias_n && a.bias_m == b.bias_m && a.aux == b.aux && a.ldaux == b.ldaux &&
+           a.resid == b.resid && a.ldr == b.ldr && a.act == b.act && a.ldc_f32 == b.ldc_f32 && a.out_bf16_pre == b.out_bf16_pre &&
+           a.ldc_bf16 == b.ldc_bf16 && a.gn_stats == b.gn_stats && a.gn_gs == b.gn_gs && a.gnb_x == b.gnb_x && a.gnb_fstats == b.gnb_fstats &&
+           a.gnb_gamma == b.gnb_gamma && a.gnb_beta == b.gnb_beta && a.gnb_swish == b.gnb_swish && a.row16 == b.row16 && a.gnb_eps == b.gnb_eps &&
+           (a.out_f32 == nullptr) == (b.out_f32 == nullptr) && (a.out_bf16 == nullptr) == (b.out_bf16 == nullptr);
+}
+static bool same_launch(const GemmLaunchPlan& a, const GemmLaunchPlan& b) {
+    return a.family == b.family && a.bm == b.bm && a.bn == b.bn && a.splits == b.splits && a.kt_per_split == b.kt_per_split &&
+           a.stages == b.stages && a.c64 == b.c64 && a.vec_epi == b.vec_epi && a.xcd_swizzle == b.xcd_swizzle && a.fit_flags == b.fit_flags;
+}
+
+int prx_gemm_launch_group(const GemmDesc* d, int n, float* ws, size_t ws_bytes, hipStream_t stream, GemmCtx* ctx) {
+    PRX_REQUIRE(d != nullptr && n >= 1 && n <= GEMM_GROUP_MAX, "gemm group: 1 to %d members (got %d)", GEMM_GROUP_MAX, n);
+    const int n_cu = launch_n_cu(ctx);
+    // the plan of member 0 decides; the other members must plan alike (the vector epilogue is a property of each member's pointers)
+    GemmPlan plan;
+    bool grouped = true;
+    for (int i = 0; i < n && grouped; ++i) {
+        GemmPlan pi;
+        const int r = prx_gemm_plan_impl(d[i], ctx, n_cu, ws ? ws_bytes : 0, ((uintptr_t)ws & 15) == 0, &pi);
+        if (r) return r;
+        if (i == 0) plan = pi;
+        grouped = same_but_operands(d[0], d[i]) && pi.n_launch == 1 && !pi.stats_pass && pi.dbg_used == 0 && same_launch(plan.launch[0], pi.launch[0]);
+    }
+    const GemmLaunchPlan& l0 = plan.launch[0];
+    grouped = grouped && l0.family == GEMM_TILED_GLDS && l0.splits == 1 && d[0].a_mode == PRX_A_ROWMAJOR && d[0].gn_stats == nullptr &&
+              fourwave_tile(l0.bm, l0.bn) && glds_group_stages(l0.bm, l0.bn, l0.stages);
+    if (!grouped) {      // another family, split-K, an 8-phase row split, members that differ: the members one after another
+        for (int i = 0; i < n; ++i) {
+            const int e = prx_gemm_launch(d[i], ws, ws_bytes, stream, ctx);
+            if (e) return e;
+        }
+        return 0;
+    }
+    GemmGroupArg<1> grp{};
+    for (int i = 0; i < n; ++i) { grp.A[i] = d[i].A; grp.B[i] = d[i].B; grp.out_f32[i] = d[i].out_f32; grp.out_bf16[i] = d[i].out_bf16; }
+    const int e = launch_planned(d[0], l0, ws, n_cu, stream, ctx, &grp, n);
+    if (e) return e;
+    g_group_launches.fetch_add(1, std::memory_order_relaxed);
+    return 0;
 }

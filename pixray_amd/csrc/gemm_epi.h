@@ -15,6 +15,20 @@ struct GemmArgs {
     float* ws;
 };
 
+// Grouped launch (prx_gemm_launch_group): the fields in which the members of a group differ, by value beside the shared GemmArgs.
+// Member g of the grid's z dimension runs the product of GemmArgs::d with these four pointers in place.  GROUP == 0 (every ordinary
+// launch) carries nothing.
+constexpr int GEMM_GROUP_MAX = 4;
+template <int GROUP>
+struct GemmGroupArg {
+    const void* A[GEMM_GROUP_MAX];
+    const void* B[GEMM_GROUP_MAX];
+    float* out_f32[GEMM_GROUP_MAX];
+    void* out_bf16[GEMM_GROUP_MAX];
+};
+template <>
+struct GemmGroupArg<0> {};
+
 __device__ __forceinline__ float quickgelu_f(float t) { return t * sigmoidf_(1.702f * t); }
 __device__ __forceinline__ float dquickgelu_f(float t) {
     float s = sigmoidf_(1.702f * t);

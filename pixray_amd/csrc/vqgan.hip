@@ -104,6 +104,9 @@ struct PrxVqgan {
     // fp32 stream plus a 16-bit twin (40 % of the iteration's HBM writes).  GroupNorm sums are still taken from the fp32
     // accumulators in the producing epilogue.
     int lean;
+    // AttnBlock launch sequence (PRX_VQ_ATTN_GROUP, read once at create; default 1): the two transposes ride on the softmax launches
+    // and dq / dk / dv are one grouped GEMM launch -- 6 + 6 launches per block instead of 7 + 9, the same bits; 0: the separate launches
+    int attn_group;
     float* gs;        // half mode: device {S, 1/S} = the power-of-two scale of the backward in flight (common.h) + 256 partials; else null
     GemmCtx gctx;     // this handle's engine state
     DevArena mem;     // every device buffer below: freed with the handle
@@ -243,6 +246,7 @@ int prx_vqgan_create_impl(PrxVqgan** out, int ch, const int* ch_mult, int n_mult
     v->prec = precision; v->f32 = prec_is_f32(precision); v->h16 = prec_is_h16(precision);
     v->gs = nullptr;
     { const char* e = getenv("PRX_LEAN"); v->lean = (v->h16 && !(e && atoi(e) == 0)) ? 1 : 0; }
+    { const char* e = getenv("PRX_VQ_ATTN_GROUP"); v->attn_group = (e && atoi(e) == 0) ? 0 : 1; }
     v->n_gn = 0; v->zc = z_channels; v->D = embed_dim; v->NC = n_embed; v->ch = ch; v->out_ch = out_ch; v->h0 = h0; v->w0 = w0;
     WCursor cur{w, n_w, 0};
     int r;
@@ -368,12 +372,15 @@ static void vq_trace(const PrxVqgan* v, const char* tag, int i, const void* p_, 
     fprintf(stderr, "[vq] %s %2d n=%zu l2 %.9e max %.6e\n", tag, i, n, sqrt(q), mx);
 }
 
-static int vg(PrxVqgan* v, GemmDesc& d, hipStream_t s) {
+static void vg_prec(const PrxVqgan* v, GemmDesc& d) {
     if (v->f32) {
         d.f32 = 1; d.a_is_f32 = 0;
         if (d.out_bf16 == (void*)d.out_f32) d.out_bf16 = nullptr;   // the "twin" is the fp32 output itself
     }
     d.h16 = v->h16;
+}
+static int vg(PrxVqgan* v, GemmDesc& d, hipStream_t s) {
+    vg_prec(v, d);
     return prx_gemm_launch(d, v->ws, v->ws_bytes, s, &v->gctx);
 }
 GemmCtx* prx_vqgan_gemm_ctx_impl(PrxVqgan* v) { return v ? &v->gctx : nullptr; }
@@ -496,11 +503,13 @@ int prx_vqgan_synth_impl(PrxVqgan* v, const float* z, float* img, int* indices, 
                 d.bias_n = b.qkv.b; d.out_bf16 = b.qkvb; d.ldc_bf16 = 3 * C;
                 if ((r = vg(v, d, s))) return r; }
             const int P8 = pad8(P);
-            if ((r = prx_transpose_op(b.qkvb, 3 * C, b.qkvT, P8, P, 3 * C, v->f32, s))) return r;  // q^T | k^T | v^T [3C, P8] (pad columns stay zero)
+            // q^T | k^T | v^T [3C, P8] (pad columns stay zero): nothing reads it before the P v product, so the copy rides on the softmax launch
+            if (!v->attn_group && (r = prx_transpose_op(b.qkvb, 3 * C, b.qkvT, P8, P, 3 * C, v->f32, s))) return r;
             {   GemmDesc d; d.A = b.qkvb; d.lda = 3 * C; d.B = op_off(b.qkvb, C, v->f32); d.ldb = 3 * C; d.M = P; d.N = P; d.K = C;
                 d.out_f32 = v->S; d.ldc_f32 = P;
                 if ((r = vg(v, d, s))) return r; }
-            if ((r = prx_softmax_rows(v->S, P, 1.f / sqrtf((float)C), b.Pm, P8, b.PT, P8, P, P, v->prec, s))) return r;
+            if (v->attn_group) { if ((r = prx_softmax_rows_tr(v->S, P, 1.f / sqrtf((float)C), b.Pm, P8, b.PT, P8, P, P, b.qkvb, 3 * C, b.qkvT, P8, P, 3 * C, v->prec, s))) return r; }
+            else if ((r = prx_softmax_rows(v->S, P, 1.f / sqrtf((float)C), b.Pm, P8, b.PT, P8, P, P, v->prec, s))) return r;
             {   GemmDesc d; d.A = b.Pm; d.lda = P8; d.B = op_off(b.qkvT, (size_t)2 * C * P8, v->f32); d.ldb = P8; d.M = P; d.N = C; d.K = P8;
                 d.out_bf16 = v->tB; d.ldc_bf16 = C;
                 if ((r = vg(v, d, s))) return r; }
@@ -606,18 +615,29 @@ int prx_vqgan_backward_impl(PrxVqgan* v, const float* g_img, float* dz, hipStrea
             const int P8 = pad8(P);
             if ((r = zero_if_padded(v, v->tB, P, P, s))) return r;
             if ((r = zero_if_padded(v, v->tC, P, P, s))) return r;
-            if ((r = prx_softmax_rows_bwd(b.Pm, P8, v->S, P, 1.f / sqrtf((float)C), v->tB, P8, v->tC, P8, P, P, v->prec, s))) return r;  // tB = dS, tC = dS^T
-            {   GemmDesc d; d.A = v->tB; d.lda = P8; d.B = op_off(b.qkvT, (size_t)C * P8, v->f32); d.ldb = P8; d.M = P; d.N = C; d.K = P8;
-                d.out_bf16 = v->dqkv; d.ldc_bf16 = 3 * C;                               // dq = dS k   (k^T from the forward's transpose)
-                if ((r = vg(v, d, s))) return r; }
-            {   GemmDesc d; d.A = v->tC; d.lda = P8; d.B = b.qkvT; d.ldb = P8; d.M = P; d.N = C; d.K = P8;
-                d.out_bf16 = op_off(v->dqkv, C, v->f32); d.ldc_bf16 = 3 * C;            // dk = dS^T q  (q^T likewise)
-                if ((r = vg(v, d, s))) return r; }
-            if ((r = zero_if_padded(v, v->tD, C, P, s))) return r;
-            if ((r = prx_transpose_op(v->tA, C, v->tD, P8, P, C, v->f32, s))) return r;                // tD = do^T
-            {   GemmDesc d; d.A = b.PT; d.lda = P8; d.B = v->tD; d.ldb = P8; d.M = P; d.N = C; d.K = P8;
-                d.out_bf16 = op_off(v->dqkv, 2 * C, v->f32); d.ldc_bf16 = 3 * C;        // dv = P^T do
-                if ((r = vg(v, d, s))) return r; }
+            GemmDesc dq, dk, dv;
+            dq.A = v->tB; dq.lda = P8; dq.B = op_off(b.qkvT, (size_t)C * P8, v->f32); dq.ldb = P8; dq.M = P; dq.N = C; dq.K = P8;
+            dq.out_bf16 = v->dqkv; dq.ldc_bf16 = 3 * C;                                  // dq = dS k   (k^T from the forward's transpose)
+            dk.A = v->tC; dk.lda = P8; dk.B = b.qkvT; dk.ldb = P8; dk.M = P; dk.N = C; dk.K = P8;
+            dk.out_bf16 = op_off(v->dqkv, C, v->f32); dk.ldc_bf16 = 3 * C;               // dk = dS^T q  (q^T likewise)
+            dv.A = b.PT; dv.lda = P8; dv.B = v->tD; dv.ldb = P8; dv.M = P; dv.N = C; dv.K = P8;
+            dv.out_bf16 = op_off(v->dqkv, 2 * C, v->f32); dv.ldc_bf16 = 3 * C;           // dv = P^T do  (tD = do^T)
+            if (v->attn_group) {
+                // tD = do^T rides on the softmax backward (its padding cleared first, in stream order); the three products, which share
+                // one shape and write disjoint column slices of dqkv, are one grouped launch
+                if ((r = zero_if_padded(v, v->tD, C, P, s))) return r;
+                if ((r = prx_softmax_rows_bwd_tr(b.Pm, P8, v->S, P, 1.f / sqrtf((float)C), v->tB, P8, v->tC, P8, P, P, v->tA, C, v->tD, P8, P, C, v->prec, s))) return r;  // tB = dS, tC = dS^T
+                GemmDesc grp[3] = {dq, dk, dv};
+                for (GemmDesc& d : grp) vg_prec(v, d);
+                if ((r = prx_gemm_launch_group(grp, 3, v->ws, v->ws_bytes, s, &v->gctx))) return r;
+            } else {
+                if ((r = prx_softmax_rows_bwd(b.Pm, P8, v->S, P, 1.f / sqrtf((float)C), v->tB, P8, v->tC, P8, P, P, v->prec, s))) return r;  // tB = dS, tC = dS^T
+                if ((r = vg(v, dq, s))) return r;
+                if ((r = vg(v, dk, s))) return r;
+                if ((r = zero_if_padded(v, v->tD, C, P, s))) return r;
+                if ((r = prx_transpose_op(v->tA, C, v->tD, P8, P, C, v->f32, s))) return r;                // tD = do^T
+                if ((r = vg(v, dv, s))) return r;
+            }
             {   GemmDesc d; d.A = v->dqkv; d.lda = 3 * C; d.B = b.qkv.WT; d.ldb = 3 * C; d.M = P; d.N = C; d.K = 3 * C;
                 out_stream(v, d, t1.f, C, nullptr);                                      // d GN(x)
                 set_gnb(v, d, &b.n, b.x_in, 0);
