@@ -168,7 +168,10 @@ int prx_k_nhwc_to_nchw(const float* in, int ldc, float* out, int NB, int C, int 
 int prx_k_image_head_fwd(const float* x, int ldc, float* img, int NB, int C, int HW, prx_stream_t s);
 int prx_k_image_head_bwd(const float* x, int ldc, const float* gimg, float* dx, void* dx_bf16, int ldo, int NB, int C,
                          int HW, prx_stream_t s);
-/* nn.MultiheadAttention core of CLIP's ResidualAttentionBlock, T <= 64, head dim 64 */
+/* nn.MultiheadAttention core of CLIP's ResidualAttentionBlock.  Every prx_k_mha_* call is a view of the one attention dispatcher
+ * (csrc/attention.h: a descriptor of the problem, one function that picks the kernel family or refuses): the call's name and
+ * arguments fill the descriptor, the dispatcher checks and launches.  These two: bf16, head dim 64, the recomputing form (no lse, the
+ * backward reads no `out`), which has kernels for T <= 64 */
 int prx_k_mha_fwd(const void* qkv, void* out, int N, int T, int C, int heads, prx_stream_t s);
 int prx_k_mha_bwd(const void* qkv, const void* dout, void* dqkv, int N, int T, int C, int heads, prx_stream_t s);
 
@@ -190,13 +193,15 @@ int prx_k_layernorm_fwd_op(const void* x, long long ldx, const float* gamma, con
 int prx_k_layernorm_bwd_op(const void* g, long long ldg, const void* x, long long ldx, const float* gamma, const float* mean,
                            const float* rstd, const void* add, long long ldadd, float* dx, long long lddx, void* dx16,
                            long long lddxb, int rows, int C, int h16, int add_every, int s16, prx_stream_t s);
+/* the dispatcher's views with the 16-bit format as an argument: _op the recomputing form (T <= 64), _gen_op the saving form (any T:
+ * `out` and `lse` are kept for the backward), both at head dim 64 */
 int prx_k_mha_fwd_op(const void* qkv, void* out, int N, int T, int C, int heads, int h16, prx_stream_t s);
 int prx_k_mha_bwd_op(const void* qkv, const void* dout, void* dqkv, int N, int T, int C, int heads, int h16, prx_stream_t s);
 int prx_k_mha_fwd_gen_op(const void* qkv, void* out, float* lse, int N, int T, int C, int heads, int h16, prx_stream_t s);
 int prx_k_mha_bwd_gen_op(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int N, int T, int C,
                          int heads, int h16, prx_stream_t s);
-/* prx_k_mha_{fwd,bwd}_gen_op with the operand columns per head as an argument.  head_cols 64: the two calls above, bit for bit.
- * head_cols 96: heads of dim 80 zero-padded to 96 columns (OpenCLIP ViT-H/14; the 96-wide instances of csrc/attention_kernels.h): C == heads * 96, head h at
+/* prx_k_mha_{fwd,bwd}_gen_op with the operand columns per head as an argument (64 | 96, anything else is refused here): the
+ * descriptor's head dim is 64 or 80.  head_cols 64: the two calls above, bit for bit.  head_cols 96: heads of dim 80 zero-padded to 96 columns (OpenCLIP ViT-H/14; the 96-wide instances of csrc/attention_kernels.h): C == heads * 96, head h at
  * columns 96h .. 96h+95 of q, k, v, out and their gradients, the caller's columns 80 .. 95 of every head zero, softmax scale
  * 1 / sqrt(80), 1 <= T <= 640; columns 80 .. 95 of `out` and `dqkv` are written as exact zeros. */
 int prx_k_mha_fwd_hd_op(const void* qkv, void* out, float* lse, int N, int T, int C, int heads, int h16, int head_cols, prx_stream_t s);
@@ -205,10 +210,12 @@ int prx_k_mha_bwd_hd_op(const void* qkv, const void* out, const void* dout, cons
 /* the head padding prx_vit_tower_create applies when it packs a block's weights (fp32 device tensors, width == heads * hd):
  * qkv_w [3 width, width] -> qkv_w_pad [3 heads hp, width] (every head's hd rows of q, k and v become the first hd of hp rows),
  * out_w [width, width] -> out_w_pad [width, heads hp] (the matching input columns); pad rows / columns are zero. */
-/* the same two calls with the head dim as an argument: head_dim 64 at head_cols 64 are prx_k_mha_{fwd,bwd}_gen_op; 80 | 88 at
+/* the same two calls with the descriptor's head dim as an argument (>= 64, checked here; the dispatcher derives the columns per head
+ * from it and refuses a C that is not heads times that many, so head_cols only says what C / heads has to be): head_dim 64 at
+ * head_cols 64 are prx_k_mha_{fwd,bwd}_gen_op; 80 | 88 at
  * head_cols 96 and 104 at head_cols 128 (OpenCLIP ViT-H-14 | ViT-g-14 and ViT-bigG-14) run the 96- / 128-wide instances with the softmax
  * scale 1 / sqrt(head_dim).  The caller's columns head_dim .. head_cols - 1 of every head are zero, and so are those of `out` and `dqkv`.
- * Any other pair is refused. */
+ * Any other pair is refused by the dispatcher. */
 int prx_k_mha_fwd_hdim_op(const void* qkv, void* out, float* lse, int N, int T, int C, int heads, int h16, int head_cols, int head_dim,
                           prx_stream_t s);
 int prx_k_mha_bwd_hdim_op(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int N, int T, int C,
@@ -222,7 +229,7 @@ int prx_k_layernorm_bwd_rag_op(const void* g, long long ldg, const void* x, long
                                int rows, int C, int h16, int add_every, int s16, prx_stream_t s);
 int prx_k_vit_pad_heads(const float* qkv_w, float* qkv_w_pad, const float* out_w, float* out_w_pad, int width, int heads, int hd, int hp,
                         prx_stream_t s);
-/* forward only, causal mask (CLIP text transformer) */
+/* the dispatcher's causal view: forward only, head dim 64, no lse (CLIP text transformer) */
 int prx_k_mha_fwd_causal_op(const void* qkv, void* out, int N, int T, int C, int heads, int h16, prx_stream_t s);
 int prx_k_softmax_rows_op(const float* S, int lds_, float scale, void* P, int ldp, void* PT, int ldpt, int rows, int cols,
                           int prec, prx_stream_t s);
@@ -827,18 +834,27 @@ int prx_k_vq_nearest(const float* z, long long tok_stride, long long ch_stride, 
                      prx_stream_t s);
 int prx_k_sqnorm_rows(const float* w, float* out, int rows, int D, prx_stream_t s);
 
-/* same attention for any sequence length T >= 1, head dim 64; `out` and `lse` (fp32 [N*heads*T]) are kept for the backward.  Two kernel
+/* the dispatcher's saving form in bf16 at head dim 64: any sequence length T >= 1; `out` and `lse` (fp32 [N*heads*T]) are kept for the
+ * backward.  Two kernel
  * families: workgroups per (image, head) with a wave per 32 tokens for T <= 640 (ViT-B/16 197 tokens, ViT-L/14 257, ViT-L/14@336px 577,
  * the ModifiedResNet attention pools 50 ... 197), and one wave per 64-token tile with an online softmax for every larger T.
  * prx_mha_route chooses the family of the following general-T calls of the process: -1 that rule (PRX_MHA_TILES=1 in the environment:
  * tiles everywhere), 0 the workgroup family wherever it is able (T <= 640), 1 the tile kernels; it returns the previous setting.
  * Both families are atomic-free and bit-reproducible. */
 int prx_mha_route(int route);
+/* What the dispatcher does with a problem (host only, nothing is launched; the same routing function the launches go through):
+ * precision a PRX_PREC_* value, head_dim as the operands carry it, `recompute` 1 for the recomputing form, `route` as for
+ * prx_mha_route (it is an argument here; the process setting is neither read nor changed).  Fills *family with 1 the wave-per-head
+ * recomputing kernels, 2 the workgroup family, 3 the tile kernels, 4 the exact-f32 kernels; *head_cols with the operand columns per
+ * head (64 | 96 | 128); *saves_out with whether the caller keeps `out` + `lse` for the backward.  A problem without a kernel returns
+ * nonzero with *family 0 and the refusal in prx_last_error. */
+int prx_mha_describe(int precision, int head_dim, int T, int causal, int recompute, int route, int* family, int* head_cols,
+                     int* saves_out);
 int prx_k_mha_fwd_gen(const void* qkv, void* out, float* lse, int N, int T, int C, int heads, prx_stream_t s);
 int prx_k_mha_bwd_gen(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int N, int T, int C,
                       int heads, prx_stream_t s);
 
-/* the exact-f32 attention of the PRX_PREC_F32 mode (fp32 qkv / out / dout / dqkv, any T, head dim 64) */
+/* the dispatcher's fp32 view: the exact-f32 attention of the PRX_PREC_F32 mode (fp32 qkv / out / dout / dqkv, any T, head dim 64) */
 int prx_k_mha_fwd_f32(const float* qkv, float* out, float* lse, int N, int T, int C, int heads, prx_stream_t s);
 int prx_k_mha_bwd_f32(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int N, int T, int C,
                       int heads, prx_stream_t s);

@@ -72,27 +72,34 @@ int prx_k_image_head_bwd(const float* x, int ldc, const float* gimg, float* dx, 
                          int HW, prx_stream_t s) {
     return prx_image_head_bwd(x, ldc, gimg, dx, B_(dx_bf16), ldo, NB, C, HW, S_(s));
 }
+// ---- attention: every prx_k_mha_* call is a view of the one dispatcher (attention.h): it fills the descriptor and calls it ----------
+static MhaDesc mha_desc(int N, int T, int C, int heads, int hd, int prec, int recompute = 0, int causal = 0) {
+    MhaDesc d;
+    d.N = N; d.T = T; d.C = C; d.heads = heads; d.hd = hd; d.prec = prec; d.recompute = recompute; d.causal = causal;
+    return d;
+}
+static int prec16(int h16) { return h16 ? PRX_PREC_F16 : PRX_PREC_BF16; }
 int prx_k_mha_fwd(const void* qkv, void* out, int N, int T, int C, int heads, prx_stream_t s) {
-    return prx_mha_fwd(CB_(qkv), B_(out), N, T, C, heads, S_(s));
+    return prx_mha_fwd(mha_desc(N, T, C, heads, 64, PRX_PREC_BF16, 1), qkv, out, nullptr, S_(s));
 }
 int prx_k_mha_bwd(const void* qkv, const void* dout, void* dqkv, int N, int T, int C, int heads, prx_stream_t s) {
-    return prx_mha_bwd(CB_(qkv), CB_(dout), B_(dqkv), N, T, C, heads, S_(s));
+    return prx_mha_bwd(mha_desc(N, T, C, heads, 64, PRX_PREC_BF16, 1), qkv, nullptr, dout, nullptr, dqkv, S_(s));
 }
 
 int prx_k_mha_fwd_gen(const void* qkv, void* out, float* lse, int N, int T, int C, int heads, prx_stream_t s) {
-    return prx_mha_fwd_gen(CB_(qkv), B_(out), lse, N, T, C, heads, S_(s));
+    return prx_mha_fwd(mha_desc(N, T, C, heads, 64, PRX_PREC_BF16), qkv, out, lse, S_(s));
 }
 int prx_k_mha_bwd_gen(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int N, int T, int C,
                       int heads, prx_stream_t s) {
-    return prx_mha_bwd_gen(CB_(qkv), CB_(out), CB_(dout), lse, B_(dqkv), N, T, C, heads, S_(s));
+    return prx_mha_bwd(mha_desc(N, T, C, heads, 64, PRX_PREC_BF16), qkv, out, dout, lse, dqkv, S_(s));
 }
 
 int prx_k_mha_fwd_f32(const float* qkv, float* out, float* lse, int N, int T, int C, int heads, prx_stream_t s) {
-    return prx_mha_fwd_f32(qkv, out, lse, N, T, C, heads, S_(s));
+    return prx_mha_fwd(mha_desc(N, T, C, heads, 64, PRX_PREC_F32), qkv, out, lse, S_(s));
 }
 int prx_k_mha_bwd_f32(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int N, int T, int C,
                       int heads, prx_stream_t s) {
-    return prx_mha_bwd_f32(qkv, out, dout, lse, dqkv, N, T, C, heads, S_(s));
+    return prx_mha_bwd(mha_desc(N, T, C, heads, 64, PRX_PREC_F32), qkv, out, dout, lse, dqkv, S_(s));
 }
 
 // ---- OpenCLIP ConvNeXt runner kernels (convnext.hip; tests/test_convnext_gpu.py) ------------------------------------------------
@@ -145,48 +152,39 @@ int prx_k_layernorm_bwd_op(const void* g, long long ldg, const void* x, long lon
                              add_every, s16);
 }
 int prx_k_mha_fwd_op(const void* qkv, void* out, int N, int T, int C, int heads, int h16, prx_stream_t s) {
-    return prx_mha_fwd(CB_(qkv), B_(out), N, T, C, heads, S_(s), h16);
+    return prx_mha_fwd(mha_desc(N, T, C, heads, 64, prec16(h16), 1), qkv, out, nullptr, S_(s));
 }
 int prx_k_mha_bwd_op(const void* qkv, const void* dout, void* dqkv, int N, int T, int C, int heads, int h16, prx_stream_t s) {
-    return prx_mha_bwd(CB_(qkv), CB_(dout), B_(dqkv), N, T, C, heads, S_(s), h16);
+    return prx_mha_bwd(mha_desc(N, T, C, heads, 64, prec16(h16), 1), qkv, nullptr, dout, nullptr, dqkv, S_(s));
 }
 int prx_k_mha_fwd_gen_op(const void* qkv, void* out, float* lse, int N, int T, int C, int heads, int h16, prx_stream_t s) {
-    return prx_mha_fwd_gen(CB_(qkv), B_(out), lse, N, T, C, heads, S_(s), h16);
+    return prx_mha_fwd(mha_desc(N, T, C, heads, 64, prec16(h16)), qkv, out, lse, S_(s));
 }
 int prx_k_mha_bwd_gen_op(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int N, int T, int C,
                          int heads, int h16, prx_stream_t s) {
-    return prx_mha_bwd_gen(CB_(qkv), CB_(out), CB_(dout), lse, B_(dqkv), N, T, C, heads, S_(s), h16);
+    return prx_mha_bwd(mha_desc(N, T, C, heads, 64, prec16(h16)), qkv, out, dout, lse, dqkv, S_(s));
 }
-// columns per head 64: the calls above; 96: head dim 80 zero-padded, softmax scale 1 / sqrt(80) (the 96-wide instances of attention_kernels.h)
+// columns per head as the argument: 64 is head dim 64, 96 is head dim 80 zero-padded
 int prx_k_mha_fwd_hd_op(const void* qkv, void* out, float* lse, int N, int T, int C, int heads, int h16, int head_cols, prx_stream_t s) {
     PRX_REQUIRE(head_cols == 64 || head_cols == 96, "mha_fwd_hd: %d columns per head (64 | 96)", head_cols);
-    if (head_cols == 64) return prx_mha_fwd_gen(CB_(qkv), B_(out), lse, N, T, C, heads, S_(s), h16);
-    return prx_mha_fwd_hd96(CB_(qkv), B_(out), lse, N, T, C, heads, 1.f / sqrtf(80.f), S_(s), h16);
+    return prx_mha_fwd(mha_desc(N, T, C, heads, head_cols == 64 ? 64 : 80, prec16(h16)), qkv, out, lse, S_(s));
 }
 int prx_k_mha_bwd_hd_op(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int N, int T, int C,
                         int heads, int h16, int head_cols, prx_stream_t s) {
     PRX_REQUIRE(head_cols == 64 || head_cols == 96, "mha_bwd_hd: %d columns per head (64 | 96)", head_cols);
-    if (head_cols == 64) return prx_mha_bwd_gen(CB_(qkv), CB_(out), CB_(dout), lse, B_(dqkv), N, T, C, heads, S_(s), h16);
-    return prx_mha_bwd_hd96(CB_(qkv), CB_(out), CB_(dout), lse, B_(dqkv), N, T, C, heads, 1.f / sqrtf(80.f), S_(s), h16);
+    return prx_mha_bwd(mha_desc(N, T, C, heads, head_cols == 64 ? 64 : 80, prec16(h16)), qkv, out, dout, lse, dqkv, S_(s));
 }
-// the head dim as an argument: the scale is 1 / sqrt(head_dim), the columns come from the runner's own mapping (prx_vit_head_cols)
+// the head dim as the argument.  The dispatcher derives the columns per head from it and holds C against them, so `head_cols`
+// (what C / heads has to be) adds nothing and is not read
 int prx_k_mha_fwd_hdim_op(const void* qkv, void* out, float* lse, int N, int T, int C, int heads, int h16, int head_cols, int head_dim,
                           prx_stream_t s) {
-    PRX_REQUIRE(head_dim >= 64 && prx_vit_head_cols(head_dim) == head_cols, "mha_fwd_hdim: head dim %d at %d columns per head (64 at 64, 80 | 88 at 96, 104 at 128)",
-                head_dim, head_cols);
-    const float scale = 1.f / sqrtf((float)head_dim);
-    if (head_cols == 64) return prx_mha_fwd_gen(CB_(qkv), B_(out), lse, N, T, C, heads, S_(s), h16);
-    if (head_cols == 96) return prx_mha_fwd_hd96(CB_(qkv), B_(out), lse, N, T, C, heads, scale, S_(s), h16);
-    return prx_mha_fwd_hd128(CB_(qkv), B_(out), lse, N, T, C, heads, scale, S_(s), h16);
+    PRX_REQUIRE(head_dim >= 64, "mha_fwd_hdim: head dim %d at %d columns per head (the kernels take head dims >= 64)", head_dim, head_cols);
+    return prx_mha_fwd(mha_desc(N, T, C, heads, head_dim, prec16(h16)), qkv, out, lse, S_(s));
 }
 int prx_k_mha_bwd_hdim_op(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int N, int T, int C,
                           int heads, int h16, int head_cols, int head_dim, prx_stream_t s) {
-    PRX_REQUIRE(head_dim >= 64 && prx_vit_head_cols(head_dim) == head_cols, "mha_bwd_hdim: head dim %d at %d columns per head (64 at 64, 80 | 88 at 96, 104 at 128)",
-                head_dim, head_cols);
-    const float scale = 1.f / sqrtf((float)head_dim);
-    if (head_cols == 64) return prx_mha_bwd_gen(CB_(qkv), CB_(out), CB_(dout), lse, B_(dqkv), N, T, C, heads, S_(s), h16);
-    if (head_cols == 96) return prx_mha_bwd_hd96(CB_(qkv), CB_(out), CB_(dout), lse, B_(dqkv), N, T, C, heads, scale, S_(s), h16);
-    return prx_mha_bwd_hd128(CB_(qkv), CB_(out), CB_(dout), lse, B_(dqkv), N, T, C, heads, scale, S_(s), h16);
+    PRX_REQUIRE(head_dim >= 64, "mha_bwd_hdim: head dim %d at %d columns per head (the kernels take head dims >= 64)", head_dim, head_cols);
+    return prx_mha_bwd(mha_desc(N, T, C, heads, head_dim, prec16(h16)), qkv, out, dout, lse, dqkv, S_(s));
 }
 int prx_k_layernorm_fwd_rag_op(const void* x, long long ldx, const float* gamma, const float* beta, void* out16, float* out_f32,
                                float* mean, float* rstd, int rows, int C, float eps, int h16, int s16, prx_stream_t s) {
@@ -205,7 +203,7 @@ int prx_k_vit_pad_heads(const float* qkv_w, float* qkv_w_pad, const float* out_w
     return r ? r : prx_vit_pad_head_cols(out_w, out_w_pad, width, heads, hd, hp, S_(s));
 }
 int prx_k_mha_fwd_causal_op(const void* qkv, void* out, int N, int T, int C, int heads, int h16, prx_stream_t s) {
-    return prx_mha_fwd_causal(CB_(qkv), B_(out), N, T, C, heads, S_(s), h16);
+    return prx_mha_fwd(mha_desc(N, T, C, heads, 64, prec16(h16), 0, 1), qkv, out, nullptr, S_(s));
 }
 int prx_k_softmax_rows_op(const float* S, int lds_, float scale, void* P, int ldp, void* PT, int ldpt, int rows, int cols,
                           int prec, prx_stream_t s) {

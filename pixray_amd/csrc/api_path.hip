@@ -127,7 +127,7 @@ int prx_vit_tower_create_mlp(prx_clip_vit** out, const prx_vit_tower_config* c, 
     PRX_REQUIRE(mlp_width >= 0, "prx_vit_tower_create: MLP width %d", mlp_width);
     PRX_REQUIRE(c->family == PRX_VIT_FAMILY_CLIP || c->family == PRX_VIT_FAMILY_SLIP || c->family == PRX_VIT_FAMILY_OPENCLIP,
                 "prx_vit_tower_create: unknown family %d", c->family);
-    PRX_REQUIRE(c->head_dim == 0 || prx_vit_head_cols(c->head_dim) != 0,
+    PRX_REQUIRE(c->head_dim == 0 || prx_mha_head_cols(c->head_dim) != 0,
                 "prx_vit_tower_create: head dim %d (want 64, or 32 / 16: padded to 64, or 80 / 88: padded to 96, or 104: padded to 128)", c->head_dim);
     VitFamily f = prx_vit_family_clip();
     if (c->family == PRX_VIT_FAMILY_SLIP) { f.patch_bias = 1; f.ln_pre = 0; f.act = PRX_ACT_GELU; f.dact = PRX_ACT_MUL_DGELU; }

@@ -1,35 +1,30 @@
 #pragma once
 #include "common.h"
-// 16-bit operand buffers (`bf16_t*`): bf16, or IEEE half when h16 != 0
-// qkv: bf16 [N*T, 3C] (q | k | v, head h at columns h*64..), out/dout: bf16 [N*T, C]
-int prx_mha_fwd(const bf16_t* qkv, bf16_t* out, int N, int T, int C, int heads, hipStream_t s, int h16 = 0);
-int prx_mha_bwd(const bf16_t* qkv, const bf16_t* dout, bf16_t* dqkv, int N, int T, int C, int heads, hipStream_t s, int h16 = 0);
-// any sequence length (64-token tiles, online softmax); out must be kept for the backward, lse: fp32 [N*heads*T]
-int prx_mha_fwd_gen(const bf16_t* qkv, bf16_t* out, float* lse, int N, int T, int C, int heads, hipStream_t s, int h16 = 0);
-int prx_mha_bwd_gen(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, int N, int T,
-                    int C, int heads, hipStream_t s, int h16 = 0);
-// forward only, causal mask (CLIP text transformer, context 77)
-int prx_mha_fwd_causal(const bf16_t* qkv, bf16_t* out, int N, int T, int C, int heads, hipStream_t s, int h16 = 0);
-// exact-f32 attention of the PRX_PREC_F32 parity mode (attention_f32.hip): any T, fp32 operands; `out` and `lse`
-// ([N*heads*T]) are kept for the backward
-int prx_mha_fwd_f32(const float* qkv, float* out, float* lse, int N, int T, int C, int heads, hipStream_t s);
-int prx_mha_bwd_f32(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int N, int T, int C,
-                    int heads, hipStream_t s);
-// heads of 96 operand columns = head dim 80 zero-padded (the 96-wide instances of attention_kernels.h; OpenCLIP ViT-H/14): qkv [N*T, 3C] with head h at columns
-// h*96.., C == heads * 96, 1 <= T <= 640, `scale` the softmax scale (1 / sqrt(80)); pad columns of out / dqkv come out as exact zeros
-int prx_mha_fwd_hd96(const bf16_t* qkv, bf16_t* out, float* lse, int N, int T, int C, int heads, float scale, hipStream_t s, int h16 = 0);
-int prx_mha_bwd_hd96(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, int N, int T, int C,
-                     int heads, float scale, hipStream_t s, int h16 = 0);
-// ... and their exact-f32 form (attention_f32.hip instantiated for head dim 80 at column stride 96, scale 1 / sqrt(80); any T)
-int prx_mha_fwd_f32_hd96(const float* qkv, float* out, float* lse, int N, int T, int C, int heads, hipStream_t s);
-int prx_mha_bwd_f32_hd96(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int N, int T, int C,
-                         int heads, hipStream_t s);
-// heads of 128 operand columns = head dim 104 zero-padded (OpenCLIP ViT-bigG-14): the 128-wide instances of the same family, same contract
-// (heads of 88, ViT-g-14, run on prx_mha_*_hd96 with scale 1 / sqrt(88))
-int prx_mha_fwd_hd128(const bf16_t* qkv, bf16_t* out, float* lse, int N, int T, int C, int heads, float scale, hipStream_t s, int h16 = 0);
-int prx_mha_bwd_hd128(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, int N, int T, int C,
-                      int heads, float scale, hipStream_t s, int h16 = 0);
-// exact-f32 form for any padded head dim hd: 80 | 88 in 96 columns, 104 in 128; scale 1 / sqrt(hd); any T
-int prx_mha_fwd_f32_pad(const float* qkv, float* out, float* lse, int N, int T, int C, int heads, int hd, hipStream_t s);
-int prx_mha_bwd_f32_pad(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int N, int T, int C,
-                        int heads, int hd, hipStream_t s);
+#include <math.h>
+// Multi-head self-attention, softmax(q k^T / sqrt(head dim)) v per (image, head): one description of the problem, one place that
+// decides which kernel family takes it and refuses what has none (attention.hip).  Callers only describe.
+// Operands: qkv [N*T, 3C] (q | k | v, head h at columns h * cols..), out / dout [N*T, C], dqkv like qkv, lse fp32 [N*heads*T];
+// bf16, IEEE half or fp32 by `prec`.  cols = prx_mha_head_cols(hd) >= hd; the cols - hd pad columns of a head are zeros in qkv and
+// come out as exact zeros in out / dqkv.
+struct MhaDesc {
+    int N = 0, T = 0, heads = 0;
+    int hd = 64;                 // head dim as the operands carry it: 64 (also the 16- and 32-wide heads a runner folds into 64 columns), 80, 88, 104
+    int C = 0;                   // columns of out: must be heads * prx_mha_head_cols(hd)
+    int prec = PRX_PREC_BF16;    // PRX_PREC_*
+    int causal = 0;              // causal mask (CLIP text transformer): forward only, 16-bit, head dim 64; takes no lse, `recompute` is not read
+    int recompute = 0;           // 0: the caller keeps out + lse for the backward (any T).  1: the recomputing form, which takes no lse and
+                                 // whose backward does not read out: the wave-per-head kernels, where prx_mha_can_recompute holds
+};
+// operand columns per head for a head dim of the weights: {16, 32, 64} -> 64, {80, 88} -> 96, 104 -> 128, else 0 (no kernel)
+int prx_mha_head_cols(int hd);
+// the recomputing form has a kernel for this problem (16-bit operands, head dim 64, T <= 64, not causal): what a runner that can
+// work either way sets `recompute` from
+bool prx_mha_can_recompute(const MhaDesc& d);
+// the caller must allocate out + lse per layer and hand the same buffers to the backward
+inline bool prx_mha_saves_out(const MhaDesc& d) { return !d.causal && !d.recompute; }
+// the softmax scale of every family
+inline float prx_mha_scale(int hd) { return 1.f / sqrtf((float)hd); }
+
+// `lse` is null where !prx_mha_saves_out(d); the backward then reads neither `out` nor `lse`
+int prx_mha_fwd(const MhaDesc& d, const void* qkv, void* out, float* lse, hipStream_t s);
+int prx_mha_bwd(const MhaDesc& d, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, hipStream_t s);

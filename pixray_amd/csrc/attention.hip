@@ -7,142 +7,157 @@
 // 32-lane butterflies.  Backward recomputes P and produces dQ/dK/dV in one pass.
 //
 // The kernels live in attention_kernels.h, templates on the 16-bit operand format: bf16 (FmtBf16, v_mfma_f32_32x32x16_bf16) and
-// IEEE half (FmtF16, v_mfma_f32_32x32x16_f16, PRX_PREC_F16 -- the arithmetic of the reference's fp16 CLIP towers, slip.py:175); the
-// public entry points pick the instantiation from `h16`.  The workgroup-per-(image, head) family is also a template on the operand
-// columns per head: 64, and 96 for heads of 80 zero-padded (OpenCLIP ViT-H/14, prx_mha_*_hd96).
+// IEEE half (FmtF16, v_mfma_f32_32x32x16_f16, PRX_PREC_F16 -- the arithmetic of the reference's fp16 CLIP towers, slip.py:175).
+// The workgroup-per-(image, head) family ("blk") is also a template on the operand columns per head: 64, 96 for heads of 80
+// (OpenCLIP ViT-H/14) and 88 (ViT-g-14) zero-padded, 128 for heads of 104 (ViT-bigG-14).  The exact-f32 family is attention_f32.hip.
+//
+// This file is the host layer of all of them: prx_mha_fwd / prx_mha_bwd take a description of the problem (MhaDesc, attention.h),
+// mha_plan decides which family takes it or refuses it, and the launchers below it only launch.
 #include "attention_kernels.h"
+#include "attention_f32.h"
 #include <stdlib.h>
 #include <atomic>
 
-// Which family takes a general-T call.  The workgroup-per-(image, head) kernels (attention_kernels.h, "blk") split a head over
-// gridDim.z workgroups of <= 5 waves, each streaming the head's whole K / V (or Q / dO), so nothing in them depends on T; they take
-// T <= MHA_BLK_MAX_T = 640 (ViT-L/14@336px: 577 tokens = 19 token blocks on 4 x 5 waves), the tile kernels everything longer.  At N = 32,
-// T = 577, 16 heads they measured 147 us forward / 441 us backward against the tile kernels' 623 / 3269 us.
+// Which family takes a general-T call at 64 columns.  The blk kernels split a head over gridDim.z workgroups of <= 5 waves, each
+// streaming the head's whole K / V (or Q / dO), so nothing in them depends on T; they take T <= MHA_BLK_MAX_T = 640 (ViT-L/14@336px:
+// 577 tokens = 19 token blocks on 4 x 5 waves), the tile kernels everything longer.  At N = 32, T = 577, 16 heads they measured
+// 147 us forward / 441 us backward against the tile kernels' 623 / 3269 us.
 // prx_mha_route (include/prx.h) chooses the route of the NEXT calls: -1 the rule above (PRX_MHA_TILES=1 in the environment: tiles
-// everywhere, A/B measurements), 0 the workgroup family wherever it is able, 1 the tile kernels.  The 96-wide instances have no tile
-// fallback: prx_mha_*_hd96 refuse T > MHA_BLK_MAX_T and ignore the route.
+// everywhere, A/B measurements), 0 the blk family wherever it is able, 1 the tile kernels.  It is read at every launch, never kept
+// in a handle.  The 96- and 128-wide instances have no tile fallback: they refuse T > MHA_BLK_MAX_T and ignore the route.
 constexpr int MHA_BLK_MAX_T = 640;
 static std::atomic<int> g_mha_route{-1};
 extern "C" int prx_mha_route(int route) { return g_mha_route.exchange(route < 0 ? -1 : (route ? 1 : 0)); }
-static bool prx_mha_blk_route(int T) {
+static bool prx_mha_blk_route(int T, int route) {
     static const bool env_tiles = [] { const char* e = getenv("PRX_MHA_TILES"); return e && e[0] == '1'; }();
-    const int route = g_mha_route.load(std::memory_order_relaxed);
     return T <= MHA_BLK_MAX_T && route != 1 && !(route < 0 && env_tiles);
 }
 
+int prx_mha_head_cols(int hd) {
+    return (hd == 16 || hd == 32 || hd == 64) ? 64 : (hd == 80 || hd == 88) ? 96 : hd == 104 ? 128 : 0;
+}
+bool prx_mha_can_recompute(const MhaDesc& d) { return !prec_is_f32(d.prec) && !d.causal && d.hd == 64 && d.T <= 64; }
+
 namespace {
 
-template <typename F>
-int mha_fwd(const El<F>* qkv, El<F>* out, int N, int T, int C, int heads, hipStream_t s) {
-    PRX_REQUIRE(T <= 64 && C == heads * 64, "mha: needs T <= 64 and head dim 64 (T=%d C=%d heads=%d)", T, C, heads);
-    hipLaunchKernelGGL(mha_fwd_kernel<F>, dim3(heads, N), dim3(128), 0, s, qkv, out, T, C, 0.125f, prx_xcd_local());
-    PRX_LAUNCH_CHECK();
-    return 0;
-}
-template <typename F>
-int mha_bwd(const El<F>* qkv, const El<F>* dout, El<F>* dqkv, int N, int T, int C, int heads, hipStream_t s) {
-    PRX_REQUIRE(T <= 64 && C == heads * 64, "mha bwd: needs T <= 64 and head dim 64 (T=%d C=%d heads=%d)", T, C, heads);
-    hipLaunchKernelGGL(mha_bwd_kernel<F>, dim3(heads, N), dim3(128), 0, s, qkv, dout, dqkv, T, C, 0.125f, prx_xcd_local());
-    PRX_LAUNCH_CHECK();
+// the family codes of prx_mha_describe (include/prx.h)
+enum { MHA_WAVE = 1, MHA_BLK = 2, MHA_TILE = 3, MHA_F32 = 4 };
+
+// The routing table: the family that takes `d` under `route` and the operand columns per head, or a refusal.
+int mha_plan(const MhaDesc& d, int route, bool backward, int* family, int* cols_out) {
+    PRX_REQUIRE(prec_valid(d.prec) && d.N >= 1 && d.T >= 1 && d.heads >= 1,
+                "mha: needs a PRX_PREC_* precision and N, T, heads >= 1 (precision %d N=%d T=%d heads=%d)", d.prec, d.N, d.T, d.heads);
+    const int cols = d.hd >= 64 ? prx_mha_head_cols(d.hd) : 0;
+    PRX_REQUIRE(cols != 0, "mha: no kernel for head dim %d at %d columns per head (64 runs at 64, 80 | 88 at 96, 104 at 128)", d.hd,
+                d.C / d.heads);
+    PRX_REQUIRE(d.C == d.heads * cols, "mha: head dim %d at %d columns per head (C=%d heads=%d): it needs %d columns per head", d.hd,
+                d.C / d.heads, d.C, d.heads, cols);
+    *cols_out = cols;
+    if (d.causal) {
+        PRX_REQUIRE(!backward && !prec_is_f32(d.prec) && d.hd == 64,
+                    "mha: the causal form is forward only, on 16-bit operands, and needs head dim 64 (head dim %d, precision %d)", d.hd, d.prec);
+        *family = MHA_TILE;
+    } else if (d.recompute) {
+        PRX_REQUIRE(prx_mha_can_recompute(d), "mha: the recomputing form needs 16-bit operands, T <= 64 and head dim 64 (T=%d, head dim %d, precision %d)",
+                    d.T, d.hd, d.prec);
+        *family = MHA_WAVE;
+    } else if (prec_is_f32(d.prec)) {
+        *family = MHA_F32;
+    } else if (cols != 64) {
+        PRX_REQUIRE(d.T <= MHA_BLK_MAX_T, "mha: heads of %d columns have the blk family alone, which needs 1 <= T <= %d (T=%d, head dim %d)", cols,
+                    MHA_BLK_MAX_T, d.T, d.hd);
+        *family = MHA_BLK;
+    } else {
+        *family = prx_mha_blk_route(d.T, route) ? MHA_BLK : MHA_TILE;
+    }
     return 0;
 }
 
 // the blk family: workgroups of <= WPB waves per (image, head), one wave per 32 tokens
 template <typename F, int HDP>
-int mha_fwd_blk(const El<F>* qkv, El<F>* out, float* lse, int N, int T, int C, int heads, float scale, hipStream_t s) {
-    const int nw = ceil_div(T, 32), nsplit = ceil_div(nw, WPB), wpb = ceil_div(nw, nsplit);
-    hipLaunchKernelGGL((mha_fwd_blk_kernel<F, HDP>), dim3(heads, N, nsplit), dim3(64 * wpb), 0, s, qkv, out, lse, T, C, heads, scale,
-                       prx_xcd_local());
+int mha_fwd_blk(const MhaDesc& d, const El<F>* qkv, El<F>* out, float* lse, hipStream_t s) {
+    const int nw = ceil_div(d.T, 32), nsplit = ceil_div(nw, WPB), wpb = ceil_div(nw, nsplit);
+    hipLaunchKernelGGL((mha_fwd_blk_kernel<F, HDP>), dim3(d.heads, d.N, nsplit), dim3(64 * wpb), 0, s, qkv, out, lse, d.T, d.C, d.heads,
+                       prx_mha_scale(d.hd), prx_xcd_local());
     PRX_LAUNCH_CHECK();
     return 0;
 }
 template <typename F, int HDP>
-int mha_bwd_blk(const El<F>* qkv, const El<F>* out, const El<F>* dout, const float* lse, El<F>* dqkv, int N, int T, int C, int heads,
-                float scale, hipStream_t s) {
-    const int nw = ceil_div(T, 32), nsplit = ceil_div(nw, WPB), wpb = ceil_div(nw, nsplit);
-    const dim3 g(heads, N, nsplit), b(64 * wpb);
+int mha_bwd_blk(const MhaDesc& d, const El<F>* qkv, const El<F>* out, const El<F>* dout, const float* lse, El<F>* dqkv, hipStream_t s) {
+    const int nw = ceil_div(d.T, 32), nsplit = ceil_div(nw, WPB), wpb = ceil_div(nw, nsplit);
+    const dim3 g(d.heads, d.N, nsplit), b(64 * wpb);
+    const float scale = prx_mha_scale(d.hd);
     const int xcd = prx_xcd_local();
-    hipLaunchKernelGGL((mha_bwd_dq_blk_kernel<F, HDP>), g, b, 0, s, qkv, out, dout, lse, dqkv, T, C, heads, scale, xcd);
+    hipLaunchKernelGGL((mha_bwd_dq_blk_kernel<F, HDP>), g, b, 0, s, qkv, out, dout, lse, dqkv, d.T, d.C, d.heads, scale, xcd);
     PRX_LAUNCH_CHECK();
-    hipLaunchKernelGGL((mha_bwd_dkv_blk_kernel<F, HDP>), g, b, 0, s, qkv, out, dout, lse, dqkv, T, C, heads, scale, xcd);
+    hipLaunchKernelGGL((mha_bwd_dkv_blk_kernel<F, HDP>), g, b, 0, s, qkv, out, dout, lse, dqkv, d.T, d.C, d.heads, scale, xcd);
     PRX_LAUNCH_CHECK();
     return 0;
 }
 
 template <typename F>
-int mha_fwd_gen(const El<F>* qkv, El<F>* out, float* lse, int N, int T, int C, int heads, hipStream_t s) {
-    PRX_REQUIRE(C == heads * 64 && T >= 1, "mha(gen): needs head dim 64 (T=%d C=%d heads=%d)", T, C, heads);
-    if (prx_mha_blk_route(T)) return mha_fwd_blk<F, 64>(qkv, out, lse, N, T, C, heads, 0.125f, s);
-    hipLaunchKernelGGL((mha_fwd_gen_kernel<F, false>), dim3(ceil_div(T, 64), heads, N), dim3(64), 0, s, qkv, out, lse, T, C, heads, 0.125f);
+int mha_fwd_16(const MhaDesc& d, int family, int cols, const El<F>* qkv, El<F>* out, float* lse, hipStream_t s) {
+    if (family == MHA_BLK)
+        return cols == 64 ? mha_fwd_blk<F, 64>(d, qkv, out, lse, s) : cols == 96 ? mha_fwd_blk<F, 96>(d, qkv, out, lse, s)
+                                                                                 : mha_fwd_blk<F, 128>(d, qkv, out, lse, s);
+    const float scale = prx_mha_scale(d.hd);
+    if (family == MHA_WAVE) {        // one wave per (image, head), T <= 64
+        hipLaunchKernelGGL(mha_fwd_kernel<F>, dim3(d.heads, d.N), dim3(128), 0, s, qkv, out, d.T, d.C, scale, prx_xcd_local());
+    } else if (d.causal) {           // the tile kernels: one wave per 64-token tile, online softmax
+        hipLaunchKernelGGL((mha_fwd_gen_kernel<F, true>), dim3(ceil_div(d.T, 64), d.heads, d.N), dim3(64), 0, s, qkv, out, (float*)nullptr, d.T,
+                           d.C, d.heads, scale);
+    } else {
+        hipLaunchKernelGGL((mha_fwd_gen_kernel<F, false>), dim3(ceil_div(d.T, 64), d.heads, d.N), dim3(64), 0, s, qkv, out, lse, d.T, d.C,
+                           d.heads, scale);
+    }
     PRX_LAUNCH_CHECK();
     return 0;
 }
 template <typename F>
-int mha_fwd_causal(const El<F>* qkv, El<F>* out, int N, int T, int C, int heads, hipStream_t s) {
-    PRX_REQUIRE(C == heads * 64 && T >= 1, "mha(causal): needs head dim 64 (T=%d C=%d heads=%d)", T, C, heads);
-    hipLaunchKernelGGL((mha_fwd_gen_kernel<F, true>), dim3(ceil_div(T, 64), heads, N), dim3(64), 0, s, qkv, out, (float*)nullptr, T, C,
-                       heads, 0.125f);
+int mha_bwd_16(const MhaDesc& d, int family, int cols, const El<F>* qkv, const El<F>* out, const El<F>* dout, const float* lse, El<F>* dqkv,
+               hipStream_t s) {
+    if (family == MHA_BLK)
+        return cols == 64 ? mha_bwd_blk<F, 64>(d, qkv, out, dout, lse, dqkv, s) : cols == 96 ? mha_bwd_blk<F, 96>(d, qkv, out, dout, lse, dqkv, s)
+                                                                                             : mha_bwd_blk<F, 128>(d, qkv, out, dout, lse, dqkv, s);
+    const float scale = prx_mha_scale(d.hd);
+    if (family == MHA_WAVE) {
+        hipLaunchKernelGGL(mha_bwd_kernel<F>, dim3(d.heads, d.N), dim3(128), 0, s, qkv, dout, dqkv, d.T, d.C, scale, prx_xcd_local());
+        PRX_LAUNCH_CHECK();
+        return 0;
+    }
+    const dim3 grid(ceil_div(d.T, 64), d.heads, d.N);
+    hipLaunchKernelGGL(mha_bwd_dq_gen_kernel<F>, grid, dim3(64), 0, s, qkv, out, dout, lse, dqkv, d.T, d.C, d.heads, scale);
     PRX_LAUNCH_CHECK();
-    return 0;
-}
-template <typename F>
-int mha_bwd_gen(const El<F>* qkv, const El<F>* out, const El<F>* dout, const float* lse, El<F>* dqkv, int N, int T, int C, int heads,
-                hipStream_t s) {
-    PRX_REQUIRE(C == heads * 64 && T >= 1, "mha(gen) bwd: needs head dim 64 (T=%d C=%d heads=%d)", T, C, heads);
-    if (prx_mha_blk_route(T)) return mha_bwd_blk<F, 64>(qkv, out, dout, lse, dqkv, N, T, C, heads, 0.125f, s);
-    dim3 grid(ceil_div(T, 64), heads, N);
-    hipLaunchKernelGGL(mha_bwd_dq_gen_kernel<F>, grid, dim3(64), 0, s, qkv, out, dout, lse, dqkv, T, C, heads, 0.125f);
-    PRX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(mha_bwd_dkv_gen_kernel<F>, grid, dim3(64), 0, s, qkv, out, dout, lse, dqkv, T, C, heads, 0.125f);
+    hipLaunchKernelGGL(mha_bwd_dkv_gen_kernel<F>, grid, dim3(64), 0, s, qkv, out, dout, lse, dqkv, d.T, d.C, d.heads, scale);
     PRX_LAUNCH_CHECK();
     return 0;
 }
 
 }  // namespace
 
-#define H(p) reinterpret_cast<const half_t*>(p)
-#define HM(p) reinterpret_cast<half_t*>(p)
-int prx_mha_fwd(const bf16_t* qkv, bf16_t* out, int N, int T, int C, int heads, hipStream_t s, int h16) {
-    return h16 ? mha_fwd<FmtF16>(H(qkv), HM(out), N, T, C, heads, s) : mha_fwd<FmtBf16>(qkv, out, N, T, C, heads, s);
+int prx_mha_fwd(const MhaDesc& d, const void* qkv, void* out, float* lse, hipStream_t s) {
+    int family, cols, r;
+    if ((r = mha_plan(d, g_mha_route.load(std::memory_order_relaxed), false, &family, &cols))) return r;
+    if (family == MHA_F32) return prx_mha_f32_fwd(d, (const float*)qkv, (float*)out, lse, s);
+    return prec_is_h16(d.prec) ? mha_fwd_16<FmtF16>(d, family, cols, (const half_t*)qkv, (half_t*)out, lse, s)
+                               : mha_fwd_16<FmtBf16>(d, family, cols, (const bf16_t*)qkv, (bf16_t*)out, lse, s);
 }
-int prx_mha_bwd(const bf16_t* qkv, const bf16_t* dout, bf16_t* dqkv, int N, int T, int C, int heads, hipStream_t s, int h16) {
-    return h16 ? mha_bwd<FmtF16>(H(qkv), H(dout), HM(dqkv), N, T, C, heads, s) : mha_bwd<FmtBf16>(qkv, dout, dqkv, N, T, C, heads, s);
+int prx_mha_bwd(const MhaDesc& d, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, hipStream_t s) {
+    int family, cols, r;
+    if ((r = mha_plan(d, g_mha_route.load(std::memory_order_relaxed), true, &family, &cols))) return r;
+    if (family == MHA_F32) return prx_mha_f32_bwd(d, (const float*)qkv, (const float*)out, (const float*)dout, lse, (float*)dqkv, s);
+    return prec_is_h16(d.prec)
+               ? mha_bwd_16<FmtF16>(d, family, cols, (const half_t*)qkv, (const half_t*)out, (const half_t*)dout, lse, (half_t*)dqkv, s)
+               : mha_bwd_16<FmtBf16>(d, family, cols, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, (bf16_t*)dqkv, s);
 }
-int prx_mha_fwd_gen(const bf16_t* qkv, bf16_t* out, float* lse, int N, int T, int C, int heads, hipStream_t s, int h16) {
-    return h16 ? mha_fwd_gen<FmtF16>(H(qkv), HM(out), lse, N, T, C, heads, s) : mha_fwd_gen<FmtBf16>(qkv, out, lse, N, T, C, heads, s);
-}
-int prx_mha_fwd_causal(const bf16_t* qkv, bf16_t* out, int N, int T, int C, int heads, hipStream_t s, int h16) {
-    return h16 ? mha_fwd_causal<FmtF16>(H(qkv), HM(out), N, T, C, heads, s) : mha_fwd_causal<FmtBf16>(qkv, out, N, T, C, heads, s);
-}
-int prx_mha_bwd_gen(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, int N, int T,
-                    int C, int heads, hipStream_t s, int h16) {
-    return h16 ? mha_bwd_gen<FmtF16>(H(qkv), H(out), H(dout), lse, HM(dqkv), N, T, C, heads, s)
-               : mha_bwd_gen<FmtBf16>(qkv, out, dout, lse, dqkv, N, T, C, heads, s);
-}
-int prx_mha_fwd_hd96(const bf16_t* qkv, bf16_t* out, float* lse, int N, int T, int C, int heads, float scale, hipStream_t s, int h16) {
-    PRX_REQUIRE(C == heads * 96 && T >= 1 && T <= MHA_BLK_MAX_T && N >= 1,
-                "mha(hd96): needs 96 columns per head and 1 <= T <= %d (T=%d C=%d heads=%d)", MHA_BLK_MAX_T, T, C, heads);
-    return h16 ? mha_fwd_blk<FmtF16, 96>(H(qkv), HM(out), lse, N, T, C, heads, scale, s)
-               : mha_fwd_blk<FmtBf16, 96>(qkv, out, lse, N, T, C, heads, scale, s);
-}
-int prx_mha_bwd_hd96(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, int N, int T, int C,
-                     int heads, float scale, hipStream_t s, int h16) {
-    PRX_REQUIRE(C == heads * 96 && T >= 1 && T <= MHA_BLK_MAX_T && N >= 1,
-                "mha(hd96) bwd: needs 96 columns per head and 1 <= T <= %d (T=%d C=%d heads=%d)", MHA_BLK_MAX_T, T, C, heads);
-    return h16 ? mha_bwd_blk<FmtF16, 96>(H(qkv), H(out), H(dout), lse, HM(dqkv), N, T, C, heads, scale, s)
-               : mha_bwd_blk<FmtBf16, 96>(qkv, out, dout, lse, dqkv, N, T, C, heads, scale, s);
-}
-// heads of 104 zero-padded to 128 columns (OpenCLIP ViT-bigG-14); the chunked kernels do not depend on T, so the cap is the family's
-int prx_mha_fwd_hd128(const bf16_t* qkv, bf16_t* out, float* lse, int N, int T, int C, int heads, float scale, hipStream_t s, int h16) {
-    PRX_REQUIRE(C == heads * 128 && T >= 1 && T <= MHA_BLK_MAX_T && N >= 1,
-                "mha(hd128): needs 128 columns per head and 1 <= T <= %d (T=%d C=%d heads=%d)", MHA_BLK_MAX_T, T, C, heads);
-    return h16 ? mha_fwd_blk<FmtF16, 128>(H(qkv), HM(out), lse, N, T, C, heads, scale, s)
-               : mha_fwd_blk<FmtBf16, 128>(qkv, out, lse, N, T, C, heads, scale, s);
-}
-int prx_mha_bwd_hd128(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, int N, int T, int C,
-                      int heads, float scale, hipStream_t s, int h16) {
-    PRX_REQUIRE(C == heads * 128 && T >= 1 && T <= MHA_BLK_MAX_T && N >= 1,
-                "mha(hd128) bwd: needs 128 columns per head and 1 <= T <= %d (T=%d C=%d heads=%d)", MHA_BLK_MAX_T, T, C, heads);
-    return h16 ? mha_bwd_blk<FmtF16, 128>(H(qkv), H(out), H(dout), lse, HM(dqkv), N, T, C, heads, scale, s)
-               : mha_bwd_blk<FmtBf16, 128>(qkv, out, dout, lse, dqkv, N, T, C, heads, scale, s);
+
+// include/prx.h: what the two functions above would do with such a problem under `route`, from the same mha_plan
+extern "C" int prx_mha_describe(int precision, int head_dim, int T, int causal, int recompute, int route, int* family, int* head_cols,
+                                int* saves_out) {
+    MhaDesc d;
+    d.N = 1; d.T = T; d.heads = 1; d.hd = head_dim; d.prec = precision; d.causal = causal; d.recompute = recompute;
+    d.C = (head_dim >= 64 && prx_mha_head_cols(head_dim)) ? prx_mha_head_cols(head_dim) : head_dim;
+    *family = 0; *head_cols = 0;       // a refusal leaves the family at 0; its text is prx_last_error's
+    *saves_out = prx_mha_saves_out(d);
+    return mha_plan(d, route < 0 ? -1 : (route ? 1 : 0), false, family, head_cols);
 }

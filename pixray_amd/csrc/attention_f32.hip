@@ -1,11 +1,12 @@
 // Exact-f32 multi-head self-attention for the PRX_PREC_F32 parity mode (same operator as attention.hip:
 // nn.MultiheadAttention inside clip.model.ResidualAttentionBlock [UPSTREAM openai/CLIP clip/model.py], call site
-// slip.py:65), any sequence length, head dim 64, forward and activation-gradient backward.
+// slip.py:65), any sequence length, head dims 64 | 80 | 88 | 104, forward and activation-gradient backward.  Reached through the
+// dispatcher of attention.hip alone (attention_f32.h).
 //
 // This is the checker's arithmetic, not the fast path: fp32 operands, fp32 VALU fma chains, one query (or key) per lane,
 // the other side of the product broadcast from LDS in 64-token blocks with an online softmax.  What it must be is
 // simple and exact; the bf16 MFMA kernels in attention.hip are measured against it.
-#include "attention.h"
+#include "attention_f32.h"
 
 namespace {
 
@@ -242,80 +243,44 @@ __global__ __launch_bounds__(64) void mha_bwd_dkv_f32_kernel(const float* __rest
     }
 }
 
-}  // namespace
-
-int prx_mha_fwd_f32(const float* qkv, float* out, float* lse, int N, int T, int C, int heads, hipStream_t s) {
-    PRX_REQUIRE(C == heads * 64 && T >= 1, "mha(f32): needs head dim 64 (T=%d C=%d heads=%d)", T, C, heads);
-    hipLaunchKernelGGL((mha_fwd_f32_kernel<64, 64>), dim3(ceil_div(T, 64), heads, N), dim3(64), 0, s, qkv, out, lse, T, C, heads, 0.125f);
-    PRX_LAUNCH_CHECK();
-    return 0;
-}
-
-int prx_mha_bwd_f32(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int N, int T, int C,
-                    int heads, hipStream_t s) {
-    PRX_REQUIRE(C == heads * 64 && T >= 1, "mha(f32) bwd: needs head dim 64 (T=%d C=%d heads=%d)", T, C, heads);
-    const dim3 grid(ceil_div(T, 64), heads, N);
-    hipLaunchKernelGGL((mha_bwd_dq_f32_kernel<64, 64>), grid, dim3(64), 0, s, qkv, out, dout, lse, dqkv, T, C, heads, 0.125f);
-    PRX_LAUNCH_CHECK();
-    hipLaunchKernelGGL((mha_bwd_dkv_f32_kernel<64, 64>), grid, dim3(64), 0, s, qkv, out, dout, lse, dqkv, T, C, heads, 0.125f);
-    PRX_LAUNCH_CHECK();
-    return 0;
-}
-
-// head dim 80 in 96 columns per head, softmax scale 1 / sqrt(80)
-int prx_mha_fwd_f32_hd96(const float* qkv, float* out, float* lse, int N, int T, int C, int heads, hipStream_t s) {
-    PRX_REQUIRE(C == heads * 96 && T >= 1, "mha(f32, hd96): needs 96 columns per head (T=%d C=%d heads=%d)", T, C, heads);
-    hipLaunchKernelGGL((mha_fwd_f32_kernel<80, 96>), dim3(ceil_div(T, 64), heads, N), dim3(64), 0, s, qkv, out, lse, T, C, heads,
-                       0.11180339887498948f);
-    PRX_LAUNCH_CHECK();
-    return 0;
-}
-
-int prx_mha_bwd_f32_hd96(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int N, int T, int C,
-                         int heads, hipStream_t s) {
-    PRX_REQUIRE(C == heads * 96 && T >= 1, "mha(f32, hd96) bwd: needs 96 columns per head (T=%d C=%d heads=%d)", T, C, heads);
-    const dim3 grid(ceil_div(T, 64), heads, N);
-    hipLaunchKernelGGL((mha_bwd_dq_f32_kernel<80, 96>), grid, dim3(64), 0, s, qkv, out, dout, lse, dqkv, T, C, heads, 0.11180339887498948f);
-    PRX_LAUNCH_CHECK();
-    hipLaunchKernelGGL((mha_bwd_dkv_f32_kernel<80, 96>), grid, dim3(64), 0, s, qkv, out, dout, lse, dqkv, T, C, heads, 0.11180339887498948f);
-    PRX_LAUNCH_CHECK();
-    return 0;
-}
-
-// head dim `hd` zero-padded to its operand columns per head: 88 in 96 (OpenCLIP ViT-g-14), 104 in 128 (ViT-bigG-14); scale 1 / sqrt(hd)
-namespace {
+// one launcher per direction: the tile grid, one wave per workgroup, any T
 template <int HD, int HS>
-int mha_fwd_f32_pad(const float* qkv, float* out, float* lse, int N, int T, int C, int heads, hipStream_t s) {
-    PRX_REQUIRE(C == heads * HS && T >= 1, "mha(f32, head dim %d): needs %d columns per head (T=%d C=%d heads=%d)", HD, HS, T, C, heads);
-    hipLaunchKernelGGL((mha_fwd_f32_kernel<HD, HS>), dim3(ceil_div(T, 64), heads, N), dim3(64), 0, s, qkv, out, lse, T, C, heads,
-                       1.f / sqrtf((float)HD));
+int mha_fwd_f32(const MhaDesc& d, const float* qkv, float* out, float* lse, hipStream_t s) {
+    hipLaunchKernelGGL((mha_fwd_f32_kernel<HD, HS>), dim3(ceil_div(d.T, 64), d.heads, d.N), dim3(64), 0, s, qkv, out, lse, d.T, d.C, d.heads,
+                       prx_mha_scale(HD));
     PRX_LAUNCH_CHECK();
     return 0;
 }
 template <int HD, int HS>
-int mha_bwd_f32_pad(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int N, int T, int C, int heads,
-                    hipStream_t s) {
-    PRX_REQUIRE(C == heads * HS && T >= 1, "mha(f32, head dim %d) bwd: needs %d columns per head (T=%d C=%d heads=%d)", HD, HS, T, C, heads);
-    const dim3 grid(ceil_div(T, 64), heads, N);
-    const float scale = 1.f / sqrtf((float)HD);
-    hipLaunchKernelGGL((mha_bwd_dq_f32_kernel<HD, HS>), grid, dim3(64), 0, s, qkv, out, dout, lse, dqkv, T, C, heads, scale);
+int mha_bwd_f32(const MhaDesc& d, const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, hipStream_t s) {
+    const dim3 grid(ceil_div(d.T, 64), d.heads, d.N);
+    const float scale = prx_mha_scale(HD);
+    hipLaunchKernelGGL((mha_bwd_dq_f32_kernel<HD, HS>), grid, dim3(64), 0, s, qkv, out, dout, lse, dqkv, d.T, d.C, d.heads, scale);
     PRX_LAUNCH_CHECK();
-    hipLaunchKernelGGL((mha_bwd_dkv_f32_kernel<HD, HS>), grid, dim3(64), 0, s, qkv, out, dout, lse, dqkv, T, C, heads, scale);
+    hipLaunchKernelGGL((mha_bwd_dkv_f32_kernel<HD, HS>), grid, dim3(64), 0, s, qkv, out, dout, lse, dqkv, d.T, d.C, d.heads, scale);
     PRX_LAUNCH_CHECK();
     return 0;
 }
+
+// head dim -> instance <HD, HS = prx_mha_head_cols(HD)>, for both directions: `launch` is called with the instance as its argument
+template <int HD_, int HS_>
+struct Inst { static constexpr int HD = HD_, HS = HS_; };
+template <typename Launch>
+int mha_f32_instance(int hd, Launch launch) {
+    switch (hd) {
+        case 64: return launch(Inst<64, 64>{});
+        case 80: return launch(Inst<80, 96>{});
+        case 88: return launch(Inst<88, 96>{});
+        case 104: return launch(Inst<104, 128>{});
+    }
+    PRX_REQUIRE(false, "mha(f32): no instance for head dim %d (64 | 80 | 88 | 104)", hd);
+}
+
 }  // namespace
 
-int prx_mha_fwd_f32_pad(const float* qkv, float* out, float* lse, int N, int T, int C, int heads, int hd, hipStream_t s) {
-    if (hd == 80) return prx_mha_fwd_f32_hd96(qkv, out, lse, N, T, C, heads, s);
-    if (hd == 88) return mha_fwd_f32_pad<88, 96>(qkv, out, lse, N, T, C, heads, s);
-    PRX_REQUIRE(hd == 104, "mha(f32): no padded instance for head dim %d (80 | 88 | 104)", hd);
-    return mha_fwd_f32_pad<104, 128>(qkv, out, lse, N, T, C, heads, s);
+int prx_mha_f32_fwd(const MhaDesc& d, const float* qkv, float* out, float* lse, hipStream_t s) {
+    return mha_f32_instance(d.hd, [&](auto i) { return mha_fwd_f32<decltype(i)::HD, decltype(i)::HS>(d, qkv, out, lse, s); });
 }
-int prx_mha_bwd_f32_pad(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, int N, int T, int C,
-                        int heads, int hd, hipStream_t s) {
-    if (hd == 80) return prx_mha_bwd_f32_hd96(qkv, out, dout, lse, dqkv, N, T, C, heads, s);
-    if (hd == 88) return mha_bwd_f32_pad<88, 96>(qkv, out, dout, lse, dqkv, N, T, C, heads, s);
-    PRX_REQUIRE(hd == 104, "mha(f32) bwd: no padded instance for head dim %d (80 | 88 | 104)", hd);
-    return mha_bwd_f32_pad<104, 128>(qkv, out, dout, lse, dqkv, N, T, C, heads, s);
+int prx_mha_f32_bwd(const MhaDesc& d, const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv, hipStream_t s) {
+    return mha_f32_instance(d.hd, [&](auto i) { return mha_bwd_f32<decltype(i)::HD, decltype(i)::HS>(d, qkv, out, dout, lse, dqkv, s); });
 }

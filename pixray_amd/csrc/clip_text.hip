@@ -66,7 +66,8 @@ int prx_gather_rows(const float* x, const int* eot, float* out, int n, int ctx, 
 struct PrxClipText {
     int vocab, ctx, width, layers, heads, out_dim, max_n;
     int act;          // PRX_ACT_QUICKGELU | PRX_ACT_GELU: the epilogue code of the c_fc product
-    DevArena mem;     // every device buffer below: freed with the handle
+    MhaDesc mha;      // every block's attention: causal, bf16, forward only (N is set per call)
+    DevArena mem;    // every device buffer below: freed with the handle
     float *tok, *pos, *lnf_g, *lnf_b;
     bf16_t* projT;
     std::vector<TextLayer> L;
@@ -97,6 +98,7 @@ int prx_clip_text_create_impl(PrxClipText** out, int vocab, int ctx, int width, 
                     max_n, ctx, width, layers);
     t->vocab = vocab; t->ctx = ctx; t->width = width; t->layers = layers; t->heads = heads; t->out_dim = out_dim; t->max_n = max_n;
     t->act = gelu ? PRX_ACT_GELU : PRX_ACT_QUICKGELU;
+    t->mha.T = ctx; t->mha.heads = heads; t->mha.hd = 64; t->mha.C = width; t->mha.prec = PRX_PREC_BF16; t->mha.causal = 1;
     const int W = width;
     int r;
     if ((r = m.copy_f32(&t->tok, w[0], (size_t)vocab * W, s))) return r;
@@ -142,6 +144,7 @@ void prx_clip_text_destroy_impl(PrxClipText* t) { delete t; }
 int prx_clip_text_encode_impl(PrxClipText* t, const int* tokens, int n, float* embeds, hipStream_t s) {
     PRX_REQUIRE(n >= 1 && n <= t->max_n, "clip_text: batch %d exceeds handle capacity %d", n, t->max_n);
     const int W = t->width, T = t->ctx, R = n * T;
+    MhaDesc mha = t->mha; mha.N = n;
     int r;
     if ((r = prx_text_embed(tokens, t->tok, t->pos, t->x, t->eot, n, T, W, t->vocab, s))) return r;
     for (int l = 0; l < t->layers; ++l) {
@@ -150,7 +153,7 @@ int prx_clip_text_encode_impl(PrxClipText* t, const int* tokens, int n, float* e
         {   GemmDesc d; d.A = t->h; d.lda = W; d.B = y.Wqkv; d.ldb = W; d.M = R; d.N = 3 * W; d.K = W;
             d.bias_n = y.bqkv; d.out_bf16 = t->qkv; d.ldc_bf16 = 3 * W;
             if ((r = tg(t, d, s))) return r; }
-        if ((r = prx_mha_fwd_causal(t->qkv, t->att, n, T, W, t->heads, s))) return r;
+        if ((r = prx_mha_fwd(mha, t->qkv, t->att, nullptr, s))) return r;
         {   GemmDesc d; d.A = t->att; d.lda = W; d.B = y.Wo; d.ldb = W; d.M = R; d.N = W; d.K = W;
             d.bias_n = y.bo; d.resid = t->x; d.ldr = W; d.out_f32 = t->x_mid; d.ldc_f32 = W;
             if ((r = tg(t, d, s))) return r; }

@@ -377,6 +377,7 @@ struct PrxResNet {
     int res, width, heads, out_dim, max_n, C, G, T, cur_n;
     int prec;         // PRX_PREC_*
     int f32, h16;     // derived: operands are fp32 / the 16-bit operand format is IEEE half
+    MhaDesc mha;      // the attention pool's problem (N is set per call)
     // The lean layout (half mode, PRX_RN_LEAN, as vit.hip's PRX_LEAN): the residual stream of the Bottleneck stack and its
     // gradient live in IEEE half only -- the reference's own activation precision (CLIP's convert_weights runs the
     // tower in half).  The conv3 / downsample GEMMs then write 2 bytes per element instead of 6 and read a 2-byte
@@ -463,6 +464,8 @@ int prx_resnet_create_impl(PrxResNet** out, int res, int width, const int* layer
     { const char* ev = getenv("PRX_RN_LEAN"); r->lean = (r->h16 && !(ev && atoi(ev) == 0)) ? 1 : 0; }
     r->res = res; r->width = width; r->heads = heads; r->out_dim = out_dim; r->max_n = max_n; r->cur_n = 0;
     r->C = width * 32; r->G = res / 32; r->T = r->G * r->G + 1;
+    // the pool keeps out + lse at every token count (the saving form), also at the 50 tokens of RN50
+    r->mha.T = r->T; r->mha.heads = heads; r->mha.hd = 64; r->mha.C = r->C; r->mha.prec = precision;
     RCur cur{w, n_w, 0};
     int e;
     {   const float *ww, *bb; RNEXT(cur, ww); RNEXT(cur, bb);
@@ -577,8 +580,8 @@ int prx_resnet_forward_impl(PrxResNet* r, const float* cutouts, int n, const flo
     const int C = r->C, T = r->T, P = T - 1;
     if ((e = prx_tokens_fwd(x_f32, r->pos, r->tok, n, P, C, r->prec, s))) return e;
     if ((e = lin(r, r->tok, n * T, C, r->Win, 3 * C, r->bin, nullptr, PRX_ACT_NONE, nullptr, nullptr, r->qkv, s))) return e;
-    if (r->f32) { if ((e = prx_mha_fwd_f32((const float*)r->qkv, (float*)r->att, r->lse, n, T, C, r->heads, s))) return e; }
-    else if ((e = prx_mha_fwd_gen((const bf16_t*)r->qkv, (bf16_t*)r->att, r->lse, n, T, C, r->heads, s, r->h16))) return e;
+    MhaDesc mha = r->mha; mha.N = n;
+    if ((e = prx_mha_fwd(mha, r->qkv, r->att, r->lse, s))) return e;
     if ((e = prx_tok0_gather(r->att, r->o0, n, T, C, r->prec, s))) return e;
     if ((e = lin(r, r->o0, n, C, r->Wc, r->out_dim, r->bc, nullptr, PRX_ACT_NONE, nullptr, r->e, nullptr, s))) return e;
     return prx_l2norm_fwd(r->e, embeds, n, r->out_dim, s);
@@ -604,8 +607,8 @@ int prx_resnet_backward_a_impl(PrxResNet* r, const float* cutouts, const float* 
         }
         if ((e = rg(r, d, s))) return e; }
     if ((e = prx_tok0_scatter(r->do0, r->dtok, n, T, C, r->prec, s))) return e;
-    if (r->f32) { if ((e = prx_mha_bwd_f32((const float*)r->qkv, (const float*)r->att, (const float*)r->dtok, r->lse, (float*)r->dqkv, n, T, C, r->heads, s))) return e; }
-    else if ((e = prx_mha_bwd_gen((const bf16_t*)r->qkv, (const bf16_t*)r->att, (const bf16_t*)r->dtok, r->lse, (bf16_t*)r->dqkv, n, T, C, r->heads, s, r->h16))) return e;
+    MhaDesc mha = r->mha; mha.N = n;
+    if ((e = prx_mha_bwd(mha, r->qkv, r->att, r->dtok, r->lse, r->dqkv, s))) return e;
     if ((e = lin(r, r->dqkv, n * T, 3 * C, r->WinT, C, nullptr, nullptr, PRX_ACT_NONE, nullptr, r->dtokf, nullptr, s))) return e;
     float* g = r->gA; float* g2 = r->gB;
     const int lean = r->lean;

@@ -1,6 +1,7 @@
 #pragma once
 #include "common.h"
 #include "cutouts.h"
+#include "attention.h"     // prx_mha_head_cols: the head dims VitFamily::head_dim may take
 struct PrxVit;
 // What differs between the tower families this runner serves.  CLIP (clip.model.VisionTransformer): no patch-embed bias, ln_pre,
 // eps 1e-5, QuickGELU, CLIP's preprocessing constants.  SLIP (timm VisionTransformer): a bias, no ln_pre, eps 1e-6, exact GELU,
@@ -16,7 +17,6 @@ struct VitFamily {
     int mlp_width;      // hidden width of the MLP; 0 = 4 * width (OpenCLIP ViT-g-14: 6144 on 1408, ViT-bigG-14: 8192 on 1664)
 };
 VitFamily prx_vit_family_clip();
-int prx_vit_head_cols(int hd);     // operand columns per head for a head dim: {16, 32, 64} -> 64, {80, 88} -> 96, 104 -> 128, else 0
 struct GemmCtx;
 int prx_pack_bf16(const float* in, bf16_t* out, size_t n, hipStream_t s);
 int prx_pack_transpose_bf16(const float* in, bf16_t* out, int R, int C, hipStream_t s);

@@ -151,7 +151,7 @@ struct VitLayer {
     void *x_in, *x_mid;
     float *mean1, *rstd1, *mean2, *rstd2;
     void *qkv, *t;    // operand precision
-    void* o_save;     // attention output, kept for the general-T backward (T > 64) and the fp32 attention
+    void* o_save;     // attention output and log-sum-exp, kept for the backward where prx_mha_saves_out(PrxVit::att); else null
     float* lse;
 };
 
@@ -166,8 +166,9 @@ struct PrxVit {
     // Heads of 80 (OpenCLIP ViT-H/14: 16 heads on width 1280) are padded the same way to hp = 96 columns and run on the 96-wide
     // attention family (the 96-wide instances of attention_kernels.h), which takes the softmax scale 1 / sqrt(80) as an argument: nothing is folded into q.
     // Heads of 88 (ViT-g-14: 16 heads on width 1408) run there too with 1 / sqrt(88); heads of 104 (ViT-bigG-14: 16 on 1664) are padded to
-    // hp = 128 and run on the 128-wide instances with 1 / sqrt(104) (prx_vit_head_cols below is the mapping).
+    // hp = 128 and run on the 128-wide instances with 1 / sqrt(104) (prx_mha_head_cols, attention.h, is the mapping).
     int hd, hp, aw;    // head dim of the weights; operand columns per head (64 | 96 | 128); attention width = heads * hp (== width when hd == 64)
+    MhaDesc att;       // the attention of every block (N is set per call): the recomputing form where it has a kernel, else out + lse are saved
     int mlp;           // hidden width of the MLP: fam.mlp_width, or 4 * width (every tower but OpenCLIP's ViT-g-14 6144 and ViT-bigG-14 8192)
     int prec;         // PRX_PREC_*: element type of every operand buffer below (void*)
     int f32, h16;     // derived: operands are fp32 / the 16-bit operand format is IEEE half
@@ -207,11 +208,6 @@ int pack_both(PrxVit* v, void** W, void** WT, const float* src, int out, int in,
 }
 }  // namespace
 
-// operand columns per head of the attention kernels that take a head dim; 0: no kernel
-int prx_vit_head_cols(int hd) {
-    return (hd == 16 || hd == 32 || hd == 64) ? 64 : (hd == 80 || hd == 88) ? 96 : hd == 104 ? 128 : 0;
-}
-
 VitFamily prx_vit_family_clip() {
     VitFamily f;
     f.patch_bias = 0; f.ln_pre = 1; f.eps = 1e-5f; f.act = PRX_ACT_QUICKGELU; f.dact = PRX_ACT_MUL_DQUICKGELU;
@@ -227,7 +223,7 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
     PRX_REQUIRE(prec_valid(precision), "vit_create: unknown precision %d", precision);
     PRX_REQUIRE(n_w == n_head + 12 * layers + 3, "vit_create: expected %d weight tensors, got %d", n_head + 12 * layers + 3, n_w);
     const int hd = fam.head_dim > 0 ? fam.head_dim : 64;
-    const int hp = prx_vit_head_cols(hd);
+    const int hp = prx_mha_head_cols(hd);
     PRX_REQUIRE(hp != 0, "vit_create: no attention kernel for a head dim of %d (16 | 32 | 64 run at 64 columns, 80 | 88 at 96, 104 at 128)", hd);
     PRX_REQUIRE(res % patch == 0 && width == heads * hd && width % 128 == 0 && width <= 2048,
                 "vit_create: unsupported geometry (width %d, %d heads of %d; the width must be heads * head dim, a multiple of 128 and <= 2048)", width, heads, hd);
@@ -251,6 +247,9 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
     v->prec = precision; v->f32 = prec_is_f32(precision); v->h16 = prec_is_h16(precision);
     v->gs = nullptr; v->fam = fam; v->bp = nullptr; v->hd = hd; v->hp = hp; v->aw = heads * hp; v->mlp = MW;
     const int AW = v->aw;
+    // heads narrower than 64 reach the kernels as heads of 64 (folded below)
+    v->att.T = T; v->att.heads = heads; v->att.hd = hd < 64 ? 64 : hd; v->att.C = AW; v->att.prec = precision;
+    v->att.recompute = prx_mha_can_recompute(v->att);
     float *pad_w = nullptr, *pad_b = nullptr;       // fp32 staging of the padded qkv / out-projection weights, reused by every block (stream order)
     if (hd != 64) {
         DEV_ALLOC(m, alloc, pad_w, (size_t)3 * AW * width);
@@ -315,7 +314,7 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
         DEV_ALLOC(m, alloc, y.mean1, R); DEV_ALLOC(m, alloc, y.rstd1, R); DEV_ALLOC(m, alloc, y.mean2, R); DEV_ALLOC(m, alloc, y.rstd2, R);
         DEV_ALLOC(m, alloc_op, y.qkv, R * 3 * AW, f32); DEV_ALLOC(m, alloc_op, y.t, R * MW, f32);
         y.o_save = nullptr; y.lse = nullptr;
-        if (T > 64 || v->f32 || hp != 64) { DEV_ALLOC(m, alloc_op, y.o_save, R * AW, f32); DEV_ALLOC(m, alloc, y.lse, (size_t)max_n * heads * T); }
+        if (prx_mha_saves_out(v->att)) { DEV_ALLOC(m, alloc_op, y.o_save, R * AW, f32); DEV_ALLOC(m, alloc, y.lse, (size_t)max_n * heads * T); }
     }
     const float* const* q = w + n_head + 12 * layers;
     if ((r = v->mem.copy_f32(&v->lnpost_g, q[0], W, s))) return r;
@@ -393,6 +392,7 @@ int prx_vit_forward_impl(PrxVit* v, const float* cutouts, int n, const float* mm
         if ((r = vit_gemm(v, d, s))) return r;
     }
     const int lean = v->lean;
+    MhaDesc mha = v->att; mha.N = n;
     void* x0 = v->layers > 0 ? v->L[0].x_in : v->x_final;
     if (v->fam.ln_pre) {
         if ((r = prx_vit_add_cls_pos(v->xpre, v->cls, v->pos, n, T, W, s))) return r;
@@ -408,16 +408,8 @@ int prx_vit_forward_impl(PrxVit* v, const float* cutouts, int n, const float* mm
         {   GemmDesc d; d.A = v->h; d.lda = W; d.B = y.Wqkv; d.ldb = W; d.M = R; d.N = 3 * AW; d.K = W;
             d.bias_n = y.bqkv; d.out_bf16 = y.qkv; d.ldc_bf16 = 3 * AW;
             if ((r = vit_gemm(v, d, s))) return r; }
-        const void* att = v->att_o;
-        if (v->hp != 64) {
-            if (v->f32) { if ((r = prx_mha_fwd_f32_pad((const float*)y.qkv, (float*)y.o_save, y.lse, n, T, AW, v->heads, v->hd, s))) return r; }
-            else if (v->hp == 96) { if ((r = prx_mha_fwd_hd96((const bf16_t*)y.qkv, (bf16_t*)y.o_save, y.lse, n, T, AW, v->heads, 1.f / sqrtf((float)v->hd), s, v->h16))) return r; }
-            else if ((r = prx_mha_fwd_hd128((const bf16_t*)y.qkv, (bf16_t*)y.o_save, y.lse, n, T, AW, v->heads, 1.f / sqrtf((float)v->hd), s, v->h16))) return r;
-            att = y.o_save;
-        }
-        else if (v->f32) { if ((r = prx_mha_fwd_f32((const float*)y.qkv, (float*)y.o_save, y.lse, n, T, AW, v->heads, s))) return r; att = y.o_save; }
-        else if (T <= 64) { if ((r = prx_mha_fwd((const bf16_t*)y.qkv, (bf16_t*)v->att_o, n, T, AW, v->heads, s, v->h16))) return r; }
-        else { if ((r = prx_mha_fwd_gen((const bf16_t*)y.qkv, (bf16_t*)y.o_save, y.lse, n, T, AW, v->heads, s, v->h16))) return r; att = y.o_save; }
+        void* att = prx_mha_saves_out(mha) ? y.o_save : v->att_o;
+        if ((r = prx_mha_fwd(mha, y.qkv, att, y.lse, s))) return r;
         // the class-token tail: rows = the n class tokens, reached through a row stride of T * W in the token-major buffers;
         // LN / MLP intermediates of those rows are stored densely ([n][...]) at the start of their buffers
         const bool tail = v->cls_tail && l == v->layers - 1;
@@ -479,6 +471,7 @@ int prx_vit_backward_a_impl(PrxVit* v, const float* cutouts, const float* mm, co
     // backward, which takes the incoming gradient as zero on every other row (add_every = T) and writes all of them -- so the
     // streams need no clearing (two fills of 14.7 MB per iteration at the headline)
     const int lean = v->lean;
+    MhaDesc mha = v->att; mha.N = n;
     if (v->layers == 0 || !v->cls_tail) PRX_CHECK_HIP(hipMemsetAsync(lean ? v->dx_bf : (void*)v->dx, 0, (lean ? sizeof(bf16_t) : sizeof(float)) * (size_t)R * W, s));
     // lean layout: dxs / dhs are the 16-bit gradient streams themselves (no fp32 copies exist)
     const void* dxs = lean ? v->dx_bf : (const void*)v->dx;
@@ -510,16 +503,7 @@ int prx_vit_backward_a_impl(PrxVit* v, const float* cutouts, const float* mm, co
         {   GemmDesc d; d.A = v->dx_bf; d.lda = ldt; d.B = y.WoT; d.ldb = W; d.M = rows; d.N = AW; d.K = W;
             d.out_bf16 = v->do_; d.ldc_bf16 = tail ? T * AW : AW;
             if ((r = vit_gemm(v, d, s))) return r; }
-        if (v->hp != 64) {
-            if (v->f32) { if ((r = prx_mha_bwd_f32_pad((const float*)y.qkv, (const float*)y.o_save, (const float*)v->do_, y.lse, (float*)v->dqkv, n, T, AW, v->heads, v->hd, s))) return r; }
-            else if (v->hp == 96) { if ((r = prx_mha_bwd_hd96((const bf16_t*)y.qkv, (const bf16_t*)y.o_save, (const bf16_t*)v->do_, y.lse, (bf16_t*)v->dqkv, n, T, AW, v->heads,
-                                                              1.f / sqrtf((float)v->hd), s, v->h16))) return r; }
-            else if ((r = prx_mha_bwd_hd128((const bf16_t*)y.qkv, (const bf16_t*)y.o_save, (const bf16_t*)v->do_, y.lse, (bf16_t*)v->dqkv, n, T, AW, v->heads,
-                                            1.f / sqrtf((float)v->hd), s, v->h16))) return r;
-        }
-        else if (v->f32) { if ((r = prx_mha_bwd_f32((const float*)y.qkv, (const float*)y.o_save, (const float*)v->do_, y.lse, (float*)v->dqkv, n, T, AW, v->heads, s))) return r; }
-        else if (T <= 64) { if ((r = prx_mha_bwd((const bf16_t*)y.qkv, (const bf16_t*)v->do_, (bf16_t*)v->dqkv, n, T, AW, v->heads, s, v->h16))) return r; }
-        else { if ((r = prx_mha_bwd_gen((const bf16_t*)y.qkv, (const bf16_t*)y.o_save, (const bf16_t*)v->do_, y.lse, (bf16_t*)v->dqkv, n, T, AW, v->heads, s, v->h16))) return r; }
+        if ((r = prx_mha_bwd(mha, y.qkv, y.o_save, v->do_, y.lse, v->dqkv, s))) return r;
         {   GemmDesc d; d.A = v->dqkv; d.lda = 3 * AW; d.B = y.WqkvT; d.ldb = 3 * AW; d.M = R; d.N = W; d.K = 3 * AW;
             if (lean) { d.out_bf16 = v->dh_bf; d.ldc_bf16 = W; } else { d.out_f32 = v->dh; d.ldc_f32 = W; }
             if ((r = vit_gemm(v, d, s))) return r; }

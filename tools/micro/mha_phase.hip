@@ -1,11 +1,12 @@
 // Phase timing of the T<=64 attention forward/backward (one wave per head): instrumented copies of the kernels with
 // s_memtime stamps, plus end-to-end timing of the real kernels.  Build:
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I pixray_amd/csrc tools/micro/mha_phase.hip -o mha_phase
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I pixray_amd/csrc tools/micro/mha_phase.hip pixray_amd/csrc/attention_f32.hip -o mha_phase
 #include "../../pixray_amd/csrc/attention.hip"
 #include <cstdio>
 #include <cstdarg>
 #include <vector>
 void prx_set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); fputc(10, stderr); }
+int prx_xcd_local() { return 1; }
 using F = FmtBf16;
 
 // softmax over j in the C layout (one wave holds all 64 keys of a row: 32-lane butterflies); s holds raw q.k sums; returns p in s
@@ -78,11 +79,13 @@ int main() {
         for (int i = 0; i < 7; ++i) printf("  %s %lld", names[i], h[i + 1] - h[i]);
         printf("  total %lld\n", h[7] - h[0]);
     }
+    MhaDesc d;      // the recomputing form: the wave-per-head kernels
+    d.N = N; d.T = T; d.heads = heads; d.C = C; d.recompute = 1;
     hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);
     for (int which = 0; which < 2; ++which) {
-        for (int i = 0; i < 3; ++i) { if (which == 0) prx_mha_fwd(qkv, out, N, T, C, heads, 0); else prx_mha_bwd(qkv, dout, dqkv, N, T, C, heads, 0); }
+        for (int i = 0; i < 3; ++i) { if (which == 0) prx_mha_fwd(d, qkv, out, nullptr, 0); else prx_mha_bwd(d, qkv, nullptr, dout, nullptr, dqkv, 0); }
         hipEventRecord(a, 0);
-        for (int i = 0; i < 200; ++i) { if (which == 0) prx_mha_fwd(qkv, out, N, T, C, heads, 0); else prx_mha_bwd(qkv, dout, dqkv, N, T, C, heads, 0); }
+        for (int i = 0; i < 200; ++i) { if (which == 0) prx_mha_fwd(d, qkv, out, nullptr, 0); else prx_mha_bwd(d, qkv, nullptr, dout, nullptr, dqkv, 0); }
         hipEventRecord(b, 0); hipEventSynchronize(b);
         float ms; hipEventElapsedTime(&ms, a, b);
         printf("%s: %.2f us per launch (back-to-back)\n", which == 0 ? "mha_fwd" : "mha_bwd", ms * 1e3f / 200);
