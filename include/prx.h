@@ -356,6 +356,10 @@ int prx_k_l2norm_bwd(const float* e, const float* g, float* de, int n, int D, pr
 int prx_k_vqgan_pack_conv3x3(const float* w, void* Wf, void* Wd, int Cout, int Cin, int CoP, int prec, prx_stream_t s);
 int prx_k_vqgan_enc_pack_conv3x3(const float* w, void* Wf, int Cout, int Cin, int CiP, prx_stream_t s);
 int prx_k_colminmax(const float* w, float* mn, float* mx, int rows, int D, prx_stream_t s);
+/* The one 3x3 weight pack behind the four pack entries above (csrc/weight_pack.h), with both paddings at once:
+ * Wf [Cout][9*CiP], Wf[co][tap*CiP + ci] = w[co][ci][ky][kx]; Wd [CiP][9*CoP], Wd[ci][tap*CoP + co] = w[co][ci][2-ky][2-kx]; the
+ * padding is zero.  Either pack may be null, not both; CiP >= Cin and CoP >= Cout. */
+int prx_k_pack_conv3x3(const float* w, void* Wf, void* Wd, int Cout, int Cin, int CiP, int CoP, int prec, prx_stream_t s);
 
 /* ------------------------------------------------------------------------ */
 /* Path-level operators: the drop-in boundary of the hot path                */

@@ -17,6 +17,7 @@
 #include "prompt_vq.h"
 #include "vqgan.h"
 #include "vqgan_enc.h"
+#include "weight_pack.h"
 #include "fft_drawer.h"
 #include "../../include/prx.h"
 
@@ -263,7 +264,7 @@ int prx_k_add_f32(const float* a, const float* b, float* out, size_t n, prx_stre
 
 // ---- the runners' own kernels through the launchers the runners call (tests/test_kernels_runner_gpu.py) -----------------------
 int prx_k_rn_pack_conv3x3(const float* w, void* Wf, void* Wd, int Cout, int Cin, int prec, prx_stream_t s) {
-    return prx_rn_pack_conv3x3(w, Wf, Wd, Cout, Cin, prec, S_(s));
+    return prx_pack_conv3x3(w, Wf, Wd, Cout, Cin, Cin, Cout, prec, S_(s));
 }
 int prx_k_stem1_fwd(const float* cut, const float* mm, const float* w, const float* b, void* out, int N, int S, int CO, int prec, prx_stream_t s) {
     return prx_stem1_fwd(cut, mm, w, b, out, N, S, CO, prec, S_(s));
@@ -354,7 +355,7 @@ int prx_k_warp_b_bwd(const float* a, int Ha, int Wa, const double* desc, const f
     return prx_warp_b_bwd(a, Ha, Wa, desc, g, grgb, uv, ga, n_cut, S, S_(s), maps_scratch, maps_scratch_bytes, form);
 }
 int prx_k_vgg_pack(const float* w, void* Wf, void* Wd, int Cout, int Cin, int CiP, int prec, prx_stream_t s) {
-    return prx_vgg_pack(w, Wf, Wd, Cout, Cin, CiP, prec, S_(s));
+    return prx_pack_conv3x3(w, Wf, Wd, Cout, Cin, CiP, Cout, prec, S_(s));
 }
 int prx_k_vgg_input(const float* x, void* out, int HW, int prec, prx_stream_t s) {
     return prx_vgg_input(x, out, HW, prec, S_(s));
@@ -367,6 +368,9 @@ int prx_k_vgg_maxpool(const void* x, void* out, void* arg, int H, int W, int C, 
 }
 int prx_k_vgg_combine(const float* above, const void* arg, const float* gcap, const void* act, void* gpre, int H, int W, int C, const float* gscale, int prec, prx_stream_t s) {
     return prx_vgg_combine(above, (const unsigned char*)arg, gcap, act, gpre, H, W, C, gscale, prec, S_(s));
+}
+int prx_k_pack_conv3x3(const float* w, void* Wf, void* Wd, int Cout, int Cin, int CiP, int CoP, int prec, prx_stream_t s) {
+    return prx_pack_conv3x3(w, Wf, Wd, Cout, Cin, CiP, CoP, prec, S_(s));
 }
 int prx_k_pack_transpose_op(const float* in, void* out, int R, int C, int prec, prx_stream_t s) {
     return prx_pack_transpose_op(in, out, R, C, prec, S_(s));
@@ -396,10 +400,10 @@ int prx_k_l2norm_bwd(const float* e, const float* g, float* de, int n, int D, pr
     return prx_l2norm_bwd(e, g, de, n, D, S_(s));
 }
 int prx_k_vqgan_pack_conv3x3(const float* w, void* Wf, void* Wd, int Cout, int Cin, int CoP, int prec, prx_stream_t s) {
-    return prx_vqgan_pack_conv3x3(w, Wf, Wd, Cout, Cin, CoP, prec, S_(s));
+    return prx_pack_conv3x3(w, Wf, Wd, Cout, Cin, Cin, CoP, prec, S_(s));
 }
 int prx_k_vqgan_enc_pack_conv3x3(const float* w, void* Wf, int Cout, int Cin, int CiP, prx_stream_t s) {
-    return prx_vqgan_enc_pack_conv3x3(w, Wf, Cout, Cin, CiP, S_(s));
+    return prx_pack_conv3x3(w, Wf, nullptr, Cout, Cin, CiP, Cout, PRX_PREC_BF16, S_(s));
 }
 int prx_k_colminmax(const float* w, float* mn, float* mx, int rows, int D, prx_stream_t s) {
     return prx_colminmax(w, mn, mx, rows, D, S_(s));

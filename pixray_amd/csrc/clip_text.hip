@@ -10,8 +10,7 @@
 #include "norms.h"
 #include "attention.h"
 #include "elementwise.h"
-#include "vit.h"  // prx_pack_* helpers
-#include "dev_arena.h"
+#include "weight_pack.h"
 #include <vector>
 #include <memory>
 

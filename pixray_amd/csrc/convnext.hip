@@ -17,8 +17,8 @@
 #include "cutouts.h"
 #include "prompt_vq.h"
 #include "elementwise.h"
-#include "vit.h"
-#include "dev_arena.h"
+#include "vit.h"  // prx_vit_gelu_f32
+#include "weight_pack.h"
 #include <vector>
 #include <memory>
 
@@ -382,12 +382,6 @@ struct PrxConvNext {
 };
 
 namespace {
-int cnx_pack_both(PrxConvNext* v, void** W, void** WT, const float* src, int out, int in, hipStream_t s) {
-    DEV_ALLOC(v->mem, alloc_op, *W, (size_t)out * in, v->f32);
-    DEV_ALLOC(v->mem, alloc_op, *WT, (size_t)out * in, v->f32);
-    if (int r = prx_pack_op(src, *W, (size_t)out * in, v->prec, s)) return r;
-    return prx_pack_transpose_op(src, *WT, out, in, v->prec, s);
-}
 int cnx_gemm(PrxConvNext* v, GemmDesc& d, hipStream_t s) {
     if (v->f32) { d.f32 = 1; d.a_is_f32 = 0; }
     d.h16 = v->h16;
@@ -441,7 +435,7 @@ int prx_convnext_create_impl(PrxConvNext** out, int res, const int* depths, cons
     int r;
     const float* const* q = w;
     const int d0 = dims[0];
-    if ((r = cnx_pack_both(v, &v->Wstem, &v->WstemT, q[0], d0, 48, s))) return r;
+    if ((r = prx_pack_pair(m, &v->Wstem, &v->WstemT, q[0], d0, 48, precision, s))) return r;
     if ((r = m.copy_f32(&v->stem_b, q[1], d0, s))) return r;
     if ((r = m.copy_f32(&v->stem_ln_g, q[2], d0, s))) return r;
     if ((r = m.copy_f32(&v->stem_ln_b, q[3], d0, s))) return r;
@@ -456,7 +450,7 @@ int prx_convnext_create_impl(PrxConvNext** out, int res, const int* depths, cons
             const int Cp = dims[i - 1];
             if ((r = m.copy_f32(&st.ds_ln_g, q[0], Cp, s))) return r;
             if ((r = m.copy_f32(&st.ds_ln_b, q[1], Cp, s))) return r;
-            if ((r = cnx_pack_both(v, &st.Wd, &st.WdT, q[2], C, 4 * Cp, s))) return r;
+            if ((r = prx_pack_pair(m, &st.Wd, &st.WdT, q[2], C, 4 * Cp, precision, s))) return r;
             if ((r = m.copy_f32(&st.ds_b, q[3], C, s))) return r;
             q += 4;
             DEV_ALLOC(m, alloc, st.ds_mean, 4 * M); DEV_ALLOC(m, alloc, st.ds_rstd, 4 * M);
@@ -473,9 +467,9 @@ int prx_convnext_create_impl(PrxConvNext** out, int res, const int* depths, cons
             if ((r = m.copy_f32(&b.dwb, q[1], C, s))) return r;
             if ((r = m.copy_f32(&b.ln_g, q[2], C, s))) return r;
             if ((r = m.copy_f32(&b.ln_b, q[3], C, s))) return r;
-            if ((r = cnx_pack_both(v, &b.W1, &b.W1T, q[4], 4 * C, C, s))) return r;
+            if ((r = prx_pack_pair(m, &b.W1, &b.W1T, q[4], 4 * C, C, precision, s))) return r;
             if ((r = m.copy_f32(&b.b1, q[5], 4 * C, s))) return r;
-            if ((r = cnx_pack_both(v, &b.W2, &b.W2T, q[6], C, 4 * C, s))) return r;
+            if ((r = prx_pack_pair(m, &b.W2, &b.W2T, q[6], C, 4 * C, precision, s))) return r;
             if ((r = m.copy_f32(&b.b2, q[7], C, s))) return r;
             q += 8;
             DEV_ALLOC(m, alloc_op, b.y, M * C, f32); DEV_ALLOC(m, alloc_op, b.t, M * 4 * C, f32);
@@ -487,11 +481,11 @@ int prx_convnext_create_impl(PrxConvNext** out, int res, const int* depths, cons
     if ((r = m.copy_f32(&v->head_ln_b, q[1], d3, s))) return r;
     v->P1 = v->P1T = nullptr; v->hb1 = nullptr;
     if (proj_mlp) {
-        if ((r = cnx_pack_both(v, &v->P0, &v->P0T, q[2], 2 * E, d3, s))) return r;
+        if ((r = prx_pack_pair(m, &v->P0, &v->P0T, q[2], 2 * E, d3, precision, s))) return r;
         if ((r = m.copy_f32(&v->hb1, q[3], 2 * E, s))) return r;
-        if ((r = cnx_pack_both(v, &v->P1, &v->P1T, q[4], E, 2 * E, s))) return r;
+        if ((r = prx_pack_pair(m, &v->P1, &v->P1T, q[4], E, 2 * E, precision, s))) return r;
     } else {
-        if ((r = cnx_pack_both(v, &v->P0, &v->P0T, q[2], E, d3, s))) return r;
+        if ((r = prx_pack_pair(m, &v->P0, &v->P0T, q[2], E, d3, precision, s))) return r;
     }
     const size_t RT = (size_t)max_n * v->T, N = max_n;
     DEV_ALLOC(m, alloc_op, v->A0, RT * 48, f32); DEV_ALLOC(m, alloc, v->xpre, RT * d0); DEV_ALLOC(m, alloc, v->dA0, RT * 48);

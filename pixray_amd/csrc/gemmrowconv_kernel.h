@@ -9,7 +9,7 @@
 //   * transposed MFMA: 8 (lone tile: 4) consecutive output channels per lane, epilogue from registers -- bias + ReLU forward, the
 //     saved activation's ReLU mask backward.
 //
-// The K index is tap * Cin + ci (resnet.hip rn_pack_conv3x3_kernel: forward and flipped dgrad weights share it), so 16-byte chunk c
+// The K index is tap * Cin + ci (weight_pack.hip pack_conv3x3_kernel: forward and flipped dgrad weights share it), so 16-byte chunk c
 // of a K row is tap c / (Cin / 8), channels 8 (c % (Cin / 8)) ..: never straddling a tap.
 #pragma once
 #include "gemmrow_kernel.h"

@@ -16,7 +16,6 @@ int prx_resnet_backward_b_impl(PrxResNet* r, const float* cutouts, const float* 
                                hipStream_t s);
 // One host launcher per runner-private kernel: grid computation and the operand-type (`prec` = PRX_PREC_*) / CO dispatch.  The runner
 // calls these; csrc/api_kernels.hip exports them as prx_k_* for the kernel-level tests.  Operand-format buffers are `void*`.
-int prx_rn_pack_conv3x3(const float* w, void* Wf, void* Wd, int Cout, int Cin, int prec, hipStream_t s);
 // CO = width / 2, one of 8, 16, 32, 40, 48, 64 (anything else is refused)
 int prx_stem1_fwd(const float* cut, const float* mm, const float* w, const float* b, void* out, int N, int S, int CO, int prec,
                   hipStream_t s);

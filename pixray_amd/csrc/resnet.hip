@@ -12,8 +12,7 @@
 #include "elementwise.h"
 #include "cutouts.h"
 #include "prompt_vq.h"
-#include "vit.h"  // prx_pack_* helpers
-#include "dev_arena.h"
+#include "weight_pack.h"
 #include <cstdlib>
 #include <vector>
 #include <memory>
@@ -25,25 +24,6 @@ __constant__ float r_clip_mean[3] = {0.48145466f, 0.4578275f, 0.40821073f};
 __constant__ float r_clip_std[3] = {0.26862954f, 0.26130258f, 0.27577711f};
 
 inline int rgrid(size_t total) { return (int)std::min<size_t>((total + 255) / 256, 16384); }
-
-// Wf[co][tap*Cin + ci] = w[co][ci][ky][kx];  Wd[ci][tap'*Cout + co] = w[co][ci][2-ky][2-kx]
-template <typename TOp>
-__global__ __launch_bounds__(256) void rn_pack_conv3x3_kernel(const float* __restrict__ w, void* __restrict__ Wf_, void* __restrict__ Wd_,
-                                                              int Cout, int Cin) {
-    TOp* Wf = reinterpret_cast<TOp*>(Wf_);
-    TOp* Wd = reinterpret_cast<TOp*>(Wd_);
-    const size_t total = (size_t)Cout * 9 * Cin;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * total; i += (size_t)gridDim.x * blockDim.x) {
-        if (i < total) {
-            const int ci = (int)(i % Cin), tap = (int)((i / Cin) % 9), co = (int)(i / ((size_t)9 * Cin));
-            Wf[i] = op_cvt<TOp>(w[(((size_t)co * Cin + ci) * 3 + tap / 3) * 3 + tap % 3]);
-        } else {
-            const size_t j = i - total;
-            const int co = (int)(j % Cout), tap = (int)((j / Cout) % 9), ci = (int)(j / ((size_t)9 * Cout));
-            Wd[j] = op_cvt<TOp>(w[(((size_t)co * Cin + ci) * 3 + (2 - tap / 3)) * 3 + (2 - tap % 3)]);
-        }
-    }
-}
 
 // stem conv1: y = relu(conv3x3 stride 2 pad 1 (normalise(cutouts)) + b) -> NHWC bf16 [n, Ho*Wo, Co]
 // normalise = slip.py:21-42: (x - min) / (max - min) with the batch-global min / max, then CLIP mean / std.
@@ -327,10 +307,6 @@ struct RBlock {
         PRX_LAUNCH_CHECK();                                                                                              \
     } while (0)
 
-int prx_rn_pack_conv3x3(const float* w, void* Wf, void* Wd, int Cout, int Cin, int prec, hipStream_t s) {
-    RLAUNCH(prec, rn_pack_conv3x3_kernel, (size_t)1024 * 256, w, Wf, Wd, Cout, Cin);
-    return 0;
-}
 int prx_stem1_fwd(const float* cut, const float* mm, const float* w, const float* b, void* out, int N, int S, int CO, int prec,
                   hipStream_t s) {
     PRX_REQUIRE(N >= 1 && S >= 2, "resnet stem: %d cutouts of side %d", N, S);
@@ -400,24 +376,18 @@ struct PrxResNet {
 };
 
 namespace {
-struct RCur { const float* const* w; int n, pos; };
-#define RNEXT(cur, dst) do { PRX_REQUIRE((cur).pos < (cur).n, "resnet_create: weight list too short"); (dst) = (cur).w[(cur).pos++]; } while (0)
-
-int mk1(PrxResNet* r, RConv1& c, int Cin, int Cout, RCur& cur, hipStream_t s) {
-    const float *w, *b; RNEXT(cur, w); RNEXT(cur, b);
+int mk1(PrxResNet* r, RConv1& c, int Cin, int Cout, WeightCursor& cur, hipStream_t s) {
+    const float *w, *b; NEXT_WEIGHT(cur, w); NEXT_WEIGHT(cur, b);
     c.Cin = Cin; c.Cout = Cout;
-    DEV_ALLOC(r->mem, alloc_op, c.W, (size_t)Cout * Cin, r->f32); DEV_ALLOC(r->mem, alloc_op, c.WT, (size_t)Cout * Cin, r->f32);
-    int e;
-    if ((e = prx_pack_op(w, c.W, (size_t)Cout * Cin, r->prec, s))) return e;
-    if ((e = prx_pack_transpose_op(w, c.WT, Cout, Cin, r->prec, s))) return e;
+    if (int e = prx_pack_pair(r->mem, &c.W, &c.WT, w, Cout, Cin, r->prec, s)) return e;
     return r->mem.copy_f32(&c.b, b, Cout, s);
 }
-int mk3(PrxResNet* r, RConv3& c, int Cin, int Cout, RCur& cur, hipStream_t s) {
-    const float *w, *b; RNEXT(cur, w); RNEXT(cur, b);
+int mk3(PrxResNet* r, RConv3& c, int Cin, int Cout, WeightCursor& cur, hipStream_t s) {
+    const float *w, *b; NEXT_WEIGHT(cur, w); NEXT_WEIGHT(cur, b);
     c.Cin = Cin; c.Cout = Cout;
     DEV_ALLOC(r->mem, alloc_op, c.Wf, (size_t)Cout * 9 * Cin, r->f32); DEV_ALLOC(r->mem, alloc_op, c.Wd, (size_t)Cout * 9 * Cin, r->f32);
     int e;
-    if ((e = prx_rn_pack_conv3x3(w, c.Wf, c.Wd, Cout, Cin, r->prec, s))) return e;
+    if ((e = prx_pack_conv3x3(w, c.Wf, c.Wd, Cout, Cin, Cin, Cout, r->prec, s))) return e;
     return r->mem.copy_f32(&c.b, b, Cout, s);
 }
 int rg(PrxResNet* r, GemmDesc& d, hipStream_t s) {
@@ -466,9 +436,9 @@ int prx_resnet_create_impl(PrxResNet** out, int res, int width, const int* layer
     r->C = width * 32; r->G = res / 32; r->T = r->G * r->G + 1;
     // the pool keeps out + lse at every token count (the saving form), also at the 50 tokens of RN50
     r->mha.T = r->T; r->mha.heads = heads; r->mha.hd = 64; r->mha.C = r->C; r->mha.prec = precision;
-    RCur cur{w, n_w, 0};
+    WeightCursor cur{w, n_w, 0, "resnet_create"};
     int e;
-    {   const float *ww, *bb; RNEXT(cur, ww); RNEXT(cur, bb);
+    {   const float *ww, *bb; NEXT_WEIGHT(cur, ww); NEXT_WEIGHT(cur, bb);
         if ((e = m.copy_f32(&r->w1, ww, (size_t)(width / 2) * 27, s))) return e;
         if ((e = m.copy_f32(&r->b1, bb, width / 2, s))) return e; }
     if ((e = mk3(r, r->s2, width / 2, width / 2, cur, s))) return e;
@@ -500,17 +470,13 @@ int prx_resnet_create_impl(PrxResNet** out, int res, int width, const int* layer
     }
     PRX_REQUIRE(inplanes == r->C && H == r->G, "resnet_create: internal geometry mismatch");
     const float *pos, *win, *bin, *wc, *bc;
-    RNEXT(cur, pos); RNEXT(cur, win); RNEXT(cur, bin); RNEXT(cur, wc); RNEXT(cur, bc);
-    PRX_REQUIRE(cur.pos == n_w, "resnet_create: %d weight tensors given, %d consumed", n_w, cur.pos);
+    NEXT_WEIGHT(cur, pos); NEXT_WEIGHT(cur, win); NEXT_WEIGHT(cur, bin); NEXT_WEIGHT(cur, wc); NEXT_WEIGHT(cur, bc);
+    if ((e = cur.done())) return e;
     const int C = r->C, T = r->T;
     if ((e = m.copy_f32(&r->pos, pos, (size_t)T * C, s))) return e;
-    DEV_ALLOC(m, alloc_op, r->Win, (size_t)3 * C * C, f32); DEV_ALLOC(m, alloc_op, r->WinT, (size_t)3 * C * C, f32);
-    if ((e = prx_pack_op(win, r->Win, (size_t)3 * C * C, r->prec, s))) return e;
-    if ((e = prx_pack_transpose_op(win, r->WinT, 3 * C, C, r->prec, s))) return e;
+    if ((e = prx_pack_pair(m, &r->Win, &r->WinT, win, 3 * C, C, r->prec, s))) return e;
     if ((e = m.copy_f32(&r->bin, bin, 3 * C, s))) return e;
-    DEV_ALLOC(m, alloc_op, r->Wc, (size_t)out_dim * C, f32); DEV_ALLOC(m, alloc_op, r->WcT, (size_t)out_dim * C, f32);
-    if ((e = prx_pack_op(wc, r->Wc, (size_t)out_dim * C, r->prec, s))) return e;
-    if ((e = prx_pack_transpose_op(wc, r->WcT, out_dim, C, r->prec, s))) return e;
+    if ((e = prx_pack_pair(m, &r->Wc, &r->WcT, wc, out_dim, C, r->prec, s))) return e;
     if ((e = m.copy_f32(&r->bc, bc, out_dim, s))) return e;
     const size_t S2 = (size_t)(res / 2) * (res / 2), S4 = (size_t)(res / 4) * (res / 4);
     DEV_ALLOC(m, alloc_op, r->s1, N * S2 * (width / 2), f32); DEV_ALLOC(m, alloc_op, r->s2a, N * S2 * (width / 2), f32);

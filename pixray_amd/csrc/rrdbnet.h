@@ -43,4 +43,3 @@ struct RrdbConvArgs {
     int accum;                               // out_f32 += v instead of = v
 };
 int rrdb_conv_launch(const RrdbConvArgs& a, int dgrad, int f32, hipStream_t s);
-int rrdb_pack_launch(const float* w, void* out, int Cout, int Cin, int dgrad, int f32, hipStream_t s);

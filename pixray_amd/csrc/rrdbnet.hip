@@ -23,7 +23,7 @@
 #include <new>
 #include <vector>
 
-#include "dev_arena.h"
+#include "weight_pack.h"
 
 #include "../../include/prx.h"
 
@@ -159,24 +159,6 @@ __global__ __launch_bounds__(256) void rrdb_conv_kernel(RrdbConvArgs a) {
             }
             if (a.out) op_st4<T>(reinterpret_cast<T*>(a.out), (size_t)pix * a.ld_out + a.out_off + n, v[0], v[1], v[2], v[3]);
         }
-    }
-}
-
-// torch weight [Cout][Cin][3][3] -> forward pack [Cout][tap * Cin + ci], or (dgrad) the flipped, transposed pack
-// [Cin][tap * Cout + co] = w[co][ci][8 - tap]
-template <typename T>
-__global__ __launch_bounds__(256) void rrdb_pack_kernel(const float* __restrict__ w, T* __restrict__ out, int Cout, int Cin, int dgrad) {
-    const int total = Cout * Cin * 9;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-        float v;
-        if (!dgrad) {
-            const int n = i / (9 * Cin), k = i - n * 9 * Cin, tap = k / Cin, ci = k - tap * Cin;
-            v = w[((size_t)n * Cin + ci) * 9 + tap];
-        } else {
-            const int n = i / (9 * Cout), k = i - n * 9 * Cout, tap = k / Cout, co = k - tap * Cout;
-            v = w[((size_t)co * Cin + n) * 9 + (8 - tap)];
-        }
-        out[i] = op_cvt<T>(v);
     }
 }
 
@@ -324,14 +306,6 @@ int rrdb_conv_launch(const RrdbConvArgs& a, int dgrad, int f32, hipStream_t s) {
     return 0;
 }
 
-int rrdb_pack_launch(const float* w, void* out, int Cout, int Cin, int dgrad, int f32, hipStream_t s) {
-    const int grid = ceil_div(Cout * Cin * 9, 256);
-    if (f32) hipLaunchKernelGGL((rrdb_pack_kernel<float>), dim3(grid), dim3(256), 0, s, w, (float*)out, Cout, Cin, dgrad);
-    else hipLaunchKernelGGL((rrdb_pack_kernel<half_t>), dim3(grid), dim3(256), 0, s, w, (half_t*)out, Cout, Cin, dgrad);
-    PRX_LAUNCH_CHECK();
-    return 0;
-}
-
 static int rrdb_prec(int prec, int* f32) {
     PRX_REQUIRE(prec != PRX_PREC_BF16, "rrdbnet: bf16 operands are not built (the kernels exist for \"fp16\" and \"f32\")");
     PRX_REQUIRE(prec == PRX_PREC_F32 || prec == PRX_PREC_F16, "rrdbnet: unknown precision %d", prec);
@@ -398,7 +372,7 @@ extern "C" int prx_rrdbnet_create(prx_rrdbnet** out, int num_feat, int num_grow,
         float* bias;
         if ((rc = m.copy_f32(&bias, weights[2 * i + 1], cout, s))) return rc;
         cw.bias = bias;
-        if ((rc = rrdb_pack_launch(weights[2 * i], cw.wf, cout, cin, 0, f32, s)) || (rc = rrdb_pack_launch(weights[2 * i], cw.wd, cout, cin, 1, f32, s))) return rc;
+        if ((rc = prx_pack_conv3x3(weights[2 * i], cw.wf, cw.wd, cout, cin, cin, cout, precision, s))) return rc;
         r->convs.push_back(cw);
     }
     for (int j = 0; j < 3 * num_block; ++j) { void* c; DEV_ALLOC(m, alloc_op, c, hw * 192, f32); r->cat.push_back(c); }
@@ -538,7 +512,7 @@ extern "C" int prx_k_rrdb_conv(int dgrad, const void* in, int ld_in, int in_off,
     hipStream_t s = (hipStream_t)stream;
     void* pack = nullptr;
     PRX_CHECK_HIP(hipMalloc(&pack, (size_t)Cin * Cout * 9 * (f32 ? 4 : 2)));
-    int rc = rrdb_pack_launch(wt, pack, Cout, Cin, dgrad, f32, s);
+    int rc = prx_pack_conv3x3(wt, dgrad ? nullptr : pack, dgrad ? pack : nullptr, Cout, Cin, Cin, Cout, prec, s);      // the one side this convolution reads
     if (!rc) {
         RrdbConvArgs a = rrdb_args0();
         a.in = in; a.ld_in = ld_in; a.in_off = in_off; a.act = act; a.ld_act = ld_act; a.act_off = act_off;

@@ -14,7 +14,6 @@ int prx_vgg16_forward_impl(PrxVgg16* v, const float* x, int H, int W, void* work
 int prx_vgg16_backward_impl(PrxVgg16* v, int H, int W, const void* workspace, const float* const* g_feats, float* g_x, hipStream_t s);
 // One host launcher per runner-private kernel (grid computation, operand-type dispatch on `prec` = PRX_PREC_*): the runner calls
 // these, csrc/api_kernels.hip exports them as prx_k_* for the kernel-level tests.
-int prx_vgg_pack(const float* w, void* Wf, void* Wd, int Cout, int Cin, int CiP, int prec, hipStream_t s);
 int prx_vgg_input(const float* x, void* out, int HW, int prec, hipStream_t s);
 int prx_vgg_input_grad(const float* d, float* gx, int HW, const float* unscale, hipStream_t s);
 int prx_vgg_maxpool(const void* x, void* out, unsigned char* arg, int H, int W, int C, int prec, hipStream_t s);

@@ -15,7 +15,7 @@
 #include "vgg.h"
 #include "gemm.h"
 #include "elementwise.h"
-#include "dev_arena.h"
+#include "weight_pack.h"
 #include <memory>
 #include <vector>
 #include <algorithm>
@@ -55,25 +55,6 @@ VLayout vlayout(int H, int W, int f32) {
     }
     L.total = off;
     return L;
-}
-
-// Wf[co][tap*CiP + ci] = w[co][ci][ky][kx] (ci zero-padded to CiP);  Wd[ci][tap'*Cout + co] = w[co][ci][2-ky][2-kx]
-template <typename TOp>
-__global__ __launch_bounds__(256) void vgg_pack_kernel(const float* __restrict__ w, void* __restrict__ Wf_, void* __restrict__ Wd_,
-                                                       int Cout, int Cin, int CiP) {
-    TOp* Wf = reinterpret_cast<TOp*>(Wf_);
-    TOp* Wd = reinterpret_cast<TOp*>(Wd_);
-    const size_t total = (size_t)Cout * 9 * CiP;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * total; i += (size_t)gridDim.x * blockDim.x) {
-        if (i < total) {
-            const int ci = (int)(i % CiP), tap = (int)((i / CiP) % 9), co = (int)(i / ((size_t)9 * CiP));
-            Wf[i] = op_cvt<TOp>(ci < Cin ? w[(((size_t)co * Cin + ci) * 3 + tap / 3) * 3 + tap % 3] : 0.f);
-        } else {
-            const size_t j = i - total;
-            const int co = (int)(j % Cout), tap = (int)((j / Cout) % 9), ci = (int)(j / ((size_t)9 * Cout));
-            Wd[j] = op_cvt<TOp>(ci < Cin ? w[(((size_t)co * Cin + ci) * 3 + (2 - tap / 3)) * 3 + (2 - tap % 3)] : 0.f);
-        }
-    }
 }
 
 // x [3][H][W] fp32 -> NHWC bf16 with 8 channels (5 zeros)
@@ -164,10 +145,6 @@ struct VConv { int Cin, CiP, Cout; void *Wf, *Wd; float* b; };   // weight packs
                         hipLaunchKernelGGL(kernel<TV>, dim3(vgrid(total)), dim3(256), 0, s, __VA_ARGS__));               \
         PRX_LAUNCH_CHECK();                                                                                              \
     } while (0)
-int prx_vgg_pack(const float* w, void* Wf, void* Wd, int Cout, int Cin, int CiP, int prec, hipStream_t s) {
-    VLAUNCH(prec, vgg_pack_kernel, (size_t)1024 * 256, w, Wf, Wd, Cout, Cin, CiP);
-    return 0;
-}
 int prx_vgg_input(const float* x, void* out, int HW, int prec, hipStream_t s) {
     VLAUNCH(prec, vgg_input_kernel, (size_t)HW, x, out, HW);
     return 0;
@@ -238,7 +215,7 @@ int prx_vgg16_create_impl(PrxVgg16** out, const float* const* weights, int n_wei
         const size_t n = (size_t)c.Cout * 9 * c.CiP;
         DEV_ALLOC(v->mem, alloc_op, c.Wf, n, v->f32); DEV_ALLOC(v->mem, alloc_op, c.Wd, n, v->f32);
         DEV_ALLOC(v->mem, alloc, c.b, (size_t)c.Cout);
-        if (int e = prx_vgg_pack(weights[2 * l], c.Wf, c.Wd, c.Cout, c.Cin, c.CiP, v->prec, s)) return e;
+        if (int e = prx_pack_conv3x3(weights[2 * l], c.Wf, c.Wd, c.Cout, c.Cin, c.CiP, c.Cout, v->prec, s)) return e;
         PRX_CHECK_HIP(hipMemcpyAsync(c.b, weights[2 * l + 1], sizeof(float) * c.Cout, hipMemcpyDeviceToDevice, s));
     }
     const size_t big = (size_t)max_h * max_w * 64;

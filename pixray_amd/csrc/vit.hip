@@ -15,31 +15,11 @@
 #include "cutouts.h"
 #include "prompt_vq.h"
 #include "elementwise.h"
-#include "dev_arena.h"
+#include "weight_pack.h"
 #include <vector>
 #include <memory>
 
 namespace {
-
-template <typename TOp>
-__global__ __launch_bounds__(256) void pack_transpose_kernel(const float* __restrict__ in, TOp* __restrict__ out,
-                                                             int R, int C) {
-    // out[c][r] = TOp(in[r][c])
-    __shared__ float tile[32][33];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        int r = r0 + ty + 8 * i, c = c0 + tx;
-        tile[ty + 8 * i][tx] = (r < R && c < C) ? in[(size_t)r * C + c] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        int c = c0 + ty + 8 * i, r = r0 + tx;
-        if (c < C && r < R) out[(size_t)c * R + r] = op_cvt<TOp>(tile[tx][ty + 8 * i]);
-    }
-}
 
 __global__ __launch_bounds__(256) void add_cls_pos_kernel(float* __restrict__ x, const float* __restrict__ cls,
                                                           const float* __restrict__ pos, int N, int T, int W) {
@@ -87,20 +67,6 @@ __global__ __launch_bounds__(256) void gelu_f32_kernel(const float* __restrict__
 
 }  // namespace
 
-int prx_pack_op(const float* in, void* out, size_t n, int prec, hipStream_t s) {
-    if (!prec_is_f32(prec)) return prx_f32_to_bf16(in, (bf16_t*)out, n, s, prec_is_h16(prec));
-    PRX_CHECK_HIP(hipMemcpyAsync(out, in, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return 0;
-}
-int prx_pack_transpose_op(const float* in, void* out, int R, int C, int prec, hipStream_t s) {
-    const dim3 grid(ceil_div(C, 32), ceil_div(R, 32));
-    PRX_OP_DISPATCH(prec_is_f32(prec), prec_is_h16(prec), TO,
-                    hipLaunchKernelGGL(pack_transpose_kernel<TO>, grid, dim3(256), 0, s, in, (TO*)out, R, C));
-    PRX_LAUNCH_CHECK();
-    return 0;
-}
-int prx_pack_bf16(const float* in, bf16_t* out, size_t n, hipStream_t s) { return prx_pack_op(in, out, n, 0, s); }
-int prx_pack_transpose_bf16(const float* in, bf16_t* out, int R, int C, hipStream_t s) { return prx_pack_transpose_op(in, out, R, C, 0, s); }
 // launchers of the token-embedding and exact-mode activation kernels (vit.h): shared by the runner below and the kernel-level tests
 int prx_vit_add_cls_pos(float* x, const float* cls, const float* pos, int N, int T, int W, hipStream_t s) {
     hipLaunchKernelGGL(add_cls_pos_kernel, dim3(2048), dim3(256), 0, s, x, cls, pos, N, T, W);
@@ -198,16 +164,6 @@ struct PrxVit {
     // device: 140.1 -> 141.2 and 138.0 -> 139.5 it/s, profiles/r05_first_call/, r05_timeline/.)
 };
 
-namespace {
-int pack_both(PrxVit* v, void** W, void** WT, const float* src, int out, int in, hipStream_t s) {
-    DEV_ALLOC(v->mem, alloc_op, *W, (size_t)out * in, v->f32);
-    DEV_ALLOC(v->mem, alloc_op, *WT, (size_t)out * in, v->f32);
-    int r = prx_pack_op(src, *W, (size_t)out * in, v->prec, s);
-    if (r) return r;
-    return prx_pack_transpose_op(src, *WT, out, in, v->prec, s);
-}
-}  // namespace
-
 VitFamily prx_vit_family_clip() {
     VitFamily f;
     f.patch_bias = 0; f.ln_pre = 1; f.eps = 1e-5f; f.act = PRX_ACT_QUICKGELU; f.dact = PRX_ACT_MUL_DQUICKGELU;
@@ -267,7 +223,7 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
         PRX_CHECK_HIP(hipMemsetAsync(padded, 0, sizeof(float) * (size_t)W * KP, s));
         PRX_CHECK_HIP(hipMemcpy2DAsync(padded, sizeof(float) * KP, w[0], sizeof(float) * K0, sizeof(float) * K0, W,
                                        hipMemcpyDeviceToDevice, s));
-        if ((r = pack_both(v, &v->Wp, &v->WpT, padded, W, KP, s))) return r;
+        if ((r = prx_pack_pair(v->mem, &v->Wp, &v->WpT, padded, W, KP, v->prec, s))) return r;
     }
     const float* const* wh = w + 1;
     if (fam.patch_bias) { if ((r = v->mem.copy_f32(&v->bp, *wh++, W, s))) return r; }
@@ -286,9 +242,9 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
         if ((r = v->mem.copy_f32(&y.ln1_g, q[0], W, s))) return r;
         if ((r = v->mem.copy_f32(&y.ln1_b, q[1], W, s))) return r;
         if (hd == 64) {
-            if ((r = pack_both(v, &y.Wqkv, &y.WqkvT, q[2], 3 * W, W, s))) return r;
+            if ((r = prx_pack_pair(v->mem, &y.Wqkv, &y.WqkvT, q[2], 3 * W, W, v->prec, s))) return r;
             if ((r = v->mem.copy_f32(&y.bqkv, q[3], 3 * W, s))) return r;
-            if ((r = pack_both(v, &y.Wo, &y.WoT, q[4], W, W, s))) return r;
+            if ((r = prx_pack_pair(v->mem, &y.Wo, &y.WoT, q[4], W, W, v->prec, s))) return r;
         } else {
             if ((r = prx_vit_pad_head_rows(q[2], pad_w, heads, hd, hp, W, s))) return r;
             if ((r = prx_vit_pad_head_rows(q[3], pad_b, heads, hd, hp, 1, s))) return r;
@@ -297,17 +253,17 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
                 if ((r = prx_vit_scale_f32(pad_w, (size_t)AW * W, qs, 256, s))) return r;
                 if ((r = prx_vit_scale_f32(pad_b, (size_t)AW, qs, 1, s))) return r;
             }
-            if ((r = pack_both(v, &y.Wqkv, &y.WqkvT, pad_w, 3 * AW, W, s))) return r;
+            if ((r = prx_pack_pair(v->mem, &y.Wqkv, &y.WqkvT, pad_w, 3 * AW, W, v->prec, s))) return r;
             if ((r = v->mem.copy_f32(&y.bqkv, pad_b, 3 * AW, s))) return r;
             if ((r = prx_vit_pad_head_cols(q[4], pad_w, W, heads, hd, hp, s))) return r;
-            if ((r = pack_both(v, &y.Wo, &y.WoT, pad_w, W, AW, s))) return r;
+            if ((r = prx_pack_pair(v->mem, &y.Wo, &y.WoT, pad_w, W, AW, v->prec, s))) return r;
         }
         if ((r = v->mem.copy_f32(&y.bo, q[5], W, s))) return r;
         if ((r = v->mem.copy_f32(&y.ln2_g, q[6], W, s))) return r;
         if ((r = v->mem.copy_f32(&y.ln2_b, q[7], W, s))) return r;
-        if ((r = pack_both(v, &y.W1, &y.W1T, q[8], MW, W, s))) return r;
+        if ((r = prx_pack_pair(v->mem, &y.W1, &y.W1T, q[8], MW, W, v->prec, s))) return r;
         if ((r = v->mem.copy_f32(&y.b1, q[9], MW, s))) return r;
-        if ((r = pack_both(v, &y.W2, &y.W2T, q[10], W, MW, s))) return r;
+        if ((r = prx_pack_pair(v->mem, &y.W2, &y.W2T, q[10], W, MW, v->prec, s))) return r;
         if ((r = v->mem.copy_f32(&y.b2, q[11], W, s))) return r;
         if (v->lean) { DEV_ALLOC(m, alloc_op, y.x_in, R * W, f32); DEV_ALLOC(m, alloc_op, y.x_mid, R * W, f32); }
         else { float *a_, *b_; DEV_ALLOC(m, alloc, a_, R * W); DEV_ALLOC(m, alloc, b_, R * W); y.x_in = a_; y.x_mid = b_; }
@@ -320,7 +276,7 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
     if ((r = v->mem.copy_f32(&v->lnpost_g, q[0], W, s))) return r;
     if ((r = v->mem.copy_f32(&v->lnpost_b, q[1], W, s))) return r;
     // proj is [width, out]: forward Bt = proj^T [out, width]; dgrad Bt = proj [width, out]
-    if ((r = pack_both(v, &v->proj, &v->projT, q[2], W, out_dim, s))) return r;
+    if ((r = prx_pack_pair(v->mem, &v->proj, &v->projT, q[2], W, out_dim, v->prec, s))) return r;
     DEV_ALLOC(m, alloc_op, v->A0, R * KP, f32); DEV_ALLOC(m, alloc_op, v->h, R * W, f32);
     DEV_ALLOC(m, alloc_op, v->att_o, R * AW, f32); DEV_ALLOC(m, alloc_op, v->u, R * MW, f32);
     DEV_ALLOC(m, alloc_op, v->hpost, (size_t)max_n * W, f32); DEV_ALLOC(m, alloc_op, v->de16, (size_t)max_n * out_dim, f32);

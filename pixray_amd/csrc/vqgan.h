@@ -11,8 +11,6 @@ int prx_vqgan_bounds_impl(PrxVqgan* v, float* zmin, float* zmax, hipStream_t s);
 int prx_vqgan_synth_impl(PrxVqgan* v, const float* z, float* img, int* indices, int quantize, hipStream_t s);
 int prx_vqgan_backward_impl(PrxVqgan* v, const float* g_img, float* dz, hipStream_t s);
 long long prx_vqgan_debug_stage_impl(PrxVqgan* v, int stage, float* dst, long long max_floats, hipStream_t s);
-// launchers of the runner's own kernels (the runner calls these; exported as prx_k_* for the kernel-level tests)
-// Wf[co][tap*Cin + ci] = w[co][ci][ky][kx]; Wd[ci][tap*CoP + co] = w[co][ci][2-ky][2-kx], co zero-padded to CoP; operand precision `prec`
-int prx_vqgan_pack_conv3x3(const float* w, void* Wf, void* Wd, int Cout, int Cin, int CoP, int prec, hipStream_t s);
+// launcher of the runner's own kernel (the runner calls it; exported as prx_k_* for the kernel-level tests):
 // per-column minimum / maximum of w[rows][D]
 int prx_colminmax(const float* w, float* mn, float* mx, int rows, int D, hipStream_t s);

@@ -13,38 +13,12 @@
 #include "norms.h"
 #include "elementwise.h"
 #include "prompt_vq.h"
-#include "vit.h"  // prx_pack_* helpers
-#include "dev_arena.h"
+#include "weight_pack.h"
 #include <vector>
 #include <memory>
 #include <stdlib.h>
 
 namespace {
-
-// Wf[co][tap*Cin + ci] = w[co][ci][ky][kx]           (forward pack)
-// Wd[ci][tap*CoP + co] = w[co][ci][2-ky][2-kx]       (dgrad pack; co padded with zeros to CoP)
-template <typename TOp>
-__global__ __launch_bounds__(256) void pack_conv3x3_kernel(const float* __restrict__ w, TOp* __restrict__ Wf,
-                                                           TOp* __restrict__ Wd, int Cout, int Cin, int CoP) {
-    const size_t total_f = (size_t)Cout * 9 * Cin;
-    const size_t total_d = (size_t)Cin * 9 * CoP;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total_f + total_d;
-         i += (size_t)gridDim.x * blockDim.x) {
-        if (i < total_f) {
-            int ci = (int)(i % Cin);
-            int tap = (int)((i / Cin) % 9);
-            int co = (int)(i / ((size_t)9 * Cin));
-            Wf[i] = op_cvt<TOp>(w[(((size_t)co * Cin + ci) * 3 + tap / 3) * 3 + tap % 3]);
-        } else {
-            size_t j = i - total_f;
-            int co = (int)(j % CoP);
-            int tap = (int)((j / CoP) % 9);
-            int ci = (int)(j / ((size_t)9 * CoP));
-            int ky = 2 - tap / 3, kx = 2 - tap % 3;
-            Wd[j] = op_cvt<TOp>((co < Cout) ? w[(((size_t)co * Cin + ci) * 3 + ky) * 3 + kx] : 0.f);
-        }
-    }
-}
 
 __global__ __launch_bounds__(256) void colminmax_kernel(const float* __restrict__ w, float* __restrict__ mn,
                                                         float* __restrict__ mx, int rows, int D) {
@@ -57,14 +31,7 @@ __global__ __launch_bounds__(256) void colminmax_kernel(const float* __restrict_
 
 }  // namespace
 
-// launchers of the two kernels above (vqgan.h): shared by the runner and the kernel-level tests
-int prx_vqgan_pack_conv3x3(const float* w, void* Wf, void* Wd, int Cout, int Cin, int CoP, int prec, hipStream_t s) {
-    PRX_REQUIRE(prec_valid(prec), "vqgan pack_conv3x3: unknown precision %d", prec);
-    PRX_OP_DISPATCH(prec_is_f32(prec), prec_is_h16(prec), TO,
-                    hipLaunchKernelGGL(pack_conv3x3_kernel<TO>, dim3(1024), dim3(256), 0, s, w, (TO*)Wf, (TO*)Wd, Cout, Cin, CoP));
-    PRX_LAUNCH_CHECK();
-    return 0;
-}
+// launcher of the kernel above (vqgan.h): shared by the runner and the kernel-level tests
 int prx_colminmax(const float* w, float* mn, float* mx, int rows, int D, hipStream_t s) {
     hipLaunchKernelGGL(colminmax_kernel, dim3(ceil_div(D, 256)), dim3(256), 0, s, w, mn, mx, rows, D);
     PRX_LAUNCH_CHECK();
@@ -132,11 +99,8 @@ namespace {
 // `count` stream elements: fp32, or 16-bit in the lean layout
 int alloc_stream(PrxVqgan* v, void** p, size_t count) { return v->mem.alloc_op(p, count, !v->lean); }
 
-struct WCursor { const float* const* w; int n, pos; };
-#define NEXTW(cur, dst) do { PRX_REQUIRE((cur).pos < (cur).n, "vqgan_create: weight list too short"); (dst) = (cur).w[(cur).pos++]; } while (0)
-
-int make_gn(PrxVqgan* v, GN& g, int C, WCursor& cur, hipStream_t s) {
-    const float *w, *b; NEXTW(cur, w); NEXTW(cur, b);
+int make_gn(PrxVqgan* v, GN& g, int C, WeightCursor& cur, hipStream_t s) {
+    const float *w, *b; NEXT_WEIGHT(cur, w); NEXT_WEIGHT(cur, b);
     g.C = C;
     int r;
     if ((r = v->mem.copy_f32(&g.g, w, C, s))) return r;
@@ -145,30 +109,27 @@ int make_gn(PrxVqgan* v, GN& g, int C, WCursor& cur, hipStream_t s) {
     g.stats = g.bstats = nullptr;   // assigned once every GroupNorm is known
     return 0;
 }
-int make_conv3(PrxVqgan* v, Conv3& c, int Cin, int Cout, WCursor& cur, hipStream_t s) {
-    const float *w, *b; NEXTW(cur, w); NEXTW(cur, b);
+int make_conv3(PrxVqgan* v, Conv3& c, int Cin, int Cout, WeightCursor& cur, hipStream_t s) {
+    const float *w, *b; NEXT_WEIGHT(cur, w); NEXT_WEIGHT(cur, b);
     c.Cin = Cin; c.Cout = Cout; c.CoP = (Cout + 7) / 8 * 8;
     // the forward pack has CoP rows too (zero rows beyond Cout, zero bias): N % 8 == 0 puts conv_out (3 channels) on the MFMA tiles
     // with vector epilogues like every other convolution; its fp32 output is [pixels][CoP]
     DEV_ALLOC(v->mem, alloc_op, c.Wf, (size_t)c.CoP * 9 * Cin, v->f32);
     if (c.CoP != Cout) PRX_CHECK_HIP(hipMemsetAsync(c.Wf, 0, (size_t)c.CoP * 9 * Cin * op_esz(v->f32), s));
     DEV_ALLOC(v->mem, alloc_op, c.Wd, (size_t)Cin * 9 * c.CoP, v->f32);
-    { int e_ = prx_vqgan_pack_conv3x3(w, c.Wf, c.Wd, Cout, Cin, c.CoP, v->prec, s); if (e_) return e_; }
+    if (int e_ = prx_pack_conv3x3(w, c.Wf, c.Wd, Cout, Cin, Cin, c.CoP, v->prec, s)) return e_;
     DEV_ALLOC(v->mem, alloc, c.b, c.CoP);
     if (c.CoP != Cout) PRX_CHECK_HIP(hipMemsetAsync(c.b, 0, sizeof(float) * c.CoP, s));
     PRX_CHECK_HIP(hipMemcpyAsync(c.b, b, sizeof(float) * Cout, hipMemcpyDeviceToDevice, s));
     return 0;
 }
-int make_conv1(PrxVqgan* v, Conv1& c, int Cin, int Cout, WCursor& cur, hipStream_t s) {
-    const float *w, *b; NEXTW(cur, w); NEXTW(cur, b);
+int make_conv1(PrxVqgan* v, Conv1& c, int Cin, int Cout, WeightCursor& cur, hipStream_t s) {
+    const float *w, *b; NEXT_WEIGHT(cur, w); NEXT_WEIGHT(cur, b);
     c.Cin = Cin; c.Cout = Cout;
-    DEV_ALLOC(v->mem, alloc_op, c.W, (size_t)Cout * Cin, v->f32); DEV_ALLOC(v->mem, alloc_op, c.WT, (size_t)Cout * Cin, v->f32);
-    int r;
-    if ((r = prx_pack_op(w, c.W, (size_t)Cout * Cin, v->prec, s))) return r;
-    if ((r = prx_pack_transpose_op(w, c.WT, Cout, Cin, v->prec, s))) return r;
+    if (int r = prx_pack_pair(v->mem, &c.W, &c.WT, w, Cout, Cin, v->prec, s)) return r;
     return v->mem.copy_f32(&c.b, b, Cout, s);
 }
-int make_res(PrxVqgan* v, int Cin, int Cout, int rh, int rw, WCursor& cur, hipStream_t s) {
+int make_res(PrxVqgan* v, int Cin, int Cout, int rh, int rw, WeightCursor& cur, hipStream_t s) {
     ResBlock rb{};
     rb.Cin = Cin; rb.Cout = Cout; rb.rh = rh; rb.rw = rw; rb.has_sc = Cin != Cout;
     int r;
@@ -187,25 +148,16 @@ int make_res(PrxVqgan* v, int Cin, int Cout, int rh, int rw, WCursor& cur, hipSt
     v->res.push_back(rb);
     return 0;
 }
-int make_attn(PrxVqgan* v, int C, int rh, int rw, WCursor& cur, hipStream_t s) {
+int make_attn(PrxVqgan* v, int C, int rh, int rw, WeightCursor& cur, hipStream_t s) {
     AttnBlock ab{};
     ab.C = C; ab.rh = rh; ab.rw = rw;
     int r;
     if ((r = make_gn(v, ab.n, C, cur, s))) return r;
     // q, k, v 1x1 convs are concatenated into one [3C, C] GEMM
-    const float *wq, *bq, *wk, *bk, *wv, *bv;
-    NEXTW(cur, wq); NEXTW(cur, bq); NEXTW(cur, wk); NEXTW(cur, bk); NEXTW(cur, wv); NEXTW(cur, bv);
     float *wcat, *bcat;
-    DEV_ALLOC(v->mem, alloc, wcat, (size_t)3 * C * C); DEV_ALLOC(v->mem, alloc, bcat, 3 * C);
-    const float* ws_[3] = {wq, wk, wv}; const float* bs_[3] = {bq, bk, bv};
-    for (int i = 0; i < 3; ++i) {
-        PRX_CHECK_HIP(hipMemcpyAsync(wcat + (size_t)i * C * C, ws_[i], sizeof(float) * C * C, hipMemcpyDeviceToDevice, s));
-        PRX_CHECK_HIP(hipMemcpyAsync(bcat + i * C, bs_[i], sizeof(float) * C, hipMemcpyDeviceToDevice, s));
-    }
+    if ((r = prx_cat_qkv(v->mem, &wcat, &bcat, cur, C, s))) return r;
     ab.qkv.Cin = C; ab.qkv.Cout = 3 * C; ab.qkv.b = bcat;
-    DEV_ALLOC(v->mem, alloc_op, ab.qkv.W, (size_t)3 * C * C, v->f32); DEV_ALLOC(v->mem, alloc_op, ab.qkv.WT, (size_t)3 * C * C, v->f32);
-    if ((r = prx_pack_op(wcat, ab.qkv.W, (size_t)3 * C * C, v->prec, s))) return r;
-    if ((r = prx_pack_transpose_op(wcat, ab.qkv.WT, 3 * C, C, v->prec, s))) return r;
+    if ((r = prx_pack_pair(v->mem, &ab.qkv.W, &ab.qkv.WT, wcat, 3 * C, C, v->prec, s))) return r;
     if ((r = make_conv1(v, ab.proj, C, C, cur, s))) return r;
     const size_t P = (size_t)rh * rw;
     const size_t P8 = (size_t)pad8((int)P);
@@ -220,7 +172,7 @@ int make_attn(PrxVqgan* v, int C, int rh, int rw, WCursor& cur, hipStream_t s) {
     v->attn.push_back(ab);
     return 0;
 }
-int make_up(PrxVqgan* v, int C, int rh, int rw, WCursor& cur, hipStream_t s) {
+int make_up(PrxVqgan* v, int C, int rh, int rw, WeightCursor& cur, hipStream_t s) {
     UpBlock ub{};
     ub.C = C; ub.rh = rh; ub.rw = rw;
     int r;
@@ -248,9 +200,9 @@ int prx_vqgan_create_impl(PrxVqgan** out, int ch, const int* ch_mult, int n_mult
     { const char* e = getenv("PRX_LEAN"); v->lean = (v->h16 && !(e && atoi(e) == 0)) ? 1 : 0; }
     { const char* e = getenv("PRX_VQ_ATTN_GROUP"); v->attn_group = (e && atoi(e) == 0) ? 0 : 1; }
     v->n_gn = 0; v->zc = z_channels; v->D = embed_dim; v->NC = n_embed; v->ch = ch; v->out_ch = out_ch; v->h0 = h0; v->w0 = w0;
-    WCursor cur{w, n_w, 0};
+    WeightCursor cur{w, n_w, 0, "vqgan_create"};
     int r;
-    const float* cb; NEXTW(cur, cb);
+    const float* cb; NEXT_WEIGHT(cur, cb);
     if ((r = m.copy_f32(&v->codebook, cb, (size_t)n_embed * embed_dim, s))) return r;
     DEV_ALLOC(m, alloc, v->cnorm, n_embed); DEV_ALLOC(m, alloc, v->zmin, embed_dim); DEV_ALLOC(m, alloc, v->zmax, embed_dim);
     if ((r = prx_sqnorm_rows(v->codebook, v->cnorm, n_embed, embed_dim, s))) return r;
@@ -279,7 +231,7 @@ int prx_vqgan_create_impl(PrxVqgan** out, int ch, const int* ch_mult, int n_mult
     v->H = rh; v->W = rw;
     if ((r = make_gn(v, v->norm_out, block_in, cur, s))) return r;
     if ((r = make_conv3(v, v->conv_out, block_in, out_ch, cur, s))) return r;
-    PRX_REQUIRE(cur.pos == n_w, "vqgan_create: %d weight tensors given, %d consumed", n_w, cur.pos);
+    if ((r = cur.done())) return r;
     // activations / scratch
     const size_t P0 = (size_t)h0 * w0, PH = (size_t)rh * rw;
     size_t maxPC = P0 * (size_t)std::max(z_channels, embed_dim), maxAttnPC = 1;      // conv_in's / post_quant_conv's input gradients land in the gradient streams too

@@ -9,6 +9,3 @@ int prx_vqgan_enc_create_impl(PrxVqganEnc** out, int ch, const int* ch_mult, int
                               const float* const* w, int n_w, hipStream_t s);
 void prx_vqgan_enc_destroy_impl(PrxVqganEnc* e);
 int prx_vqgan_encode_impl(PrxVqganEnc* e, const float* img, float* z, float* z_pre, int* indices, hipStream_t s);
-// launcher of the runner's forward weight pack (the runner calls it; exported as prx_k_* for the kernel-level tests):
-// Wf[co][tap*CiP + ci] = bf16(w[co][ci][ky][kx]), ci zero-padded to CiP
-int prx_vqgan_enc_pack_conv3x3(const float* w, void* Wf, int Cout, int Cin, int CiP, hipStream_t s);

@@ -11,26 +11,13 @@
 #include "norms.h"
 #include "elementwise.h"
 #include "prompt_vq.h"
-#include "vit.h"  // prx_pack_* helpers
-#include "dev_arena.h"
+#include "weight_pack.h"
 #include <vector>
 #include <memory>
 #include <algorithm>
 #include <math.h>
 
 namespace {
-
-// Wf[co][tap*CiP + ci] = w[co][ci][ky][kx], ci padded with zeros to CiP (conv_in: 3 -> 8 input channels)
-__global__ __launch_bounds__(256) void pack_conv3x3_fwd_kernel(const float* __restrict__ w, bf16_t* __restrict__ Wf, int Cout,
-                                                               int Cin, int CiP) {
-    const size_t total = (size_t)Cout * 9 * CiP;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int ci = (int)(i % CiP);
-        const int tap = (int)((i / CiP) % 9);
-        const int co = (int)(i / ((size_t)9 * CiP));
-        Wf[i] = ci < Cin ? (bf16_t)w[(((size_t)co * Cin + ci) * 3 + tap / 3) * 3 + tap % 3] : (bf16_t)0.f;
-    }
-}
 
 struct EConv3 { int Cin, CiP, Cout; bf16_t* W; float* b; };
 struct EConv1 { int Cin, Cout; bf16_t* W; float* b; };
@@ -40,13 +27,6 @@ struct EAttn { int C; EGN n; EConv1 qkv, proj; };
 struct EOp { int kind; int idx; int H, W; };   // 0 res, 1 attn, 2 downsample conv (H, W = output size)
 
 }  // namespace
-
-// launcher of the kernel above (vqgan_enc.h): shared by the runner and the kernel-level tests; the encoder runs in bf16 only
-int prx_vqgan_enc_pack_conv3x3(const float* w, void* Wf, int Cout, int Cin, int CiP, hipStream_t s) {
-    hipLaunchKernelGGL(pack_conv3x3_fwd_kernel, dim3(512), dim3(256), 0, s, w, (bf16_t*)Wf, Cout, Cin, CiP);
-    PRX_LAUNCH_CHECK();
-    return 0;
-}
 
 struct PrxVqganEnc {
     int in_ch, zc, D, NC, H, W, h0, w0;
@@ -62,32 +42,29 @@ struct PrxVqganEnc {
 };
 
 namespace {
-struct ECursor { const float* const* w; int n, pos; };
-#define ENEXT(cur, dst) do { PRX_REQUIRE((cur).pos < (cur).n, "vqgan_enc_create: weight list too short"); (dst) = (cur).w[(cur).pos++]; } while (0)
-
-int e_gn(PrxVqganEnc* e, EGN& g, int C, ECursor& cur, hipStream_t s) {
-    const float *w, *b; ENEXT(cur, w); ENEXT(cur, b);
+int e_gn(PrxVqganEnc* e, EGN& g, int C, WeightCursor& cur, hipStream_t s) {
+    const float *w, *b; NEXT_WEIGHT(cur, w); NEXT_WEIGHT(cur, b);
     g.C = C;
     int r;
     if ((r = e->mem.copy_f32(&g.g, w, C, s))) return r;
     return e->mem.copy_f32(&g.b, b, C, s);
 }
-int e_conv3(PrxVqganEnc* e, EConv3& c, int Cin, int Cout, ECursor& cur, hipStream_t s) {
-    const float *w, *b; ENEXT(cur, w); ENEXT(cur, b);
+int e_conv3(PrxVqganEnc* e, EConv3& c, int Cin, int Cout, WeightCursor& cur, hipStream_t s) {
+    const float *w, *b; NEXT_WEIGHT(cur, w); NEXT_WEIGHT(cur, b);
     c.Cin = Cin; c.CiP = (Cin + 7) / 8 * 8; c.Cout = Cout;
     DEV_ALLOC(e->mem, alloc, c.W, (size_t)Cout * 9 * c.CiP);
-    { int r_ = prx_vqgan_enc_pack_conv3x3(w, c.W, Cout, Cin, c.CiP, s); if (r_) return r_; }
+    if (int r_ = prx_pack_conv3x3(w, c.W, nullptr, Cout, Cin, c.CiP, Cout, PRX_PREC_BF16, s)) return r_;      // forward only
     return e->mem.copy_f32(&c.b, b, Cout, s);
 }
-int e_conv1(PrxVqganEnc* e, EConv1& c, int Cin, int Cout, ECursor& cur, hipStream_t s) {
-    const float *w, *b; ENEXT(cur, w); ENEXT(cur, b);
+int e_conv1(PrxVqganEnc* e, EConv1& c, int Cin, int Cout, WeightCursor& cur, hipStream_t s) {
+    const float *w, *b; NEXT_WEIGHT(cur, w); NEXT_WEIGHT(cur, b);
     c.Cin = Cin; c.Cout = Cout;
     DEV_ALLOC(e->mem, alloc, c.W, (size_t)Cout * Cin);
     int r;
     if ((r = prx_pack_bf16(w, c.W, (size_t)Cout * Cin, s))) return r;
     return e->mem.copy_f32(&c.b, b, Cout, s);
 }
-int e_res(PrxVqganEnc* e, int Cin, int Cout, int H, int W, ECursor& cur, hipStream_t s) {
+int e_res(PrxVqganEnc* e, int Cin, int Cout, int H, int W, WeightCursor& cur, hipStream_t s) {
     ERes rb{};
     rb.Cin = Cin; rb.Cout = Cout; rb.has_sc = Cin != Cout;
     int r;
@@ -100,20 +77,13 @@ int e_res(PrxVqganEnc* e, int Cin, int Cout, int H, int W, ECursor& cur, hipStre
     e->res.push_back(rb);
     return 0;
 }
-int e_attn(PrxVqganEnc* e, int C, int H, int W, ECursor& cur, hipStream_t s) {
+int e_attn(PrxVqganEnc* e, int C, int H, int W, WeightCursor& cur, hipStream_t s) {
     EAttn ab{};
     ab.C = C;
     int r;
     if ((r = e_gn(e, ab.n, C, cur, s))) return r;
-    const float *wq, *bq, *wk, *bk, *wv, *bv;
-    ENEXT(cur, wq); ENEXT(cur, bq); ENEXT(cur, wk); ENEXT(cur, bk); ENEXT(cur, wv); ENEXT(cur, bv);
     float *wcat, *bcat;
-    DEV_ALLOC(e->mem, alloc, wcat, (size_t)3 * C * C); DEV_ALLOC(e->mem, alloc, bcat, 3 * C);
-    const float* ws_[3] = {wq, wk, wv}; const float* bs_[3] = {bq, bk, bv};
-    for (int i = 0; i < 3; ++i) {
-        PRX_CHECK_HIP(hipMemcpyAsync(wcat + (size_t)i * C * C, ws_[i], sizeof(float) * C * C, hipMemcpyDeviceToDevice, s));
-        PRX_CHECK_HIP(hipMemcpyAsync(bcat + i * C, bs_[i], sizeof(float) * C, hipMemcpyDeviceToDevice, s));
-    }
+    if ((r = prx_cat_qkv(e->mem, &wcat, &bcat, cur, C, s))) return r;
     ab.qkv.Cin = C; ab.qkv.Cout = 3 * C; ab.qkv.b = bcat;
     DEV_ALLOC(e->mem, alloc, ab.qkv.W, (size_t)3 * C * C);
     if ((r = prx_pack_bf16(wcat, ab.qkv.W, (size_t)3 * C * C, s))) return r;
@@ -149,9 +119,9 @@ int prx_vqgan_enc_create_impl(PrxVqganEnc** out, int ch, const int* ch_mult, int
     DevArena& m = e->mem;
     m.describe("vqgan_enc_create", ": the encoder keeps the activations of one %d x %d image", H, W);
     e->in_ch = in_ch; e->zc = z_channels; e->D = embed_dim; e->NC = n_embed; e->H = H; e->W = W; e->h0 = H / f; e->w0 = W / f;
-    ECursor cur{w, n_w, 0};
+    WeightCursor cur{w, n_w, 0, "vqgan_enc_create"};
     int r;
-    const float* cb; ENEXT(cur, cb);
+    const float* cb; NEXT_WEIGHT(cur, cb);
     if ((r = m.copy_f32(&e->codebook, cb, (size_t)n_embed * embed_dim, s))) return r;
     DEV_ALLOC(m, alloc, e->cnorm, n_embed);
     if ((r = prx_sqnorm_rows(e->codebook, e->cnorm, n_embed, embed_dim, s))) return r;
@@ -182,7 +152,7 @@ int prx_vqgan_enc_create_impl(PrxVqganEnc** out, int ch, const int* ch_mult, int
     if ((r = e_gn(e, e->norm_out, block_in, cur, s))) return r;
     if ((r = e_conv3(e, e->conv_out, block_in, z_channels, cur, s))) return r;
     if ((r = e_conv1(e, e->quant, z_channels, embed_dim, cur, s))) return r;
-    PRX_REQUIRE(cur.pos == n_w, "vqgan_enc_create: %d weight tensors given, %d consumed", n_w, cur.pos);
+    if ((r = cur.done())) return r;
     PRX_REQUIRE(h == e->h0 && wd == e->w0, "vqgan_enc_create: internal size mismatch");
     const size_t P0 = (size_t)e->h0 * e->w0;
     size_t maxAttnC = 1;

@@ -160,6 +160,43 @@ def test_vqgan_enc_pack_conv3x3(Cout, Cin, CiP):
     assert untouched(ff, Cout, 9 * CiP)
 
 
+@prec_all
+@pytest.mark.parametrize("Cout,Cin,CiP,CoP,sides", [(5, 3, 8, 8, "fd"), (8, 8, 8, 8, "fd"), (5, 3, 8, 8, "f"), (5, 3, 8, 8, "d")])
+def test_pack_conv3x3(Cout, Cin, CiP, CoP, sides, prec):
+    """the one pack kernel behind the four entries above: input channels zero-padded to CiP and output channels to CoP at once;
+    Wf gets Cout rows; a null pack is not written (`sides`: f = Wf, d = Wd)"""
+    torch.manual_seed(Cout)
+    w = _pack_weights(Cout, Cin)
+    wi = F.pad(w, (0, 0, 0, 0, 0, CiP - Cin))
+    wp = F.pad(wi, (0, 0, 0, 0, 0, 0, 0, CoP - Cout))
+    ff, Wf = guarded(Cout, 9 * CiP, odt(prec))
+    fd, Wd = guarded(CiP, 9 * CoP, odt(prec))
+    call("prx_k_pack_conv3x3", w, ff if "f" in sides else None, fd if "d" in sides else None, Cout, Cin, CiP, CoP, prec, stream())
+    sync()
+    if "f" in sides:
+        same_bits(Wf, cvt(wi.permute(0, 2, 3, 1).reshape(Cout, 9 * CiP), prec))
+        assert untouched(ff, Cout, 9 * CiP)
+    else:
+        assert bool(torch.isnan(ff).all())
+    if "d" in sides:
+        same_bits(Wd, cvt(wp.flip(2, 3).permute(1, 2, 3, 0).reshape(CiP, 9 * CoP), prec))
+        assert untouched(fd, CiP, 9 * CoP)
+    else:
+        assert bool(torch.isnan(fd).all())
+
+
+def test_pack_conv3x3_refuses_no_pack_and_a_padded_size_below_the_channels():
+    w = _pack_weights(5, 3)
+    ff, _ = guarded(5, 9 * 8, torch.float16)
+    fd, _ = guarded(8, 9 * 8, torch.float16)
+    with pytest.raises(PrxError, match="neither pack"):
+        call("prx_k_pack_conv3x3", w, None, None, 5, 3, 8, 8, PREC_F16, stream())
+    with pytest.raises(PrxError, match="do not fit"):
+        call("prx_k_pack_conv3x3", w, ff, fd, 5, 3, 2, 8, PREC_F16, stream())
+    sync()
+    assert bool(torch.isnan(ff).all()) and bool(torch.isnan(fd).all())          # no launch
+
+
 @pytest.mark.parametrize("rows,D", [(7, 1), (5, 300)])
 def test_colminmax(rows, D):
     """per-column minimum / maximum (exact); D = 300: a second, partial workgroup"""
@@ -873,6 +910,7 @@ def emu_subset(lib=None):
         test_rn_pack_conv3x3(5, 3, prec)
         test_vgg_pack(5, 3, 8, prec)
         test_vqgan_pack_conv3x3(3, 8, 8, prec)
+        test_pack_conv3x3(5, 3, 8, 8, "fd", prec)
         test_pack_transpose(33, 70, prec)
         for CO in STEM_CO:
             stem_fwd_case(5, 18, CO, prec)
@@ -896,6 +934,7 @@ def emu_subset(lib=None):
         test_vgg_combine(4, 4, 64, "routed+gcap", None, prec)
         test_vgg_input_and_input_grad(prec)
     test_stem_refuses_a_width_it_has_no_kernel_for()
+    test_pack_conv3x3_refuses_no_pack_and_a_padded_size_below_the_channels()
     test_vqgan_enc_pack_conv3x3(5, 3, 8)
     test_colminmax(5, 300)
     for n in (1, 7, 4099):
