@@ -12,6 +12,7 @@
 #include "elementwise.h"
 #include "optim.h"
 #include "gemm.h"
+#include "runner_core.h"
 #include "../../include/prx.h"
 
 #define S_(x) ((hipStream_t)(x))
@@ -28,7 +29,6 @@ int prx_vqgan_create(prx_vqgan** out, const prx_vqgan_config* c, const float* co
                                  c->latent_w, c->precision, weights, n_weights, S_(s));
 }
 void prx_vqgan_destroy(prx_vqgan* h) { prx_vqgan_destroy_impl((PrxVqgan*)h); }
-prx_gemm_ctx* prx_vqgan_gemm_ctx(prx_vqgan* h) { return (prx_gemm_ctx*)prx_vqgan_gemm_ctx_impl((PrxVqgan*)h); }
 int prx_vqgan_z_bounds(prx_vqgan* h, float* zmin, float* zmax, prx_stream_t s) {
     PRX_REQUIRE(h, "null handle");
     return prx_vqgan_bounds_impl((PrxVqgan*)h, zmin, zmax, S_(s));
@@ -56,7 +56,6 @@ int prx_vgg16_create(prx_vgg16** out, const float* const* weights, int n_weights
     return prx_vgg16_create_impl((PrxVgg16**)out, weights, n_weights, max_h, max_w, precision, S_(s));
 }
 void prx_vgg16_destroy(prx_vgg16* h) { prx_vgg16_destroy_impl((PrxVgg16*)h); }
-prx_gemm_ctx* prx_vgg16_gemm_ctx(prx_vgg16* h) { return (prx_gemm_ctx*)prx_vgg16_gemm_ctx_impl((PrxVgg16*)h); }
 long long prx_vgg16_workspace_bytes(int H, int W, int precision) { return prx_vgg16_workspace_bytes_impl(H, W, precision); }
 int prx_vgg16_feature_shape(int H, int W, int k, int* h, int* w, int* c) {
     PRX_REQUIRE(h && w && c, "prx_vgg16_feature_shape: null argument");
@@ -110,11 +109,11 @@ int prx_cutouts_backward(const float* g_out, const double* desc, const unsigned 
     return prx_pool_bwd(g_pooled, argmax, spot_mask, g_img, 3, H, W, S, S_(s));
 }
 
-// ---- CLIP visual tower ------------------------------------------------------------------------
+// ---- the image towers: CLIP / SLIP / OpenCLIP ViT, CLIP ModifiedResNet, OpenCLIP ConvNeXt --------
 int prx_clip_vit_create(prx_clip_vit** out, const prx_clip_vit_config* c, const float* const* weights, int n_weights,
                         prx_stream_t s) {
     PRX_REQUIRE(out && c && weights, "prx_clip_vit_create: null argument");
-    return prx_vit_create_impl((PrxVit**)out, c->input_resolution, c->patch_size, c->width, c->layers, c->heads,
+    return prx_vit_create_impl((ImageTower**)out, c->input_resolution, c->patch_size, c->width, c->layers, c->heads,
                                c->output_dim, c->max_batch, c->precision, weights, n_weights, S_(s));
 }
 int prx_vit_tower_create(prx_clip_vit** out, const prx_vit_tower_config* c, const float* const* weights, int n_weights,
@@ -134,32 +133,48 @@ int prx_vit_tower_create_mlp(prx_clip_vit** out, const prx_vit_tower_config* c, 
     if (c->family == PRX_VIT_FAMILY_OPENCLIP) { f.act = PRX_ACT_GELU; f.dact = PRX_ACT_MUL_DGELU; }      // CLIP's layout, the exact GELU
     f.eps = c->ln_eps; f.head_dim = c->head_dim; f.mlp_width = mlp_width;
     for (int i = 0; i < 3; ++i) { f.norm.mean[i] = c->mean[i]; f.norm.std[i] = c->std[i]; }
-    return prx_vit_create_impl((PrxVit**)out, c->input_resolution, c->patch_size, c->width, c->layers, c->heads,
+    return prx_vit_create_impl((ImageTower**)out, c->input_resolution, c->patch_size, c->width, c->layers, c->heads,
                                c->output_dim, c->max_batch, c->precision, weights, n_weights, S_(s), &f);
 }
 long long prx_vit_tower_debug_dqkv(prx_clip_vit* h, void* dst, long long max_bytes, prx_stream_t s) {
-    return prx_vit_debug_dqkv_impl((PrxVit*)h, dst, max_bytes, S_(s));
+    return prx_vit_debug_dqkv_impl((ImageTower*)h, dst, max_bytes, S_(s));
 }
-void prx_clip_vit_destroy(prx_clip_vit* h) { prx_vit_destroy_impl((PrxVit*)h); }
-prx_gemm_ctx* prx_clip_vit_gemm_ctx(prx_clip_vit* h) { return (prx_gemm_ctx*)prx_vit_gemm_ctx_impl((PrxVit*)h); }
-int prx_clip_vit_minmax(prx_clip_vit* h, const float* cutouts, int n, float* mm, prx_stream_t s) {
-    PRX_REQUIRE(h && cutouts && mm, "prx_clip_vit_minmax: null argument");
-    return prx_vit_minmax_impl((PrxVit*)h, cutouts, n, mm, S_(s));
+int prx_clip_resnet_create(prx_clip_resnet** out, const prx_clip_resnet_config* c, const float* const* weights, int n_weights,
+                           prx_stream_t s) {
+    PRX_REQUIRE(out && c && weights, "prx_clip_resnet_create: null argument");
+    return prx_resnet_create_impl((ImageTower**)out, c->input_resolution, c->width, c->layers, c->heads, c->output_dim,
+                                  c->max_batch, c->precision, weights, n_weights, S_(s));
 }
-int prx_clip_vit_encode(prx_clip_vit* h, const float* cutouts, int n, const float* mm, float* embeds, prx_stream_t s) {
-    PRX_REQUIRE(h && cutouts && mm && embeds, "prx_clip_vit_encode: null argument");
-    return prx_vit_forward_impl((PrxVit*)h, cutouts, n, mm, embeds, S_(s));
+int prx_clip_convnext_create(prx_clip_convnext** out, const prx_clip_convnext_config* c, const float* const* weights, int n_weights,
+                             prx_stream_t s) {
+    PRX_REQUIRE(out && c && weights, "prx_clip_convnext_create: null argument");
+    return prx_convnext_create_impl((ImageTower**)out, c->input_resolution, c->depths, c->dims, c->output_dim, c->proj_mlp, c->ln_eps,
+                                    c->max_batch, c->precision, weights, n_weights, S_(s));
 }
-int prx_clip_vit_backward_reduce(prx_clip_vit* h, const float* cutouts, const float* mm, const float* d_embeds,
-                                 double* acc, prx_stream_t s) {
-    PRX_REQUIRE(h && cutouts && mm && d_embeds && acc, "prx_clip_vit_backward_reduce: null argument");
-    return prx_vit_backward_a_impl((PrxVit*)h, cutouts, mm, d_embeds, acc, S_(s));
-}
-int prx_clip_vit_backward_finish(prx_clip_vit* h, const float* cutouts, const float* mm, const double* acc,
-                                 float* g_cutouts, prx_stream_t s) {
-    PRX_REQUIRE(h && cutouts && mm && acc && g_cutouts, "prx_clip_vit_backward_finish: null argument");
-    return prx_vit_backward_b_impl((PrxVit*)h, cutouts, mm, acc, g_cutouts, S_(s));
-}
+// One protocol (runner_core.h ImageTower) behind three opaque handle types: T is the exported prefix
+#define TOWER_(h) ((ImageTower*)(h))
+#define PRX_TOWER_ABI(T)                                                                                                       \
+    void T##_destroy(T* h) { delete TOWER_(h); }                                                                               \
+    prx_gemm_ctx* T##_gemm_ctx(T* h) { return h ? (prx_gemm_ctx*)&TOWER_(h)->gctx : nullptr; }                                 \
+    int T##_minmax(T* h, const float* cutouts, int n, float* mm, prx_stream_t s) {                                             \
+        PRX_REQUIRE(h && cutouts && mm, #T "_minmax: null argument");                                                          \
+        return TOWER_(h)->minmax(cutouts, n, mm, S_(s));                                                                       \
+    }                                                                                                                          \
+    int T##_encode(T* h, const float* cutouts, int n, const float* mm, float* embeds, prx_stream_t s) {                        \
+        PRX_REQUIRE(h && cutouts && mm && embeds, #T "_encode: null argument");                                                \
+        return TOWER_(h)->forward(cutouts, n, mm, embeds, S_(s));                                                              \
+    }                                                                                                                          \
+    int T##_backward_reduce(T* h, const float* cutouts, const float* mm, const float* d_embeds, double* acc, prx_stream_t s) { \
+        PRX_REQUIRE(h && cutouts && mm && d_embeds && acc, #T "_backward_reduce: null argument");                              \
+        return TOWER_(h)->backward_a(cutouts, mm, d_embeds, acc, S_(s));                                                       \
+    }                                                                                                                          \
+    int T##_backward_finish(T* h, const float* cutouts, const float* mm, const double* acc, float* g_cutouts, prx_stream_t s) { \
+        PRX_REQUIRE(h && cutouts && mm && acc && g_cutouts, #T "_backward_finish: null argument");                             \
+        return TOWER_(h)->backward_b(cutouts, mm, acc, g_cutouts, S_(s));                                                      \
+    }
+PRX_TOWER_ABI(prx_clip_vit)
+PRX_TOWER_ABI(prx_clip_resnet)
+PRX_TOWER_ABI(prx_clip_convnext)
 
 // ---- Prompt loss, optimiser -------------------------------------------------------------------
 int prx_prompt_loss_fwd_bwd(const float* input, const float* embed, int n, int m, int D, float weight, float stop,
@@ -227,59 +242,5 @@ void prx_clip_text_destroy(prx_clip_text* h) { prx_clip_text_destroy_impl((PrxCl
 int prx_clip_text_encode(prx_clip_text* h, const int* tokens, int n, float* embeds, prx_stream_t s) {
     PRX_REQUIRE(h && tokens && embeds, "prx_clip_text_encode: null argument");
     return prx_clip_text_encode_impl((PrxClipText*)h, tokens, n, embeds, S_(s));
-}
-// ---- CLIP ModifiedResNet tower -----------------------------------------------------------------
-int prx_clip_resnet_create(prx_clip_resnet** out, const prx_clip_resnet_config* c, const float* const* weights, int n_weights,
-                           prx_stream_t s) {
-    PRX_REQUIRE(out && c && weights, "prx_clip_resnet_create: null argument");
-    return prx_resnet_create_impl((PrxResNet**)out, c->input_resolution, c->width, c->layers, c->heads, c->output_dim,
-                                  c->max_batch, c->precision, weights, n_weights, S_(s));
-}
-void prx_clip_resnet_destroy(prx_clip_resnet* h) { prx_resnet_destroy_impl((PrxResNet*)h); }
-prx_gemm_ctx* prx_clip_resnet_gemm_ctx(prx_clip_resnet* h) { return (prx_gemm_ctx*)prx_resnet_gemm_ctx_impl((PrxResNet*)h); }
-int prx_clip_resnet_minmax(prx_clip_resnet* h, const float* cutouts, int n, float* mm, prx_stream_t s) {
-    PRX_REQUIRE(h && cutouts && mm, "prx_clip_resnet_minmax: null argument");
-    return prx_resnet_minmax_impl((PrxResNet*)h, cutouts, n, mm, S_(s));
-}
-int prx_clip_resnet_encode(prx_clip_resnet* h, const float* cutouts, int n, const float* mm, float* embeds, prx_stream_t s) {
-    PRX_REQUIRE(h && cutouts && mm && embeds, "prx_clip_resnet_encode: null argument");
-    return prx_resnet_forward_impl((PrxResNet*)h, cutouts, n, mm, embeds, S_(s));
-}
-int prx_clip_resnet_backward_reduce(prx_clip_resnet* h, const float* cutouts, const float* mm, const float* d_embeds,
-                                    double* acc, prx_stream_t s) {
-    PRX_REQUIRE(h && cutouts && mm && d_embeds && acc, "prx_clip_resnet_backward_reduce: null argument");
-    return prx_resnet_backward_a_impl((PrxResNet*)h, cutouts, mm, d_embeds, acc, S_(s));
-}
-// ---- OpenCLIP ConvNeXt tower ------------------------------------------------------------------
-int prx_clip_convnext_create(prx_clip_convnext** out, const prx_clip_convnext_config* c, const float* const* weights, int n_weights,
-                             prx_stream_t s) {
-    PRX_REQUIRE(out && c && weights, "prx_clip_convnext_create: null argument");
-    return prx_convnext_create_impl((PrxConvNext**)out, c->input_resolution, c->depths, c->dims, c->output_dim, c->proj_mlp, c->ln_eps,
-                                    c->max_batch, c->precision, weights, n_weights, S_(s));
-}
-void prx_clip_convnext_destroy(prx_clip_convnext* h) { prx_convnext_destroy_impl((PrxConvNext*)h); }
-prx_gemm_ctx* prx_clip_convnext_gemm_ctx(prx_clip_convnext* h) { return (prx_gemm_ctx*)prx_convnext_gemm_ctx_impl((PrxConvNext*)h); }
-int prx_clip_convnext_minmax(prx_clip_convnext* h, const float* cutouts, int n, float* mm, prx_stream_t s) {
-    PRX_REQUIRE(h && cutouts && mm, "prx_clip_convnext_minmax: null argument");
-    return prx_convnext_minmax_impl((PrxConvNext*)h, cutouts, n, mm, S_(s));
-}
-int prx_clip_convnext_encode(prx_clip_convnext* h, const float* cutouts, int n, const float* mm, float* embeds, prx_stream_t s) {
-    PRX_REQUIRE(h && cutouts && mm && embeds, "prx_clip_convnext_encode: null argument");
-    return prx_convnext_forward_impl((PrxConvNext*)h, cutouts, n, mm, embeds, S_(s));
-}
-int prx_clip_convnext_backward_reduce(prx_clip_convnext* h, const float* cutouts, const float* mm, const float* d_embeds,
-                                      double* acc, prx_stream_t s) {
-    PRX_REQUIRE(h && cutouts && mm && d_embeds && acc, "prx_clip_convnext_backward_reduce: null argument");
-    return prx_convnext_backward_a_impl((PrxConvNext*)h, cutouts, mm, d_embeds, acc, S_(s));
-}
-int prx_clip_convnext_backward_finish(prx_clip_convnext* h, const float* cutouts, const float* mm, const double* acc,
-                                      float* g_cutouts, prx_stream_t s) {
-    PRX_REQUIRE(h && cutouts && mm && acc && g_cutouts, "prx_clip_convnext_backward_finish: null argument");
-    return prx_convnext_backward_b_impl((PrxConvNext*)h, cutouts, mm, acc, g_cutouts, S_(s));
-}
-int prx_clip_resnet_backward_finish(prx_clip_resnet* h, const float* cutouts, const float* mm, const double* acc,
-                                    float* g_cutouts, prx_stream_t s) {
-    PRX_REQUIRE(h && cutouts && mm && acc && g_cutouts, "prx_clip_resnet_backward_finish: null argument");
-    return prx_resnet_backward_b_impl((PrxResNet*)h, cutouts, mm, acc, g_cutouts, S_(s));
 }
 }  // extern "C"

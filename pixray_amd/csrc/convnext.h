@@ -2,18 +2,9 @@
 #pragma once
 #include "common.h"
 
-struct PrxConvNext;
-struct GemmCtx;
-GemmCtx* prx_convnext_gemm_ctx_impl(PrxConvNext* r);
-int prx_convnext_create_impl(PrxConvNext** out, int res, const int* depths, const int* dims, int out_dim, int proj_mlp, float ln_eps,
+struct ImageTower;      // runner_core.h: the tower protocol the created handle is driven through
+int prx_convnext_create_impl(ImageTower** out, int res, const int* depths, const int* dims, int out_dim, int proj_mlp, float ln_eps,
                              int max_n, int precision, const float* const* w, int n_w, hipStream_t s);
-void prx_convnext_destroy_impl(PrxConvNext* r);
-int prx_convnext_minmax_impl(PrxConvNext* r, const float* cutouts, int n, float* mm, hipStream_t s);
-int prx_convnext_forward_impl(PrxConvNext* r, const float* cutouts, int n, const float* mm, float* embeds, hipStream_t s);
-int prx_convnext_backward_a_impl(PrxConvNext* r, const float* cutouts, const float* mm, const float* d_embeds, double* acc,
-                                 hipStream_t s);
-int prx_convnext_backward_b_impl(PrxConvNext* r, const float* cutouts, const float* mm, const double* acc, float* g_cutouts,
-                                 hipStream_t s);
 // One host launcher per runner-private kernel (the runner calls these; csrc/api_kernels.hip exports them as prx_k_cnx_* for the
 // kernel-level tests).  Maps are NHWC [N][H][W][C]; `prec` = PRX_PREC_* is the element type of the `void*` buffers; C % 8 == 0.
 // pack: the depthwise weight [C][7*7] (fp32) as [2][49][C] in the operand format -- the taps channel-contiguous, then the same with

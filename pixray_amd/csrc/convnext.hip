@@ -17,8 +17,8 @@
 #include "cutouts.h"
 #include "prompt_vq.h"
 #include "elementwise.h"
-#include "vit.h"  // prx_vit_gelu_f32
 #include "weight_pack.h"
+#include "runner_core.h"
 #include <vector>
 #include <memory>
 
@@ -366,45 +366,22 @@ struct CnxStage {
     float* xs[2]; void* xo[2];                      // the residual stream, ping-pong: fp32 and its operand-format twin (one buffer in the exact mode)
     std::vector<CnxBlock> B;
 };
-struct PrxConvNext {
-    int res, out_dim, proj_mlp, max_n, prec, f32, h16, T, cur_n;
+struct PrxConvNext : ImageTower {
+    int proj_mlp, T;
     float eps;
-    GemmCtx gctx;
-    DevArena mem;
     CnxStage S[4];
     void *Wstem, *WstemT; float *stem_b, *stem_ln_g, *stem_ln_b, *stem_mean, *stem_rstd;
     float *head_ln_g, *head_ln_b, *head_mean, *head_rstd, *hb1;
     void *P0, *P0T, *P1, *P1T;                      // linear: P0 = proj [E, d3]; mlp: P0 = fc1 [2E, d3], P1 = fc2 [E, 2E]
     // workspace
-    void *A0, *h, *u, *dt, *dy, *dx_op, *dxpre, *hpost, *ht, *hu, *dht, *de16;
-    float *xpre, *dA0, *dh, *dh2, *dx, *pooled, *dpool, *dhpost, *e, *de, *mm_part, *gs, *ws;
-    size_t ws_bytes;
+    void *A0, *h, *u, *dt, *dy, *dx_op, *dxpre, *hpost, *ht, *hu, *dht;
+    float *xpre, *dA0, *dh, *dh2, *dx, *pooled, *dpool, *dhpost;
+    int forward(const float* cutouts, int n, const float* mm, float* embeds, hipStream_t s) override;
+    int backward_a(const float* cutouts, const float* mm, const float* d_embeds, double* acc, hipStream_t s) override;
+    int backward_b(const float* cutouts, const float* mm, const double* acc, float* g_cutouts, hipStream_t s) override;
 };
 
-namespace {
-int cnx_gemm(PrxConvNext* v, GemmDesc& d, hipStream_t s) {
-    if (v->f32) { d.f32 = 1; d.a_is_f32 = 0; }
-    d.h16 = v->h16;
-    return prx_gemm_launch(d, v->ws, v->ws_bytes, s, &v->gctx);
-}
-// out = act(A W^T + b): GELU in the epilogue (16-bit modes) or in a pass of its own (the fp32 kernels carry no erff); `pre` keeps the pre-activation
-int cnx_gemm_gelu(PrxConvNext* v, const void* A, const void* W, const float* b, void* pre, void* out, int M, int N, int K, hipStream_t s) {
-    GemmDesc d; d.A = A; d.lda = K; d.B = W; d.ldb = K; d.M = M; d.N = N; d.K = K; d.bias_n = b; d.ldc_bf16 = N;
-    if (v->f32) { d.out_bf16 = pre; }
-    else { d.act = PRX_ACT_GELU; d.out_bf16 = out; d.out_bf16_pre = pre; }
-    if (int r = cnx_gemm(v, d, s)) return r;
-    return v->f32 ? prx_vit_gelu_f32((const float*)pre, (float*)out, (size_t)M * N, 0, s) : 0;
-}
-// out = (A W^T) * gelu'(pre)
-int cnx_gemm_dgelu(PrxConvNext* v, const void* A, const void* WT, const void* pre, void* out, int M, int N, int K, hipStream_t s) {
-    GemmDesc d; d.A = A; d.lda = K; d.B = WT; d.ldb = K; d.M = M; d.N = N; d.K = K; d.out_bf16 = out; d.ldc_bf16 = N;
-    if (!v->f32) { d.act = PRX_ACT_MUL_DGELU; d.aux = pre; d.ldaux = N; }
-    if (int r = cnx_gemm(v, d, s)) return r;
-    return v->f32 ? prx_vit_gelu_f32((const float*)pre, (float*)out, (size_t)M * N, 1, s) : 0;
-}
-}  // namespace
-
-int prx_convnext_create_impl(PrxConvNext** out, int res, const int* depths, const int* dims, int out_dim, int proj_mlp, float ln_eps,
+int prx_convnext_create_impl(ImageTower** out, int res, const int* depths, const int* dims, int out_dim, int proj_mlp, float ln_eps,
                              int max_n, int precision, const float* const* w, int n_w, hipStream_t s) {
     PRX_REQUIRE(prec_valid(precision), "convnext_create: unknown precision %d", precision);
     PRX_REQUIRE(res >= 32 && res % 32 == 0, "convnext_create: the input resolution must be a multiple of 32 (R=%d)", res);
@@ -429,8 +406,8 @@ int prx_convnext_create_impl(PrxConvNext** out, int res, const int* depths, cons
     DevArena& m = v->mem;
     m.describe("convnext_create", ": the runner keeps one forward's activations for max_batch = %d cutouts of %d x %d (%d blocks, widths %d..%d)",
                max_n, res, res, n_blocks, dims[0], dims[3]);
-    v->res = res; v->out_dim = out_dim; v->proj_mlp = proj_mlp; v->max_n = max_n; v->prec = precision; v->eps = ln_eps;
-    v->f32 = prec_is_f32(precision); v->h16 = prec_is_h16(precision); v->T = G0 * G0 + 1; v->cur_n = 0; v->gs = nullptr;
+    v->name = "convnext"; v->res = res; v->out_dim = out_dim; v->proj_mlp = proj_mlp; v->max_n = max_n; v->eps = ln_eps;
+    v->set_precision(precision); v->T = G0 * G0 + 1; v->cur_n = 0;
     const int f32 = v->f32;
     int r;
     const float* const* q = w;
@@ -501,31 +478,21 @@ int prx_convnext_create_impl(PrxConvNext** out, int res, const int* depths, cons
     DEV_ALLOC(m, alloc, v->head_mean, N); DEV_ALLOC(m, alloc, v->head_rstd, N);
     DEV_ALLOC(m, alloc_op, v->hpost, N * d3, f32); DEV_ALLOC(m, alloc_op, v->ht, N * 2 * E, f32); DEV_ALLOC(m, alloc_op, v->hu, N * 2 * E, f32);
     DEV_ALLOC(m, alloc_op, v->dht, N * 2 * E, f32); DEV_ALLOC(m, alloc_op, v->de16, N * E, f32);
-    DEV_ALLOC(m, alloc, v->e, N * E); DEV_ALLOC(m, alloc, v->de, N * E); DEV_ALLOC(m, alloc, v->mm_part, 2 * 1024);
-    if (v->h16) DEV_ALLOC(m, alloc, v->gs, 2 + 64);
-    v->ws_bytes = (size_t)64 << 20;
-    DEV_ALLOC(m, alloc, v->ws, v->ws_bytes / sizeof(float));
+    DEV_ALLOC(m, alloc, v->e, N * E); DEV_ALLOC(m, alloc, v->de, N * E);
+    if ((r = v->alloc_tail())) return r;
     *out = guard.release();
     return 0;
 }
 
-void prx_convnext_destroy_impl(PrxConvNext* v) { delete v; }
-GemmCtx* prx_convnext_gemm_ctx_impl(PrxConvNext* v) { return v ? &v->gctx : nullptr; }
-
-int prx_convnext_minmax_impl(PrxConvNext* v, const float* cutouts, int n, float* mm, hipStream_t s) {
-    PRX_REQUIRE(n >= 1 && n <= v->max_n, "convnext: batch %d exceeds handle capacity %d", n, v->max_n);
-    return prx_minmax(cutouts, (size_t)n * 3 * v->res * v->res, v->mm_part, 1024, mm, s);
-}
-
-int prx_convnext_forward_impl(PrxConvNext* v, const float* cutouts, int n, const float* mm, float* embeds, hipStream_t s) {
-    PRX_REQUIRE(n >= 1 && n <= v->max_n, "convnext: batch %d exceeds handle capacity %d", n, v->max_n);
-    const int T = v->T, prec = v->prec;
+int PrxConvNext::forward(const float* cutouts, int n, const float* mm, float* embeds, hipStream_t s) {
+    PrxConvNext* const v = this;
     int r;
-    v->cur_n = n;
+    if ((r = begin_forward(n))) return r;
+    const int T = v->T, prec = v->prec;
     if ((r = prx_patchify_fwd(cutouts, mm, v->A0, prec, n, v->res, 4, T, s))) return r;
     {   GemmDesc d; d.A = v->A0; d.lda = 48; d.B = v->Wstem; d.ldb = 48; d.M = n * T; d.N = v->S[0].C; d.K = 48;
         d.bias_n = v->stem_b; d.out_f32 = v->xpre; d.ldc_f32 = v->S[0].C;
-        if ((r = cnx_gemm(v, d, s))) return r; }
+        if ((r = v->gemm(d, s))) return r; }
     if ((r = prx_cnx_layernorm_fwd(v->xpre, 1, v->stem_ln_g, v->stem_ln_b, v->f32 ? nullptr : v->S[0].xo[0], v->S[0].xs[0], v->stem_mean,
                                    v->stem_rstd, n * (T - 1), v->S[0].C, v->eps, T - 1, prec, s))) return r;
     for (int i = 0; i < 4; ++i) {
@@ -540,18 +507,18 @@ int prx_convnext_forward_impl(PrxConvNext* v, const float* cutouts, int n, const
             GemmDesc d; d.A = v->u; d.lda = 4 * Cp; d.B = st.Wd; d.ldb = 4 * Cp; d.M = M; d.N = C; d.K = 4 * Cp;
             d.bias_n = st.ds_b; d.out_f32 = st.xs[0]; d.ldc_f32 = C;
             if (!v->f32) { d.out_bf16 = st.xo[0]; d.ldc_bf16 = C; }
-            if ((r = cnx_gemm(v, d, s))) return r;
+            if ((r = v->gemm(d, s))) return r;
         }
         for (int k = 0; k < st.depth; ++k) {
             CnxBlock& b = st.B[k];
             const int in = k & 1, on = in ^ 1;
             if ((r = prx_cnx_dwconv(st.xo[in], b.dwpack, b.dwb, nullptr, b.y, nullptr, n, G, G, C, 0, prec, s))) return r;
             if ((r = prx_cnx_layernorm_fwd(b.y, 0, b.ln_g, b.ln_b, v->h, nullptr, b.mean, b.rstd, M, C, v->eps, 0, prec, s))) return r;
-            if ((r = cnx_gemm_gelu(v, v->h, b.W1, b.b1, b.t, v->u, M, 4 * C, C, s))) return r;
+            if ((r = linear_act(PRX_ACT_GELU, v->h, C, b.W1, b.b1, b.t, v->u, M, 4 * C, C, s))) return r;
             GemmDesc d; d.A = v->u; d.lda = 4 * C; d.B = b.W2; d.ldb = 4 * C; d.M = M; d.N = C; d.K = 4 * C;
             d.bias_n = b.b2; d.resid = st.xs[in]; d.ldr = C; d.out_f32 = st.xs[on]; d.ldc_f32 = C;
             if (!v->f32) { d.out_bf16 = st.xo[on]; d.ldc_bf16 = C; }
-            if ((r = cnx_gemm(v, d, s))) return r;
+            if ((r = v->gemm(d, s))) return r;
         }
     }
     const CnxStage& l = v->S[3];
@@ -560,39 +527,36 @@ int prx_convnext_forward_impl(PrxConvNext* v, const float* cutouts, int n, const
     if ((r = prx_cnx_layernorm_fwd(v->pooled, 1, v->head_ln_g, v->head_ln_b, v->hpost, nullptr, v->head_mean, v->head_rstd, n, d3, v->eps, 0, prec, s))) return r;
     const void* last = v->hpost; const void* Wl = v->P0; int Kl = d3;
     if (v->proj_mlp) {
-        if ((r = cnx_gemm_gelu(v, v->hpost, v->P0, v->hb1, v->ht, v->hu, n, 2 * E, d3, s))) return r;
+        if ((r = linear_act(PRX_ACT_GELU, v->hpost, d3, v->P0, v->hb1, v->ht, v->hu, n, 2 * E, d3, s))) return r;
         last = v->hu; Wl = v->P1; Kl = 2 * E;
     }
     {   GemmDesc d; d.A = last; d.lda = Kl; d.B = Wl; d.ldb = Kl; d.M = n; d.N = E; d.K = Kl; d.out_f32 = v->e; d.ldc_f32 = E;
-        if ((r = cnx_gemm(v, d, s))) return r; }
-    return prx_l2norm_fwd(v->e, embeds, n, E, s);
+        if ((r = v->gemm(d, s))) return r; }
+    return head_fwd(embeds, n, s);
 }
 
 // Backward part A: from d(embeds) down to the stem product's input gradient and the sums the batch-global min/max renormalisation
 // needs (acc[4] doubles, summed over ranks by the caller when the cutout batch is sharded).  Half mode: everything between the
 // L2-normalisation backward and the stem dgrad runs under the device-chosen power-of-two scale S (every step is linear in the gradient).
-int prx_convnext_backward_a_impl(PrxConvNext* v, const float* cutouts, const float* mm, const float* d_embeds, double* acc, hipStream_t s) {
-    const int n = v->cur_n;
-    PRX_REQUIRE(n >= 1, "convnext backward: no forward in flight on this handle");
+int PrxConvNext::backward_a(const float* cutouts, const float* mm, const float* d_embeds, double* acc, hipStream_t s) {
+    PrxConvNext* const v = this;
+    int n, r;
+    if ((r = backward_n(&n))) return r;
     const int T = v->T, prec = v->prec, E = v->out_dim, d3 = v->S[3].C;
-    int r;
-    if ((r = prx_l2norm_bwd(v->e, d_embeds, v->de, n, E, s))) return r;
+    if ((r = head_bwd(d_embeds, n, s))) return r;
+    // the next product reads d(e) itself in the exact mode, else a 16-bit twin: the scaled one head_bwd wrote (half), or a bf16 copy
     const void* dE = v->de;
-    if (v->h16) {
-        if ((r = prx_grad_scale(v->de, (size_t)n * E, v->gs + 2, 64, prx_grad_target_log2(), v->gs, s))) return r;
-        if ((r = prx_scale_dev(v->de, (size_t)n * E, v->gs, s, (bf16_t*)v->de16, 1))) return r;
-        dE = v->de16;
-    } else if (!v->f32) {
-        if ((r = prx_f32_to_bf16(v->de, (bf16_t*)v->de16, (size_t)n * E, s, 0))) return r;
+    if (!v->f32) {
+        if (!v->h16 && (r = prx_f32_to_bf16(v->de, (bf16_t*)v->de16, (size_t)n * E, s, 0))) return r;
         dE = v->de16;
     }
     if (v->proj_mlp) {
-        if ((r = cnx_gemm_dgelu(v, dE, v->P1T, v->ht, v->dht, n, 2 * E, E, s))) return r;
+        if ((r = linear_dact(PRX_ACT_MUL_DGELU, dE, E, v->P1T, v->ht, v->dht, n, 2 * E, E, s))) return r;
         GemmDesc d; d.A = v->dht; d.lda = 2 * E; d.B = v->P0T; d.ldb = 2 * E; d.M = n; d.N = d3; d.K = 2 * E; d.out_f32 = v->dhpost; d.ldc_f32 = d3;
-        if ((r = cnx_gemm(v, d, s))) return r;
+        if ((r = v->gemm(d, s))) return r;
     } else {
         GemmDesc d; d.A = dE; d.lda = E; d.B = v->P0T; d.ldb = E; d.M = n; d.N = d3; d.K = E; d.out_f32 = v->dhpost; d.ldc_f32 = d3;
-        if ((r = cnx_gemm(v, d, s))) return r;
+        if ((r = v->gemm(d, s))) return r;
     }
     if ((r = prx_cnx_layernorm_bwd(v->dhpost, v->pooled, 1, v->head_ln_g, v->head_mean, v->head_rstd, nullptr, v->dpool, n, d3, 0, prec, s))) return r;
     void* dxo = v->f32 ? nullptr : v->dx_op;           // the operand twin of the stream gradient (the exact mode reads the fp32 stream itself)
@@ -602,9 +566,9 @@ int prx_convnext_backward_a_impl(PrxConvNext* v, const float* cutouts, const flo
         const int C = st.C, G = st.G, M = n * G * G;
         for (int k = st.depth - 1; k >= 0; --k) {
             CnxBlock& b = st.B[k];
-            if ((r = cnx_gemm_dgelu(v, v->dx_op, b.W2T, b.t, v->dt, M, 4 * C, C, s))) return r;
+            if ((r = linear_dact(PRX_ACT_MUL_DGELU, v->dx_op, C, b.W2T, b.t, v->dt, M, 4 * C, C, s))) return r;
             {   GemmDesc d; d.A = v->dt; d.lda = 4 * C; d.B = b.W1T; d.ldb = 4 * C; d.M = M; d.N = C; d.K = 4 * C; d.out_f32 = v->dh; d.ldc_f32 = C;
-                if ((r = cnx_gemm(v, d, s))) return r; }
+                if ((r = v->gemm(d, s))) return r; }
             if ((r = prx_cnx_layernorm_bwd(v->dh, b.y, 0, b.ln_g, b.mean, b.rstd, v->dy, nullptr, M, C, 0, prec, s))) return r;
             // d(block input) = stencil^T d(y) + the gradient that went round the branch
             if ((r = prx_cnx_dwconv(v->dy, b.dwpack, nullptr, v->dx, dxo, v->dx, n, G, G, C, 1, prec, s))) return r;
@@ -613,7 +577,7 @@ int prx_convnext_backward_a_impl(PrxConvNext* v, const float* cutouts, const flo
             CnxStage& pv = v->S[i - 1];
             const int Cp = pv.C, Mp = n * pv.G * pv.G;
             GemmDesc d; d.A = v->dx_op; d.lda = C; d.B = st.WdT; d.ldb = C; d.M = M; d.N = 4 * Cp; d.K = C; d.out_f32 = v->dh; d.ldc_f32 = 4 * Cp;
-            if ((r = cnx_gemm(v, d, s))) return r;
+            if ((r = v->gemm(d, s))) return r;
             if ((r = prx_cnx_depth_to_space(v->dh, v->dh2, n, pv.G, pv.G, Cp, PRX_PREC_F32, s))) return r;
             if ((r = prx_cnx_layernorm_bwd(v->dh2, pv.xs[pv.depth & 1], 1, st.ds_ln_g, st.ds_mean, st.ds_rstd, dxo, v->dx, Mp, Cp, 0, prec, s))) return r;
         }
@@ -622,12 +586,12 @@ int prx_convnext_backward_a_impl(PrxConvNext* v, const float* cutouts, const flo
     if ((r = prx_cnx_layernorm_bwd(v->dx, v->xpre, 1, v->stem_ln_g, v->stem_mean, v->stem_rstd, v->dxpre, nullptr, n * (T - 1), d0, T - 1, prec, s))) return r;
     {   GemmDesc d; d.A = v->dxpre; d.lda = d0; d.B = v->WstemT; d.ldb = d0; d.M = n * T; d.N = 48; d.K = d0; d.out_f32 = v->dA0; d.ldc_f32 = 48;
         if (v->h16) d.alpha_dev = v->gs + 1;        // unscaled (1/S) here, before the (rank-summed) renormalisation sums
-        if ((r = cnx_gemm(v, d, s))) return r; }
+        if ((r = v->gemm(d, s))) return r; }
     return prx_patchify_bwd_reduce(cutouts, mm, v->dA0, acc, n, v->res, 4, T, s);
 }
 
-int prx_convnext_backward_b_impl(PrxConvNext* v, const float* cutouts, const float* mm, const double* acc, float* g_cutouts, hipStream_t s) {
-    const int n = v->cur_n;
-    PRX_REQUIRE(n >= 1, "convnext backward: no forward in flight on this handle");
-    return prx_patchify_bwd_apply(cutouts, mm, v->dA0, acc, g_cutouts, n, v->res, 4, v->T, s);
+int PrxConvNext::backward_b(const float* cutouts, const float* mm, const double* acc, float* g_cutouts, hipStream_t s) {
+    int n;
+    if (int r = backward_n(&n)) return r;
+    return prx_patchify_bwd_apply(cutouts, mm, dA0, acc, g_cutouts, n, res, 4, T, s);
 }

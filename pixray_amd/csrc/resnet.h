@@ -2,18 +2,9 @@
 #pragma once
 #include "common.h"
 
-struct PrxResNet;
-struct GemmCtx;
-GemmCtx* prx_resnet_gemm_ctx_impl(PrxResNet* r);
-int prx_resnet_create_impl(PrxResNet** out, int res, int width, const int* layers, int heads, int out_dim, int max_n,
+struct ImageTower;      // runner_core.h: the tower protocol the created handle is driven through
+int prx_resnet_create_impl(ImageTower** out, int res, int width, const int* layers, int heads, int out_dim, int max_n,
                            int precision, const float* const* w, int n_w, hipStream_t s);
-void prx_resnet_destroy_impl(PrxResNet* r);
-int prx_resnet_minmax_impl(PrxResNet* r, const float* cutouts, int n, float* mm, hipStream_t s);
-int prx_resnet_forward_impl(PrxResNet* r, const float* cutouts, int n, const float* mm, float* embeds, hipStream_t s);
-int prx_resnet_backward_a_impl(PrxResNet* r, const float* cutouts, const float* mm, const float* d_embeds, double* acc,
-                               hipStream_t s);
-int prx_resnet_backward_b_impl(PrxResNet* r, const float* cutouts, const float* mm, const double* acc, float* g_cutouts,
-                               hipStream_t s);
 // One host launcher per runner-private kernel: grid computation and the operand-type (`prec` = PRX_PREC_*) / CO dispatch.  The runner
 // calls these; csrc/api_kernels.hip exports them as prx_k_* for the kernel-level tests.  Operand-format buffers are `void*`.
 // CO = width / 2, one of 8, 16, 32, 40, 48, 64 (anything else is refused)

@@ -13,6 +13,7 @@
 #include "cutouts.h"
 #include "prompt_vq.h"
 #include "weight_pack.h"
+#include "runner_core.h"
 #include <cstdlib>
 #include <vector>
 #include <memory>
@@ -349,10 +350,8 @@ int prx_tok0_scatter(const void* g0, void* dt, int N, int T, int C, int prec, hi
     return 0;
 }
 
-struct PrxResNet {
-    int res, width, heads, out_dim, max_n, C, G, T, cur_n;
-    int prec;         // PRX_PREC_*
-    int f32, h16;     // derived: operands are fp32 / the 16-bit operand format is IEEE half
+struct PrxResNet : ImageTower {
+    int width, heads, C, G, T;
     MhaDesc mha;      // the attention pool's problem (N is set per call)
     // The lean layout (half mode, PRX_RN_LEAN, as vit.hip's PRX_LEAN): the residual stream of the Bottleneck stack and its
     // gradient live in IEEE half only -- the reference's own activation precision (CLIP's convert_weights runs the
@@ -360,19 +359,21 @@ struct PrxResNet {
     // identity, the conv1 dgrad reads a 2-byte identity gradient and writes 2 bytes instead of 6: these 1x1 GEMMs are
     // bound by exactly those streams.  The last block keeps its fp32 output (the attention pool's token mean reads it).
     int lean;
-    float* gs;        // half mode: device {S, 1/S} = the power-of-two scale of the backward in flight (common.h) + 64 partials; else null
-    GemmCtx gctx;     // this handle's engine state
-    DevArena mem;     // every device buffer below (weights + one forward's activations for max_n cutouts): freed with the handle
+    // RunnerEngine::mem holds every device buffer below (weights + one forward's activations for max_n cutouts); de16 stays null: the
+    // c_proj dgrad reads the fp32 d(e)
     float *w1, *b1;                      // stem conv1 (fp32, BN folded)
     RConv3 s2, s3;
     std::vector<RBlock> blocks;
     float* pos; void *Win, *WinT, *Wc, *WcT; float *bin, *bc;
     // activations
     void *s1, *s2a, *s3a, *s0_bf; float* s0_f32;     // stem outputs; s0 = pooled stem output (layer1 input)
-    void *tok, *qkv, *att, *o0, *dtok, *dqkv, *do0; float *lse, *e, *de, *dtokf;
+    void *tok, *qkv, *att, *o0, *dtok, *dqkv, *do0; float *lse, *dtokf;
     float *gA, *gB, *tf; void *tb1, *tb2, *gbf;      // backward ping-pong / temporaries
     void *gb2, *gb3;                                 // lean layout: second gradient stream, downsample-branch gradient
-    float *dY, *mm_part, *ws; size_t ws_bytes;
+    float* dY;
+    int forward(const float* cutouts, int n, const float* mm, float* embeds, hipStream_t s) override;
+    int backward_a(const float* cutouts, const float* mm, const float* d_embeds, double* acc, hipStream_t s) override;
+    int backward_b(const float* cutouts, const float* mm, const double* acc, float* g_cutouts, hipStream_t s) override;
 };
 
 namespace {
@@ -390,34 +391,26 @@ int mk3(PrxResNet* r, RConv3& c, int Cin, int Cout, WeightCursor& cur, hipStream
     if ((e = prx_pack_conv3x3(w, c.Wf, c.Wd, Cout, Cin, Cin, Cout, r->prec, s))) return e;
     return r->mem.copy_f32(&c.b, b, Cout, s);
 }
-int rg(PrxResNet* r, GemmDesc& d, hipStream_t s) {
-    if (r->f32) { d.f32 = 1; d.a_is_f32 = 0; }
-    d.h16 = r->h16;
-    return prx_gemm_launch(d, r->ws, r->ws_bytes, s, &r->gctx);
-}
-
 // 1x1 conv forward / dgrad as GEMMs
 int lin(PrxResNet* r, const void* A, int M, int K, const void* Bt, int N, const float* bias, const float* resid, int act,
         const void* aux, float* of, void* ob, hipStream_t s, int resid16 = 0) {
     GemmDesc d; d.A = A; d.lda = K; d.B = Bt; d.ldb = K; d.M = M; d.N = N; d.K = K;
     d.bias_n = bias; d.resid = resid; d.ldr = N; d.act = act; d.aux = aux; d.ldaux = N; d.row16 = resid16 ? 1 : 0;
     d.out_f32 = of; d.ldc_f32 = N; d.out_bf16 = ob; d.ldc_bf16 = N;
-    return rg(r, d, s);
+    return r->gemm(d, s);
 }
 int conv3(PrxResNet* r, const void* x, int NB, int H, int Cin, const void* Bt, int Cout, const float* bias, int act,
           const void* aux, float* of, void* ob, hipStream_t s) {
     GemmDesc d; d.A = x; d.a_mode = PRX_A_CONV3X3; d.lda = Cin; d.B = Bt; d.ldb = 9 * Cin; d.M = NB * H * H; d.N = Cout; d.K = 9 * Cin;
     d.H = H; d.W = H; d.Cin = Cin; d.bias_n = bias; d.act = act; d.aux = aux; d.ldaux = Cout;
     d.out_f32 = of; d.ldc_f32 = Cout; d.out_bf16 = ob; d.ldc_bf16 = Cout;
-    return rg(r, d, s);
+    return r->gemm(d, s);
 }
 }  // namespace
 
 // weights (fp32 device, BatchNorm folded on the host, pixray_amd/weights.py::fold_clip_resnet_params): stem1 {w,b}, stem2,
 // stem3, per Bottleneck c1, c2, c3 [, ds], attnpool positional_embedding, in_proj {w [3C,C], b}, c_proj {w, b}
-GemmCtx* prx_resnet_gemm_ctx_impl(PrxResNet* r) { return r ? &r->gctx : nullptr; }
-
-int prx_resnet_create_impl(PrxResNet** out, int res, int width, const int* layers, int heads, int out_dim, int max_n,
+int prx_resnet_create_impl(ImageTower** out, int res, int width, const int* layers, int heads, int out_dim, int max_n,
                            int precision, const float* const* w, int n_w, hipStream_t s) {
     PRX_REQUIRE(prec_valid(precision), "resnet_create: unknown precision %d", precision);
     PRX_REQUIRE(res % 32 == 0 && width % 16 == 0 && max_n >= 1, "resnet_create: unsupported geometry (res %d width %d)", res, width);
@@ -429,8 +422,7 @@ int prx_resnet_create_impl(PrxResNet** out, int res, int width, const int* layer
     // the runner keeps one forward's activations for max_n cutouts, so a smaller max_batch is the way out of a failed allocation
     m.describe("resnet_create", ": the runner keeps one forward's activations for max_batch = %d cutouts of %d x %d (width %d)", max_n, res, res,
                width);
-    r->prec = precision; r->f32 = prec_is_f32(precision); r->h16 = prec_is_h16(precision);
-    r->gs = nullptr;
+    r->name = "resnet"; r->set_precision(precision);
     { const char* ev = getenv("PRX_RN_LEAN"); r->lean = (r->h16 && !(ev && atoi(ev) == 0)) ? 1 : 0; }
     r->res = res; r->width = width; r->heads = heads; r->out_dim = out_dim; r->max_n = max_n; r->cur_n = 0;
     r->C = width * 32; r->G = res / 32; r->T = r->G * r->G + 1;
@@ -491,26 +483,17 @@ int prx_resnet_create_impl(PrxResNet** out, int res, int width, const int* layer
     r->gB = nullptr; r->gb2 = r->gb3 = nullptr;
     if (r->lean) { DEV_ALLOC(m, alloc_op, r->gb2, maxMC, f32); DEV_ALLOC(m, alloc_op, r->gb3, maxMC, f32); } else DEV_ALLOC(m, alloc, r->gB, maxMC);
     DEV_ALLOC(m, alloc_op, r->tb1, maxMC, f32); DEV_ALLOC(m, alloc_op, r->tb2, maxMC, f32); DEV_ALLOC(m, alloc_op, r->gbf, maxMC, f32);
-    DEV_ALLOC(m, alloc, r->dY, N * 3 * (size_t)res * res); DEV_ALLOC(m, alloc, r->mm_part, 2 * 1024);
-    if (r->h16) DEV_ALLOC(m, alloc, r->gs, 2 + 64);
-    r->ws_bytes = (size_t)64 << 20;
-    DEV_ALLOC(m, alloc, r->ws, r->ws_bytes / sizeof(float));
+    DEV_ALLOC(m, alloc, r->dY, N * 3 * (size_t)res * res);
+    if ((e = r->alloc_tail())) return e;
     *out = guard.release();
     return 0;
 }
 
-void prx_resnet_destroy_impl(PrxResNet* r) { delete r; }
-
-int prx_resnet_minmax_impl(PrxResNet* r, const float* cutouts, int n, float* mm, hipStream_t s) {
-    PRX_REQUIRE(n >= 1 && n <= r->max_n, "resnet: batch %d exceeds handle capacity %d", n, r->max_n);
-    return prx_minmax(cutouts, (size_t)n * 3 * r->res * r->res, r->mm_part, 1024, mm, s);
-}
-
-int prx_resnet_forward_impl(PrxResNet* r, const float* cutouts, int n, const float* mm, float* embeds, hipStream_t s) {
-    PRX_REQUIRE(n >= 1 && n <= r->max_n, "resnet: batch %d exceeds handle capacity %d", n, r->max_n);
-    const int S = r->res, S2 = S / 2, S4 = S / 4, w = r->width, wh = w / 2;
+int PrxResNet::forward(const float* cutouts, int n, const float* mm, float* embeds, hipStream_t s) {
+    PrxResNet* const r = this;
     int e;
-    r->cur_n = n;
+    if ((e = begin_forward(n))) return e;
+    const int S = r->res, S2 = S / 2, S4 = S / 4, w = r->width, wh = w / 2;
     if ((e = prx_stem1_fwd(cutouts, mm, r->w1, r->b1, r->s1, n, S, wh, r->prec, s))) return e;
     if ((e = conv3(r, r->s1, n, S2, wh, r->s2.Wf, wh, r->s2.b, PRX_ACT_RELU, nullptr, nullptr, r->s2a, s))) return e;
     if ((e = conv3(r, r->s2a, n, S2, wh, r->s3.Wf, w, r->s3.b, PRX_ACT_RELU, nullptr, nullptr, r->s3a, s))) return e;
@@ -550,28 +533,22 @@ int prx_resnet_forward_impl(PrxResNet* r, const float* cutouts, int n, const flo
     if ((e = prx_mha_fwd(mha, r->qkv, r->att, r->lse, s))) return e;
     if ((e = prx_tok0_gather(r->att, r->o0, n, T, C, r->prec, s))) return e;
     if ((e = lin(r, r->o0, n, C, r->Wc, r->out_dim, r->bc, nullptr, PRX_ACT_NONE, nullptr, r->e, nullptr, s))) return e;
-    return prx_l2norm_fwd(r->e, embeds, n, r->out_dim, s);
+    return head_fwd(embeds, n, s);
 }
 
 // Backward part A: from d(embeds) down to the gradient w.r.t. the normalised image (dY) and the four sums the
 // batch-global min/max renorm needs (to be summed over ranks when the cutout batch is sharded)
-int prx_resnet_backward_a_impl(PrxResNet* r, const float* cutouts, const float* mm, const float* d_embeds, double* acc,
-                               hipStream_t s) {
-    const int n = r->cur_n;
-    PRX_REQUIRE(n >= 1, "resnet backward: no forward in flight on this handle");
+int PrxResNet::backward_a(const float* cutouts, const float* mm, const float* d_embeds, double* acc, hipStream_t s) {
+    PrxResNet* const r = this;
+    int n, e;
+    if ((e = backward_n(&n))) return e;
     const int C = r->C, T = r->T, P = T - 1;
-    int e;
-    if ((e = prx_l2norm_bwd(r->e, d_embeds, r->de, n, r->out_dim, s))) return e;
+    // half mode: the whole backward runs under the scale head_bwd chooses; stem1_bwd unscales
+    if ((e = head_bwd(d_embeds, n, s))) return e;
     // c_proj dgrad: A fp32 -> the register-staged GEMM converts on load
     {   GemmDesc d; d.A = r->de; d.a_is_f32 = 1; d.lda = r->out_dim; d.B = r->WcT; d.ldb = r->out_dim; d.M = n; d.N = C; d.K = r->out_dim;
         d.out_bf16 = r->do0; d.ldc_bf16 = C;
-        // half mode: the whole backward runs scaled by a power of two S chosen from max|d e|; stem1_bwd unscales
-        // (S multiplies d e in fp32 before the load converts it to half: see vit.hip)
-        if (r->h16) {
-            if ((e = prx_grad_scale(r->de, (size_t)n * r->out_dim, r->gs + 2, 64, prx_grad_target_log2(), r->gs, s))) return e;
-            if ((e = prx_scale_dev(r->de, (size_t)n * r->out_dim, r->gs, s))) return e;
-        }
-        if ((e = rg(r, d, s))) return e; }
+        if ((e = r->gemm(d, s))) return e; }
     if ((e = prx_tok0_scatter(r->do0, r->dtok, n, T, C, r->prec, s))) return e;
     MhaDesc mha = r->mha; mha.N = n;
     if ((e = prx_mha_bwd(mha, r->qkv, r->att, r->dtok, r->lse, r->dqkv, s))) return e;
@@ -639,8 +616,8 @@ int prx_resnet_backward_a_impl(PrxResNet* r, const float* cutouts, const float* 
     return prx_preproc_bwd_reduce(cutouts, mm, r->dY, acc, n, S, s);
 }
 
-int prx_resnet_backward_b_impl(PrxResNet* r, const float* cutouts, const float* mm, const double* acc, float* g_cutouts,
-                               hipStream_t s) {
-    PRX_REQUIRE(r->cur_n >= 1, "resnet backward: no forward in flight on this handle");
-    return prx_preproc_bwd_apply(cutouts, mm, r->dY, acc, g_cutouts, r->cur_n, r->res, s);
+int PrxResNet::backward_b(const float* cutouts, const float* mm, const double* acc, float* g_cutouts, hipStream_t s) {
+    int n;
+    if (int e = backward_n(&n)) return e;
+    return prx_preproc_bwd_apply(cutouts, mm, dY, acc, g_cutouts, n, res, s);
 }

@@ -4,8 +4,6 @@
 #include "common.h"
 
 struct PrxVgg16;
-struct GemmCtx;
-GemmCtx* prx_vgg16_gemm_ctx_impl(PrxVgg16* v);
 int prx_vgg16_create_impl(PrxVgg16** out, const float* const* weights, int n_weights, int max_h, int max_w, int precision, hipStream_t s);
 void prx_vgg16_destroy_impl(PrxVgg16* v);
 long long prx_vgg16_workspace_bytes_impl(int H, int W, int precision);

@@ -16,6 +16,8 @@
 #include "gemm.h"
 #include "elementwise.h"
 #include "weight_pack.h"
+#include "runner_core.h"
+#include "../../include/prx.h"
 #include <memory>
 #include <vector>
 #include <algorithm>
@@ -164,17 +166,11 @@ int prx_vgg_combine(const float* above, const unsigned char* arg, const float* g
     return 0;
 }
 
-struct PrxVgg16 {
+struct PrxVgg16 : RunnerEngine {     // gs: 2 + NFEAT * 256 floats
     int max_h, max_w;
-    int prec;         // PRX_PREC_*
-    int f32, h16;     // derived: operands are fp32 / the 16-bit operand format is IEEE half
-    float* gs;        // half mode: device {S, 1/S} of the backward in flight + partial maxima; else null
-    GemmCtx gctx;     // this handle's engine state
-    DevArena mem;     // every device buffer below: freed with the handle
     VConv conv[NCONV];
-    float *dA, *dB, *ws;       // dgrad ping-pong (fp32), split-K scratch
+    float *dA, *dB;   // dgrad ping-pong (fp32)
     void* gpre;       // operand precision
-    size_t ws_bytes;
 };
 
 namespace {
@@ -183,13 +179,12 @@ int vconv(PrxVgg16* v, const void* x, int H, int W, int Cin, const void* Bt, int
     GemmDesc d; d.A = x; d.a_mode = PRX_A_CONV3X3; d.lda = Cin; d.B = Bt; d.ldb = 9 * Cin; d.M = H * W; d.N = Cout; d.K = 9 * Cin;
     d.H = H; d.W = W; d.Cin = Cin; d.bias_n = bias; d.act = act;
     d.out_f32 = of; d.ldc_f32 = Cout; d.out_bf16 = ob; d.ldc_bf16 = Cout;
-    d.f32 = v->f32; d.h16 = v->h16;
-    return prx_gemm_launch(d, v->ws, v->ws_bytes, s, &v->gctx);
+    return v->gemm(d, s);
 }
 }  // namespace
 
 long long prx_vgg16_workspace_bytes_impl(int H, int W, int precision) { return (H < 16 || W < 16) ? -1 : (long long)vlayout(H, W, prec_is_f32(precision)).total; }
-GemmCtx* prx_vgg16_gemm_ctx_impl(PrxVgg16* v) { return v ? &v->gctx : nullptr; }
+extern "C" prx_gemm_ctx* prx_vgg16_gemm_ctx(prx_vgg16* h) { return h ? (prx_gemm_ctx*)&((PrxVgg16*)h)->gctx : nullptr; }
 
 int prx_vgg16_feature_shape_impl(int H, int W, int k, int* h, int* w, int* c) {
     PRX_REQUIRE(k >= 0 && k < NFEAT && H >= 16 && W >= 16, "vgg16_feature_shape: feature %d of a %dx%d input", k, H, W);
@@ -206,8 +201,7 @@ int prx_vgg16_create_impl(PrxVgg16** out, const float* const* weights, int n_wei
     PRX_REQUIRE(max_h >= 16 && max_w >= 16, "vgg16_create: the input must be at least 16x16 (got %dx%d)", max_h, max_w);
     std::unique_ptr<PrxVgg16> guard(new PrxVgg16());      // a failed create frees what it allocated (DevArena)
     PrxVgg16* v = guard.get();
-    v->max_h = max_h; v->max_w = max_w; v->prec = precision; v->f32 = prec_is_f32(precision); v->h16 = prec_is_h16(precision);
-    v->gs = nullptr;
+    v->max_h = max_h; v->max_w = max_w; v->set_precision(precision);
     v->mem.describe("vgg16_create", ": the extractor keeps its weight packs and the gradient streams of a %d x %d input", max_h, max_w);
     for (int l = 0; l < NCONV; ++l) {
         VConv& c = v->conv[l];
@@ -220,8 +214,7 @@ int prx_vgg16_create_impl(PrxVgg16** out, const float* const* weights, int n_wei
     }
     const size_t big = (size_t)max_h * max_w * 64;
     DEV_ALLOC(v->mem, alloc, v->dA, big); DEV_ALLOC(v->mem, alloc, v->dB, big); DEV_ALLOC(v->mem, alloc_op, v->gpre, big, v->f32);
-    v->ws_bytes = (size_t)64 << 20;
-    DEV_ALLOC(v->mem, alloc, v->ws, v->ws_bytes / sizeof(float));
+    if (int e = v->alloc_ws()) return e;
     if (v->h16) DEV_ALLOC(v->mem, alloc, v->gs, (size_t)2 + NFEAT * 256);
     *out = guard.release();
     return 0;

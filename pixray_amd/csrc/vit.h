@@ -2,7 +2,6 @@
 #include "common.h"
 #include "cutouts.h"
 #include "attention.h"     // prx_mha_head_cols: the head dims VitFamily::head_dim may take
-struct PrxVit;
 // What differs between the tower families this runner serves.  CLIP (clip.model.VisionTransformer): no patch-embed bias, ln_pre,
 // eps 1e-5, QuickGELU, CLIP's preprocessing constants.  SLIP (timm VisionTransformer): a bias, no ln_pre, eps 1e-6, exact GELU,
 // the ImageNet constants.
@@ -17,18 +16,10 @@ struct VitFamily {
     int mlp_width;      // hidden width of the MLP; 0 = 4 * width (OpenCLIP ViT-g-14: 6144 on 1408, ViT-bigG-14: 8192 on 1664)
 };
 VitFamily prx_vit_family_clip();
-struct GemmCtx;
-int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers, int heads, int out_dim, int max_n,
+struct ImageTower;      // runner_core.h: the tower protocol the created handle is driven through
+int prx_vit_create_impl(ImageTower** out, int res, int patch, int width, int layers, int heads, int out_dim, int max_n,
                         int precision, const float* const* w, int n_w, hipStream_t s, const VitFamily* family = nullptr);
-GemmCtx* prx_vit_gemm_ctx_impl(PrxVit* v);
-long long prx_vit_debug_dqkv_impl(PrxVit* v, void* dst, long long max_bytes, hipStream_t s);
-void prx_vit_destroy_impl(PrxVit* v);
-int prx_vit_minmax_impl(PrxVit* v, const float* cutouts, int n, float* mm, hipStream_t s);
-int prx_vit_forward_impl(PrxVit* v, const float* cutouts, int n, const float* mm, float* embeds, hipStream_t s);
-int prx_vit_backward_a_impl(PrxVit* v, const float* cutouts, const float* mm, const float* d_embeds, double* acc,
-                            hipStream_t s);
-int prx_vit_backward_b_impl(PrxVit* v, const float* cutouts, const float* mm, const double* acc, float* g_cutouts,
-                            hipStream_t s);
+long long prx_vit_debug_dqkv_impl(ImageTower* v, void* dst, long long max_bytes, hipStream_t s);   // a handle of this runner only
 // launchers of the runner's own token-embedding / exact-mode activation kernels (the runner calls these; exported as prx_k_* for
 // the kernel-level tests).  embed_tokens: `out` is IEEE half when out16, else fp32; scale_f32: x *= scale on `blocks` workgroups
 int prx_vit_add_cls_pos(float* x, const float* cls, const float* pos, int N, int T, int W, hipStream_t s);

@@ -16,6 +16,7 @@
 #include "prompt_vq.h"
 #include "elementwise.h"
 #include "weight_pack.h"
+#include "runner_core.h"
 #include <vector>
 #include <memory>
 
@@ -121,8 +122,8 @@ struct VitLayer {
     float* lse;
 };
 
-struct PrxVit {
-    int res, patch, width, layers, heads, out_dim, T, max_n, KP;
+struct PrxVit : ImageTower {
+    int patch, width, layers, heads, T, KP;
     // Padded heads (SLIP's ViT-S/16: 12 heads of 32 on width 384): the attention kernels are head-dim-64, so every head's q, k and v
     // rows of the qkv projection (weight and bias) are zero-padded to 64 at packing time, and so are the matching input columns of the
     // out-projection; sqrt(64 / head dim) is folded into the q rows before they are rounded to the operand format, because the
@@ -136,17 +137,13 @@ struct PrxVit {
     int hd, hp, aw;    // head dim of the weights; operand columns per head (64 | 96 | 128); attention width = heads * hp (== width when hd == 64)
     MhaDesc att;       // the attention of every block (N is set per call): the recomputing form where it has a kernel, else out + lse are saved
     int mlp;           // hidden width of the MLP: fam.mlp_width, or 4 * width (every tower but OpenCLIP's ViT-g-14 6144 and ViT-bigG-14 8192)
-    int prec;         // PRX_PREC_*: element type of every operand buffer below (void*)
-    int f32, h16;     // derived: operands are fp32 / the 16-bit operand format is IEEE half
-    float* gs;        // half mode: device {S, 1/S} = the power-of-two scale of the backward in flight (common.h) + 64 partials; else null
-    GemmCtx gctx;     // this handle's engine state (tile overrides, timing log)
-    DevArena mem;     // every device buffer below (weights + one forward's activations for max_n cutouts): freed with the handle
+    // RunnerEngine::mem holds every device buffer below (weights + one forward's activations for max_n cutouts)
     void *Wp, *WpT, *projT, *proj;
     float *cls, *pos, *lnpre_g, *lnpre_b, *lnpost_g, *lnpost_b;
     std::vector<VitLayer> L;
     // workspace
-    void *A0, *h, *att_o, *u, *hpost, *dt, *do_, *dqkv, *dx_bf, *dh_bf, *de16;   // operand precision
-    float *xpre, *mean_pre, *rstd_pre, *mean_post, *rstd_post, *e, *dx, *dh, *dA0, *de, *dhpost, *mm_part;
+    void *A0, *h, *att_o, *u, *hpost, *dt, *do_, *dqkv, *dx_bf, *dh_bf;   // operand precision
+    float *xpre, *mean_pre, *rstd_pre, *mean_post, *rstd_post, *dx, *dh, *dA0, *dhpost;
     void* x_final;
     // The lean layout (half mode, PRX_LEAN): the residual stream and its gradient live in IEEE half only -- the reference's own
     // GPU arithmetic for this tower (slip.py:175: the CLIP model runs in fp16, residual adds included).  One 16-bit tensor is
@@ -155,13 +152,14 @@ struct PrxVit {
     VitFamily fam;     // what differs between the CLIP and the SLIP towers (vit.h)
     float* bp;         // patch-embed bias (fam.patch_bias), else null
     int cls_tail;      // 1 (default): the class-token tail below; PRX_VIT_CLS_TAIL=0 runs the last block on every token row (A/B, bisection)
-    float* ws; size_t ws_bytes;
-    int cur_n;
     // The class-token tail: only the class token of the LAST block's output is ever read (ln_post on token 0, slip.py:66 / clip
     // VisionTransformer), so that block's out-projection, MLP and their backward run on the n class-token rows (row stride
     // T * width into the same buffers) instead of all n * T token rows: the same values for everything that is read, 3 + 3 of
     // the tower's 48 + 48 wide products reduced to M = n.  K and V of that block still need every token.  (Round-5 A/B on the
     // device: 140.1 -> 141.2 and 138.0 -> 139.5 it/s, profiles/r05_first_call/, r05_timeline/.)
+    int forward(const float* cutouts, int n, const float* mm, float* embeds, hipStream_t s) override;
+    int backward_a(const float* cutouts, const float* mm, const float* d_embeds, double* acc, hipStream_t s) override;
+    int backward_b(const float* cutouts, const float* mm, const double* acc, float* g_cutouts, hipStream_t s) override;
 };
 
 VitFamily prx_vit_family_clip() {
@@ -171,7 +169,7 @@ VitFamily prx_vit_family_clip() {
     return f;
 }
 
-int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers, int heads, int out_dim, int max_n,
+int prx_vit_create_impl(ImageTower** out, int res, int patch, int width, int layers, int heads, int out_dim, int max_n,
                         int precision, const float* const* w, int n_w, hipStream_t s, const VitFamily* family) {
     const VitFamily fam = family ? *family : prx_vit_family_clip();
     // weights ahead of the blocks: conv weight [, conv bias], class token, positions [, ln_pre gamma, beta]
@@ -198,10 +196,10 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
     // the runner keeps one forward's activations for max_n cutouts, so a smaller max_batch is the way out of a failed allocation
     v->mem.describe("vit_create", ": the runner keeps one forward's activations for max_batch = %d cutouts of %d tokens (width %d, %d layers)",
                     max_n, T, width, layers);
-    v->T = T; v->max_n = max_n;
+    v->name = "vit"; v->T = T; v->max_n = max_n;
     v->res = res; v->patch = patch; v->width = width; v->layers = layers; v->heads = heads; v->out_dim = out_dim;
-    v->prec = precision; v->f32 = prec_is_f32(precision); v->h16 = prec_is_h16(precision);
-    v->gs = nullptr; v->fam = fam; v->bp = nullptr; v->hd = hd; v->hp = hp; v->aw = heads * hp; v->mlp = MW;
+    v->set_precision(precision);
+    v->fam = fam; v->bp = nullptr; v->hd = hd; v->hp = hp; v->aw = heads * hp; v->mlp = MW;
     const int AW = v->aw;
     // heads narrower than 64 reach the kernels as heads of 64 (folded below)
     v->att.T = T; v->att.heads = heads; v->att.hd = hd < 64 ? 64 : hd; v->att.C = AW; v->att.prec = precision;
@@ -292,23 +290,14 @@ int prx_vit_create_impl(PrxVit** out, int res, int patch, int width, int layers,
     // in the lean layout they ARE the gradient streams
     if (v->f32) { v->dx_bf = v->dx; v->dh_bf = v->dh; }
     else { DEV_ALLOC(m, alloc_op, v->dx_bf, R * W, f32); DEV_ALLOC(m, alloc_op, v->dh_bf, R * W, f32); }
-    DEV_ALLOC(m, alloc, v->dhpost, (size_t)max_n * W); DEV_ALLOC(m, alloc, v->mm_part, 2 * 1024);
-    if (v->h16) DEV_ALLOC(m, alloc, v->gs, 2 + 64);
-    v->ws_bytes = (size_t)64 << 20;
-    DEV_ALLOC(m, alloc, v->ws, v->ws_bytes / sizeof(float));
+    DEV_ALLOC(m, alloc, v->dhpost, (size_t)max_n * W);
+    if ((r = v->alloc_tail())) return r;
     *out = guard.release();
     return 0;
 }
 
-void prx_vit_destroy_impl(PrxVit* v) { delete v; }
-
-static int vit_gemm(PrxVit* v, GemmDesc& d, hipStream_t s) {
-    if (v->f32) { d.f32 = 1; d.a_is_f32 = 0; }
-    d.h16 = v->h16;
-    return prx_gemm_launch(d, v->ws, v->ws_bytes, s, &v->gctx);
-}
-GemmCtx* prx_vit_gemm_ctx_impl(PrxVit* v) { return v ? &v->gctx : nullptr; }
-long long prx_vit_debug_dqkv_impl(PrxVit* v, void* dst, long long max_bytes, hipStream_t s) {
+long long prx_vit_debug_dqkv_impl(ImageTower* h, void* dst, long long max_bytes, hipStream_t s) {
+    const PrxVit* v = static_cast<const PrxVit*>(h);
     if (!v || v->cur_n < 1) return -1;
     const long long bytes = (long long)op_esz(v->f32) * v->cur_n * v->T * 3 * v->aw;
     if (bytes > max_bytes || hipMemcpyAsync(dst, v->dqkv, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) return -1;
@@ -330,22 +319,17 @@ static int ln_bwd_op(PrxVit* v, const void* g, long long ldg, const void* x, lon
                              v->width, s, v->h16, add_every, s16, 1);
 }
 
-int prx_vit_minmax_impl(PrxVit* v, const float* cutouts, int n, float* mm, hipStream_t s) {
-    PRX_REQUIRE(n >= 1 && n <= v->max_n, "vit: batch %d exceeds handle capacity %d", n, v->max_n);
-    return prx_minmax(cutouts, (size_t)n * 3 * v->res * v->res, v->mm_part, 1024, mm, s);
-}
-
-int prx_vit_forward_impl(PrxVit* v, const float* cutouts, int n, const float* mm, float* embeds, hipStream_t s) {
-    PRX_REQUIRE(n >= 1 && n <= v->max_n, "vit: batch %d exceeds handle capacity %d", n, v->max_n);
-    const int W = v->width, T = v->T, R = n * T, KP = v->KP, AW = v->aw, MW = v->mlp;
+int PrxVit::forward(const float* cutouts, int n, const float* mm, float* embeds, hipStream_t s) {
+    PrxVit* const v = this;
     int r;
-    v->cur_n = n;
+    if ((r = begin_forward(n))) return r;
+    const int W = v->width, T = v->T, R = n * T, KP = v->KP, AW = v->aw, MW = v->mlp;
     if ((r = prx_patchify_fwd(cutouts, mm, v->A0, v->prec, n, v->res, v->patch, T, s, v->fam.norm))) return r;
     {   // conv1 (patch embed) as GEMM
         GemmDesc d; d.A = v->A0; d.lda = KP; d.B = v->Wp; d.ldb = KP; d.M = R; d.N = W; d.K = KP;
         d.bias_n = v->bp;
         d.out_f32 = v->xpre; d.ldc_f32 = W;
-        if ((r = vit_gemm(v, d, s))) return r;
+        if ((r = v->gemm(d, s))) return r;
     }
     const int lean = v->lean;
     MhaDesc mha = v->att; mha.N = n;
@@ -363,7 +347,7 @@ int prx_vit_forward_impl(PrxVit* v, const float* cutouts, int n, const float* mm
         if ((r = ln_op(v, y.x_in, W, y.ln1_g, y.ln1_b, v->h, y.mean1, y.rstd1, R, s))) return r;
         {   GemmDesc d; d.A = v->h; d.lda = W; d.B = y.Wqkv; d.ldb = W; d.M = R; d.N = 3 * AW; d.K = W;
             d.bias_n = y.bqkv; d.out_bf16 = y.qkv; d.ldc_bf16 = 3 * AW;
-            if ((r = vit_gemm(v, d, s))) return r; }
+            if ((r = v->gemm(d, s))) return r; }
         void* att = prx_mha_saves_out(mha) ? y.o_save : v->att_o;
         if ((r = prx_mha_fwd(mha, y.qkv, att, y.lse, s))) return r;
         // the class-token tail: rows = the n class tokens, reached through a row stride of T * W in the token-major buffers;
@@ -375,53 +359,38 @@ int prx_vit_forward_impl(PrxVit* v, const float* cutouts, int n, const float* mm
             d.bias_n = y.bo; d.ldr = ldt;
             if (lean) { d.resid = (const float*)y.x_in; d.row16 = 1; d.out_bf16 = y.x_mid; d.ldc_bf16 = ldt; }
             else { d.resid = (const float*)y.x_in; d.out_f32 = (float*)y.x_mid; d.ldc_f32 = ldt; }
-            if ((r = vit_gemm(v, d, s))) return r; }
+            if ((r = v->gemm(d, s))) return r; }
         if ((r = ln_op(v, y.x_mid, ldt, y.ln2_g, y.ln2_b, v->h, y.mean2, y.rstd2, rows, s))) return r;
-        {   GemmDesc d; d.A = v->h; d.lda = W; d.B = y.W1; d.ldb = W; d.M = rows; d.N = MW; d.K = W;
-            d.bias_n = y.b1; d.act = v->fam.act; d.out_bf16 = v->u; d.out_bf16_pre = y.t; d.ldc_bf16 = MW;
-            const bool own_pass = v->f32 && v->fam.act == PRX_ACT_GELU;      // see gelu_f32_kernel
-            if (own_pass) { d.act = PRX_ACT_NONE; d.out_bf16 = y.t; d.out_bf16_pre = nullptr; }
-            if ((r = vit_gemm(v, d, s))) return r;
-            if (own_pass) {
-                if ((r = prx_vit_gelu_f32((const float*)y.t, (float*)v->u, (size_t)rows * MW, 0, s))) return r;
-            } }
+        if ((r = linear_act(v->fam.act, v->h, W, y.W1, y.b1, y.t, v->u, rows, MW, W, s))) return r;
         {   GemmDesc d; d.A = v->u; d.lda = MW; d.B = y.W2; d.ldb = MW; d.M = rows; d.N = W; d.K = MW;
             d.bias_n = y.b2; d.ldr = ldt;
             if (lean) { d.resid = (const float*)y.x_mid; d.row16 = 1; d.out_bf16 = x_next; d.ldc_bf16 = ldt; }
             else { d.resid = (const float*)y.x_mid; d.out_f32 = (float*)x_next; d.ldc_f32 = ldt; }
-            if ((r = vit_gemm(v, d, s))) return r; }
+            if ((r = v->gemm(d, s))) return r; }
     }
     // ln_post on the class token, projection, L2 normalisation (slip.py:66)
     if ((r = ln_op(v, v->x_final, (long long)T * W, v->lnpost_g, v->lnpost_b, v->hpost, v->mean_post, v->rstd_post, n, s))) return r;
     {   GemmDesc d; d.A = v->hpost; d.lda = W; d.B = v->projT; d.ldb = W; d.M = n; d.N = v->out_dim; d.K = W;
         d.out_f32 = v->e; d.ldc_f32 = v->out_dim;
-        if ((r = vit_gemm(v, d, s))) return r; }
-    return prx_l2norm_fwd(v->e, embeds, n, v->out_dim, s);
+        if ((r = v->gemm(d, s))) return r; }
+    return head_fwd(embeds, n, s);
 }
 
 // Backward part A: from d(embeds) down to the patch-embed input gradient and the reduction the
 // batch-global min/max renorm needs (acc[4] doubles, to be summed over ranks when the cutout
 // batch is sharded).
-int prx_vit_backward_a_impl(PrxVit* v, const float* cutouts, const float* mm, const float* d_embeds, double* acc,
-                            hipStream_t s) {
-    const int n = v->cur_n;
-    PRX_REQUIRE(n >= 1, "vit backward: no forward in flight on this handle");
+int PrxVit::backward_a(const float* cutouts, const float* mm, const float* d_embeds, double* acc, hipStream_t s) {
+    PrxVit* const v = this;
+    int n, r;
+    if ((r = backward_n(&n))) return r;
     const int W = v->width, T = v->T, R = n * T, KP = v->KP, AW = v->aw, MW = v->mlp;
-    int r;
-    if ((r = prx_l2norm_bwd(v->e, d_embeds, v->de, n, v->out_dim, s))) return r;
+    if ((r = head_bwd(d_embeds, n, s))) return r;
     {   GemmDesc d; d.A = v->de; d.a_is_f32 = 1; d.lda = v->out_dim; d.B = v->proj; d.ldb = v->out_dim;
         d.M = n; d.N = W; d.K = v->out_dim; d.out_f32 = v->dhpost; d.ldc_f32 = W;
-        // half mode: everything below runs scaled by a power of two S chosen from max|d e| (exact: the backward is linear in g).
-        // S multiplies d e in fp32, BEFORE the GEMM's load converts it to half: entries of d e are ~1e-5 at the headline and
-        // shrink with the prompt weight and the world size -- unscaled they would land in half's subnormals or flush to zero
-        if (v->h16) {
-            if ((r = prx_grad_scale(v->de, (size_t)n * v->out_dim, v->gs + 2, 64, prx_grad_target_log2(), v->gs, s))) return r;
-            // ... and leaves as the half operand of this product too (hpost is free by now): a 16-bit A puts the M = n product on a
-            // fit tile with K groups (6 us) instead of the register-staged 128 x 64 kernel on 12 workgroups (26 us)
-            if ((r = prx_scale_dev(v->de, (size_t)n * v->out_dim, v->gs, s, (bf16_t*)v->de16, v->h16))) return r;
-            d.A = v->de16; d.a_is_f32 = 0;
-        }
-        if ((r = vit_gemm(v, d, s))) return r; }
+        // half mode: the scaled d e leaves head_bwd as the half operand of this product too: a 16-bit A puts the M = n product on a
+        // fit tile with K groups (6 us) instead of the register-staged 128 x 64 kernel on 12 workgroups (26 us)
+        if (v->h16) { d.A = v->de16; d.a_is_f32 = 0; }
+        if ((r = v->gemm(d, s))) return r; }
     // the residual-stream gradient is kept in fp32 (dx) with a bf16 twin (dx_bf) that feeds the dgrad GEMMs.  It enters the last
     // block on the class-token rows only; that block's kernels read those rows alone (the class-token tail) until its ln_1
     // backward, which takes the incoming gradient as zero on every other row (add_every = T) and writes all of them -- so the
@@ -441,28 +410,21 @@ int prx_vit_backward_a_impl(PrxVit* v, const float* cutouts, const float* mm, co
         const int rows = tail ? n : R;
         const int ldt = tail ? T * W : W;
         // MLP: x_next = x_mid + c_proj(act(c_fc(ln_2(x_mid)))), act = QuickGELU (CLIP) | GELU (SLIP)
-        {   GemmDesc d; d.A = v->dx_bf; d.lda = ldt; d.B = y.W2T; d.ldb = W; d.M = rows; d.N = MW; d.K = W;
-            d.act = v->fam.dact; d.aux = y.t; d.ldaux = MW; d.out_bf16 = v->dt; d.ldc_bf16 = MW;
-            const bool own_pass = v->f32 && v->fam.dact == PRX_ACT_MUL_DGELU;      // see gelu_f32_kernel
-            if (own_pass) { d.act = PRX_ACT_NONE; d.aux = nullptr; }
-            if ((r = vit_gemm(v, d, s))) return r;
-            if (own_pass) {
-                if ((r = prx_vit_gelu_f32((const float*)y.t, (float*)v->dt, (size_t)rows * MW, 1, s))) return r;
-            } }
+        if ((r = linear_dact(v->fam.dact, v->dx_bf, ldt, y.W2T, y.t, v->dt, rows, MW, W, s))) return r;
         {   GemmDesc d; d.A = v->dt; d.lda = MW; d.B = y.W1T; d.ldb = MW; d.M = rows; d.N = W; d.K = MW;
             if (lean) { d.out_bf16 = v->dh_bf; d.ldc_bf16 = W; } else { d.out_f32 = v->dh; d.ldc_f32 = W; }
-            if ((r = vit_gemm(v, d, s))) return r; }
+            if ((r = v->gemm(d, s))) return r; }
         if ((r = ln_bwd_op(v, dhs, W, y.x_mid, ldt, y.ln2_g, y.mean2, y.rstd2, dxs, ldt, v->dx, ldt, v->dx_bf, rows, s, 0, lean ? 7 : 0))) return r;
         // attention: x_mid = x_in + out_proj(mha(ln_1(x_in)))
         if (tail)       // d(attention output) is written on the class-token rows only: the other rows must read as zero
             PRX_CHECK_HIP(hipMemsetAsync(v->do_, 0, op_esz(v->f32) * (size_t)R * AW, s));
         {   GemmDesc d; d.A = v->dx_bf; d.lda = ldt; d.B = y.WoT; d.ldb = W; d.M = rows; d.N = AW; d.K = W;
             d.out_bf16 = v->do_; d.ldc_bf16 = tail ? T * AW : AW;
-            if ((r = vit_gemm(v, d, s))) return r; }
+            if ((r = v->gemm(d, s))) return r; }
         if ((r = prx_mha_bwd(mha, y.qkv, y.o_save, v->do_, y.lse, v->dqkv, s))) return r;
         {   GemmDesc d; d.A = v->dqkv; d.lda = 3 * AW; d.B = y.WqkvT; d.ldb = 3 * AW; d.M = R; d.N = W; d.K = 3 * AW;
             if (lean) { d.out_bf16 = v->dh_bf; d.ldc_bf16 = W; } else { d.out_f32 = v->dh; d.ldc_f32 = W; }
-            if ((r = vit_gemm(v, d, s))) return r; }
+            if ((r = v->gemm(d, s))) return r; }
         if ((r = ln_bwd_op(v, dhs, W, y.x_in, W, y.ln1_g, y.mean1, y.rstd1, dxs, W, v->dx, W, v->dx_bf, R, s, tail ? T : 0, lean ? 7 : 0))) return r;
     }
     // ln_pre backward (in place on dx), then patch-embed dgrad; without ln_pre the stream's gradient is the token gradient itself and
@@ -472,14 +434,12 @@ int prx_vit_backward_a_impl(PrxVit* v, const float* cutouts, const float* mm, co
     {   GemmDesc d; d.A = v->fam.ln_pre ? v->dh_bf : v->dx_bf; d.lda = W; d.B = v->WpT; d.ldb = W; d.M = R; d.N = KP; d.K = W;
         d.out_f32 = v->dA0; d.ldc_f32 = KP;
         if (v->h16) d.alpha_dev = v->gs + 1;      // ... and is unscaled (1/S) here, before the (rank-summed) renormalisation sums
-        if ((r = vit_gemm(v, d, s))) return r; }
+        if ((r = v->gemm(d, s))) return r; }
     return prx_patchify_bwd_reduce(cutouts, mm, v->dA0, acc, n, v->res, v->patch, T, s, v->fam.norm);
 }
 
-int prx_vit_backward_b_impl(PrxVit* v, const float* cutouts, const float* mm, const double* acc, float* g_cutouts,
-                            hipStream_t s) {
-    const int n = v->cur_n;
-    PRX_REQUIRE(n >= 1, "vit backward: no forward in flight on this handle");
-    int r = prx_patchify_bwd_apply(cutouts, mm, v->dA0, acc, g_cutouts, n, v->res, v->patch, v->T, s, v->fam.norm);
-    return r;
+int PrxVit::backward_b(const float* cutouts, const float* mm, const double* acc, float* g_cutouts, hipStream_t s) {
+    int n;
+    if (int r = backward_n(&n)) return r;
+    return prx_patchify_bwd_apply(cutouts, mm, dA0, acc, g_cutouts, n, res, patch, T, s, fam.norm);
 }

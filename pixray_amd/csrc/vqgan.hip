@@ -14,6 +14,8 @@
 #include "elementwise.h"
 #include "prompt_vq.h"
 #include "weight_pack.h"
+#include "runner_core.h"
+#include "../../include/prx.h"
 #include <vector>
 #include <memory>
 #include <stdlib.h>
@@ -62,10 +64,8 @@ struct UpBlock { int C, rh, rw; Conv3 c; void *x_in, *out; void *x_in_bf, *out_b
 
 struct Stage { int kind; int idx; };  // 0 res, 1 attn, 2 up
 
-struct PrxVqgan {
+struct PrxVqgan : RunnerEngine {     // gs: 2 + 256 floats
     int zc, D, NC, ch, out_ch, h0, w0, H, W, nstage;
-    int prec;         // PRX_PREC_*
-    int f32, h16;     // derived: operands are fp32 / the 16-bit operand format is IEEE half
     // The lean layout (half mode, PRX_LEAN): every feature map and every gradient map lives in IEEE half ONLY -- one tensor is
     // the saved activation (GroupNorm backward reads it), the residual operand and the next convolution's A matrix -- instead of an
     // fp32 stream plus a 16-bit twin (40 % of the iteration's HBM writes).  GroupNorm sums are still taken from the fp32
@@ -74,9 +74,6 @@ struct PrxVqgan {
     // AttnBlock launch sequence (PRX_VQ_ATTN_GROUP, read once at create; default 1): the two transposes ride on the softmax launches
     // and dq / dk / dv are one grouped GEMM launch -- 6 + 6 launches per block instead of 7 + 9, the same bits; 0: the separate launches
     int attn_group;
-    float* gs;        // half mode: device {S, 1/S} = the power-of-two scale of the backward in flight (common.h) + 256 partials; else null
-    GemmCtx gctx;     // this handle's engine state
-    DevArena mem;     // every device buffer below: freed with the handle
     float *codebook, *cnorm, *zmin, *zmax;
     Conv1 pq; Conv3 conv_in, conv_out; GN norm_out;
     std::vector<ResBlock> res; std::vector<AttnBlock> attn; std::vector<UpBlock> ups; std::vector<Stage> stages;
@@ -91,7 +88,6 @@ struct PrxVqgan {
     void *g0, *g1, *g2;      // gradient ping-pong streams (max P*C): fp32, 16-bit in the lean layout
     void *g0b, *g1b, *g2b;   // their operand twins (dgrad GEMM operands); aliases of g0..g2 in the exact mode and in the lean layout
     double* all_stats; int n_gn;   // [n_gn][64] forward stats followed by [n_gn][64] backward stats
-    float* ws; size_t ws_bytes;
     void* x_last;   // input of norm_out (a stream)
 };
 
@@ -195,8 +191,7 @@ int prx_vqgan_create_impl(PrxVqgan** out, int ch, const int* ch_mult, int n_mult
     DevArena& m = v->mem;
     const int f32 = prec_is_f32(precision);
     m.describe("vqgan_create", ": the decoder keeps one forward's activations and the backward's gradient streams for a %d x %d latent", h0, w0);
-    v->prec = precision; v->f32 = prec_is_f32(precision); v->h16 = prec_is_h16(precision);
-    v->gs = nullptr;
+    v->set_precision(precision);
     { const char* e = getenv("PRX_LEAN"); v->lean = (v->h16 && !(e && atoi(e) == 0)) ? 1 : 0; }
     { const char* e = getenv("PRX_VQ_ATTN_GROUP"); v->attn_group = (e && atoi(e) == 0) ? 0 : 1; }
     v->n_gn = 0; v->zc = z_channels; v->D = embed_dim; v->NC = n_embed; v->ch = ch; v->out_ch = out_ch; v->h0 = h0; v->w0 = w0;
@@ -284,8 +279,7 @@ int prx_vqgan_create_impl(PrxVqgan** out, int ch, const int* ch_mult, int n_mult
         for (auto& b : v->attn) fix(b.n);
         fix(v->norm_out);
     }
-    v->ws_bytes = (size_t)64 << 20;
-    DEV_ALLOC(m, alloc, v->ws, v->ws_bytes / sizeof(float));
+    if ((r = v->alloc_ws())) return r;
     if (v->h16) DEV_ALLOC(m, alloc, v->gs, 2 + 256);
     *out = guard.release();
     return 0;
@@ -325,17 +319,14 @@ static void vq_trace(const PrxVqgan* v, const char* tag, int i, const void* p_, 
 }
 
 static void vg_prec(const PrxVqgan* v, GemmDesc& d) {
-    if (v->f32) {
-        d.f32 = 1; d.a_is_f32 = 0;
-        if (d.out_bf16 == (void*)d.out_f32) d.out_bf16 = nullptr;   // the "twin" is the fp32 output itself
-    }
-    d.h16 = v->h16;
+    if (v->f32 && d.out_bf16 == (void*)d.out_f32) d.out_bf16 = nullptr;   // the "twin" is the fp32 output itself
+    v->operands(d);
 }
 static int vg(PrxVqgan* v, GemmDesc& d, hipStream_t s) {
     vg_prec(v, d);
-    return prx_gemm_launch(d, v->ws, v->ws_bytes, s, &v->gctx);
+    return v->gemm(d, s);
 }
-GemmCtx* prx_vqgan_gemm_ctx_impl(PrxVqgan* v) { return v ? &v->gctx : nullptr; }
+extern "C" prx_gemm_ctx* prx_vqgan_gemm_ctx(prx_vqgan* h) { return h ? (prx_gemm_ctx*)&((PrxVqgan*)h)->gctx : nullptr; }
 
 // A GEMM's stream output / residual / GroupNorm-input operands in the handle's layout: fp32 stream (+ optional 16-bit twin), or -- lean --
 // the one 16-bit tensor

@@ -78,6 +78,33 @@ class _Handle:
                 pass
 
 
+class _EngineHandle(_Handle):
+    """A runner handle on the GEMM engine (csrc/runner_core.h RunnerEngine): `abi` is the prefix of its exported functions, and
+    `gemm_ctx` the `prx_gemm_ctx` it owns (tile overrides, timing log)."""
+    abi = None
+
+    @property
+    def gemm_ctx(self):
+        return getattr(_lib.load(), self.abi + "_gemm_ctx")(self.h)
+
+
+class _ImageTowerHandle(_EngineHandle):
+    """An image tower behind `clip_encode_image`: `<abi>_minmax / _encode / _backward_reduce / _backward_finish / _gemm_ctx / _destroy`
+    (csrc/runner_core.h ImageTower).  A subclass prepares its weights and its config struct and hands them to `_create`."""
+
+    def _create(self, fn_name, cfg_struct, weights, *extra, cfg, device):
+        """`fn_name(&h, &cfg_struct, *extra, weights, n, stream)`; `cfg_struct` carries max_batch and the precision code"""
+        self.precision = cfg_struct.precision
+        h = ctypes.c_void_p()
+        call(fn_name, ctypes.addressof(h), ctypes.addressof(cfg_struct), *extra, _keep(self, _weight_array(weights)), len(weights), _stream())
+        torch.cuda.synchronize(device)   # weight tensors may now be released
+        self.h = h
+        self.cfg = cfg
+        self.max_batch = cfg_struct.max_batch
+        self.device = device
+        self.generation = 0              # bumped by every forward: the handle keeps ONE forward's activations (_ClipEncodeFn)
+
+
 # --------------------------------------------------------------------------------------- cutouts
 class _MakeCutoutsFn(torch.autograd.Function):
     @staticmethod
@@ -141,7 +168,7 @@ def _weights_in_abi_order(params, shapes, device, what):
     return ws
 
 
-class ClipVitHandle(_Handle):
+class ClipVitHandle(_ImageTowerHandle):
     """Owns a `prx_clip_vit` (packed weights + activation workspace for `max_batch` cutouts, allocated at create time; an allocation
     that fails raises PrxError with the bytes asked for and held, and the partly built handle is freed).
     `precision`: "fp16" (default) / "bf16" (fast paths) or "f32" (exact-f32 MFMA parity mode, include/prx.h PRX_PREC_*)."""
@@ -151,20 +178,8 @@ class ClipVitHandle(_Handle):
     def __init__(self, cfg, params, max_batch: int, device, precision=None):
         from .weights import clip_vit_param_shapes
         ws = _weights_in_abi_order(params, clip_vit_param_shapes(cfg), device, f"CLIP ViT {getattr(cfg, 'name', '')}")
-        self.precision = precision_code(precision)
-        c = _ClipCfg(cfg.input_resolution, cfg.patch_size, cfg.width, cfg.layers, cfg.heads, cfg.output_dim, max_batch, self.precision)
-        h = ctypes.c_void_p()
-        call("prx_clip_vit_create", ctypes.addressof(h), ctypes.addressof(c), _keep(self, _weight_array(ws)), len(ws), _stream())
-        torch.cuda.synchronize(device)   # weight tensors may now be released
-        self.h = h
-        self.cfg = cfg
-        self.max_batch = max_batch
-        self.device = device
-        self.generation = 0              # bumped by every forward: the handle keeps ONE forward's activations (_ClipEncodeFn)
-
-    @property
-    def gemm_ctx(self):
-        return _lib.load().prx_clip_vit_gemm_ctx(self.h)
+        c = _ClipCfg(cfg.input_resolution, cfg.patch_size, cfg.width, cfg.layers, cfg.heads, cfg.output_dim, max_batch, precision_code(precision))
+        self._create("prx_clip_vit_create", c, ws, cfg=cfg, device=device)
 
 
 class _VitTowerCfg(ctypes.Structure):
@@ -184,17 +199,9 @@ class SlipVitHandle(ClipVitHandle):
     def __init__(self, cfg, params, max_batch: int, device, precision=None):
         from .weights import IMAGENET_MEAN, IMAGENET_STD, slip_vit_param_shapes
         ws = _weights_in_abi_order(params, slip_vit_param_shapes(cfg), device, f"SLIP ViT {getattr(cfg, 'name', '')}")
-        self.precision = precision_code(precision)
-        c = _VitTowerCfg(cfg.input_resolution, cfg.patch_size, cfg.width, cfg.layers, cfg.heads, cfg.output_dim, max_batch, self.precision,
+        c = _VitTowerCfg(cfg.input_resolution, cfg.patch_size, cfg.width, cfg.layers, cfg.heads, cfg.output_dim, max_batch, precision_code(precision),
                          VIT_FAMILY_SLIP, cfg.head_dim, cfg.ln_eps, (ctypes.c_float * 3)(*IMAGENET_MEAN), (ctypes.c_float * 3)(*IMAGENET_STD))
-        h = ctypes.c_void_p()
-        call("prx_vit_tower_create", ctypes.addressof(h), ctypes.addressof(c), _keep(self, _weight_array(ws)), len(ws), _stream())
-        torch.cuda.synchronize(device)   # weight tensors may now be released
-        self.h = h
-        self.cfg = cfg
-        self.max_batch = max_batch
-        self.device = device
-        self.generation = 0
+        self._create("prx_vit_tower_create", c, ws, cfg=cfg, device=device)
 
 
 class OpenClipVitHandle(ClipVitHandle):
@@ -207,22 +214,13 @@ class OpenClipVitHandle(ClipVitHandle):
         from .perceptor import ClipVitPerceptor
         from .weights import clip_vit_param_shapes
         ws = _weights_in_abi_order(params, clip_vit_param_shapes(cfg), device, f"OpenCLIP ViT {getattr(cfg, 'name', '')}")
-        self.precision = precision_code(precision)
-        c = _VitTowerCfg(cfg.input_resolution, cfg.patch_size, cfg.width, cfg.layers, cfg.heads, cfg.output_dim, max_batch, self.precision,
+        c = _VitTowerCfg(cfg.input_resolution, cfg.patch_size, cfg.width, cfg.layers, cfg.heads, cfg.output_dim, max_batch, precision_code(precision),
                          VIT_FAMILY_OPENCLIP, cfg.head_dim, 1e-5, (ctypes.c_float * 3)(*ClipVitPerceptor.CLIP_MEAN),
                          (ctypes.c_float * 3)(*ClipVitPerceptor.CLIP_STD))
-        h = ctypes.c_void_p()
         if getattr(cfg, "mlp_width", 0):
-            call("prx_vit_tower_create_mlp", ctypes.addressof(h), ctypes.addressof(c), int(cfg.mlp_width), _keep(self, _weight_array(ws)), len(ws),
-                 _stream())
+            self._create("prx_vit_tower_create_mlp", c, ws, int(cfg.mlp_width), cfg=cfg, device=device)
         else:
-            call("prx_vit_tower_create", ctypes.addressof(h), ctypes.addressof(c), _keep(self, _weight_array(ws)), len(ws), _stream())
-        torch.cuda.synchronize(device)   # weight tensors may now be released
-        self.h = h
-        self.cfg = cfg
-        self.max_batch = max_batch
-        self.device = device
-        self.generation = 0
+            self._create("prx_vit_tower_create", c, ws, cfg=cfg, device=device)
 
 
 class _ClipResNetCfg(ctypes.Structure):
@@ -230,7 +228,7 @@ class _ClipResNetCfg(ctypes.Structure):
                 ("output_dim", ctypes.c_int), ("max_batch", ctypes.c_int), ("precision", ctypes.c_int)]
 
 
-class ClipResNetHandle(_Handle):
+class ClipResNetHandle(_ImageTowerHandle):
     """Owns a `prx_clip_resnet` (CLIP ModifiedResNet tower: RN50, RN101, RN50x4, RN50x16, RN50x64); same protocol as ClipVitHandle.
     `params` is the OpenAI `visual.*` state dict (BatchNorm un-folded); the fold happens here.
 
@@ -247,24 +245,12 @@ class ClipResNetHandle(_Handle):
         _weights_in_abi_order(params, clip_resnet_param_shapes(cfg), "cpu", f"CLIP ModifiedResNet {getattr(cfg, 'name', '')}")   # names / shapes only
         folded = fold_clip_resnet_params(cfg, params)
         ws = [t.to(device=device, dtype=torch.float32).contiguous() for t in folded.values()]
-        self.precision = precision_code(precision)
         c = _ClipResNetCfg()
         c.input_resolution, c.width, c.heads, c.output_dim, c.max_batch = cfg.input_resolution, cfg.width, cfg.heads, cfg.output_dim, max_batch
-        c.precision = self.precision
+        c.precision = precision_code(precision)
         for i, l in enumerate(cfg.layers):
             c.layers[i] = l
-        h = ctypes.c_void_p()
-        call("prx_clip_resnet_create", ctypes.addressof(h), ctypes.addressof(c), _keep(self, _weight_array(ws)), len(ws), _stream())
-        torch.cuda.synchronize(device)
-        self.h = h
-        self.cfg = cfg
-        self.max_batch = max_batch
-        self.device = device
-        self.generation = 0
-
-    @property
-    def gemm_ctx(self):
-        return _lib.load().prx_clip_resnet_gemm_ctx(self.h)
+        self._create("prx_clip_resnet_create", c, ws, cfg=cfg, device=device)
 
 
 class _ClipConvNextCfg(ctypes.Structure):
@@ -273,7 +259,7 @@ class _ClipConvNextCfg(ctypes.Structure):
                 ("proj_mlp", ctypes.c_int), ("ln_eps", ctypes.c_float), ("max_batch", ctypes.c_int), ("precision", ctypes.c_int)]
 
 
-class ClipConvNextHandle(_Handle):
+class ClipConvNextHandle(_ImageTowerHandle):
     """Owns a `prx_clip_convnext` (OpenCLIP ConvNeXt tower: convnext_base ... convnext_xxlarge); same protocol as ClipVitHandle.
     `params` is the open_clip `visual.*` state dict (`trunk.*`, `head.*`, the layer scale `gamma` un-folded); the fold into fc2 and
     the matrix layouts of the convolutions happen here (weights.fold_clip_convnext_params).
@@ -289,24 +275,12 @@ class ClipConvNextHandle(_Handle):
         _weights_in_abi_order(params, clip_convnext_param_shapes(cfg), "cpu", f"OpenCLIP ConvNeXt {getattr(cfg, 'name', '')}")   # names / shapes only
         folded = fold_clip_convnext_params(cfg, params)
         ws = [t.to(device=device, dtype=torch.float32).contiguous() for t in folded.values()]
-        self.precision = precision_code(precision)
         c = _ClipConvNextCfg()
         c.input_resolution, c.output_dim, c.proj_mlp, c.ln_eps = cfg.input_resolution, cfg.output_dim, int(cfg.proj == "mlp"), cfg.ln_eps
-        c.max_batch, c.precision = max_batch, self.precision
+        c.max_batch, c.precision = max_batch, precision_code(precision)
         for i in range(4):
             c.depths[i], c.dims[i] = cfg.depths[i], cfg.dims[i]
-        h = ctypes.c_void_p()
-        call("prx_clip_convnext_create", ctypes.addressof(h), ctypes.addressof(c), _keep(self, _weight_array(ws)), len(ws), _stream())
-        torch.cuda.synchronize(device)   # weight tensors may now be released
-        self.h = h
-        self.cfg = cfg
-        self.max_batch = max_batch
-        self.device = device
-        self.generation = 0
-
-    @property
-    def gemm_ctx(self):
-        return _lib.load().prx_clip_convnext_gemm_ctx(self.h)
+        self._create("prx_clip_convnext_create", c, ws, cfg=cfg, device=device)
 
 
 class _ClipCfg(ctypes.Structure):
@@ -461,9 +435,10 @@ def _single_attn_resolution(cfg) -> int:
     return hits[0] if hits else -1
 
 
-class VqganHandle(_Handle):
+class VqganHandle(_EngineHandle):
     """Owns a `prx_vqgan` (codebook, weight packs, activations of one forward).  `precision`: "fp16" (default) | "bf16" | "f32"."""
     _destroy = "prx_vqgan_destroy"
+    abi = "prx_vqgan"
 
     def __init__(self, cfg, params, latent_hw, device, precision=None):
         from .weights import vqgan_param_shapes
@@ -493,10 +468,6 @@ class VqganHandle(_Handle):
         self.device = device
         self.last_indices = None
         self.generation = 0              # see _ClipEncodeFn: one forward's activations per handle
-
-    @property
-    def gemm_ctx(self):
-        return _lib.load().prx_vqgan_gemm_ctx(self.h)
 
     def z_bounds(self):
         zmin = torch.empty(self.cfg.embed_dim, device=self.device)
@@ -702,10 +673,11 @@ VGG16_CONV_INDICES = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)       # to
 VGG16_CAPTURE_LAYERS = (1, 3, 6, 8, 11, 13, 15, 22, 29)                     # Losses/StyleLoss.py:31
 
 
-class Vgg16Handle(_Handle):
+class Vgg16Handle(_EngineHandle):
     """Owns a `prx_vgg16` (torchvision VGG16 `features` up to relu5_3, frozen) for inputs up to `max_hw`.
     `params`: {"features.N.weight", "features.N.bias"} (torchvision state-dict names)."""
     _destroy = "prx_vgg16_destroy"
+    abi = "prx_vgg16"
 
     def __init__(self, params, max_hw, device, precision=None):
         self.precision = precision_code(precision)
@@ -718,10 +690,6 @@ class Vgg16Handle(_Handle):
         self.h = h
         self.max_hw = (int(max_hw[0]), int(max_hw[1]))
         self.device = device
-
-    @property
-    def gemm_ctx(self):
-        return _lib.load().prx_vgg16_gemm_ctx(self.h)
 
     def feature_shape(self, H, W, k):
         h, w, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()

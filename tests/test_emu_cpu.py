@@ -161,6 +161,13 @@ def _runner_cases():
     p_vit, p_rn, p_vq = weights.synthetic_clip_vit_params(vit, 0), weights.synthetic_clip_resnet_params(rn, 0), weights.synthetic_vqgan_params(vq, 0)
     p_tx, p_enc = weights.synthetic_clip_text_params(tx, 0), weights.synthetic_vqgan_encoder_params(vq, 0)
     p_vgg, p_rr = weights.synthetic_vgg16_params(0), weights.synthetic_rrdbnet_params(rr, 0)
+    cnx, cnx_d = weights.CLIP_CONVNEXT_CONFIGS["tiny-cnx"], weights.CLIP_CONVNEXT_CONFIGS["tiny-cnx-d"]
+    slip, oc = weights.SLIP_CONFIGS["tiny-SLIP/16"], weights.OPENCLIP_CONFIGS["tiny-H-32"]          # oc: heads of 80
+    p_cnx, p_cnx_d = weights.synthetic_clip_convnext_params(cnx, 0), weights.synthetic_clip_convnext_params(cnx_d, 0)
+    p_slip, p_oc = weights.synthetic_slip_vit_params(slip, 0), weights.synthetic_clip_vit_params(oc, 0)
+
+    def encode(cfg):
+        return lambda h: ops.clip_encode_image(torch.rand(1, 3, cfg.input_resolution, cfg.input_resolution), h)
     return [
         ("vit", lambda: ops.ClipVitHandle(vit, p_vit, 1, cpu), lambda h: ops.clip_encode_image(torch.rand(1, 3, 224, 224), h)),
         ("resnet", lambda: ops.ClipResNetHandle(rn, p_rn, 1, cpu), lambda h: ops.clip_encode_image(torch.rand(1, 3, 96, 96), h)),
@@ -171,13 +178,20 @@ def _runner_cases():
         ("vgg", lambda: ops.Vgg16Handle(p_vgg, (32, 32), cpu), lambda h: torch.cat([f.flatten() for f in ops.vgg16_features(torch.randn(1, 3, 32, 32), h)])),
         ("rrdbnet", lambda: ops.RrdbNetHandle(rr, p_rr, (4, 4), cpu), lambda h: ops.rrdbnet_synth(torch.rand(1, 3, 4, 4), h)),
         ("fft_drawer", lambda: ops.FftDrawerHandle(8, 6), lambda h: ops.fft_synth(fft_ref.rand_init((8, 6), 3).detach(), h)),
+        ("convnext", lambda: ops.ClipConvNextHandle(cnx, p_cnx, 1, cpu), encode(cnx)),
+        ("convnext_mlp", lambda: ops.ClipConvNextHandle(cnx_d, p_cnx_d, 1, cpu), encode(cnx_d)),
+        ("slip_vit", lambda: ops.SlipVitHandle(slip, p_slip, 1, cpu), encode(slip)),
+        ("openclip_vit", lambda: ops.OpenClipVitHandle(oc, p_oc, 1, cpu), encode(oc)),
     ]
 
 
 # (allocations, bytes) of one successful create, measured with the same hooks on the PARENT commit's sources (every runner with its own
 # allocation helpers): the move onto DevArena changed neither the number nor the sizes of the hipMalloc calls
 _PARENT_ALLOCS = {"vit": (83, 81787872), "resnet": (121, 74024360), "vqgan": (190, 111966312), "clip_text": (41, 21634668),
-                  "vqgan_enc": (92, 82447936), "vgg": (44, 126643720), "rrdbnet": (83, 3803148), "fft_drawer": (15, 33588332)}
+                  "vqgan_enc": (92, 82447936), "vgg": (44, 126643720), "rrdbnet": (83, 3803148), "fft_drawer": (15, 33588332),
+                  # ... and on the parent of the move onto csrc/runner_core.h (every tower with its own create tail)
+                  "convnext": (145, 85135960), "convnext_mlp": (134, 104351232), "slip_vit": (86, 80203640),
+                  "openclip_vit": (89, 134828896)}
 
 
 def test_a_failed_create_frees_its_device_memory_and_a_dropped_handle_all_of_it(emu):

@@ -901,6 +901,63 @@ def test_text_embed_and_gather_rows():
     assert untouched(ofull, n, W)
 
 
+# ================================================================================================ the tower boundary (csrc/runner_core.h)
+def tower_handle(model, max_batch, precision, dev=None):
+    """(handle, cutout side) of a reduced tower of every kind behind clip_encode_image"""
+    from pixray_amd import ops, weights as W
+    dev = torch.device(dev or DEV)
+    if model in W.CLIP_CONFIGS:
+        cfg = W.CLIP_CONFIGS[model]
+        h = ops.ClipVitHandle(cfg, W.synthetic_clip_vit_params(cfg, 0), max_batch, dev, precision)
+    elif model in W.SLIP_CONFIGS:
+        cfg = W.SLIP_CONFIGS[model]
+        h = ops.SlipVitHandle(cfg, W.synthetic_slip_vit_params(cfg, 0), max_batch, dev, precision)
+    elif model in W.OPENCLIP_CONFIGS:
+        cfg = W.OPENCLIP_CONFIGS[model]
+        h = ops.OpenClipVitHandle(cfg, W.synthetic_clip_vit_params(cfg, 0), max_batch, dev, precision)
+    elif model in W.CLIP_RESNET_CONFIGS:
+        cfg = W.CLIP_RESNET_CONFIGS[model]
+        h = ops.ClipResNetHandle(cfg, W.synthetic_clip_resnet_params(cfg, 0), max_batch, dev, precision)
+    else:
+        cfg = W.CLIP_CONVNEXT_CONFIGS[model]
+        h = ops.ClipConvNextHandle(cfg, W.synthetic_clip_convnext_params(cfg, 0), max_batch, dev, precision)
+    return h, cfg.input_resolution
+
+
+def shared_handle_case(model, precision):
+    """A handle made for two cutouts runs two, then one; a fresh handle made for one runs the same one.  Embeddings and cutout gradient
+    of the two one-cutout runs must agree bit for bit: nothing of a tower may depend on the capacity of its handle (buffer strides,
+    the batch the backward differentiates, what the larger batch left behind in the activations)."""
+    from pixray_amd import ops
+    big, R = tower_handle(model, 2, precision)
+    one, _ = tower_handle(model, 1, precision)
+    gen = torch.Generator().manual_seed(11)
+    cut = torch.rand(2, 3, R, R, generator=gen).to(DEV)
+    g = (torch.randn(2, big.cfg.output_dim, generator=gen) * 1e-3).to(DEV)
+
+    def run(h, c, gg):
+        c = c.clone().requires_grad_(True)
+        e = ops.clip_encode_image(c, h)
+        e.backward(gg)
+        sync()
+        return e.detach(), c.grad
+
+    e_two, g_two = run(big, cut, g)
+    e_big, g_big = run(big, cut[1:], g[1:])
+    e_one, g_one = run(one, cut[1:], g[1:])
+    for t in (e_two, g_two, e_big, g_big):
+        assert bool(torch.isfinite(t).all())
+    assert float(g_big.abs().max()) > 0
+    same_bits(e_big, e_one)
+    same_bits(g_big, g_one)
+
+
+@pytest.mark.parametrize("precision", ["fp16", "bf16", "f32"])
+@pytest.mark.parametrize("model", ["tiny-B/32", "tiny-RN", "tiny-cnx-d"])
+def test_tower_results_do_not_depend_on_the_handle_capacity(model, precision):
+    shared_handle_case(model, precision)
+
+
 # ================================================================================================ a CPU-sized subset (tests/test_emu_cpu.py)
 def emu_subset(lib=None):
     """one small case per kernel on the emulated kernels (DEV = "cpu").  With the emulator's library handle: the renormalisation sums
